@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - env-steps/s of the batched MsjRobot physics step on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
 
 One "step" = one lock-step advance of every env of the rank's shard by one
 integrator step of dt = 0.1: the batched ``forward_step_command``.
@@ -41,6 +41,15 @@ rounds 4-5, recorded the events in every region: the two records - markers with
 a system-scope fence - cost a 20-step region 5-10 us of its wall time, which is
 instrumentation, not the workload.  Protocol 1, rounds 1-3, printed the median
 and reduced the statistics in every region.)
+
+--dump-outputs DIR: the headline's last timed region starts from the state (and
+statistics cadence) recorded before the first one, so that what it computes does
+not depend on R; after the timed steps, the state after its last step - what a
+caller of ``rb_rollout_dev`` gets - goes to DIR/q.npy, qd.npy (float32, [envs,
+n_q]) and feasible.npy (float32 0/1, [envs]); at N > 1 each rank writes its shard
+as <name>_rank<r>.npy.  Over 64 MB in all, a fixed sample of env rows (seed 0) is
+written, their row numbers in env_index.npy (float64).  Same arguments, same inputs:
+two builds can be compared output for output.
 
 N > 1: one rank per GPU under torch.distributed.run - started by the caller (WORLD_SIZE set: behave as a rank) or, when
 `python bench.py --gpus N` is run bare, by bench.py itself as a fresh child process tree before any GPU call
@@ -198,12 +207,23 @@ def parse():
     ap.add_argument("--one-launch", action="store_true", help="N > 1: also time the headline with one launch per step over the whole shard (always on at N = 1)")
     ap.add_argument("--cpu-seconds", type=float, default=16.0)
     ap.add_argument("--repeats", type=int, default=None, help="fix the number of timed repeats (default: cover 50 ms)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline's state after its last timed step (q, qd, feasible) to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    if args.repeats is not None and args.repeats < 1:
+        ap.error("--repeats must be >= 1")
+    return args
 
 
 def run_workload(torch, robot, name, steps, warmup, envs, use_graph, rank, world, dist, substeps=None, kernel=0,
-                 repeats=None, force_chains=0):
-    """Returns dict(ms_per_step, value, kernel_us, ...) for this workload."""
+                 repeats=None, force_chains=0, keep_outputs=False):
+    """Returns dict(ms_per_step, value, kernel_us, ...) for this workload.  keep_outputs: the last timed region starts from the
+    state and statistics cadence recorded before the first one, and the dict carries `outputs`, the state after its last step -
+    the same from run to run with the same arguments, however many repeats the timing needed."""
     from gym_roboy_amd.envs.simulations import HipBatchSimulation
     n_envs, integrator, nsub, d_steps, d_warm, label = WORKLOADS[name]
     n_envs = envs or n_envs
@@ -316,8 +336,12 @@ def run_workload(torch, robot, name, steps, warmup, envs, use_graph, rank, world
         est_wall, _ = timed_region()
         repeats = max(3, min(MAX_REPEATS, int(np.ceil(1.05 * MIN_TIMED_S / max(est_wall, 1e-6)))))
     # 2 R regions, alternating: R timed by the wall clock alone (-> ms_per_step, value), R with the two events as well (-> roofline)
+    snapshot = (sim.read_state(), state["since"]) if keep_outputs else None
     walls, walls_ev, devs = [], [], []
     for i in range(2 * repeats):
+        if snapshot is not None and i == 2 * repeats - 1:     # (untimed: timed_region synchronises before its clock starts)
+            (q0, qd0, f0), state["since"] = snapshot
+            sim.set_state(q0, qd0, f0)
         w, d = timed_region(with_events=(i % 2 == 1))
         if d is None:
             walls.append(w)
@@ -364,6 +388,7 @@ def run_workload(torch, robot, name, steps, warmup, envs, use_graph, rank, world
         "stats": stats, "collective": collective,
         "finite": bool(np.isfinite(q).all() and np.isfinite(qd).all()),
         "feasible_frac": float(feas.mean()),
+        "outputs": {"q": q, "qd": qd, "feasible": feas.astype(np.float32)} if keep_outputs else None,
     }
 
 
@@ -607,6 +632,22 @@ def brief(r):
     keep = ("workload", "label", "value", "ms_per_step", "launch_us_events", "steps", "repeats", "kernel",
             "roofline", "finite", "feasible_frac", "us_per_step_events", "bytes_per_env_step")
     return {k: r[k] for k in keep if k in r}
+
+
+DUMP_CAP = 64 << 20        # bytes: --dump-outputs writes at most this much (over all ranks)
+
+
+def dump_outputs(outputs, out_dir, cap, suffix=""):
+    """Writes each array of `outputs` (one row per env) to out_dir/<name><suffix>.npy.  Above `cap` bytes in all, a fixed
+    sample of env rows (seed 0) is written instead, with their row numbers in env_index<suffix>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(outputs.values())))
+    row_bytes = sum(a.nbytes // n for a in outputs.values())
+    if n * row_bytes > cap:
+        idx = np.sort(np.random.default_rng(0).choice(n, cap // (row_bytes + 8), replace=False))
+        outputs = dict({k: a[idx] for k, a in outputs.items()}, env_index=idx.astype(np.float64))
+    for k, a in outputs.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(a))
 
 
 LINE_CAP = 4096            # bytes: the contract line on stdout never exceeds this (the driver keeps a bounded tail of stdout)
@@ -877,7 +918,9 @@ def main():
     # stream capture is not allowed on the legacy default stream: run on a side stream
     with torch.cuda.stream(torch.cuda.Stream()):
         head = run_workload(torch, robot, args.workload, args.steps, args.warmup, args.envs, use_graph,
-                            rank, world, dist, args.substeps, args.kernel, args.repeats)
+                            rank, world, dist, args.substeps, args.kernel, args.repeats,
+                            keep_outputs=args.dump_outputs is not None)
+        outputs = head.pop("outputs")
         if world == 1 and not args.no_also:
             for name in ("msj-4096-euler", "msj-262144-euler", "msj-262144-rk4", "msj-2097152-euler", "msj-2097152-rk4",
                          "upper-body-8192-euler", "upper-body-8192-rk4", "upper-body-65536-euler"):
@@ -908,6 +951,9 @@ def main():
                                args.substeps, args.kernel, max(3, (head["repeats"] + 3) // 4), force_chains=1)
         one_launch = {"us_events": one["launch_us_events"], "ms_per_step": one["ms_per_step"], "value": one["value"],
                       "frac": one["roofline"]["frac"], "hbm_frac": one["roofline"]["hbm"]["frac"], "repeats": one["repeats"]}
+
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs, DUMP_CAP // world, "_rank%d" % rank if world > 1 else "")
 
     rc = 0
     if rank == 0:

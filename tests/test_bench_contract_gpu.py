@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -196,3 +197,23 @@ def test_bare_gpus_2_starts_its_own_ranks_over_gloo():
     assert c["ok"] and c["world_size"] == 2 and c["backend"] == "gloo"
     assert c["n_env_steps_allreduced"] == c["expected"] == 2 * 262144.0 * (16 + 5 + 20 * (2 * d["repeats"] + 2))
     assert d["cpu_baseline"] is None and "starting" in out.stderr
+
+
+def test_dumped_outputs_do_not_depend_on_how_many_repeats_the_timing_took(tmp_path):
+    """--dump-outputs DIR: the headline's state after its last timed step, written as float32 .npy files.  Two runs with different
+    repeat counts (as the 50 ms rule picks them from the wall clock) write the same bits: the last region starts from the state
+    recorded before the first one."""
+    env = dict(os.environ, ROBOY_BENCH_NO_ONE_LAUNCH="1")
+    common = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-also", "--no-cpu-baseline"]
+    runs = {}
+    for repeats in (3, 5):
+        d = _run(common + ["--repeats", str(repeats), "--dump-outputs", str(tmp_path / str(repeats))], env=env)
+        assert d["steps"] == 20 and d["repeats"] == repeats and d["ms_per_step"] > 0
+        runs[repeats] = {n: np.load(tmp_path / str(repeats) / (n + ".npy")) for n in ("q", "qd", "feasible")}
+        assert sorted(os.listdir(tmp_path / str(repeats))) == ["feasible.npy", "q.npy", "qd.npy"]
+    a, b = runs[3], runs[5]
+    assert a["q"].shape == a["qd"].shape == (262144, 3) and a["feasible"].shape == (262144,)
+    assert all(x.dtype == np.float32 for x in a.values())
+    assert np.isfinite(a["q"]).all() and np.isfinite(a["qd"]).all() and set(np.unique(a["feasible"])) <= {0.0, 1.0}
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n

@@ -5,6 +5,7 @@ import math
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -192,3 +193,45 @@ def test_bare_gpus_2_starts_two_ranks_instead_of_a_usage_exit():
     import torch
     if not torch.cuda.is_available():
         assert out.returncode != 0 and "needs a GPU" in out.stderr and out.stdout.strip() == ""
+
+
+def test_dump_outputs_writes_every_array_under_the_cap(tmp_path):
+    rng = np.random.default_rng(1)
+    out = {"q": rng.standard_normal((100, 3)).astype(np.float32), "feasible": np.ones(100, np.float32)}
+    bench.dump_outputs(out, str(tmp_path / "d"), cap=1 << 20)
+    assert sorted(os.listdir(tmp_path / "d")) == ["feasible.npy", "q.npy"]
+    for k, a in out.items():
+        got = np.load(tmp_path / "d" / (k + ".npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+
+
+def test_dump_outputs_above_the_cap_writes_the_same_sample_every_time(tmp_path):
+    """Over the cap: a seeded sample of env rows, the same in every run, their row numbers beside them, the cap respected."""
+    rng = np.random.default_rng(2)
+    out = {"q": rng.standard_normal((5000, 3)).astype(np.float32), "qd": rng.standard_normal((5000, 3)).astype(np.float32)}
+    cap = 8000
+    for d in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / d), cap=cap, suffix="_rank1")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["env_index_rank1.npy", "q_rank1.npy", "qd_rank1.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) - 128 for n in names) <= cap     # (128: the .npy header)
+    idx = np.load(tmp_path / "a" / "env_index_rank1.npy")
+    assert idx.dtype == np.float64 and len(idx) > 100 and np.all(np.diff(idx) > 0)
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+    assert np.array_equal(np.load(tmp_path / "a" / "q_rank1.npy"), out["q"][idx.astype(np.int64)])
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--steps", "-3"], ["--warmup", "-1"], ["--repeats", "0"]])
+def test_counts_that_would_not_be_honoured_are_refused(monkeypatch, argv):
+    """--steps is the number of steps of every timed region: a value the run could not honour is an error, not the default."""
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    with pytest.raises(SystemExit) as e:
+        bench.parse()
+    assert e.value.code == 2
+
+
+def test_parse_keeps_the_dump_directory(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", "out/x"])
+    a = bench.parse()
+    assert a.steps == 7 and a.dump_outputs == "out/x"
