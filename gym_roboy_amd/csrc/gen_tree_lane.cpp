@@ -49,14 +49,12 @@ extern "C" int rb_gen_tree_lane_split_h(const rb_robot_desc *d, int max_parts, i
     rblg::SplitGenerated g;
     std::string err;
     // max_helpers: low byte = helper waves at most; bits 8-15 = the helpers' share of their parts' tendons in percent (0: the default)
-    // ... bit 16 = the backward pass in two sweeps (inertias before barrier T, bias forces behind it)
+    // ... bit 16 = the backward pass in two sweeps (inertias before barrier T, bias forces behind it); bit 17 unused;
+    // bit 18 = one part evaluates the trunk links' inertias for all
     const int share = (max_helpers >> 8) & 0xff;
     const bool two_sweeps = ((max_helpers >> 16) & 1) != 0;
-    // ... bit 17 = the CUT form instead (generate_split_cut: max_helpers parts cut in two, share = the distal waves' share of the tendons)
-    const bool cut = ((max_helpers >> 17) & 1) != 0;
-    const bool share_trunk = ((max_helpers >> 18) & 1) != 0;        // bit 18: one part evaluates the trunk links' inertias for all
-    const int rc = cut ? rblg::generate_split_cut(d, max_parts, g, err, max_helpers & 0xff, share)
-                       : rblg::generate_split(d, max_parts, g, err, max_helpers & 0xff, share ? share : 45, two_sweeps, share_trunk);
+    const bool share_trunk = ((max_helpers >> 18) & 1) != 0;
+    const int rc = rblg::generate_split(d, max_parts, g, err, max_helpers & 0xff, share ? share : 45, two_sweeps, share_trunk);
     if (rc) { std::fprintf(stderr, "rb_gen_tree_lane_split: %s\n", err.c_str()); return rc; }
     FILE *f = std::fopen(path, "w");
     if (!f) return RB_EINVAL;
@@ -77,4 +75,14 @@ extern "C" int rb_gen_tree_lane_split_h(const rb_robot_desc *d, int max_parts, i
 extern "C" int rb_gen_tree_lane_split(const rb_robot_desc *d, int max_parts, const char *path, int *n_parts, int *part_lds, int *x_slots,
                                       int *max_stmt, int *n_stmt, int *part_of_joint, unsigned long long *hash) {
     return rb_gen_tree_lane_split_h(d, max_parts, 0, path, n_parts, part_lds, x_slots, max_stmt, n_stmt, part_of_joint, hash, nullptr, nullptr);
+}
+
+// the library's split forms (tree_lane_gen.hpp; form 0: SPLIT_FORM, the five-wave form, 1: SPLIT2_FORM, the lean two-part form) as
+// rb_gen_tree_lane_split_h takes them: max_parts and the max_helpers word
+extern "C" int rb_gen_tree_lane_split_form(int form, int *max_parts, int *max_helpers) {
+    if (form != 0 && form != 1) return RB_EINVAL;
+    const rblg::SplitForm &f = form == 0 ? rblg::SPLIT_FORM : rblg::SPLIT2_FORM;
+    *max_parts = f.max_parts;
+    *max_helpers = f.max_helpers | f.helper_share << 8 | int(f.two_sweeps) << 16 | int(f.share_trunk) << 18;
+    return RB_OK;
 }

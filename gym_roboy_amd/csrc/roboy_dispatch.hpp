@@ -461,7 +461,7 @@ inline int resolve_form(rb_sim *s, int entry, bool build, std::string *why) {
     if (form == F_SPLIT2) {
         if (s->split2_baked) return F_SPLIT2;
         rblj::Kernel &k = kind ? s->split2_env_k : s->split2_step_k;
-        if (k.state == 1 || (build && build_split2_kernel(s, kind))) return F_SPLIT2;
+        if (k.state == 1 || (build && build_split_kernel(s, true, kind))) return F_SPLIT2;
         if (why) *why = "lean split kernel not available: " + k.why;
         return -1;                                                       // an explicit choice that cannot be served is an error, not a fallback
     }
@@ -469,7 +469,7 @@ inline int resolve_form(rb_sim *s, int entry, bool build, std::string *why) {
         if (s->split_baked) return F_SPLIT;
         rblj::Kernel &k = kind ? s->split_env_k : s->split_step_k;
         // (the plain step's kernel is built by rb_select_kernel; the env step's by rb_env_configure or here)
-        if (k.state == 1 || (build && kind == 1 && build_split_kernel(s, 1))) return F_SPLIT;
+        if (k.state == 1 || (build && kind == 1 && build_split_kernel(s, false, 1))) return F_SPLIT;
         form = tree_wants_lane(s) ? F_LANE : F_WAVE;
     }
     if (form == F_LANE) {

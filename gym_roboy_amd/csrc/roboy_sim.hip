@@ -123,47 +123,9 @@ int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #ifndef RB_TREE_SPLIT_BATCH
 #define RB_TREE_SPLIT_BATCH 16384
 #endif
-// tendon-helper waves of the split form (tree_lane_gen.hpp: generate_split): at most this many, for the longest parts.  Must be the
-// number the ahead-of-time text was generated with (tools/gen_tree_lane_baked.py: SPLIT_HELPERS).
-#ifndef RB_SPLIT_HELPERS
-#define RB_SPLIT_HELPERS 2
-#endif
-// ... and the share (percent, proximal first) of a helped part's tendons its helper takes (SPLIT_HELPER_SHARE there)
-#ifndef RB_SPLIT_HELPER_SHARE
-#define RB_SPLIT_HELPER_SHARE 80
-#endif
-// ... and whether the parts run their backward pass in two sweeps around barrier T (SPLIT_TWO_SWEEPS there): everything but the tendon
-// wrenches' part before it, beside the helpers (upper body, 8 192 envs: 9.15 -> 8.84 us Euler, 26.5 -> 25.1 us RK4 at a share of 70 %)
-#ifndef RB_SPLIT_TWO_SWEEPS
-#define RB_SPLIT_TWO_SWEEPS 1
-#endif
-// ... and whether ONE part evaluates the trunk links' inertias / bias forces for all (SPLIT_SHARE_TRUNK there): upper body, 8 192 envs,
-// share 55 ... 90 % with and without (profiles/r4_a/share_sweep_fine.log, two passes, +-0.05 us): 70 % 8.76 / 24.91 us Euler / RK4,
-// 70 % + trunk 8.62 / 24.52, 75 % + trunk 8.62 / 24.50, 80 % 8.71 / 24.37, 80 % + trunk 8.74 / 24.25, 85 % and more 9.2 / 25.6
-#ifndef RB_SPLIT_SHARE_TRUNK
-#define RB_SPLIT_SHARE_TRUNK 1
-#endif
-// ... or the CUT form instead (generate_split_cut: the RB_SPLIT_HELPERS heaviest parts as a proximal and a distal wave each;
-// RB_SPLIT_HELPER_SHARE is then the distal waves' share of the tendons).  SPLIT_CUT there.  Measured and NOT selected: 22 % fewer
-// vector instructions on the longest path of the upper body, and 10.2 / 30.1 us against 8.84 / 25.1 - all five waves are busy at once
-// there, and the two that share a SIMD run at 7 cycles per instruction instead of 5.5 (profiles/r4_a/cut_form.log).
-// The lean two-part split form (roboy_sim_split2.hip): two part waves per 64 envs and two workgroups per CU - one generation up to
-// 32 768 envs, where one wave per 64 envs leaves half of the SIMDs idle (16.1 us for the upper body's Euler step) and the five-wave
-// form needs two generations (17.5 us).  Measured: profiles/r5_a/split2_sweep.log.
+// The lean two-part split form (tree_lane_gen.hpp: SPLIT2_FORM; roboy_sim_split2.hip): AUTO uses it up to this many envs
 #ifndef RB_TREE_SPLIT2_BATCH
 #define RB_TREE_SPLIT2_BATCH 32768
-#endif
-#ifndef RB_SPLIT2_PARTS
-#define RB_SPLIT2_PARTS 2            // (tools/gen_tree_lane_baked.py: SPLIT2_PARTS, SPLIT2_SHARE_TRUNK)
-#endif
-#ifndef RB_SPLIT2_SHARE_TRUNK
-#define RB_SPLIT2_SHARE_TRUNK 1
-#endif
-#ifndef RB_SPLIT_MAX_PARTS
-#define RB_SPLIT_MAX_PARTS 4      // part waves per env group at most (the upper body has three branches: three parts)
-#endif
-#ifndef RB_SPLIT_CUT
-#define RB_SPLIT_CUT 0
 #endif
 // the two-lanes-per-env form launches one-wave workgroups up to this many envs (spread over the CUs), 256-thread ones above
 #ifndef RB_PAIR_SMALL_BATCH
@@ -607,45 +569,28 @@ size_t split_lean_lds_bytes(const rblg::SplitGenerated &g) {
 }
 size_t split_lds_bytes(const rblg::SplitGenerated &g) {      // the formula of tree_lane_split.hpp: SP_LDS_BYTES
     const int img = 3 * g.n_q + (3 * g.n_q > g.n_t ? 3 * g.n_q : g.n_t);
-    return size_t(img + g.x_buffers * g.x_slots + g.n_parts * (g.part_lds + (g.acc_slots ? g.acc_slots : 2 * g.n_q)) + 3 * g.n_parts + 1 +
-                  (g.n_helpers > 0 ? g.n_q : 0)) * 64 * 4;
+    return size_t(img + g.x_buffers * g.x_slots + g.n_parts * (g.part_lds + 2 * g.n_q) + 3 * g.n_parts + 1 + (g.n_helpers > 0 ? g.n_q : 0)) * 64 * 4;
 }
-// the hiprtc-built split kernels of a robot without ahead-of-time instances (explicit choice only); kind: 0 = step, 1 = env step
-bool build_split_kernel(rb_sim *s, int kind = 0) {
-    rblj::Kernel &k = kind == 0 ? s->split_step_k : s->split_env_k;
+// the hiprtc-built split kernels of a robot without ahead-of-time instances (explicit choice only): the five-wave form, or (lean) the
+// lean two-part form; kind: 0 = step, 1 = env step
+bool build_split_kernel(rb_sim *s, bool lean, int kind) {
+    rblj::Kernel &k = lean ? (kind == 0 ? s->split2_step_k : s->split2_env_k) : (kind == 0 ? s->split_step_k : s->split_env_k);
     if (k.state != 0) return k.state == 1;
     if (capturing(s)) return false;                      // try again outside the capture
     if (hipSetDevice(s->device) != hipSuccess) { k.state = -1; k.why = "hipSetDevice failed"; return false; }
-    // (the static_assert: the host's LDS formula - split_lds_bytes, what the launch asks for - must be the kernels' layout)
-    const std::string src = "#include \"tree_lane_defs.hpp\"\n#define RBL_NS rbl_jit_split\n" + s->split_gen.text + "#include \"tree_lane_split.hpp\"\n" +
-                            "static_assert(rbl_jit_split::SP_LDS_BYTES == " + std::to_string(split_lds_bytes(s->split_gen)) + ", \"host and kernel LDS layouts differ\");\n";
-    const std::string name = std::string(kind == 0 ? "rbl_jit_split::tree_split_step<" : "rbl_jit_split::tree_split_env_step<") + (s->integrator == RB_EULER ? "0>" : "1>");
+    const std::string form = lean ? "split2" : "split", ns = "rbl_jit_" + form;
+    const size_t lds = lean ? split_lean_lds_bytes(s->split2_gen) : split_lds_bytes(s->split_gen);
+    // (the static_assert: the host's LDS formula - what the launch asks for - must be the kernels' layout)
+    const std::string src = "#include \"tree_lane_defs.hpp\"\n#define RBL_NS " + ns + "\n" + (lean ? "#define RBL_LEAN 1\n" : "") +
+                            (lean ? s->split2_gen : s->split_gen).text + "#include \"tree_lane_split.hpp\"\n" +
+                            "static_assert(" + ns + "::SP_LDS_BYTES == " + std::to_string(lds) + ", \"host and kernel LDS layouts differ\");\n";
+    const std::string name = ns + (kind == 0 ? "::tree_split_step<" : "::tree_split_env_step<") + (s->integrator == RB_EULER ? "0>" : "1>");
     const char *names[1] = {name.c_str()};
     hipFunction_t *slots[1] = {&k.fn};
-    k.state = rbj::compile_and_load(src, "roboy_tree_split_jit.hip", names, 1, k.mod, slots, k.why) ? 1 : -1;
-    if (k.state == 1 && split_lds_bytes(s->split_gen) > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, int(split_lds_bytes(s->split_gen))) != hipSuccess) {
-        k.state = -1; k.why = "LDS of the split kernel not granted";
-    }
-    return k.state == 1;
-}
-
-// the hiprtc-built lean two-part kernels of a robot without ahead-of-time instances (explicit choice only); kind: 0 = step, 1 = env step
-bool build_split2_kernel(rb_sim *s, int kind = 0) {
-    rblj::Kernel &k = kind == 0 ? s->split2_step_k : s->split2_env_k;
-    if (k.state != 0) return k.state == 1;
-    if (capturing(s)) return false;                      // try again outside the capture
-    if (hipSetDevice(s->device) != hipSuccess) { k.state = -1; k.why = "hipSetDevice failed"; return false; }
-    const size_t lds = split_lean_lds_bytes(s->split2_gen);
-    const std::string src = "#include \"tree_lane_defs.hpp\"\n#define RBL_NS rbl_jit_split2\n#define RBL_LEAN 1\n" + s->split2_gen.text + "#include \"tree_lane_split.hpp\"\n" +
-                            "static_assert(rbl_jit_split2::SP_LDS_BYTES == " + std::to_string(lds) + ", \"host and kernel LDS layouts differ\");\n";
-    const std::string name = std::string(kind == 0 ? "rbl_jit_split2::tree_split_step<" : "rbl_jit_split2::tree_split_env_step<") + (s->integrator == RB_EULER ? "0>" : "1>");
-    const char *names[1] = {name.c_str()};
-    hipFunction_t *slots[1] = {&k.fn};
-    k.state = rbj::compile_and_load(src, "roboy_tree_split2_jit.hip", names, 1, k.mod, slots, k.why) ? 1 : -1;
+    k.state = rbj::compile_and_load(src, ("roboy_tree_" + form + "_jit.hip").c_str(), names, 1, k.mod, slots, k.why) ? 1 : -1;
     if (k.state == 1 && lds > 64 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) != hipSuccess) {
-        k.state = -1; k.why = "LDS of the lean split kernel not granted";
+        k.state = -1; k.why = std::string("LDS of the ") + (lean ? "lean " : "") + "split kernel not granted";
     }
     return k.state == 1;
 }
@@ -913,18 +858,16 @@ int rb_create(const rb_robot_desc *robot, int64_t n_envs, int integrator, double
             std::string why_gen;
             s->lane_ok = rblg::generate(robot, true, s->lane_gen, why_gen) == RB_OK;
             s->lane_baked = s->lane_ok && s->lane_gen.hash == RBL_TEXT_HASH && rblg::lane_lds_slots(s->lane_gen) == rbl_baked::LDS_SLOTS;
-            s->split_ok = (RB_SPLIT_CUT ? rblg::generate_split_cut(robot, RB_SPLIT_MAX_PARTS, s->split_gen, why_gen, RB_SPLIT_HELPERS, RB_SPLIT_HELPER_SHARE)
-                                        : rblg::generate_split(robot, RB_SPLIT_MAX_PARTS, s->split_gen, why_gen, RB_SPLIT_HELPERS, RB_SPLIT_HELPER_SHARE, RB_SPLIT_TWO_SWEEPS != 0, RB_SPLIT_SHARE_TRUNK != 0)) == RB_OK &&
-                          split_lds_bytes(s->split_gen) <= 160 * 1024;
-            if (!s->split_ok && RB_SPLIT_HELPERS > 0)        // (the exchange area of the helper form does not fit: the three-barrier-less form)
-                s->split_ok = rblg::generate_split(robot, RB_SPLIT_MAX_PARTS, s->split_gen, why_gen, 0) == RB_OK;
+            s->split_ok = rblg::generate_split(robot, rblg::SPLIT_FORM, s->split_gen, why_gen) == RB_OK && split_lds_bytes(s->split_gen) <= 160 * 1024;
+            if (!s->split_ok && rblg::SPLIT_FORM.max_helpers > 0)        // (the exchange area of the helper form does not fit: the three-barrier-less form)
+                s->split_ok = rblg::generate_split(robot, rblg::SPLIT_FORM.max_parts, s->split_gen, why_gen, 0) == RB_OK;
             // (... and the host's LDS formula is the kernels': a launch with less LDS than tree_lane_split.hpp lays out would write past it)
             s->split_baked = s->split_ok && s->split_gen.hash == RBL_SPLIT_TEXT_HASH && s->split_gen.n_parts == RBL_NPARTS &&
                              s->split_gen.n_helpers == RBL_NHELPERS && split_lds_bytes(s->split_gen) == size_t(rbl_split_baked::SP_LDS_BYTES);
             // the lean two-part form: only if the text generated for THIS robot is the text the second translation unit was compiled from
             if (s->split_ok) {
                 std::string why2;
-                s->split2_ok = rblg::generate_split(robot, RB_SPLIT2_PARTS, s->split2_gen, why2, 0, 45, false, RB_SPLIT2_SHARE_TRUNK != 0) == RB_OK &&
+                s->split2_ok = rblg::generate_split(robot, rblg::SPLIT2_FORM, s->split2_gen, why2) == RB_OK &&
                                split_lean_lds_bytes(s->split2_gen) <= 160 * 1024;
                 s->split2_baked = s->split2_ok && robot->n_q == rbs2::n_q() && robot->n_t == rbs2::n_t() && s->split2_gen.hash == rbs2::text_hash() &&
                                   s->split2_gen.n_parts == rbs2::n_parts() && split_lean_lds_bytes(s->split2_gen) == rbs2::lds_bytes();
@@ -1152,14 +1095,14 @@ int rb_select_kernel(rb_sim *s, int kernel) {
         }
         if (kernel == RB_KERNEL_ENV_PER_LANE_SPLIT2 && !s->split2_baked) {
             if (capturing(s)) { s->kernel_choice = before; return fail(RB_EINVAL, "the lean split-form kernel cannot be built during a stream capture"); }
-            if (!build_split2_kernel(s)) {
+            if (!build_split_kernel(s, true, 0)) {
                 s->kernel_choice = before;
                 return fail(RB_EUNSUPPORTED, "lean split-form kernel not available: " + s->split2_step_k.why);
             }
         }
         if (kernel == RB_KERNEL_ENV_PER_LANE_SPLIT && !s->split_baked) {
             if (capturing(s)) { s->kernel_choice = before; return fail(RB_EINVAL, "the split-form kernel cannot be built during a stream capture"); }
-            if (!build_split_kernel(s)) {
+            if (!build_split_kernel(s, false, 0)) {
                 s->kernel_choice = before;
                 return fail(RB_EUNSUPPORTED, "split-form kernel not available: " + s->split_step_k.why);
             }
@@ -1480,7 +1423,7 @@ int rb_env_configure(rb_sim *s, const rb_env_config *cfg) {
     // the run-time specialised kernels are built here, outside any capture a caller may wrap around its first step
     maybe_jit(s);
     if (s->tree && tree_wants_lane(s) && !s->lane_baked) (void)lane_kernel(s, 1);
-    if (s->tree && tree_wants_split(s) && !s->split_baked) (void)build_split_kernel(s, 1);
+    if (s->tree && tree_wants_split(s) && !s->split_baked) (void)build_split_kernel(s, false, 1);
     return rb_env_reset_dev(s, nullptr);
 }
 

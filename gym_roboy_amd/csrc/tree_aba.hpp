@@ -578,12 +578,12 @@ __device__ __forceinline__ void tree_accel(const Ctx &c, const float *qj, const 
     }
     wave_sync();
     // ---- P1: forward kinematics, one tree level at a time ----
-    if (!(RB_TREE_SKIP & 1)) sweep_p1<E, SP>(c);
+    sweep_p1<E, SP>(c);
     // the zero slot behind W that pads P4's lists (the rotation matrices or P5's exchange slots may have covered it;
     // P2 writes below it)
     if (lane < 6 * E) (c.env(lane / 6) + t.o_W + t.zoff)[lane % 6] = 0.0f;
     // ---- P2: tendons (SQ is dead: W overwrites it) ----
-    for (int it = lane; it < ((RB_TREE_SKIP & 2) ? 0 : E * t.n_t); it += 64) {
+    for (int it = lane; it < E * t.n_t; it += 64) {
         int e, k;
         split<E>(it, t.n_t, e, k);
         p2_tendon(c, e, k);
@@ -591,7 +591,7 @@ __device__ __forceinline__ void tree_accel(const Ctx &c, const float *qj, const 
     wave_sync();
     // ---- P4: pT = tendon wrenches on the link (enters the bias force); lanes = (link, env, component), link-major,
     //      lists sorted by falling length and padded to 4: every trip is 4 independent loads, added in list order ----
-    for (int it = lane; it < ((RB_TREE_SKIP & 8) ? 0 : t.n_q * E * 6); it += 64) {
+    for (int it = lane; it < t.n_q * E * 6; it += 64) {
         const int t2 = it / 6, comp = it - 6 * t2;
         const int a = t2 / E, e = t2 - a * E;
         const int i = c.ti(t.o_lc_link + a);
@@ -610,9 +610,9 @@ __device__ __forceinline__ void tree_accel(const Ctx &c, const float *qj, const 
     }
     wave_sync();
     // ---- P5: own inertia, children, articulated quantities, leaves to root ----
-    if (!(RB_TREE_SKIP & 16)) sweep_p5<E, SP>(c);
+    sweep_p5<E, SP>(c);
     // ---- P6: accelerations, root to leaves ----
-    if (!(RB_TREE_SKIP & 32)) sweep_p6<E, SP>(c);
+    sweep_p6<E, SP>(c);
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
         int e, j;

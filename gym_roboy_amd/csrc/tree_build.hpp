@@ -31,9 +31,6 @@ constexpr int MAXVP = 1024; // via-points
 #ifndef RB_TREE_MIN_WAVES
 #define RB_TREE_MIN_WAVES 4   // waves per SIMD the register allocation must allow (16 per CU: 8 192 upper-body envs in one go)
 #endif
-#ifndef RB_TREE_SKIP
-#define RB_TREE_SKIP 0      // timing-only builds: bit k set = phase P(k+1) left out (results wrong by construction)
-#endif
 constexpr int TREE_E = RB_TREE_E;   // envs per wave
 constexpr int LS = 37;      // floats per link in an env's working set (layout below); odd: lanes that hold
                             // different links of an env hit different LDS banks (strides of 64 / 48 floats

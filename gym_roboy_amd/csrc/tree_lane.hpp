@@ -299,12 +299,9 @@ tree_lane_env_step(const rbe::TreeEnvArgs a) {
     // loads with the state rows: their latency passes behind the acceleration) where the register file can carry n_q + 3 more values
     // across the step: Euler.  RK4 holds q0, v0 and the stage state beside the acceleration's live set - with the goal on top the
     // compiler put 13 values into scratch (56 bytes per lane, stored in front of the step and reloaded behind it: a private segment,
-    // and a memory round trip anyway): there the goal rows and the counters are fetched BEHIND the step (RBL_LATE_GOAL bit 1; bit 0 =
-    // Euler too).  Same values either way - nobody writes them during the step.
-#ifndef RBL_LATE_GOAL
-#define RBL_LATE_GOAL 2
-#endif
-    constexpr bool LATE_GOAL = ((RBL_LATE_GOAL >> INTEG) & 1) != 0;
+    // and a memory round trip anyway): there the goal rows and the counters are fetched BEHIND the step.  Same values either way -
+    // nobody writes them during the step.
+    constexpr bool LATE_GOAL = INTEG == 1;
     RBL_LANE_STAMP(0);
     load_inputs<!LATE_GOAL>(q, qd, act, goal, env0, live, region, lane, qq, vv, spu, gg);
     RBL_LANE_STAMP(1);

@@ -25,11 +25,6 @@
 // from two.  With helpers the exchange area is SINGLE-buffered (between a wave's reads of one acceleration and anybody's writes
 // of the next lies at least one barrier).
 //
-// The cut form (round 4, generate_split_cut; RBL_X_SINGLE, RBL_ACC_JOINTS): the heaviest parts are two waves each - the part's own
-// (proximal links, tendons) and a distal one, which is a part like any other here (it owns and integrates its joints, and the trunk's
-// like everybody); five barriers per acceleration, all in the generated text; single-buffered exchange area; the RK4 accumulators
-// take a slot per joint a part integrates instead of one per joint of the robot.
-//
 // The LEAN layout (round 5, RBL_LEAN = 1; no helpers): for batches between "one workgroup per CU" and "a wave on every SIMD" - the upper
 // body at 16 384 < n <= 32 768 envs, where the one-wave form leaves half of the SIMDs idle and the five-wave form needs two
 // generations.  Two part waves per env group and TWO workgroups per CU: the workgroup must fit 80 KB of LDS.  A part wave is alone on
@@ -61,17 +56,9 @@
 namespace RBL_NS {
 
 // K2S: how the generated part functions instantiated with this accessor write their pair constants (tree_lane_defs.hpp: RBL_K2) -
-// per half (true: the straight-line Euler step gains 1-2 %) or packed (false: RK4's stage loop keeps the pairs resident)
-#ifndef RBL_K2_SPLIT_EULER
-#define RBL_K2_SPLIT_EULER 1
-#endif
-// (RK4: per half in the part waves / the helper waves only - RBL_K2_SPLIT_RK4 bit 0 / bit 1 - was measured too: k2split_rk4_ab.log)
-#ifndef RBL_K2_SPLIT_RK4
-#define RBL_K2_SPLIT_RK4 0
-#endif
-constexpr bool sp_k2_split(int integ, bool helper = false) {
-    return integ == 0 ? RBL_K2_SPLIT_EULER != 0 : ((RBL_K2_SPLIT_RK4 >> (helper ? 1 : 0)) & 1) != 0;
-}
+// per half in the Euler instances (the straight-line Euler step gains 1-2 %), packed in the RK4 ones (RK4's stage loop keeps the pairs
+// resident; per half in its part waves or its helper waves was measured slower: profiles/r6_a/k2split_rk4_ab.log)
+constexpr bool sp_k2_split(int integ) { return integ == 0; }
 template <bool K2S>
 struct SplitLdsT {
     float *p;   // the wave's private region + lane
@@ -92,18 +79,11 @@ struct SplitRegsT {
 // fewer alive across it in kernels that sit at their 256 registers)
 constexpr int SP_IMG_SLOTS = 3 * RBL_NQ + (3 * RBL_NQ > RBL_NT ? 3 * RBL_NQ : RBL_NT);
 constexpr int SP_OV = RBL_NQ * 64, SP_OG = 2 * RBL_NQ * 64, SP_OA = 3 * RBL_NQ * 64, SP_OO = SP_OA;
-#ifndef RBL_ACC_JOINTS
-#define RBL_ACC_JOINTS RBL_NQ        // joints a part integrates at most (the cut form says; else a slot per joint of the robot)
-#endif
-#ifndef RBL_X_SINGLE
-#define RBL_X_SINGLE (RBL_NHELPERS > 0)
-#endif
-constexpr int SP_ACC_JOINTS = RBL_ACC_JOINTS;
 constexpr bool SP_LEAN = RBL_LEAN != 0;
-constexpr int SP_WAVE_SLOTS = SP_LEAN ? 0 : RBL_PART_LDS + 2 * SP_ACC_JOINTS;
+constexpr int SP_WAVE_SLOTS = SP_LEAN ? 0 : RBL_PART_LDS + 2 * RBL_NQ;
 constexpr int SP_ACC_SLOT = RBL_PART_LDS;
 constexpr int SP_NWAVES = RBL_NPARTS + RBL_NHELPERS;
-constexpr int SP_X_BUFFERS = RBL_X_SINGLE ? 1 : 2;
+constexpr int SP_X_BUFFERS = RBL_NHELPERS > 0 ? 1 : 2;
 // lean: the exchange area over the action / observation image, behind q | qd | goal; the goal rows of finished episodes behind the observation image
 constexpr int SP_X_OFF = SP_LEAN ? 3 * RBL_NQ : SP_IMG_SLOTS;
 constexpr int SP_SHARED_SLOTS = (SP_X_BUFFERS * RBL_X_SLOTS > SP_IMG_SLOTS - 3 * RBL_NQ ? SP_X_BUFFERS * RBL_X_SLOTS : SP_IMG_SLOTS - 3 * RBL_NQ) > 4 * RBL_NQ
@@ -209,15 +189,6 @@ struct SpImageStore {
 __device__ __forceinline__ float sp_sat(float v, int j) { return __builtin_amdgcn_fmed3f(v, -VMAX[j], VMAX[j]); }
 template <int PART>
 __device__ __forceinline__ constexpr bool sp_mine(int j) { return PART_OF_JOINT[j] < 0 || PART_OF_JOINT[j] == PART; }
-// the RK4 accumulator slot of joint j in part PART's region: one per joint the part integrates (the cut form: five waves' regions
-// of 2 n_q slots each would not fit the LDS), or simply j
-template <int PART>
-__device__ __forceinline__ constexpr int sp_acc(int j) {
-    if (SP_ACC_JOINTS == RBL_NQ) return j;
-    int n = 0;
-    for (int i = 0; i < j; ++i) n += sp_mine<PART>(i) ? 1 : 0;
-    return n;
-}
 
 // One env step of the joints part PART integrates (the trunk's and its own); the other entries of q / v are not touched.
 template <int INTEG, int PART, class PARK>
@@ -269,7 +240,7 @@ __device__ __forceinline__ bool split_step(const PARK &L, float *xbase, int lane
 #pragma unroll
             for (int j = 0; j < RBL_NQ; ++j) {
                 kq[j] = 0.0f; kv[j] = 0.0f;
-                if (sp_mine<PART>(j)) { L(SP_ACC_SLOT + sp_acc<PART>(j)) = 0.0f; L(SP_ACC_SLOT + SP_ACC_JOINTS + sp_acc<PART>(j)) = 0.0f; }
+                if (sp_mine<PART>(j)) { L(SP_ACC_SLOT + j) = 0.0f; L(SP_ACC_SLOT + RBL_NQ + j) = 0.0f; }
             }
 #pragma unroll 1
             for (int st = 0; st < 4; ++st) {
@@ -281,14 +252,14 @@ __device__ __forceinline__ bool split_step(const PARK &L, float *xbase, int lane
                     if (sp_mine<PART>(j)) { qs[j] = q[j] + cst * kq[j]; kq[j] = sp_sat(v[j] + cst * kv[j], j); }
                 }
 #pragma unroll
-                for (int j = 0; j < RBL_NQ; ++j) if (sp_mine<PART>(j)) L(SP_ACC_SLOT + sp_acc<PART>(j)) += wgt * kq[j];
+                for (int j = 0; j < RBL_NQ; ++j) if (sp_mine<PART>(j)) L(SP_ACC_SLOT + j) += wgt * kq[j];
                 accel(qs, kq, kv);
 #pragma unroll
-                for (int j = 0; j < RBL_NQ; ++j) if (sp_mine<PART>(j)) L(SP_ACC_SLOT + SP_ACC_JOINTS + sp_acc<PART>(j)) += wgt * kv[j];
+                for (int j = 0; j < RBL_NQ; ++j) if (sp_mine<PART>(j)) L(SP_ACC_SLOT + RBL_NQ + j) += wgt * kv[j];
             }
 #pragma unroll
             for (int j = 0; j < RBL_NQ; ++j)
-                if (sp_mine<PART>(j)) { q[j] = q[j] + h6 * L(SP_ACC_SLOT + sp_acc<PART>(j)); v[j] = v[j] + h6 * L(SP_ACC_SLOT + SP_ACC_JOINTS + sp_acc<PART>(j)); }
+                if (sp_mine<PART>(j)) { q[j] = q[j] + h6 * L(SP_ACC_SLOT + j); v[j] = v[j] + h6 * L(SP_ACC_SLOT + RBL_NQ + j); }
             }
         }
 #pragma unroll
@@ -381,10 +352,8 @@ __device__ __forceinline__ void split_helper(float *lds, int lane, int live, flo
             spu[k] = rbe::rounded_here((a * act_scale) * KSG[k]);
         }
     }
-#if !defined(RB_SPLIT_NO_HELPER_PRIO)
     __builtin_amdgcn_s_setprio(2);                      // a helper that shares a SIMD goes first: the wave beside it is the one with slack
-#endif
-    const SplitLdsT<sp_k2_split(INTEG, true)> L{lds + lane};  // (unused: a helper parks nothing; its type carries the pair-constant mode)
+    const SplitLdsT<sp_k2_split(INTEG)> L{lds + lane};  // (unused: a helper parks nothing; its type carries the pair-constant mode)
     const SplitLds X{lds + SP_X_OFF * 64 + lane};
     const int n_acc = nsub * (INTEG == 0 ? 1 : 4);
     // env layer: the goal counters of the group's envs, requested now (used behind the step)

@@ -13,8 +13,6 @@ extern "C" int gen_all_forms(const rb_robot_desc *d) {
         for (int share : {45, 80, 100})
             for (int two = 0; two < 2; ++two)
                 for (int st = 0; st < 2; ++st) { rblg::SplitGenerated g; ok += rblg::generate_split(d, 4, g, err, helpers, share, two != 0, st != 0) == 0; }
-    for (int cuts = 1; cuts <= 3; ++cuts)
-        for (int share : {0, 40, 100}) { rblg::SplitGenerated g; ok += rblg::generate_split_cut(d, 4, g, err, cuts, share) == 0; }
     for (int parts = 2; parts <= 6; ++parts) { rblg::SplitGenerated g; ok += rblg::generate_split(d, parts, g, err, 2, 70, true, true) == 0; }
     return ok;
 }

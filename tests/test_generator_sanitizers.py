@@ -1,5 +1,5 @@
 """The source generator (csrc/tree_lane_gen.hpp) under AddressSanitizer + UBSan on the CPU: every form - one function, split, split with
-tendon helpers / two sweeps / shared trunk, cut - for the committed upper body, random trees and the nine-link star.  (GPU sanitizers are
+tendon helpers / two sweeps / shared trunk - for the committed upper body, random trees and the nine-link star.  (GPU sanitizers are
 not available on the pool; the generator is host code and runs in the library at rb_create.)"""
 import os
 import subprocess
@@ -26,7 +26,7 @@ for name, d in descs:
 '''
 
 
-def test_generator_is_clean_under_asan_and_ubsan():
+def test_generator_forms_are_clean_under_asan_and_ubsan():
     asan = subprocess.run(["g++", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
     if not os.path.isabs(asan) or not os.path.exists(asan):
         pytest.skip("libasan not installed")
@@ -40,6 +40,6 @@ def test_generator_is_clean_under_asan_and_ubsan():
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     counts = dict(line.split() for line in out.stdout.strip().splitlines())
-    assert int(counts["upper"]) == 2 + 48 + 9 + 5              # every form exists for the upper body
-    assert int(counts["star"]) == 2 + 48 + 9 + 5
+    assert int(counts["upper"]) == 2 + 48 + 5                  # every form exists for the upper body
+    assert int(counts["star"]) == 2 + 48 + 5
     assert int(counts["random3"]) == 2                          # a serial chain: only the one-function forms

@@ -136,7 +136,7 @@ def test_random_shapes(shape, n_q):
     check(desc, "shape_%s%d" % (shape, n_q), tol=2e-3 if n_q > 20 else 5e-4)
 
 
-def test_in_tree_generated_headers_are_current():
+def test_in_tree_generated_headers_of_every_form_are_current():
     """`make` writes the upper body's generated headers next to the kernels (they are not committed); if they are there,
     they must be what the generator writes today - a stale header would be compiled into the library and its hash would
     no longer match the text the library regenerates at run time (the handle would silently fall back to other kernels)."""
@@ -148,8 +148,9 @@ def test_in_tree_generated_headers_are_current():
     fresh = os.path.join(BUILD, "tree_lane_baked_fresh.hpp")
     gen.generate(UpperBodyRobot().get_description(), fresh)
     assert open(fresh).read() == open(os.path.join(csrc, "tree_lane_baked.hpp")).read(), "run make -C gym_roboy_amd/csrc"
-    gen.generate_split(UpperBodyRobot().get_description(), fresh, max_helpers=gen.SPLIT_HELPERS, helper_share=gen.SPLIT_HELPER_SHARE, two_sweeps=gen.SPLIT_TWO_SWEEPS, cut=gen.SPLIT_CUT, share_trunk=gen.SPLIT_SHARE_TRUNK)
-    assert open(fresh).read() == open(os.path.join(csrc, "tree_lane_split_baked.hpp")).read(), "run make -C gym_roboy_amd/csrc"
+    for form, name in ((0, "tree_lane_split_baked.hpp"), (1, "tree_lane_split2_baked.hpp")):
+        gen.generate_split(UpperBodyRobot().get_description(), fresh, *gen.library_split_form(form))
+        assert open(fresh).read() == open(os.path.join(csrc, name)).read(), "run make -C gym_roboy_amd/csrc"
 
 
 def test_generated_text_does_not_depend_on_the_host_compiler():
@@ -226,14 +227,14 @@ def test_hiprtc_builds_the_kernels_of_a_random_robot():
 
 
 def test_hiprtc_builds_the_lean_split_kernels_of_a_random_robot():
-    """What build_split2_kernel (csrc/roboy_sim.hip) hands to hiprtc for rb_select_kernel(6) on a robot without ahead-of-time
+    """What build_split_kernel (csrc/roboy_sim.hip) hands to hiprtc for rb_select_kernel(6) on a robot without ahead-of-time
     instances: the two-part split text behind `#define RBL_LEAN 1` - parking slots in registers, exchange area over the row
     image (tree_lane_split.hpp) - compiled here for gfx950."""
     import gen_tree_lane_baked as gen
     from gym_roboy_amd.envs.robots import RobotDescription
     from random_robots import random_tree_spec
     hdr = os.path.join(BUILD, "lane_split2_rtc.hpp")
-    info = gen.generate_split(RobotDescription(random_tree_spec(5)), hdr, max_parts=2, share_trunk=1)
+    info = gen.generate_split(RobotDescription(random_tree_spec(5)), hdr, *gen.library_split_form(1))
     assert info["n_parts"] == 2 and info["n_helpers"] == 0
     text = open(hdr).read()
     text = text[:text.rindex("#define RBL_SPLIT_TEXT_HASH")]
@@ -327,7 +328,7 @@ def _sums_of_two_single_use_products(text):
     return n
 
 
-def test_generated_text_leaves_no_contraction_to_choose():
+def test_one_wave_and_library_split_texts_leave_no_contraction_to_choose():
     """a*b + c*d is written as rbl_fma(a, b, c*d) everywhere (dot products, cross products, the tendons' activation): the plain step
     and the fused env step of a robot - separate compilations of this text - then agree bit for bit (GPU:
     tests/test_random_robots_gpu.py, the hiprtc-built kernels of a random robot)."""
@@ -342,22 +343,22 @@ def test_generated_text_leaves_no_contraction_to_choose():
         text = open(one).read()
         assert "rbl_fma(" in text and _sums_of_two_single_use_products(text) == 0
         split = os.path.join(BUILD, "contract_split_%d.hpp" % k)
-        gen.generate_split(desc, split, 4, 2, 80, 1, 0, 1)
+        gen.generate_split(desc, split, *gen.library_split_form(0))
         assert _sums_of_two_single_use_products(open(split).read()) == 0
     assert _sums_of_two_single_use_products("const float t1 = a * b;\nconst float t2 = c * d;\nconst float t3 = t1 - t2;") == 1    # (the scan sees one)
 
 
-TWO_SWEEPS, CUT, SHARE_TRUNK = 1 << 16, 1 << 17, 1 << 18          # bits of the generator entry's max_helpers word (csrc/gen_tree_lane.cpp)
+TWO_SWEEPS, SHARE_TRUNK = 1 << 16, 1 << 18          # bits of the generator entry's max_helpers word (csrc/gen_tree_lane.cpp)
 
 
-def test_upper_body_split_form_with_the_backward_pass_in_two_sweeps_matches_oracle():
+def test_upper_body_library_split_form_and_the_backward_pass_in_two_sweeps_match_oracle():
     """The library's form: the bias-force recursion is linear in the forces, so the arms run the whole backward pass WITHOUT the
     tendon wrenches before barrier T (beside the helpers' tendon work) and propagate only the wrenches' part behind it."""
     from gym_roboy_amd.envs.robots import UpperBodyRobot
     import gen_tree_lane_baked as gen
     desc = UpperBodyRobot().get_description()
-    lib_form = gen.SPLIT_HELPERS | (gen.SPLIT_HELPER_SHARE << 8) | (TWO_SWEEPS if gen.SPLIT_TWO_SWEEPS else 0) | (CUT if gen.SPLIT_CUT else 0)
-    info = check_split(desc, "upper_body_lib_form", max_helpers=lib_form)
+    parts, lib_form = gen.library_split_form(0)
+    info = check_split(desc, "upper_body_lib_form", max_parts=parts, max_helpers=lib_form)
     one = check_split(desc, "upper_body_h2_s70", max_helpers=2 | (70 << 8))
     two = check_split(desc, "upper_body_h2_s70_t", max_helpers=2 | (70 << 8) | TWO_SWEEPS)
     assert info["n_parts"] == 3 and two["n_helpers"] == 2
@@ -377,7 +378,7 @@ def test_random_robots_split_form_in_two_sweeps(seed):
 
 
 def test_one_part_can_evaluate_the_trunk_links_inertias_for_all():
-    """share_trunk (measured, within the noise, not enabled in the library): the lightest part publishes the trunk links' inertias, bias
+    """share_trunk (measured, within the noise; both of the library's split forms enable it): the lightest part publishes the trunk links' inertias, bias
     forces and velocity products; the others run the trunk's frames only and fetch them behind barrier X - the same values in every
     part, so the trunk's accelerations still come out bit-identical (check_split counts mismatches)."""
     from gym_roboy_amd.envs.robots import UpperBodyRobot, RobotDescription
@@ -389,32 +390,6 @@ def test_one_part_can_evaluate_the_trunk_links_inertias_for_all():
     check_split(desc, "upper_body_st", max_helpers=SHARE_TRUNK)                       # ... and without helpers (one barrier per acceleration)
     for seed in (4, 9):
         check_split(RobotDescription(random_tree_spec(seed)), "random%dst" % seed, n=6, tol=5e-4, max_helpers=2 | (70 << 8) | TWO_SWEEPS | SHARE_TRUNK)
-
-
-def test_upper_body_cut_form_matches_oracle():
-    """The cut form (measured, not selected: csrc/roboy_sim.hip RB_SPLIT_CUT): each arm as a proximal wave (three links, the tendons) and
-    a distal one (four links) that is a part of its own; five barriers per acceleration."""
-    from gym_roboy_amd.envs.robots import UpperBodyRobot
-    desc = UpperBodyRobot().get_description()
-    info = check_split(desc, "upper_body_cut", max_helpers=2 | CUT)
-    assert info["n_parts"] == 5 and info["n_helpers"] == 0
-    assert info["part_of_joint"][6:13] == [0, 0, 0, 3, 3, 3, 3] and info["part_of_joint"][13:20] == [1, 1, 1, 4, 4, 4, 4]
-    assert info["max_stmt"] < 0.7 * 2875                      # ... of the helper form's longest part (70 % share, two sweeps)
-    text = open(os.path.join(BUILD, "lane_split_upper_body_cut.hpp")).read()
-    assert "#define RBL_X_SINGLE 1" in text and "#define RBL_ACC_JOINTS 7" in text
-    for part in range(5):                                     # the same number of workgroup barriers in every wave
-        body = text.split("RBL_FN void rbl_part%d(" % part)[1].split("\n}\n")[0]
-        assert body.count("RBL_PART_BARRIER;") == 5
-    check_split(desc, "upper_body_cut_s40", max_helpers=2 | (40 << 8) | CUT)      # the distal waves take 40 % of the tendons
-
-
-@pytest.mark.parametrize("seed", [4, 5, 9, 10])
-def test_random_robots_cut_form(seed):
-    from gym_roboy_amd.envs.robots import RobotDescription
-    from random_robots import random_tree_spec
-    desc = RobotDescription(random_tree_spec(seed))
-    check_split(desc, "random%dc" % seed, n=6, tol=5e-4, max_helpers=2 | CUT)
-    check_split(desc, "random%dcs" % seed, n=6, tol=5e-4, max_helpers=2 | (40 << 8) | CUT)
 
 
 def test_upper_body_split_in_two_parts():

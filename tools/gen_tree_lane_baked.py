@@ -48,16 +48,18 @@ def mates(desc):
     return list(m), list(tm)
 
 
-SPLIT_HELPERS = 2      # helper waves of the library's ahead-of-time split form (csrc/roboy_sim.hip: RB_SPLIT_HELPERS)
-SPLIT_HELPER_SHARE = 80    # percent of a helped part's tendons its helper takes (RB_SPLIT_HELPER_SHARE)
-SPLIT_TWO_SWEEPS = 1       # the parts' backward pass in two sweeps around barrier T (RB_SPLIT_TWO_SWEEPS)
-SPLIT_SHARE_TRUNK = 1      # one part evaluates the trunk links' inertias / bias forces for all (RB_SPLIT_SHARE_TRUNK)
-SPLIT_CUT = 0              # the cut form instead: SPLIT_HELPERS parts as a proximal and a distal wave each (RB_SPLIT_CUT)
-SPLIT2_PARTS = 2           # the lean two-part form (RB_SPLIT2_PARTS): no helpers, the trunk shared (RB_SPLIT2_SHARE_TRUNK)
-SPLIT2_SHARE_TRUNK = 1
+def library_split_form(form):
+    """(max_parts, max_helpers) of the library's split form `form` - 0: the five-wave form, 1: the lean two-part form
+    (csrc/tree_lane_gen.hpp: SPLIT_FORM, SPLIT2_FORM) - as generate_split takes them, every option in the max_helpers word."""
+    lib = load_generator()
+    parts, word = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib.rb_gen_tree_lane_split_form(int(form), ctypes.byref(parts), ctypes.byref(word))
+    if rc:
+        raise RuntimeError("rb_gen_tree_lane_split_form failed: %d" % rc)
+    return parts.value, word.value
 
 
-def generate_split(desc, path, max_parts=4, max_helpers=0, helper_share=0, two_sweeps=0, cut=0, share_trunk=0):
+def generate_split(desc, path, max_parts=4, max_helpers=0, helper_share=0, two_sweeps=0, share_trunk=0):
     """Write the split-form header (one function per wave) of `desc` to `path`; returns a dict of its figures.
     max_helpers: tendon-helper waves for the longest parts (generate_split in csrc/tree_lane_gen.hpp)."""
     lib = load_generator()
@@ -65,7 +67,7 @@ def generate_split(desc, path, max_parts=4, max_helpers=0, helper_share=0, two_s
     n_parts, part_lds, x_slots, max_stmt, n_stmt, h = c.c_int(0), c.c_int(0), c.c_int(0), c.c_int(0), c.c_int(0), c.c_ulonglong(0)
     n_helpers, helper_stmt = c.c_int(0), c.c_int(0)
     parts = (c.c_int * desc.n_q)()
-    rc = lib.rb_gen_tree_lane_split_h(c.byref(desc.as_c_struct()), int(max_parts), int(max_helpers) | (int(helper_share) << 8) | (int(bool(two_sweeps)) << 16) | (int(bool(cut)) << 17) | (int(bool(share_trunk)) << 18), path.encode(), c.byref(n_parts),
+    rc = lib.rb_gen_tree_lane_split_h(c.byref(desc.as_c_struct()), int(max_parts), int(max_helpers) | (int(helper_share) << 8) | (int(bool(two_sweeps)) << 16) | (int(bool(share_trunk)) << 18), path.encode(), c.byref(n_parts),
                                       c.byref(part_lds), c.byref(x_slots), c.byref(max_stmt), c.byref(n_stmt), parts, c.byref(h),
                                       c.byref(n_helpers), c.byref(helper_stmt))
     if rc:
@@ -80,7 +82,7 @@ if __name__ == "__main__":
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gym_roboy_amd", "csrc", "tree_lane_baked.hpp")
     print("wrote", out, generate(UpperBodyRobot().get_description(), out))
     out = os.path.join(os.path.dirname(out), "tree_lane_split_baked.hpp")
-    print("wrote", out, generate_split(UpperBodyRobot().get_description(), out, max_helpers=SPLIT_HELPERS, helper_share=SPLIT_HELPER_SHARE, two_sweeps=SPLIT_TWO_SWEEPS, cut=SPLIT_CUT, share_trunk=SPLIT_SHARE_TRUNK))
+    print("wrote", out, generate_split(UpperBodyRobot().get_description(), out, *library_split_form(0)))
     # the two-part form for the lean layout of tree_lane_split.hpp (two workgroups per CU; csrc/roboy_sim_split2.hip)
     out = os.path.join(os.path.dirname(out), "tree_lane_split2_baked.hpp")
-    print("wrote", out, generate_split(UpperBodyRobot().get_description(), out, max_parts=SPLIT2_PARTS, max_helpers=0, share_trunk=SPLIT2_SHARE_TRUNK))
+    print("wrote", out, generate_split(UpperBodyRobot().get_description(), out, *library_split_form(1)))
