@@ -24,6 +24,7 @@ CLASS_NAMES = {0: "ball8", 1: "ballx", 2: "tree"}
 ENTRY_NAMES = {0: "step", 1: "env_step", 2: "fused_rollout"}
 ENTRIES = {v: k for k, v in ENTRY_NAMES.items()}
 CONSTANTS_NAMES = {0: "kernarg", 1: "table", 2: "jit"}
+RB_SP_SCALED, RB_SP_ENV = 0, 1      # rb_setpoint_mode (rb_tendon_state*)
 RB_NEED_MIRROR, RB_NEED_NO_MIRROR, RB_NEED_SPLIT_TABLE, RB_NEED_SPLIT2_TABLE, RB_NEED_LANE = 1, 2, 4, 8, 16
 
 INTEGRATORS = {"euler": RB_EULER, "semi-implicit-euler": RB_EULER, "rk4": RB_RK4,
@@ -120,6 +121,8 @@ SIGNATURES = {
     "rb_env_step_dev": (ctypes.c_int, [_sim, _vp, _vp, _vp, _vp]),
     "rb_env_stats": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
     "rb_env_stats_dev": (ctypes.c_int, [_sim, _vp, ctypes.c_int]),
+    "rb_tendon_state_dev": (ctypes.c_int, [_sim, _vp, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp]),
+    "rb_tendon_state": (ctypes.c_int, [_sim, _fp, ctypes.c_int, ctypes.c_float, _fp, _fp, _fp, _fp]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

@@ -115,6 +115,32 @@ int msj_build(const rb_robot_desc *d, double step_size, int nsub, MsjConst<T, NT
     return RB_OK;
 }
 
+// The readout's physical-unit constants of a ball-joint robot (msj_math.hpp: TendonUnits), tendon by tendon as msj_build folds
+// the routing: lc = the segments that do not move, l0 = lc + the moving segment in the zero pose.  Records k >= n_t (up to nt_max)
+// are zero.  Call after msj_build accepted the description.
+template <typename T>
+void msj_tendon_units(const rb_robot_desc *d, TendonUnits<T> *out, int nt_max) {
+    auto seglen = [&](int va, int vb) {
+        double s = 0.0;
+        for (int a = 0; a < 3; ++a) { const double t = d->vp_pos[3 * vb + a] - d->vp_pos[3 * va + a]; s += t * t; }
+        return std::sqrt(s);
+    };
+    for (int k = 0; k < nt_max; ++k) {
+        TendonUnits<T> &u = out[k];
+        u.lc = u.vl0 = u.fmax = u.pad = T(0);
+        if (k >= d->n_t) continue;
+        const int v0 = d->vp_offset[k], v1 = d->vp_offset[k + 1];
+        int vb = v0;
+        while (d->vp_link[vb] == -1) ++vb;
+        const int va = vb - 1;
+        double lc = 0.0;
+        for (int v = v0; v + 1 < v1; ++v)
+            if (v != va) lc += seglen(v, v + 1);
+        const double l0 = lc + seglen(va, vb);
+        u.lc = T(lc); u.vl0 = T(d->v_max * l0); u.fmax = T(d->f_max[k]);
+    }
+}
+
 // Mirror symmetry of an 8-tendon ball-joint robot (msj_kernels.hpp, "mirror pairs"): a reflection S = diag(1,-1,1) (x-z
 // plane, mirror = 0) or diag(-1,1,1) (y-z plane, mirror = 1) that maps the tendon set onto itself without fixed points -
 // A' = S A, B' = S B bit for bit, same muscle constants - for a body that is itself symmetric (c.simple: principal-axis

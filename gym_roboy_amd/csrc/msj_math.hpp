@@ -126,6 +126,20 @@ struct alignas(64) MsjTendon {
     T pad[2];
 };
 
+// Per-tendon constants of the tendon-state readout (tendon_state.hpp) that turn the step's scaled quantities back into
+// physical units.  A record of its own so that MsjTendon - and with it every step kernel - stays as it is.
+template <typename T>
+struct TendonUnits {
+    T lc;          // summed length of the segments that do not move (l = |d| + lc)
+    T vl0;         // v_max * rest length: dl/dt = vl0 * v
+    T fmax;        // maximum isometric force
+    T pad;
+};
+
+// one tendon's state: length (m), length rate (m/s, > 0 lengthening), activation in [0, 1], force (N)
+template <typename T>
+struct TendonReading { T length, rate, activation, force; };
+
 template <typename T, int NT>
 struct MsjConst {
     MsjTendon<T> ten[NT];
@@ -217,6 +231,35 @@ struct MsjModel {
         const T fpe = tmax(Fast<T>::exp2(c.pe_k2s * es) * c.inv_pe_den - c.inv_pe_den, T(0));
         const T Fs = (t.fmaxv * inv) * ((act * fl) * num * rden + fpe);     // tension (v_max l0) / |d|
         tx -= Fs * mx; ty -= Fs * my; tz -= Fs * mz;
+    }
+
+    // The readout twin of tendon() + tendon_force(): the same routing and muscle arithmetic, but the tendon's length, rate,
+    // activation and force in physical units instead of its torque.  `u` is the activation offset (prescale()).
+    static RB_HD TendonReading<T> tendon_state(const C &c, const Frame &f, const MsjTendon<T> &t, const TendonUnits<T> &pu, T u) {
+        const T ax = f.r00 * t.A[0] + f.r10 * t.A[1] + f.r20 * t.A[2];
+        const T ay = f.r01 * t.A[0] + f.r11 * t.A[1] + f.r21 * t.A[2];
+        const T az = f.r02 * t.A[0] + f.r12 * t.A[1] + f.r22 * t.A[2];
+        const T d2 = ax * t.B2[0] + (ay * t.B2[1] + (az * t.B2[2] + t.ab2));
+        const T mx = ay * t.Bv[2] - az * t.Bv[1];
+        const T my = az * t.Bv[0] - ax * t.Bv[2];
+        const T mz = ax * t.Bv[1] - ay * t.Bv[0];
+        const T inv = Fast<T>::rsqrt(d2);
+        const T v = (f.wx * mx + f.wy * my + f.wz * mz) * inv;
+        const T dl = d2 * inv;                                          // |d|, the moving segment
+        const T es = dl * t.il0s + t.elcs;
+        const T act = tclamp(c.kps * es - u, T(0), T(1));
+        const T fl = Fast<T>::exp2(-(es * es));
+        const T vp = tmax(v, T(0)), p = tclamp(v + T(1), T(0), T(1));
+        const T num = c.fv_c1l * vp + p;
+        const T den = c.fv_c2l * vp + (c.fv_c2s * p + c.fv_k);
+        const T rden = Fast<T>::rcp(den);
+        const T fpe = tmax(Fast<T>::exp2(c.pe_k2s * es) * c.inv_pe_den - c.inv_pe_den, T(0));
+        TendonReading<T> r;
+        r.length = dl + pu.lc;
+        r.rate = v * pu.vl0;
+        r.activation = act;
+        r.force = pu.fmax * ((act * fl) * num * rden + fpe);
+        return r;
     }
 
     // set-point (tendon length offset, the action box +-0.3 of msj_robot.py:15-16) -> activation offset

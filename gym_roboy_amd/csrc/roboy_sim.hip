@@ -42,6 +42,7 @@
 #undef RBL_NS
 #include "tree_lane_jit.hpp"
 #include "tree_lane_split2.hpp"      // the lean two-part split instances: a translation unit of their own (roboy_sim_split2.hip)
+#include "tendon_state.hpp"           // the tendon-state readout (rb_tendon_state_dev)
 
 namespace {
 
@@ -520,6 +521,12 @@ struct rb_sim {
         void destroy() { for (hipGraphExec_t &e : exec) { if (e) (void)hipGraphExecDestroy(e); e = nullptr; } }
     };
     std::map<GraphKey, ChainGraphs> graphs;
+    // tendon-state readout (tendon_state.hpp): physical-unit constants of the ball-joint class, the same-link segment lengths of
+    // a joint tree (device copy made by the first readout), and the host form's device outputs (4 x [n][n_t], first use)
+    rbts::Units<rbk::NTX> ts_units;
+    std::vector<float> ts_tree_lconst;
+    float *d_ts_lconst = nullptr, *d_ts_out = nullptr;
+    bool ts_attr_set = false;
 };
 
 namespace {
@@ -880,6 +887,8 @@ int rb_create(const rb_robot_desc *robot, int64_t n_envs, int integrator, double
         delete s;
         return fail(rc, "no HIP kernel for this robot structure: " + why);
     }
+    if (s->tree) rbt::tree_tendon_lconst(robot, s->ts_tree_lconst);
+    else rb::msj_tendon_units(robot, s->ts_units.u, NTX);
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count < 1) {
@@ -939,6 +948,9 @@ int rb_create(const rb_robot_desc *robot, int64_t n_envs, int integrator, double
         RB_TREE_ATTR((rbt::tree_step_aba<0, rbt::TREE_E, false>)); RB_TREE_ATTR((rbt::tree_step_aba<1, rbt::TREE_E, false>));
         RB_TREE_ATTR((rbt::tree_env_step_aba<0, rbt::TREE_E, true>)); RB_TREE_ATTR((rbt::tree_env_step_aba<1, rbt::TREE_E, true>));
         RB_TREE_ATTR((rbt::tree_env_step_aba<0, rbt::TREE_E, false>)); RB_TREE_ATTR((rbt::tree_env_step_aba<1, rbt::TREE_E, false>));
+        RB_TREE_ATTR((rbt::tree_tendon_state<rbt::TREE_E, true>)); RB_TREE_ATTR((rbt::tree_tendon_state<rbt::TREE_E, false>));
+        RB_TRY(hipMalloc(&s->d_ts_lconst, sizeof(float) * s->ts_tree_lconst.size()));
+        RB_TRY(hipMemcpy(s->d_ts_lconst, s->ts_tree_lconst.data(), sizeof(float) * s->ts_tree_lconst.size(), hipMemcpyHostToDevice));
         if (s->split_baked) {
             RB_TREE_ATTR(rbl_split_baked::tree_split_step<0>); RB_TREE_ATTR(rbl_split_baked::tree_split_step<1>);
             RB_TREE_ATTR(rbl_split_baked::tree_split_env_step<0>); RB_TREE_ATTR(rbl_split_baked::tree_split_env_step<1>);
@@ -969,7 +981,7 @@ void rb_destroy(rb_sim *s) {
     rblj::unload(s->split2_step_k); rblj::unload(s->split2_env_k);
     (void)hipFree(s->d_q); (void)hipFree(s->d_qd); (void)hipFree(s->d_feas);
     (void)hipFree(s->d_goal_count); (void)hipFree(s->d_rows); (void)hipFree(s->d_u8); (void)hipFree(s->d_ten);
-    (void)hipFree(s->d_tree_words);
+    (void)hipFree(s->d_tree_words); (void)hipFree(s->d_ts_lconst); (void)hipFree(s->d_ts_out);
     (void)hipFree(s->d_state_rows); (void)hipHostFree(s->h_state_rows);
     (void)hipFree(s->d_goal); (void)hipFree(s->d_ep_ret); (void)hipFree(s->d_ep_sum); (void)hipFree(s->d_ep_cnt);
     (void)hipFree(s->d_step_num); (void)hipFree(s->d_infeas_n); (void)hipFree(s->d_stats);
@@ -1554,6 +1566,78 @@ int rb_env_stats(rb_sim *s, double *stats8, int reset) {
     RB_HIP(hipMemcpyAsync(stats8, s->d_stats, sizeof(double) * 8, hipMemcpyDeviceToHost, s->stream));
     RB_HIP(hipStreamSynchronize(s->stream));
     return reset ? stats_reset(s) : RB_OK;
+}
+
+// ---- tendon state readout (tendon_state.hpp): one kernel per robot class, not a row of the dispatch table ----
+namespace {
+int tendon_state_check(rb_sim *s, const float *act, int mode, float act_scale) {
+    if (check(s)) return RB_EINVAL;
+    if (mode != RB_SP_SCALED && mode != RB_SP_ENV) return fail(RB_EINVAL, "unknown set-point mode (RB_SP_SCALED or RB_SP_ENV)");
+    if (mode == RB_SP_ENV && !s->env_ready) return fail(RB_EINVAL, "RB_SP_ENV needs the env layer's action box: call rb_env_configure first");
+    if (mode == RB_SP_SCALED && act && !(act_scale > 0.0f)) return fail(RB_EINVAL, "act_scale must be > 0 under RB_SP_SCALED");
+    return RB_OK;
+}
+
+int tendon_state_launch(rb_sim *s, const float *d_act, int mode, float act_scale, const rbts::Outputs &out) {
+    const rbts::SetPoints sp{d_act, mode, act_scale, mode == RB_SP_ENV ? s->env.slope : 0.0f, mode == RB_SP_ENV ? s->env.act_hi : 0.0f};
+    const long n = s->n;
+    constexpr int BLOCK = 256;
+    if (s->tree) {
+        const int wv = s->tree_waves;
+        const size_t lds = rbt::tree_lds_bytes(s->tree_host, wv);
+        const long per_block = long(wv) * rbt::TREE_E;
+        const unsigned blocks = unsigned((n + per_block - 1) / per_block);
+        if (s->tree_host.dev.single_pass)
+            hipLaunchKernelGGL((rbt::tree_tendon_state<rbt::TREE_E, true>), dim3(blocks), dim3(64 * wv), lds, s->stream, s->tree_host.dev,
+                               s->d_ts_lconst, s->d_q, s->d_qd, sp, out, n);
+        else
+            hipLaunchKernelGGL((rbt::tree_tendon_state<rbt::TREE_E, false>), dim3(blocks), dim3(64 * wv), lds, s->stream, s->tree_host.dev,
+                               s->d_ts_lconst, s->d_q, s->d_qd, sp, out, n);
+    } else if (s->ntx) {
+        hipLaunchKernelGGL(rbts::msj_tendon_state_nt<BLOCK>, dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, s->stream, s->cx, s->ts_units,
+                           s->d_q, s->d_qd, sp, out, n);
+    } else {
+        rbts::Units<NT8> u8;
+        for (int k = 0; k < NT8; ++k) u8.u[k] = s->ts_units.u[k];
+        hipLaunchKernelGGL(rbts::msj_tendon_state8<BLOCK>, dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, s->stream, s->c8, u8,
+                           s->d_q, s->d_qd, sp, out, n);
+    }
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
+}  // namespace
+
+int rb_tendon_state_dev(rb_sim *s, const float *d_act, int sp_mode, float act_scale,
+                        float *d_length, float *d_rate, float *d_activation, float *d_force) {
+    int rc = tendon_state_check(s, d_act, sp_mode, act_scale);
+    if (rc) return rc;
+    for (const void *p : {static_cast<const void *>(d_act), static_cast<const void *>(d_length), static_cast<const void *>(d_rate),
+                          static_cast<const void *>(d_activation), static_cast<const void *>(d_force)})
+        if (reinterpret_cast<uintptr_t>(p) % 16) return fail(RB_EINVAL, "tendon state: device arrays must be 16-byte aligned");
+    RB_HIP(hipSetDevice(s->device));
+    return tendon_state_launch(s, d_act, sp_mode, act_scale, rbts::Outputs{d_length, d_rate, d_activation, d_force});
+}
+
+int rb_tendon_state(rb_sim *s, const float *act, int sp_mode, float act_scale,
+                    float *length, float *rate, float *activation, float *force) {
+    int rc = tendon_state_check(s, act, sp_mode, act_scale);
+    if (rc) return rc;
+    RB_HIP(hipSetDevice(s->device));
+    const size_t cnt = size_t(s->n) * size_t(s->n_t), slab = sizeof(float) * cnt;
+    if (!s->d_ts_out) RB_HIP(hipMalloc(&s->d_ts_out, 4 * slab));
+    const float *d_act = nullptr;
+    if (act) {
+        RB_HIP(hipMemcpyAsync(s->d_rows, act, slab, hipMemcpyHostToDevice, s->stream));
+        d_act = s->d_rows;
+    }
+    float *h[4] = {length, rate, activation, force}, *d[4];
+    for (int r = 0; r < 4; ++r) d[r] = h[r] ? s->d_ts_out + r * cnt : nullptr;
+    rc = tendon_state_launch(s, d_act, sp_mode, act_scale, rbts::Outputs{d[0], d[1], d[2], d[3]});
+    if (rc) return rc;
+    for (int r = 0; r < 4; ++r)
+        if (h[r]) RB_HIP(hipMemcpyAsync(h[r], d[r], slab, hipMemcpyDeviceToHost, s->stream));
+    RB_HIP(hipStreamSynchronize(s->stream));
+    return RB_OK;
 }
 
 static rb_dispatch_row g_rows[N_ROWS];

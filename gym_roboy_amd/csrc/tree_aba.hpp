@@ -275,7 +275,7 @@ __device__ __forceinline__ void point_on_link(const Ctx &c, int e, int link, V3 
     xd = ld3(lk + O_V + 3) + cross(ld3(lk + O_V), x);           // vO + w x x  (velocity about the world origin)
 }
 
-// ---- P2: one tendon: crossing geometry, Hill force, wrench of every crossing ----
+// ---- P2: one tendon: crossing geometry, Hill force, wrench of every crossing (readout twin: tendon_state.hpp, p2_tendon_state) ----
 __device__ __forceinline__ void p2_tendon(const Ctx &c, int e, int k) {
     const TreeDev &t = c.t;
     const int c0 = c.ti(t.o_t_cr_start + k), c1 = c.ti(t.o_t_cr_start + k + 1);

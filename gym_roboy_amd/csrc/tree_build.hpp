@@ -278,6 +278,23 @@ inline int tree_build(const rb_robot_desc *d, double step_size, int nsub, TreeHo
     return RB_OK;
 }
 
+// The tendon-state readout's one extra constant per tendon (tendon_state.hpp): the summed length of the segments between
+// via-points of the same link, which tree_build folds into the strain constant and the tendon phase never adds back.  A
+// buffer of its own, so that the table words - and the step kernels that stage them - stay as they are.
+inline void tree_tendon_lconst(const rb_robot_desc *d, std::vector<float> &out) {
+    out.assign(size_t(d->n_t), 0.0f);
+    for (int k = 0; k < d->n_t; ++k) {
+        double lconst = 0.0;
+        for (int v = d->vp_offset[k]; v + 1 < d->vp_offset[k + 1]; ++v) {
+            if (d->vp_link[v] != d->vp_link[v + 1]) continue;
+            double sl = 0.0;
+            for (int a = 0; a < 3; ++a) { const double dl = d->vp_pos[3 * (v + 1) + a] - d->vp_pos[3 * v + a]; sl += dl * dl; }
+            lconst += std::sqrt(sl);
+        }
+        out[size_t(k)] = float(lconst);
+    }
+}
+
 // dynamic LDS of a workgroup of `waves` waves
 inline size_t tree_lds_bytes(const TreeHost &h, int waves) { return 4 * (h.table_floats + size_t(waves) * h.ws_floats_per_wave); }
 

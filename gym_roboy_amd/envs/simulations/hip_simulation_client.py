@@ -16,6 +16,8 @@ from ... import _native as nat
 from ..robots import RobotState, RoboyRobot
 from .simulation_client import SimulationClient
 
+TENDON_STATE_KEYS = ("length", "rate", "activation", "force")
+
 
 class HipBatchSimulation:
     """N lock-step environments of one robot on one GPU."""
@@ -38,6 +40,7 @@ class HipBatchSimulation:
         self.n_q, self.n_t = self._desc.n_q, self._desc.n_t
         self.step_size = float(step_size)
         self._owned = []
+        self._stream = None            # what set_stream last handed to the library (None: the handle's own stream)
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -88,6 +91,7 @@ class HipBatchSimulation:
         else:
             arg = ctypes.c_void_p(int(stream_ptr))
         nat.check(self._lib.rb_set_stream(self._h, arg))
+        self._stream = stream_ptr
 
     def synchronize(self):
         nat.check(self._lib.rb_synchronize(self._h))
@@ -123,6 +127,39 @@ class HipBatchSimulation:
                                     nat.fptr(q), nat.fptr(qd), nat.u8ptr(f)))
         return q, qd, f.astype(bool)
 
+    def tendon_state(self, set_points=None, act_scale: float = 1.0):
+        """Per-tendon state of every env at the current state: ``{'length', 'rate', 'activation', 'force'}``, each ``[N, n_t]``
+        float32 (m, m/s with > 0 lengthening, [0, 1], N).  ``set_points`` ``[N, n_t]`` are read as ``forward_step_command``
+        reads its actions (set-point = ``act_scale * set_points``); ``None`` = all set-points 0.  Activation and force are what
+        the next step's first acceleration evaluation would use with these set-points; the state is not modified.
+        A numpy array (or None) gives numpy arrays (synchronous); a CUDA ``torch.Tensor`` gives tensors on its device,
+        computed on torch's current stream without a host copy."""
+        return self._tendon_state(set_points, nat.RB_SP_SCALED, act_scale)
+
+    def _tendon_state(self, act, sp_mode, act_scale, torch_device=None):
+        if _is_cuda_tensor(act) or (act is None and torch_device is not None):
+            return self._tendon_state_torch(act, sp_mode, act_scale, torch_device)
+        a = None if act is None else nat.as_f32(act, (self.n_envs, self.n_t), "set_points")
+        out = {k: np.empty((self.n_envs, self.n_t), np.float32) for k in TENDON_STATE_KEYS}
+        nat.check(self._lib.rb_tendon_state(self._h, None if a is None else nat.fptr(a), int(sp_mode), float(act_scale),
+                                            *[nat.fptr(out[k]) for k in TENDON_STATE_KEYS]))
+        return out
+
+    def _tendon_state_torch(self, act, sp_mode, act_scale, device=None):
+        import torch
+        if act is not None:
+            if act.dtype != torch.float32 or tuple(act.shape) != (self.n_envs, self.n_t) or not act.is_contiguous():
+                raise ValueError("set_points must be a contiguous float32 CUDA tensor of shape (%d, %d)" % (self.n_envs, self.n_t))
+            device = act.device
+        # torch's current stream: ordered behind the kernels that produced the set-points, no host sync
+        stream = torch.cuda.current_stream(device).cuda_stream
+        if stream != self._stream:
+            self.set_stream(stream)
+        out = {k: torch.empty((self.n_envs, self.n_t), dtype=torch.float32, device=device) for k in TENDON_STATE_KEYS}
+        self.tendon_state_dev(0 if act is None else act.data_ptr(), sp_mode, act_scale,
+                              *[out[k].data_ptr() for k in TENDON_STATE_KEYS])
+        return out
+
     def get_new_goal_joint_angles(self, mask=None):
         m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
         goals = np.empty((self.n_envs, self.n_q), np.float32)
@@ -154,6 +191,14 @@ class HipBatchSimulation:
 
     def step_dev(self, d_act: int, act_scale: float = 1.0):
         nat.check(self._lib.rb_step_dev(self._h, ctypes.c_void_p(d_act), float(act_scale)))
+
+    def tendon_state_dev(self, d_act: int, sp_mode: int, act_scale: float, d_length: int, d_rate: int, d_activation: int,
+                         d_force: int):
+        """Raw form of ``tendon_state`` (``rb_tendon_state_dev``): device pointers, 0 = NULL (set-points 0 / output not written);
+        ``sp_mode`` ``nat.RB_SP_SCALED`` or ``nat.RB_SP_ENV`` (the env layer's rescale; needs ``rb_env_configure``).
+        Asynchronous on the handle's stream."""
+        nat.check(self._lib.rb_tendon_state_dev(self._h, ctypes.c_void_p(d_act or 0), int(sp_mode), float(act_scale),
+                                                *[ctypes.c_void_p(p or 0) for p in (d_length, d_rate, d_activation, d_force)]))
 
     def range_capable(self, env_layer: bool = False) -> bool:
         """True if this handle's kernel form steps sub-ranges of the batch (``rb_range_capable``): the plain step, or
@@ -229,5 +274,19 @@ class HipSimulationClient(SimulationClient):
     def get_new_goal_joint_angles(self) -> np.ndarray:
         return self._sim.get_new_goal_joint_angles()[0].astype(np.float64)
 
+    def read_tendon_state(self, action=None) -> dict:
+        """Per-tendon state of the env (no counterpart in the reference): ``{'length', 'rate', 'activation', 'force'}``, each
+        ``[n_t]`` float64, under the set-points ``action`` (as ``forward_step_command`` takes them; None = all 0)."""
+        if action is not None:
+            action = np.asarray(action, dtype=np.float32)
+            if action.shape != (self._n_t,):
+                raise TypeError("action must be a sequence of %d floats" % self._n_t)
+            action = action[None, :]
+        return {k: v[0].astype(np.float64) for k, v in self._sim.tendon_state(action).items()}
+
     def close(self):
         self._sim.close()
+
+
+def _is_cuda_tensor(x):
+    return x is not None and type(x).__module__.startswith("torch") and getattr(x, "is_cuda", False)

@@ -25,6 +25,8 @@ from . import reward as rw
 from .robots import RoboyRobot
 from .simulations.hip_simulation_client import HipBatchSimulation
 
+_IN_SLAB = object()      # RoboyVecEnv._last_actions: the last step's numpy actions, uploaded into the action slab
+
 
 class RoboyVecEnv:
 
@@ -70,6 +72,8 @@ class RoboyVecEnv:
         self._d_rew = self.sim.malloc(4 * n)
         self._d_done = self.sim.malloc(4 * n)
         self._pending_actions = None
+        self._last_actions = None      # tendon_state(): the last step's actions - _IN_SLAB (numpy: in _d_act) or the torch tensor
+        self._d_ts = None              # tendon_state(): device outputs of the numpy path (4 x [N, n_t], first use)
         self._seed = int(seed)
         self._replayed_env_steps = 0.0
         self._stream = None            # the simulation's own stream
@@ -99,6 +103,7 @@ class RoboyVecEnv:
         a = nat.as_f32(actions, (self.num_envs, self.n_t), "actions")
         self.sim.upload(self._d_act, a)
         self.step_dev(self._d_act, self._d_obs, self._d_rew, self._d_done)
+        self._last_actions = _IN_SLAB
         self.sim.synchronize()
         n = self.num_envs
         return (self.sim.download(self._d_obs, (n, 3 * self.n_q)),
@@ -135,7 +140,37 @@ class RoboyVecEnv:
         rew = torch.empty((n,), dtype=torch.float32, device=actions.device)
         done = torch.empty((n,), dtype=torch.int32, device=actions.device)
         self.step_dev(actions.data_ptr(), obs.data_ptr(), rew.data_ptr(), done.data_ptr())
+        self._last_actions = actions
         return obs, rew, done.bool(), [{}] * n
+
+    def tendon_state(self, actions=None):
+        """Per-tendon state of every env at its current state (``HipBatchSimulation.tendon_state``), the set-points formed
+        from ``actions`` ``[N, n_t]`` in [-1, 1] as ``step`` forms them (``RB_SP_ENV``): ``{'length', 'rate', 'activation',
+        'force'}``, each ``[N, n_t]``.  ``actions=None``: the actions of the last ``step`` (a torch input is read again as it
+        is now, not copied), or all set-points 0 before the first step.  numpy in (or a numpy last step) gives numpy out;
+        a CUDA tensor gives tensors, on torch's current stream.
+        Auto-reset caveat: an env that was done in the last step and reset by it (``auto_reset``) reports its RESET state,
+        i.e. the tendons of the zero pose under the last actions, not the state the episode ended in."""
+        if actions is None:
+            actions = self._last_actions
+        if actions is None:
+            return self.sim._tendon_state(None, nat.RB_SP_ENV, 1.0)
+        if _is_cuda_tensor(actions):
+            import torch
+            self.set_stream(torch.cuda.current_stream(actions.device).cuda_stream)
+            return self.sim._tendon_state(actions, nat.RB_SP_ENV, 1.0)
+        if actions is _IN_SLAB:                 # the last numpy step's actions, already on the device
+            return self._tendon_state_slab()
+        return self.sim._tendon_state(actions, nat.RB_SP_ENV, 1.0)
+
+    def _tendon_state_slab(self):
+        from .simulations.hip_simulation_client import TENDON_STATE_KEYS
+        n, slab = self.num_envs, 4 * self.num_envs * self.n_t
+        if self._d_ts is None:
+            self._d_ts = [self.sim.malloc(slab) for _ in TENDON_STATE_KEYS]
+        self.sim.tendon_state_dev(self._d_act, nat.RB_SP_ENV, 1.0, *self._d_ts)
+        self.sim.synchronize()
+        return {k: self.sim.download(d, (n, self.n_t)) for k, d in zip(TENDON_STATE_KEYS, self._d_ts)}
 
     # -- the rest of stable_baselines' VecEnv surface (what PPO2 / wrappers call on the
     #    reference's SubprocVecEnv, train_parallel.py:29) ---------------------------------

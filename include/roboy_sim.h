@@ -16,6 +16,7 @@
  *   get_new_goal_joint_angles()         (ros_..py:73-81)  rb_sample_goals
  *   _check_service_available_or_timeout (ros_..py:62-64)  return codes + rb_last_error
  *   RoboyEnv.step env layer             (roboy_env.py:51-70,92-134)  rb_env_step_dev
+ *   (no counterpart: per-tendon state, the motor boards' readings)         rb_tendon_state_dev
  *
  * Layouts.  Host-facing arrays are row-major [n_envs][n] float32 (what numpy
  * and a policy network produce).  Device state is struct-of-arrays: joint
@@ -38,7 +39,7 @@
 extern "C" {
 #endif
 
-#define RB_ABI_VERSION 5
+#define RB_ABI_VERSION 6
 
 enum rb_status {
     RB_OK = 0,
@@ -276,6 +277,30 @@ int rb_env_step_range_dev(rb_sim *sim, int64_t first_env, int64_t n_envs, void *
  * torch tensor that is then all-reduced over RCCL); the host form synchronises. */
 int rb_env_stats(rb_sim *sim, double *stats8, int reset);
 int rb_env_stats_dev(rb_sim *sim, double *d_stats8, int reset);
+
+/* ---- tendon state readout (ABI 6) ----
+ * Length, length rate, activation and force of every tendon of every env: the quantities the step computes and consumes
+ * internally, at the handle's CURRENT state under the given set-points; the state is not modified.  Outputs are row-major
+ * [n_envs][n_t] float32; any output pointer may be NULL (not written).  d_act NULL = all set-points 0 (either mode).
+ *   length     m, the whole tendon (every segment, the ones that do not move included)
+ *   rate       dl/dt in m/s, > 0 lengthening
+ *   activation in [0, 1]
+ *   force      N, >= 0: the Hill-type force of DESIGN.md §2, i.e. the force the next step's first acceleration
+ *              evaluation would apply with these set-points
+ * The set-points are formed as the step forms them: RB_SP_SCALED as the plain step does (set-point = act_scale * act,
+ * act_scale > 0), RB_SP_ENV as the fused env layer does (act in [-1, 1] rescaled into the action box of rb_env_configure,
+ * which must have been called).  Pointers 16-byte aligned.  These kernels are NOT rows of the dispatch table below, which keys
+ * the three step entry kinds only (like rb_sample_goals_dev and rb_fill_actions_dev): one kernel per robot class, whichever
+ * step form the handle uses.  The device form is asynchronous on the handle's stream; the host form takes host arrays and
+ * synchronises. */
+enum rb_setpoint_mode {
+    RB_SP_SCALED = 0,   /* set-point = act_scale * act (the plain step's convention)                                          */
+    RB_SP_ENV = 1       /* the env layer's rescale of act in [-1, 1] into the action box (needs rb_env_configure)             */
+};
+int rb_tendon_state_dev(rb_sim *sim, const float *d_act, int sp_mode, float act_scale,
+                        float *d_length, float *d_rate, float *d_activation, float *d_force);
+int rb_tendon_state(rb_sim *sim, const float *act, int sp_mode, float act_scale,
+                    float *length, float *rate, float *activation, float *force);
 
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,

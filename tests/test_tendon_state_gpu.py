@@ -1,0 +1,297 @@
+"""The tendon-state readout on the GPU (include/roboy_sim.h: rb_tendon_state_dev / rb_tendon_state; csrc/tendon_state.hpp):
+parity of length, rate, activation and force with the fp64 oracle for both set-point modes on MsjRobot, random ball-joint robots,
+the upper body and random joint trees; the forces close the oracle's equation of motion; the readout leaves the state alone; the
+two set-point modes, the NULL conventions, the torch path and the single-env / vectorised-env wrappers agree with the batch."""
+import numpy as np
+import pytest
+
+from conftest import random_states
+from gym_roboy_amd import _native as nat
+
+pytestmark = pytest.mark.gpu
+
+KEYS = ("length", "rate", "activation", "force")
+
+# Tolerances of the fp32 kernels against the fp64 oracle, next to the step's parity tolerance (2e-5):
+#   length      LEN_REL of the tendon's rest length l0.  The kernels route the tendon with hardware sin / cos (v_sin_f32, ~4e-7
+#               absolute) and form |d| from |A|^2 + |B|^2 - 2 a.B, which loses ~2 bits where the moving segment is short;
+#               the joint trees add one fp32 frame composition per tree level.  (Measured: <= 5e-7 l0, the upper body.)
+#   rate        RATE_REL of v_max l0, the muscle's own velocity scale (the oracle's normalised rate v = rate / (v_max l0)).
+#   activation  kp (l - l0 - sigma sp) / l0 clamped: the length tolerance times kp / l0, plus a few ulp of the set-point
+#               product.  (Measured: <= 5.4e-6 with kp = 10.)
+#   force       2e-5 of F_max, the step's tolerance: the activation error enters through F_max f_L f_V, and f_L f_V stays
+#               below ~0.5 at the states of random_states (measured: <= 2.2e-6 F_max).
+LEN_REL = 2e-6
+RATE_REL = 2e-5
+FORCE_REL = 2e-5
+
+
+def _tolerances(o):
+    """per-tendon tolerances [n_t] of the four outputs for the oracle `o` (physics_np.TendonRobotOracle)"""
+    return {"length": LEN_REL * o.l0, "rate": RATE_REL * o.v_max * o.l0, "activation": np.full(o.n_t, o.kp * LEN_REL + 1e-6),
+            "force": np.full(o.n_t, FORCE_REL * np.max(o.f_max))}
+
+
+def _oracle(desc, q, qd, sp):
+    from oracle.physics_np import TendonRobotOracle
+    o = TendonRobotOracle(desc)
+    q, qd, sp = (np.asarray(a, np.float64) for a in (q, qd, sp))
+    length, L = o.tendon_geometry(q)
+    rate = np.einsum("nkj,nj->nk", L, qd)
+    act = np.clip(o.kp * (length - o.l0 - o.sigma * sp) / o.l0, 0.0, 1.0)
+    return {"length": length, "rate": rate, "activation": act, "force": o.muscle_force(length, rate, sp)}, o, L
+
+
+def _env_rescale64(robot, act):
+    box = robot.get_action_space()
+    lo, hi = float(box.low[0]), float(box.high[0])
+    return lo + (np.clip(np.asarray(act, np.float64), -1.0, 1.0) + 1.0) * (hi - lo) / 2.0
+
+
+def _check(got, ref, tol, idx, what):
+    for k in KEYS:
+        err = np.abs(got[k][idx].astype(np.float64) - ref[k])
+        worst = (err / tol[k]).max()
+        assert worst <= 1.0, "%s %s: max |err| %.3g = %.2f x tolerance" % (what, k, err.max(), worst)
+
+
+def _parity(robot, desc, n, seed, stride=1):
+    from gym_roboy_amd.envs.vec_env import RoboyVecEnv
+    env = RoboyVecEnv(robot, n, seed=seed)          # a configured handle: both set-point modes apply
+    sim = env.sim
+    q, qd, sp = random_states(desc, n, seed)
+    sim.set_state(q, qd)
+    idx = np.arange(0, n, stride)
+    # RB_SP_SCALED: set-points as forward_step_command takes them
+    got = sim.tendon_state(sp)
+    ref, o, _ = _oracle(desc, q[idx], qd[idx], sp[idx])
+    tol = _tolerances(o)
+    _check(got, ref, tol, idx, "%s n=%d scaled" % (desc.name, n))
+    # RB_SP_ENV: actions in [-1, 1] (and a few beyond: clamped) rescaled into the action box
+    act = np.random.default_rng(seed + 1).uniform(-1.2, 1.2, (n, desc.n_t)).astype(np.float32)
+    got = sim._tendon_state(act, nat.RB_SP_ENV, 1.0)
+    ref, _, _ = _oracle(desc, q[idx], qd[idx], _env_rescale64(robot, act[idx]))
+    _check(got, ref, tol, idx, "%s n=%d env" % (desc.name, n))
+    env.close()
+
+
+@pytest.mark.parametrize("n", [4097, 262144])
+def test_msj_robot_matches_the_oracle(n):
+    from gym_roboy_amd.envs.robots import MsjRobot
+    robot = MsjRobot()
+    _parity(robot, robot.get_description(), n, 3, stride=1 if n < 10000 else 97)
+
+
+@pytest.mark.parametrize("n_t", [1, 5, 16])
+def test_random_ball_joint_robots_match_the_oracle(n_t):
+    from random_robots import random_ball_joint_robot
+    robot, desc = random_ball_joint_robot(60 + n_t, n_t)
+    _parity(robot, desc, 1031, n_t)
+
+
+@pytest.mark.parametrize("n", [130, 66819])
+@pytest.mark.parametrize("which", ["upper", "tree1", "tree6"])
+def test_joint_trees_match_the_oracle(which, n):
+    from gym_roboy_amd.envs.robots import UpperBodyRobot
+    from random_robots import random_tree_robot
+    if which == "upper":
+        robot = UpperBodyRobot()
+        desc = robot.get_description()
+    else:
+        robot, desc = random_tree_robot(int(which[4:]))
+    _parity(robot, desc, n, 11, stride=1 if n < 1000 else 97)
+
+
+@pytest.mark.parametrize("which", ["msj", "ball5", "upper", "tree6"])
+def test_readout_forces_close_the_oracles_equation_of_motion(which):
+    """qdd = M^-1 (-L^T F_readout - D qd - b) with the oracle's M, L, b equals the oracle's acceleration: the readout reports
+    the forces the step applies.  Compared as the velocity change of one 0.1 s step, within the step's parity tolerance (MSJ
+    class: 2e-5; joint trees: test_random_robots_gpu.tolerance)."""
+    from gym_roboy_amd.envs.robots import MsjRobot, UpperBodyRobot
+    from gym_roboy_amd.envs.simulations import HipBatchSimulation
+    from random_robots import random_ball_joint_robot, random_tree_robot
+    from test_random_robots_gpu import tolerance
+    robot = {"msj": MsjRobot, "upper": UpperBodyRobot}.get(which)
+    if robot is not None:
+        robot = robot()
+        desc = robot.get_description()
+    elif which == "ball5":
+        robot, desc = random_ball_joint_robot(65, 5)
+    else:
+        robot, desc = random_tree_robot(6)
+    n, h = 257, 0.1
+    q, qd, sp = random_states(desc, n, 21)
+    sim = HipBatchSimulation(robot, n)
+    sim.set_state(q, qd)
+    F = sim.tendon_state(sp)["force"].astype(np.float64)
+    sim.close()
+    _, o, L = _oracle(desc, q, qd, sp)
+    q64, qd64 = q.astype(np.float64), qd.astype(np.float64)
+    tau = -np.einsum("nkj,nk->nj", L, F) - o.damping * qd64 - o.bias(q64, qd64)
+    qdd = np.linalg.solve(o.mass_matrix(q64), tau[:, :, None])[:, :, 0]
+    ref = o.acceleration(q64, qd64, sp.astype(np.float64))
+    tol = 2e-5 if desc.n_q == 3 else tolerance(desc, q, qd, sp, step=h)
+    assert np.all(h * np.abs(qdd - ref) < tol), (which, (h * np.abs(qdd - ref)).max())
+
+
+@pytest.mark.parametrize("which", ["msj", "upper"])
+def test_readout_is_read_only(which):
+    from gym_roboy_amd.envs.robots import MsjRobot, UpperBodyRobot
+    from gym_roboy_amd.envs.simulations import HipBatchSimulation
+    robot = {"msj": MsjRobot, "upper": UpperBodyRobot}[which]()
+    desc = robot.get_description()
+    n = 4099
+    q, qd, sp = random_states(desc, n, 5)
+    feas = (np.arange(n) % 3 != 0).astype(np.uint8)
+    a, b = HipBatchSimulation(robot, n), HipBatchSimulation(robot, n)
+    for s in (a, b):
+        s.set_state(q, qd, feas)
+    before = a.read_state()
+    a.tendon_state(sp)
+    a.tendon_state(None)
+    after = a.read_state()
+    for x, y in zip(before, after):
+        assert np.array_equal(x, y)
+    # a step behind a readout is the step without one, bit for bit
+    for x, y in zip(a.forward_step_command(sp), b.forward_step_command(sp)):
+        assert np.array_equal(x, y)
+    a.close(); b.close()
+
+
+@pytest.mark.parametrize("which", ["msj", "ball5", "upper"])
+def test_env_mode_equals_scaled_mode_with_host_rescaled_set_points(which):
+    from gym_roboy_amd.envs.robots import MsjRobot, UpperBodyRobot
+    from gym_roboy_amd.envs.vec_env import RoboyVecEnv
+    from random_robots import random_ball_joint_robot
+    if which == "ball5":
+        robot, desc = random_ball_joint_robot(65, 5)
+    else:
+        robot = {"msj": MsjRobot, "upper": UpperBodyRobot}[which]()
+        desc = robot.get_description()
+    n = 1000
+    env = RoboyVecEnv(robot, n)
+    q, qd, _ = random_states(desc, n, 8)
+    env.sim.set_state(q, qd)
+    act = np.random.default_rng(9).uniform(-1.0, 1.0, (n, desc.n_t)).astype(np.float32)
+    box = robot.get_action_space()
+    lo, hi = np.float32(box.low[0]), np.float32(box.high[0])
+    slope = np.float32(hi - lo) / np.float32(2.0)                    # the library's fp32 rescale, two roundings
+    sp = (slope * (np.clip(act, -1, 1) - np.float32(1.0))).astype(np.float32) + hi
+    e = env.sim._tendon_state(act, nat.RB_SP_ENV, 1.0)
+    s = env.sim.tendon_state(sp)
+    for k in KEYS:
+        np.testing.assert_array_max_ulp(e[k], s[k], maxulp=1)
+    env.close()
+
+
+def test_argument_errors_on_a_real_handle():
+    from gym_roboy_amd.envs.robots import MsjRobot
+    from gym_roboy_amd.envs.simulations import HipBatchSimulation
+    robot = MsjRobot()
+    sim = HipBatchSimulation(robot, 64)
+    lib = nat.load()
+    out = np.zeros((64, 8), np.float32)
+    assert lib.rb_tendon_state(sim.handle, None, 7, 1.0, nat.fptr(out), None, None, None) == nat.RB_EINVAL
+    assert b"mode" in lib.rb_last_error()
+    assert lib.rb_tendon_state(sim.handle, None, nat.RB_SP_ENV, 1.0, nat.fptr(out), None, None, None) == nat.RB_EINVAL
+    assert b"rb_env_configure" in lib.rb_last_error()
+    sp = np.zeros((64, 8), np.float32)
+    assert lib.rb_tendon_state(sim.handle, nat.fptr(sp), nat.RB_SP_SCALED, 0.0, nat.fptr(out), None, None, None) == nat.RB_EINVAL
+    assert b"act_scale" in lib.rb_last_error()
+    with pytest.raises(ValueError):
+        sim._tendon_state(None, nat.RB_SP_ENV, 1.0)
+    # the handle is still usable
+    assert np.all(np.isfinite(sim.tendon_state(sp)["force"]))
+    sim.close()
+
+
+@pytest.mark.parametrize("which", ["msj", "ball5", "upper"])
+def test_null_outputs_are_not_written_and_null_set_points_are_zeros(which):
+    from gym_roboy_amd.envs.robots import MsjRobot, UpperBodyRobot
+    from gym_roboy_amd.envs.simulations import HipBatchSimulation
+    from random_robots import random_ball_joint_robot
+    if which == "ball5":
+        robot, desc = random_ball_joint_robot(65, 5)
+    else:
+        robot = {"msj": MsjRobot, "upper": UpperBodyRobot}[which]()
+        desc = robot.get_description()
+    n = 777
+    sim = HipBatchSimulation(robot, n)
+    q, qd, sp = random_states(desc, n, 4)
+    sim.set_state(q, qd)
+    full = sim.tendon_state(sp)
+    d_sp = sim.malloc(4 * n * desc.n_t)
+    sim.upload(d_sp, sp)
+    canary = np.full((n, desc.n_t), -12345.5, np.float32)
+    bufs = []
+    for _ in KEYS:
+        d = sim.malloc(4 * n * desc.n_t)
+        sim.upload(d, canary)
+        bufs.append(d)
+    for mask in (0b0101, 0b1010, 0b1000):
+        for d in bufs:
+            sim.upload(d, canary)
+        sim.tendon_state_dev(d_sp, nat.RB_SP_SCALED, 1.0, *[d if mask >> r & 1 else 0 for r, d in enumerate(bufs)])
+        sim.synchronize()
+        for r, (k, d) in enumerate(zip(KEYS, bufs)):
+            got = sim.download(d, (n, desc.n_t))
+            assert np.array_equal(got, full[k] if mask >> r & 1 else canary), (mask, k)
+    # d_act NULL = explicit zero set-points
+    z, none = sim.tendon_state(np.zeros((n, desc.n_t), np.float32)), sim.tendon_state(None)
+    for k in KEYS:
+        assert np.array_equal(z[k], none[k])
+    sim.close()
+
+
+def test_torch_path_single_env_client_and_vec_env_agree_with_the_batch():
+    import torch
+    from gym_roboy_amd.envs.robots import MsjRobot
+    from gym_roboy_amd.envs.simulations import HipBatchSimulation, HipSimulationClient
+    from gym_roboy_amd.envs.vec_env import RoboyVecEnv
+    robot = MsjRobot()
+    desc = robot.get_description()
+    n = 2048
+    q, qd, sp = random_states(desc, n, 12)
+    sim = HipBatchSimulation(robot, n)
+    sim.set_state(q, qd)
+    ref = sim.tendon_state(sp)
+    got = sim.tendon_state(torch.from_numpy(sp).cuda())
+    for k in KEYS:
+        assert got[k].is_cuda and np.array_equal(got[k].cpu().numpy(), ref[k])
+    sim.close()
+    # the single-env client against a batch of one
+    client = HipSimulationClient(robot)
+    client.forward_step_command(sp[0])
+    one = HipBatchSimulation(robot, 1)
+    s1 = client._sim.read_state()
+    one.set_state(s1[0], s1[1])
+    c = client.read_tendon_state(sp[1])
+    b = one.tendon_state(sp[1:2])
+    for k in KEYS:
+        assert c[k].shape == (desc.n_t,) and np.array_equal(c[k], b[k][0].astype(np.float64))
+    client.close(); one.close()
+    # RoboyVecEnv: the last step's actions, numpy and torch
+    env = RoboyVecEnv(robot, n, seed=2)
+    env.reset()
+    zero = env.tendon_state()                                    # before any step: set-points 0
+    z = env.sim.tendon_state(None)
+    for k in KEYS:
+        assert np.array_equal(zero[k], z[k])
+    box = robot.get_action_space()
+    lo, hi = np.float32(box.low[0]), np.float32(box.high[0])
+    slope = np.float32(hi - lo) / np.float32(2.0)
+    rng = np.random.default_rng(13)
+    for use_torch in (False, True):
+        act = rng.uniform(-1.0, 1.0, (n, desc.n_t)).astype(np.float32)
+        if use_torch:
+            env.step(torch.from_numpy(act).cuda())
+            got = {k: v.cpu().numpy() for k, v in env.tendon_state().items()}
+            torch.cuda.synchronize()
+        else:
+            env.step(act)
+            got = env.tendon_state()
+        sp_host = (slope * (act - np.float32(1.0))).astype(np.float32) + hi
+        want = env.sim.tendon_state(sp_host)
+        for k in KEYS:
+            np.testing.assert_array_max_ulp(got[k], want[k], maxulp=1)
+    env.close()
