@@ -123,6 +123,11 @@ SIGNATURES = {
     "rb_env_stats_dev": (ctypes.c_int, [_sim, _vp, ctypes.c_int]),
     "rb_tendon_state_dev": (ctypes.c_int, [_sim, _vp, ctypes.c_int, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "rb_tendon_state": (ctypes.c_int, [_sim, _fp, ctypes.c_int, ctypes.c_float, _fp, _fp, _fp, _fp]),
+    "rb_params_enable": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_int32)]),
+    "rb_params_disable": (ctypes.c_int, [_sim]),
+    "rb_params_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]),
+    "rb_params_set_ranges": (ctypes.c_int, [_sim, _fp, _fp, ctypes.c_int]),
+    "rb_params_sample_dev": (ctypes.c_int, [_sim, _vp]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

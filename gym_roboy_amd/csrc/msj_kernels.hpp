@@ -320,11 +320,18 @@ __device__ __forceinline__ msj_env_kernarg_ptr late_env_args(int offset) {
     return (msj_env_kernarg_ptr)(p + offset);
 }
 
+// What an env's episode end does besides the goal redraw: nothing, or (env_params.hpp) the redraw of the env's physical parameters.
+// Called as on_done(i, gid, seed, auto_reset) where the goal is redrawn.
+struct NoDoneHook {
+    __device__ __forceinline__ void operator()(long, uint64_t, uint64_t, int) const {}
+};
+
 // What RoboyEnv.step does around the simulator's answer for env i of this launch (qq, vv: the new state; gg: the env's goal; ok:
 // feasible): reward, done, episode accounting, goal redraw / reset on done, and every row back.  Shared by the env-per-lane
 // kernel and the two-lanes-per-env kernel (whose even lanes call it).
-template <typename ARGS>      // const MsjEnvArgs * (the argument itself) or msj_env_kernarg_ptr (the late view of it)
-__device__ __forceinline__ void env_account(ARGS a, long i, float (&qq)[3], float (&vv)[3], float (&gg)[3], bool ok) {
+template <typename ARGS, typename HOOK = NoDoneHook>      // ARGS: const MsjEnvArgs * (the argument itself) or msj_env_kernarg_ptr (the late view of it)
+__device__ __forceinline__ void env_account(ARGS a, long i, float (&qq)[3], float (&vv)[3], float (&gg)[3], bool ok,
+                                            const HOOK &on_done = HOOK{}) {
     EnvParams e;                  // (field by field: the source may live in the constant address space)
     e.vel_penalty = a->e.vel_penalty; e.bonus = a->e.bonus; e.max_len = a->e.max_len; e.auto_reset = a->e.auto_reset;
     e.penalty = a->e.penalty; e.bonus_val = a->e.bonus_val;
@@ -372,6 +379,7 @@ __device__ __forceinline__ void env_account(ARGS a, long i, float (&qq)[3], floa
         // RoboyEnv.step draws a goal (_set_new_goal, :67-68); the VecEnv worker's env.reset() (:82-87) then draws another one, which
         // replaces it before anybody saw it: the counter advances by two, only the SECOND draw is evaluated
         draw_goal3(lo, hi, seed, gid, draw + (e.auto_reset ? 1u : 0u), gg);
+        on_done(i, gid, seed, e.auto_reset);
         draw += e.auto_reset ? 2u : 1u;
         if (e.auto_reset) {
 #pragma unroll

@@ -166,6 +166,15 @@ struct SpArray {
     RB_HD T operator()(int k) const { return v[k]; }
 };
 
+// Per-env physical parameters (env_params.hpp): a force scale enters as a per-lane copy of the tendon record with fmaxv scaled
+// (scaled_tendon); mass and damping scales enter rigid_body() through this policy: `mass` is applied to every inertia and
+// mass-moment constant (I_O, m c), `damping(j, d)` to joint j's viscous damping.  The default is the identity, which every kernel
+// without parameters uses: its code is what it was before the hook.
+struct NominalBody {
+    template <typename T> RB_HD T mass(T x) const { return x; }
+    template <typename T> RB_HD T damping(int, T x) const { return x; }
+};
+
 template <typename T, int NT>
 struct MsjModel {
     using C = MsjConst<T, NT>;
@@ -262,6 +271,14 @@ struct MsjModel {
         return r;
     }
 
+    // tendon record t with its tension scaled by fscale (F_max, passive term included): the per-env force scale of env_params.hpp.
+    // Only fmaxv becomes a per-lane value; the rest of the record stays what it was (wave-uniform).
+    static RB_HD MsjTendon<T> scaled_tendon(const MsjTendon<T> &t, T fscale) {
+        MsjTendon<T> s = t;
+        s.fmaxv = t.fmaxv * fscale;
+        return s;
+    }
+
     // set-point (tendon length offset, the action box +-0.3 of msj_robot.py:15-16) -> activation offset
     static RB_HD T prescale(const C &c, int k, T setpoint) { return c.ten[k].ksg * setpoint; }
 
@@ -269,9 +286,17 @@ struct MsjModel {
     // c.simple (wave-uniform) marks the common case - principal-axis inertia,
     // centre of mass on the body z axis, gravity along world z - in which a
     // third of the terms vanish; the branch is a scalar one.
-    static RB_HD void rigid_body(const C &c, const Frame &f, const T qd[3], T tx, T ty, T tz, T qdd[3]) {
+    // BP: the body policy - NominalBody (no object: bp stays null), or an env's mass and damping scales (env_params.hpp).
+    template <typename BP> static RB_HD T bmass(const BP *bp, T x) {
+        if constexpr (std::is_same<BP, NominalBody>::value) return x; else return bp->mass(x);
+    }
+    template <typename BP> static RB_HD T bdamp(const BP *bp, int j, T x) {
+        if constexpr (std::is_same<BP, NominalBody>::value) return x; else return bp->damping(j, x);
+    }
+    template <typename BP = NominalBody>
+    static RB_HD void rigid_body(const C &c, const Frame &f, const T qd[3], T tx, T ty, T tz, T qdd[3], const BP *bp = nullptr) {
         const T r00 = f.r00, r01 = f.r01, r02 = f.r02, s2 = f.s2, c2 = f.c2;
-        const T Ixx = c.IO[0], Iyy = c.IO[1], Izz = c.IO[2];
+        const T Ixx = bmass(bp, c.IO[0]), Iyy = bmass(bp, c.IO[1]), Izz = bmass(bp, c.IO[2]);
         // zeta_dot qd
         const T z0x = -f.s1 * c2 * qd[1] - f.c1 * s2 * qd[2];
         const T z0y = f.s1 * s2 * qd[1] - f.c1 * c2 * qd[2];
@@ -294,12 +319,12 @@ struct MsjModel {
             const T nx = Ixx * bx + (f.wy * hz - f.wz * hy);
             const T ny = Iyy * by + (f.wz * hx - f.wx * hz);
             const T nz = Izz * bz + (f.wx * hy - f.wy * hx);
-            const T k = c.mc[2] * c.g[2];                                   // (m c) x R^T g
+            const T k = bmass(bp, c.mc[2]) * c.g[2];                                   // (m c) x R^T g
             vx = tx - k * f.r21 - nx;
             vy = ty + k * f.r20 - ny;
             vz = tz - nz;
         } else {
-            const T Ixy = c.IO[3], Ixz = c.IO[4], Iyz = c.IO[5];
+            const T Ixy = bmass(bp, c.IO[3]), Ixz = bmass(bp, c.IO[4]), Iyz = bmass(bp, c.IO[5]);
             // columns I_O zeta_j
             const T a0x = Ixx * r00 + Ixy * r01 + Ixz * r02;
             const T a0y = Ixy * r00 + Iyy * r01 + Iyz * r02;
@@ -325,13 +350,13 @@ struct MsjModel {
             const T gx = r00 * c.g[0] + f.r10 * c.g[1] + f.r20 * c.g[2];
             const T gy = r01 * c.g[0] + f.r11 * c.g[1] + f.r21 * c.g[2];
             const T gz = r02 * c.g[0] + f.r12 * c.g[1] + f.r22 * c.g[2];
-            vx = tx + (c.mc[1] * gz - c.mc[2] * gy) - nx;
-            vy = ty + (c.mc[2] * gx - c.mc[0] * gz) - ny;
-            vz = tz + (c.mc[0] * gy - c.mc[1] * gx) - nz;
+            vx = tx + (bmass(bp, c.mc[1]) * gz - bmass(bp, c.mc[2]) * gy) - nx;
+            vy = ty + (bmass(bp, c.mc[2]) * gx - bmass(bp, c.mc[0]) * gz) - ny;
+            vz = tz + (bmass(bp, c.mc[0]) * gy - bmass(bp, c.mc[1]) * gx) - nz;
         }
-        const T t0 = r00 * vx + r01 * vy + r02 * vz - c.damp[0] * qd[0];
-        const T t1 = s2 * vx + c2 * vy - c.damp[1] * qd[1];
-        const T t2 = vz - c.damp[2] * qd[2];
+        const T t0 = r00 * vx + r01 * vy + r02 * vz - bdamp(bp, 0, c.damp[0]) * qd[0];
+        const T t1 = s2 * vx + c2 * vy - bdamp(bp, 1, c.damp[1]) * qd[1];
+        const T t2 = vz - bdamp(bp, 2, c.damp[2]) * qd[2];
         // 3x3 SPD solve by the adjugate (one reciprocal)
         const T k00 = m11 * m22 - m12 * m12;
         const T k01 = m02 * m12 - m01 * m22;

@@ -20,7 +20,8 @@
 
 namespace rb {
 
-enum { STREAM_ACTIONS = 0, STREAM_GOALS = 1 };
+// (stream 2 is the policy's sampling noise, mlp_common.hpp; 3 the per-env physical parameters, env_params.hpp)
+enum { STREAM_ACTIONS = 0, STREAM_GOALS = 1, STREAM_PARAMS = 3 };
 
 struct Philox4 { uint32_t v[4]; };
 

@@ -516,7 +516,15 @@ inline const Row *row_for(rb_sim *s, int entry, bool build, std::string *why = n
 }
 
 // every launch of the library's three entry kinds
+// a handle with per-env parameters enabled (rb_params_enable) launches the kernels of env_params.hpp instead of its row
+int params_launch(rb_sim *s, int entry, const Launch &L);      // (roboy_sim.hip)
 inline int dispatch(rb_sim *s, int entry, const Launch &L) {
+    if (s->params) {
+        const int rc = params_launch(s, entry, L);
+        if (rc) return rc;
+        RB_HIP(hipGetLastError());
+        return RB_OK;
+    }
     std::string why;
     const Row *r = row_for(s, entry, true, &why);
     if (!r) return fail(RB_EUNSUPPORTED, why);

@@ -17,6 +17,7 @@
 // holds the kernels that are not in a header of their own, the handle, the availability predicates and the C ABI.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -43,6 +44,7 @@
 #include "tree_lane_jit.hpp"
 #include "tree_lane_split2.hpp"      // the lean two-part split instances: a translation unit of their own (roboy_sim_split2.hip)
 #include "tendon_state.hpp"           // the tendon-state readout (rb_tendon_state_dev)
+#include "env_params.hpp"             // per-env physical parameters (rb_params_*)
 
 namespace {
 
@@ -527,6 +529,14 @@ struct rb_sim {
     std::vector<float> ts_tree_lconst;
     float *d_ts_lconst = nullptr, *d_ts_out = nullptr;
     bool ts_attr_set = false;
+    // per-env physical parameters (env_params.hpp; rb_params_*): while enabled, the step and env-step entries launch the parameter
+    // kernels instead of the dispatch table's row.  Planes [P][n], draw counters [n], ranges lo[P] | hi[P] (device and host copies)
+    bool params = false;
+    int n_params = 0;
+    float *d_params = nullptr, *d_param_ranges = nullptr;
+    uint32_t *d_param_draws = nullptr;
+    std::vector<float> param_ranges;
+    bool param_resample = false;
 };
 
 namespace {
@@ -618,6 +628,7 @@ rblj::Kernel *lane_kernel(rb_sim *s, int kind) {
     return &k;
 }
 void maybe_jit(rb_sim *s) {
+    if (s->params) return;                        // the parameter kernels are ahead of time (and a later call builds after rb_params_disable)
     if (s->tree) { if (tree_wants_lane(s) && !s->lane_baked) (void)lane_kernel(s, 0); return; }
     if (s->jit_state != 0) return;
     if (s->ntx || s->baked || s->n <= RB_SMALL_BATCH || !rbj::enabled() || jit_level() == 0) { s->jit_state = -1; return; }
@@ -695,6 +706,7 @@ bool tree_wants_split2(const rb_sim *s) {
 // kernel forms that step a sub-range of the batch (shifted pointers, own env count): what chains and the rb_*_range_dev entry points
 // need.  A pure query: the row of what is at hand, no build (rb_rollout_dev / rb_step_range_dev / rb_range_capable build first).
 bool range_capable(const rb_sim *s) {
+    if (s->params) return true;                 // the parameter kernels take sub-ranges
     const Row *r = row_for(const_cast<rb_sim *>(s), ENTRY_STEP, /*build=*/false);
     return r && r->ranges;
 }
@@ -799,6 +811,51 @@ int drop_graphs(rb_sim *s) {
     for (auto &kv : s->graphs) kv.second.destroy();
     s->graphs.clear();
     return RB_OK;
+}
+
+// ---- per-env physical parameters (env_params.hpp): what dispatch() launches while they are enabled ----
+template <int INTEG>
+int params_launch_integ(rb_sim *s, int entry, const Launch &L) {
+    constexpr int B = 256;
+    const unsigned blocks = blocks_for(L.cnt, B);
+    float *par = s->d_params + L.i0;
+    if (entry == ENTRY_STEP) {
+        float *q = s->d_q + L.i0, *qd = s->d_qd + L.i0;
+        uint32_t *feas = s->d_feas + L.i0;
+        const float *act = L.act + size_t(L.i0) * s->n_t;
+        if (s->ntx)
+            hipLaunchKernelGGL((rbp::msj_params_step_nt<INTEG, B>), dim3(blocks), dim3(B), 0, L.stream, s->cx, q, qd, feas, act, L.act_scale, par, s->n, L.cnt);
+        else if (s->baked)
+            hipLaunchKernelGGL((rbp::msj_params_step<INTEG, B, true>), dim3(blocks), dim3(B), 0, L.stream, s->c8, q, qd, feas, act, scale8(s, L.act_scale), par, s->n, L.cnt);
+        else
+            hipLaunchKernelGGL((rbp::msj_params_step<INTEG, B, false>), dim3(blocks), dim3(B), 0, L.stream, s->c8, q, qd, feas, act, scale8(s, L.act_scale), par, s->n, L.cnt);
+        return RB_OK;
+    }
+    if (entry == ENTRY_ENV) {
+        const MsjEnvArgs a = msj_env_args(s, L);
+        const rbp::ParamArgs pa{par, s->d_param_draws + L.i0, s->d_param_ranges, s->n, s->n_params, s->param_resample ? 1 : 0};
+        if (s->ntx)
+            hipLaunchKernelGGL((rbp::msj_params_env_step<INTEG, B, ConstX, false>), dim3(blocks), dim3(B), 0, L.stream, s->cx, a, pa);
+        else if (s->baked)
+            hipLaunchKernelGGL((rbp::msj_params_env_step<INTEG, B, Const8, true>), dim3(blocks), dim3(B), 0, L.stream, s->c8, a, pa);
+        else
+            hipLaunchKernelGGL((rbp::msj_params_env_step<INTEG, B, Const8, false>), dim3(blocks), dim3(B), 0, L.stream, s->c8, a, pa);
+        return RB_OK;
+    }
+    return fail(RB_EUNSUPPORTED, "per-env parameters have no fused-rollout kernel (rb_params_disable first)");
+}
+int params_launch(rb_sim *s, int entry, const Launch &L) {
+    if (L.cnt <= 0) return RB_OK;
+    return s->integrator == RB_EULER ? params_launch_integ<0>(s, entry, L) : params_launch_integ<1>(s, entry, L);
+}
+void params_free(rb_sim *s) {
+    (void)hipFree(s->d_params); (void)hipFree(s->d_param_draws); (void)hipFree(s->d_param_ranges);
+    s->d_params = nullptr; s->d_param_draws = nullptr; s->d_param_ranges = nullptr;
+    s->params = false; s->n_params = 0; s->param_resample = false; s->param_ranges.clear();
+}
+// refusal of the entry points that have no parameter form
+int params_refuse(rb_sim *s, const char *what) {
+    return fail(RB_EUNSUPPORTED, std::string(what) + " has no per-env-parameter form: the handle has parameters enabled (rb_params_disable first)");
 }
 
 }  // namespace
@@ -985,6 +1042,7 @@ void rb_destroy(rb_sim *s) {
     (void)hipFree(s->d_state_rows); (void)hipHostFree(s->h_state_rows);
     (void)hipFree(s->d_goal); (void)hipFree(s->d_ep_ret); (void)hipFree(s->d_ep_sum); (void)hipFree(s->d_ep_cnt);
     (void)hipFree(s->d_step_num); (void)hipFree(s->d_infeas_n); (void)hipFree(s->d_stats);
+    params_free(s);
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1374,6 +1432,7 @@ int rb_rollout_fused_dev(rb_sim *s, const float *d_ring, int ring, int n_steps, 
     if (ring < 1 || n_steps < 0) return fail(RB_EINVAL, "ring must be >= 1 and n_steps >= 0");
     if (reinterpret_cast<uintptr_t>(d_ring) % 16) return fail(RB_EINVAL, "action ring must be 16-byte aligned");
     if (s->tree || s->ntx) return fail(RB_EUNSUPPORTED, "fused rollout is built for 8-tendon ball-joint robots");
+    if (s->params) return params_refuse(s, "the fused rollout (rb_rollout_fused_dev)");
     if (n_steps == 0) return RB_OK;
     const long n = s->n;
     maybe_jit(s);
@@ -1520,6 +1579,7 @@ int rb_step_range_dev(rb_sim *s, int64_t first_env, int64_t n_envs, void *hip_st
 }
 int rb_range_capable(rb_sim *s) {
     if (check(s)) return -1;
+    if (s->params) return 3;                 // the parameter kernels take sub-ranges (step and env step)
     // builds what a launch would build (outside captures), then asks the table: bit 0 = the step's row takes sub-ranges, bit 1 = the env step's
     maybe_jit(s);
     const Row *step = row_for(s, ENTRY_STEP, true), *env = row_for(s, ENTRY_ENV, s->env_ready);
@@ -1572,6 +1632,7 @@ int rb_env_stats(rb_sim *s, double *stats8, int reset) {
 namespace {
 int tendon_state_check(rb_sim *s, const float *act, int mode, float act_scale) {
     if (check(s)) return RB_EINVAL;
+    if (s->params) return params_refuse(s, "the tendon-state readout (rb_tendon_state_dev)");
     if (mode != RB_SP_SCALED && mode != RB_SP_ENV) return fail(RB_EINVAL, "unknown set-point mode (RB_SP_SCALED or RB_SP_ENV)");
     if (mode == RB_SP_ENV && !s->env_ready) return fail(RB_EINVAL, "RB_SP_ENV needs the env layer's action box: call rb_env_configure first");
     if (mode == RB_SP_SCALED && act && !(act_scale > 0.0f)) return fail(RB_EINVAL, "act_scale must be > 0 under RB_SP_SCALED");
@@ -1664,12 +1725,99 @@ int rb_dispatch_current(rb_sim *s, int entry, rb_dispatch_row *out) {
     if (check(s) || !out) return fail(RB_EINVAL, "null argument");
     if (entry < ENTRY_STEP || entry > ENTRY_FUSED) return fail(RB_EINVAL, "unknown entry kind");
     if (entry == ENTRY_FUSED && (s->tree || s->ntx)) return fail(RB_EUNSUPPORTED, "fused rollout is built for 8-tendon ball-joint robots");
+    if (s->params) return fail(RB_EUNSUPPORTED, "per-env parameters are enabled: the parameter kernels (env_params.hpp) are not rows of the dispatch table");
     RB_HIP(hipSetDevice(s->device));
     if (entry != ENTRY_ENV || s->env_ready) maybe_jit(s);
     std::string why;
     const Row *r = row_for(s, entry, /*build=*/entry != ENTRY_ENV || s->env_ready, &why);
     if (!r) return fail(RB_EUNSUPPORTED, why);
     *out = public_row(*r);
+    return RB_OK;
+}
+
+// ---- per-env physical parameters (env_params.hpp) ----
+int rb_params_enable(rb_sim *s, int32_t *n_params) {
+    if (check(s)) return RB_EINVAL;
+    if (s->tree) return fail(RB_EUNSUPPORTED, "per-env parameters are built for ball-joint robots (the closed-form kernels); joint trees have none");
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);                       // nothing in flight may read the planes while they are reset
+    if (rc) return rc;
+    rc = drop_graphs(s);                     // captured graphs hold the nominal kernels' nodes
+    if (rc) return rc;
+    const int nt = s->n_t, P = rbp::n_params(nt);
+    const size_t n = size_t(s->n);
+    if (!s->d_params) {
+        hipError_t e = hipMalloc(&s->d_params, sizeof(float) * size_t(P) * n);
+        if (e == hipSuccess) e = hipMalloc(&s->d_param_draws, sizeof(uint32_t) * n);
+        if (e == hipSuccess) e = hipMalloc(&s->d_param_ranges, sizeof(float) * 2 * size_t(P));
+        if (e != hipSuccess) {
+            params_free(s);
+            return fail(e == hipErrorOutOfMemory ? RB_ENOMEM : RB_EHIP, std::string("parameter planes: ") + hipGetErrorString(e));
+        }
+    }
+    // nominal values: force scales 1, offsets 0, mass scale 1, damping scales 1; counters 0; ranges lo = hi = nominal, no redraw
+    uint32_t one, zero = 0u;
+    const float onef = 1.0f;
+    std::memcpy(&one, &onef, 4);
+    RB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->d_params), int(one), size_t(nt) * n, s->stream));
+    RB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->d_params + size_t(nt) * n), int(zero), size_t(nt) * n, s->stream));
+    RB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->d_params + size_t(2 * nt) * n), int(one), 4 * n, s->stream));
+    RB_HIP(hipMemsetAsync(s->d_param_draws, 0, sizeof(uint32_t) * n, s->stream));
+    s->param_ranges.assign(2 * size_t(P), 1.0f);
+    for (int k = 0; k < nt; ++k) s->param_ranges[nt + k] = s->param_ranges[P + nt + k] = 0.0f;
+    RB_HIP(hipMemcpyAsync(s->d_param_ranges, s->param_ranges.data(), sizeof(float) * 2 * size_t(P), hipMemcpyHostToDevice, s->stream));
+    RB_HIP(hipStreamSynchronize(s->stream));
+    s->n_params = P;
+    s->param_resample = false;
+    s->params = true;
+    if (n_params) *n_params = P;
+    return RB_OK;
+}
+int rb_params_disable(rb_sim *s) {
+    if (check(s)) return RB_EINVAL;
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);
+    if (rc) return rc;
+    rc = drop_graphs(s);                     // captured graphs hold the parameter kernels' nodes
+    if (rc) return rc;
+    params_free(s);
+    return RB_OK;
+}
+int rb_params_ptr(rb_sim *s, float **d_params, uint32_t **d_draws) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->params) return fail(RB_EINVAL, "per-env parameters are not enabled (rb_params_enable)");
+    if (d_params) *d_params = s->d_params;
+    if (d_draws) *d_draws = s->d_param_draws;
+    return RB_OK;
+}
+int rb_params_set_ranges(rb_sim *s, const float *lo, const float *hi, int resample_on_reset) {
+    if (check(s) || !lo || !hi) return fail(RB_EINVAL, "null argument");
+    if (!s->params) return fail(RB_EINVAL, "per-env parameters are not enabled (rb_params_enable)");
+    const int nt = s->n_t, P = s->n_params;
+    for (int p = 0; p < P; ++p) {
+        const std::string at = "parameter " + std::to_string(p) + ": ";
+        if (!std::isfinite(lo[p]) || !std::isfinite(hi[p])) return fail(RB_EINVAL, at + "range bounds must be finite");
+        if (lo[p] > hi[p]) return fail(RB_EINVAL, at + "lo > hi");
+        if (p == 2 * nt && !(lo[p] > 0.0f)) return fail(RB_EINVAL, at + "mass_scale must stay > 0");
+        if ((p < nt || p > 2 * nt) && lo[p] < 0.0f) return fail(RB_EINVAL, at + "force_scale and damping_scale must stay >= 0");
+    }
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);                       // (a kernel in flight may be reading the ranges)
+    if (rc) return rc;
+    s->param_ranges.assign(lo, lo + P);
+    s->param_ranges.insert(s->param_ranges.end(), hi, hi + P);
+    RB_HIP(hipMemcpyAsync(s->d_param_ranges, s->param_ranges.data(), sizeof(float) * 2 * size_t(P), hipMemcpyHostToDevice, s->stream));
+    RB_HIP(hipStreamSynchronize(s->stream));
+    s->param_resample = resample_on_reset != 0;
+    return RB_OK;
+}
+int rb_params_sample_dev(rb_sim *s, const uint8_t *d_mask) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->params) return fail(RB_EINVAL, "per-env parameters are not enabled (rb_params_enable)");
+    RB_HIP(hipSetDevice(s->device));
+    hipLaunchKernelGGL(rbp::params_sample, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->d_params, s->d_param_draws, s->d_param_ranges,
+                       d_mask, s->n_params, s->n, s->seed, uint64_t(s->env0));
+    RB_HIP(hipGetLastError());
     return RB_OK;
 }
 

@@ -15,6 +15,7 @@ import numpy as np
 from ... import _native as nat
 from ..robots import RobotState, RoboyRobot
 from .simulation_client import SimulationClient
+from .. import params as envparams
 
 TENDON_STATE_KEYS = ("length", "rate", "activation", "force")
 
@@ -41,6 +42,8 @@ class HipBatchSimulation:
         self.step_size = float(step_size)
         self._owned = []
         self._stream = None            # what set_stream last handed to the library (None: the handle's own stream)
+        self.n_params = 0              # P while per-env parameters are enabled
+        self._d_param_mask = None      # sample_params(mask): device copy of the mask (first use)
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -165,6 +168,74 @@ class HipBatchSimulation:
         goals = np.empty((self.n_envs, self.n_q), np.float32)
         nat.check(self._lib.rb_sample_goals(self._h, nat.u8ptr(m), nat.fptr(goals)))
         return goals
+
+    # -- per-env physical parameters (rb_params_*; ball-joint robots) -----
+    def enable_params(self) -> int:
+        """Give every env its own force scales, set-point offsets, mass scale and damping scales, all nominal; returns P.  The step
+        and env-step entries then launch the parameter kernels.  Calling it again resets planes, draw counters and ranges."""
+        p = ctypes.c_int32()
+        nat.check(self._lib.rb_params_enable(self._h, ctypes.byref(p)))
+        self.n_params = int(p.value)
+        return self.n_params
+
+    def disable_params(self):
+        nat.check(self._lib.rb_params_disable(self._h))
+        self.n_params = 0
+
+    def params_ptr(self):
+        """(device planes [P][N] float32, device draw counters [N] uint32)"""
+        d_p, d_d = ctypes.c_void_p(), ctypes.c_void_p()
+        nat.check(self._lib.rb_params_ptr(self._h, ctypes.byref(d_p), ctypes.byref(d_d)))
+        return d_p.value, d_d.value
+
+    def get_param_planes(self) -> np.ndarray:
+        d_p, _ = self.params_ptr()
+        return self.download(d_p, (self.n_params, self.n_envs))
+
+    def get_param_draws(self) -> np.ndarray:
+        _, d_d = self.params_ptr()
+        return self.download(d_d, (self.n_envs,), np.uint32)
+
+    def get_params(self) -> dict:
+        """{'force_scale': [N, n_t], 'setpoint_offset': [N, n_t], 'mass_scale': [N], 'damping_scale': [N, 3]} (numpy)"""
+        return envparams.planes_to_dict(self.get_param_planes(), self.n_t)
+
+    def set_params(self, **partial):
+        """Overwrite some parameters of every env: ``set_params(mass_scale=m[N], force_scale=f[N, n_t])``; a scalar or a per-tendon /
+        per-joint row broadcasts over the envs."""
+        unknown = set(partial) - set(envparams.NAMES)
+        if unknown:
+            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
+        planes = self.get_param_planes()
+        sl, w = envparams.plane_slices(self.n_t), envparams.widths(self.n_t)
+        for name, v in partial.items():
+            v = np.asarray(v, dtype=np.float32)
+            if name == "mass_scale" and v.ndim == 1:
+                v = v[:, None]                    # [N] -> [N, 1]
+            v = np.broadcast_to(v, (self.n_envs, w[name]))
+            planes[sl[name]] = v.T
+        d_p, _ = self.params_ptr()
+        self.upload(d_p, np.ascontiguousarray(planes))
+
+    def set_param_ranges(self, ranges, resample_on_reset: bool = True):
+        """``ranges``: an ``envs.params.ParamRanges``; ``resample_on_reset``: the fused env step redraws an env's parameters when it
+        auto-resets."""
+        lo, hi = ranges.to_arrays(self.n_t)
+        nat.check(self._lib.rb_params_set_ranges(self._h, nat.fptr(lo), nat.fptr(hi), int(bool(resample_on_reset))))
+
+    def sample_params(self, mask=None):
+        """Redraw the parameters of the masked envs (``mask`` [N] bool, None = all) from the ranges; synchronous."""
+        if mask is None:
+            nat.check(self._lib.rb_params_sample_dev(self._h, None))
+        else:
+            m = np.ascontiguousarray(mask, dtype=np.uint8)
+            if m.shape != (self.n_envs,):
+                raise ValueError("mask must have shape (%d,)" % self.n_envs)
+            if self._d_param_mask is None:
+                self._d_param_mask = self.malloc(self.n_envs)
+            self.upload(self._d_param_mask, m)
+            nat.check(self._lib.rb_params_sample_dev(self._h, ctypes.c_void_p(self._d_param_mask)))
+        self.synchronize()
 
     # -- device-pointer interface (no host copies) ------------------------
     def state_ptrs(self):

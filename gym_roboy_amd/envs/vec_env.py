@@ -34,7 +34,10 @@ class RoboyVecEnv:
                  joint_vel_penalty: bool = False,
                  is_agent_getting_bonus_for_reaching_goal: bool = True,
                  auto_reset: bool = True, integrator="euler", n_substeps: int = 1,
-                 device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400):
+                 device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
+                 randomization=None):
+        """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
+        ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself."""
         self.robot = robot
         self.num_envs = int(num_envs)
         self.sim = HipBatchSimulation(robot, num_envs, integrator=integrator, n_substeps=n_substeps,
@@ -77,9 +80,16 @@ class RoboyVecEnv:
         self._seed = int(seed)
         self._replayed_env_steps = 0.0
         self._stream = None            # the simulation's own stream
+        self.randomization = randomization
+        if randomization is not None:
+            # before anything is captured into a graph: the parameter kernels replace the handle's step kernels from here on
+            self.sim.enable_params()
+            self.sim.set_param_ranges(randomization, resample_on_reset=True)
 
     # ------------------------------------------------------------------
     def reset(self):
+        if self.randomization is not None:
+            self.sim.sample_params()
         nat.check(self.sim._lib.rb_env_reset_dev(self.sim.handle, ctypes.c_void_p(self._d_obs)))
         self.sim.synchronize()
         return self.sim.download(self._d_obs, (self.num_envs, 3 * self.n_q))
@@ -226,6 +236,12 @@ class RoboyVecEnv:
 
     def stats_dev(self, d_out8: int, reset: bool = False):
         nat.check(self.sim._lib.rb_env_stats_dev(self.sim.handle, ctypes.c_void_p(d_out8), int(reset)))
+
+    def get_params(self) -> dict:
+        """Every env's physical parameters (``HipBatchSimulation.get_params``); needs ``randomization``."""
+        if self.randomization is None:
+            raise RuntimeError("this RoboyVecEnv has no per-env parameters (randomization=None)")
+        return self.sim.get_params()
 
     def close(self):
         self.sim.close()

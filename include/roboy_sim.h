@@ -302,6 +302,39 @@ int rb_tendon_state_dev(rb_sim *sim, const float *d_act, int sp_mode, float act_
 int rb_tendon_state(rb_sim *sim, const float *act, int sp_mode, float act_scale,
                     float *length, float *rate, float *activation, float *force);
 
+/* ---- per-env parameters (ABI 6, additive) ----
+ * Ball-joint robots (1..16 tendons) only; a joint tree is refused with RB_EUNSUPPORTED.  Per env, fp32, struct-of-arrays planes
+ * [P][n_envs] with P = 2 n_t + 4, in this order:
+ *   planes 0 .. n_t-1          force_scale[k]      multiplies tendon k's f_max (the passive term too: F = f_max (a f_L f_V + f_PE))   nominal 1
+ *   planes n_t .. 2 n_t-1      setpoint_offset[k]  m, added to tendon k's set-point after the step's own rescale                    nominal 0
+ *   plane  2 n_t               mass_scale          multiplies every link's mass and inertia (I_O and m c; not the armature)           nominal 1
+ *   planes 2 n_t+1 .. 2 n_t+3  damping_scale[j]    multiplies joint j's viscous damping                                               nominal 1
+ * Env i with parameters p steps like the robot whose description has f_max[k] *= force_scale[k], every link's mass and inertia
+ * *= mass_scale, damping[j] *= damping_scale[j], on the set-points sp + setpoint_offset.
+ * While enabled, the step entries (rb_step, rb_step_dev, rb_step_range_dev, rb_rollout_dev) and the env-step entries
+ * (rb_env_step_dev, rb_env_step_range_dev) launch the parameter kernels, one env per lane, whatever rb_select_kernel chose; the
+ * fused rollout, the tendon-state readout and rb_dispatch_current are refused with RB_EUNSUPPORTED.  Enabling and disabling evict the
+ * handle's cached rollout graphs.
+ * Redraws: Philox4x32-10 stream 3.  Draw d of the env with global id g takes, for block b = 0 .. ceil(P/4)-1, the words of the
+ * generator at counter (g low, g high, d, 3 << 8 | b) and key (seed low, seed high); parameter p takes word p mod 4 of block p / 4
+ * and becomes lo_p + (hi_p - lo_p) * u01(word) with two roundings.  d is the env's draw counter, which each draw advances by one;
+ * the values do not depend on how the batch is sharded (env_id_offset).  The fused env step redraws an env's parameters on done
+ * with auto_reset when the ranges were set with resample_on_reset, where it redraws the goal: the step that ended the episode used
+ * the old parameters, the first step of the new episode uses the new ones.
+ *   enable:      allocates the planes and a uint32 draw-counter plane [n_envs], fills them with the nominal values and zero counts,
+ *                sets the ranges to lo = hi = nominal without redraw on reset; writes P to *n_params unless NULL.  Calling it
+ *                again resets planes, counters and ranges.
+ *   disable:     frees them; the handle steps with its usual kernels again.
+ *   ptr:         the device planes and counters (the caller may write the planes; asynchronous users order on the handle's stream).
+ *   set_ranges:  host arrays lo[P], hi[P]; RB_EINVAL for a bound that is not finite, lo > hi, a mass_scale lo <= 0, a force_scale
+ *                or damping_scale lo < 0.
+ *   sample_dev:  redraws the envs with d_mask[i] != 0 (d_mask: device [n_envs], NULL = all), asynchronous on the handle's stream. */
+int rb_params_enable(rb_sim *sim, int32_t *n_params);
+int rb_params_disable(rb_sim *sim);
+int rb_params_ptr(rb_sim *sim, float **d_params, uint32_t **d_draws);
+int rb_params_set_ranges(rb_sim *sim, const float *lo, const float *hi, int resample_on_reset);
+int rb_params_sample_dev(rb_sim *sim, const uint8_t *d_mask);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
