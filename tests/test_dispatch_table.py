@@ -172,6 +172,34 @@ def test_the_golden_env_tests_name_every_form_the_env_step_of_a_mirror_robot_tak
     assert set(g.ENV_FORMS) == {r.kernel for r in ROWS if r.robot_class == BALL8 and r.entry == ENV}
 
 
+def test_every_env_step_row_and_parameter_env_kernel_runs_the_reference_vectors_or_is_exempt_for_a_stated_reason():
+    """tests/test_env_golden_forms_gpu.py runs the reference's vectors through env-step rows BY ROW ID: with its exemptions, they
+    must be exactly the table's env-step rows (a new row without the reference's vectors fails here), and its list of the
+    per-env-parameter env kernels with their exemption must be exactly the instances in the library's code object."""
+    import re
+    import test_env_golden_forms_gpu as g
+    from test_code_objects import LIB, com
+    env_rows = {r.row_id() for r in ROWS if r.entry == ENV}
+    golden, exempt = set(g.GOLDEN_ENV_ROWS), set(g.EXEMPT)
+    assert len(golden) == len(g.GOLDEN_ENV_ROWS) and not golden & exempt
+    assert golden | exempt == env_rows, (sorted(env_rows - golden - exempt), sorted((golden | exempt) - env_rows))
+    assert set(g.EXEMPT.values()) <= {g.NOT_PARKABLE, g.NO_WIDE_LEVEL}
+    assert g.NOT_PARKABLE == "table constants (baked MsjRobot / upper body: not parkable)"
+    assert g.NO_WIDE_LEVEL == "octet variant a 3-joint robot cannot reach"
+    by_id = {r.row_id(): r for r in ROWS}
+    for rid, why in g.EXEMPT.items():
+        r = by_id[rid]
+        if why == g.NOT_PARKABLE:
+            assert nat.CONSTANTS_NAMES[r.constants] == "table", rid
+        else:
+            assert r.robot_class == TREE and nat.KERNEL_NAMES[r.kernel] == "env_per_wave" and r.variant == 0, rid
+    instances = {com.short(k) for k in com.kernel_metadata(LIB)}
+    instances = {k for k in instances if re.match(r"^rbp::msj_params_env_step<", k)}
+    assert set(g.GOLDEN_PARAM_INSTANCES) | set(g.PARAM_EXEMPT) == instances and not set(g.GOLDEN_PARAM_INSTANCES) & set(g.PARAM_EXEMPT)
+    for name in g.PARAM_EXEMPT:
+        assert re.search(r"MsjConst<float, 8>, true>$", name), name          # the baked instance only
+
+
 # ------------------------------------------------------------------------------------------------------------------ GPU
 def _tolerance(desc, q, qd, sp):
     if desc.n_q == 3:

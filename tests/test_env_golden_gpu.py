@@ -43,25 +43,72 @@ def pin_form(vec, form):
     return row
 
 
-def parked_robot(limits=None):
-    """MsjRobot boxes (what the env layer reads) over a description that does not
-    accelerate: per-joint limits default to wider than the +-pi angle box."""
-    spec = msj_platform_spec()
+def _parked(spec, limits):
+    """The description of spec made to park (see the module docstring): per-joint limits default to wider than the +-pi angle
+    box."""
     spec["gravity"] = [0.0, 0.0, 0.0]
     for k, j in enumerate(spec["joints"]):
         j["armature"] = 1.0e9
         j["damping"] = 0.0
         j["max_velocity"] = 10.0
         j["limit"] = [-3.3, 3.3] if limits is None else list(limits[k])
+    strongest = max(t["f_max"] for t in spec["tendons"])
     for t in spec["tendons"]:
-        t["f_max"] = 1.0e-6
-    desc = RobotDescription(spec)
+        t["f_max"] = 1.0e-6 * t["f_max"] / strongest       # (in proportion: the muscles keep the robot's mirror planes)
+    return RobotDescription(spec)
 
+
+def _msj_boxes(desc):
+    """MsjRobot's boxes (what the env layer reads) over another description."""
     class ParkedMsjRobot(MsjRobot):
         @classmethod
         def get_description(cls):
             return desc
     return ParkedMsjRobot()
+
+
+def parked_robot(limits=None, turned=False):
+    """MsjRobot boxes over a description of the MSJ platform that does not accelerate.  turned: the platform turned by 90
+    degrees about z ((x, y) -> (-y, x)), whose mirror plane is the y-z plane (the two-lanes-per-env form's variant 1)."""
+    spec = msj_platform_spec()
+    if turned:
+        for t in spec["tendons"]:
+            for v in t["via_points"]:
+                x, y, z = v["pos"]
+                v["pos"] = [-y, x, z]
+    return _msj_boxes(_parked(spec, limits))
+
+
+def parked_ball_robot(n_t, limits=None):
+    """The parked MSJ platform with its first n_t tendons only: a ball-joint robot of the run-time tendon count class (ballx,
+    msj_env_step_kernel<..., ConstX>) for n_t != 8."""
+    spec = msj_platform_spec()
+    spec["tendons"] = spec["tendons"][:n_t]
+    return _msj_boxes(_parked(spec, limits))
+
+
+TREE_AXES = ([1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0])
+
+
+def parked_tree_robot(limits=None):
+    """A joint tree that does not accelerate: three revolute joints, each a root of its own (a forest), joint j turning about
+    axis j, with one rigid link each and two tendons from the base to that joint's link - no tendon ties two roots together, so
+    the split forms put every joint into a part of its own.  MsjRobot's boxes over it (three joints), so the env layer reads
+    what the reference's rows were recorded with."""
+    from gym_roboy_amd.envs.robots.description import FORMAT_TAG
+    spec = msj_platform_spec()
+    joints, tendons = [], []
+    for j in range(3):
+        origin = [0.2 * (j - 1), 0.0, 0.0]
+        joints.append({"name": "root%d" % j, "parent": -1, "axis": TREE_AXES[j], "origin": origin, "mass": 0.2,
+                       "com": [0.01, 0.02, 0.05], "inertia": [3e-4, 4e-4, 5e-4, 0.0, 0.0, 0.0]})
+        for side in (1.0, -1.0):
+            tendons.append({"name": "t%d%s" % (j, "ab"[side < 0]), "f_max": 1.0,
+                            "via_points": [{"link": -1, "pos": [origin[0] + 0.06 * side, 0.05 * side, -0.1]},
+                                           {"link": j, "pos": [0.03 * side, 0.04, 0.08]}]})
+    spec = {"format": FORMAT_TAG, "name": "parked_forest", "gravity": spec["gravity"], "joints": joints, "tendons": tendons,
+            "muscle": spec["muscle"]}
+    return _msj_boxes(_parked(spec, limits))
 
 
 def pre_state(q, qd):
@@ -70,16 +117,17 @@ def pre_state(q, qd):
     return (np.asarray(q, np.float64) - H * qd32.astype(np.float64)).astype(np.float32), qd32
 
 
-def limits_hitting(q, qd):
+def limits_hitting(q, qd, j=None):
     """Joint limits and a start state such that the parked step clamps one joint exactly onto
     its recorded angle without touching its velocity, and flags the env infeasible.  limit()
     clamps to the bound and drops only the OUTWARD velocity component, and a description's
     limits must bracket the zero pose, so the joint j used is one whose recorded angle and
     velocity have opposite signs (upper bound = q[j] > 0 approached from above with v <= 0, or
-    lower bound = q[j] < 0 approached from below with v >= 0).  Returns None if no joint qualifies."""
+    lower bound = q[j] < 0 approached from below with v >= 0).  j=None: the first joint that
+    qualifies.  Returns (limits, q_pre, qd, j), or None if no joint (or joint j) qualifies."""
     q32 = np.asarray(q, np.float32).astype(np.float64)
     q_pre, qd32 = pre_state(q, qd)
-    for j in range(3):
+    for j in (range(3) if j is None else [j]):
         lim = [[-3.3, 3.3] for _ in range(3)]
         if q32[j] > 1e-3 and qd32[j] <= 0:
             lim[j][1] = float(q32[j])
@@ -114,6 +162,70 @@ def test_parked_robot_lands_on_the_recorded_state_cpu():
         assert np.abs(qa[0] - q[i].astype(np.float32)).max() < 5e-7
         hit += 1
     assert hit >= 8
+
+
+@pytest.mark.parametrize("robot", ["tree", "ball5", "turned"])
+@pytest.mark.parametrize("integrator", [0, 1])
+def test_parked_tree_and_ball_robots_land_on_the_recorded_state_cpu(robot, integrator):
+    """The construction on the other parked robots (tests/test_env_golden_forms_gpu.py), both integrators: fp32 C oracle."""
+    from oracle.c_oracle import COracle
+    make = {"tree": parked_tree_robot, "ball5": lambda lim=None: parked_ball_robot(5, lim),
+            "turned": lambda lim=None: parked_robot(lim, turned=True)}[robot]
+    rng = np.random.default_rng(1)
+    q = rng.uniform(-3, 3, (32, 3)); qd = rng.uniform(-0.5, 0.5, (32, 3))
+    desc = make().get_description()
+    assert desc.n_q == 3 and desc.n_t == {"tree": 6, "ball5": 5, "turned": 8}[robot]
+    q_pre, qd32 = pre_state(q, qd)
+    q1, qd1, feas = COracle(desc, "f32").step(q_pre, qd32, np.zeros((32, desc.n_t), np.float32), integrator=integrator)
+    assert feas.all() and np.abs(qd1 - qd32).max() < 1e-9
+    assert np.abs(q1 - q.astype(np.float32)).max() < 5e-7
+    hit = set()
+    for i in range(32):
+        for j in range(3):
+            case = limits_hitting(q[i], qd[i], j)
+            if case is None:
+                continue
+            lim, qp, v, jj = case
+            assert jj == j
+            o = COracle(make(lim).get_description(), "f32")
+            qa, va, fa = o.step(qp[None], v[None], np.zeros((1, desc.n_t), np.float32), integrator=integrator)
+            assert not fa[0] and qa[0, j] == np.float32(q[i, j]) and np.abs(va[0] - v).max() < 1e-9
+            assert np.abs(qa[0] - q[i].astype(np.float32)).max() < 5e-7
+            hit.add((i, j))
+    assert len(hit) >= 24 and {j for _, j in hit} == {0, 1, 2}
+
+
+def test_parked_forest_generated_code_and_split_parts_cpu():
+    """parked_tree_robot through the joint-tree generators (g++ builds of the generated text): the one-wave code does not
+    accelerate it, the five-wave split form puts each joint into a part of its own and gives it tendon helpers (the helper-drawn
+    goal path of tree_split_env_step), the lean form two parts {0, 2} and {1} - what tests/test_env_golden_forms_gpu.py
+    (SPLIT_PART_OF_JOINT) counts its infeasible rows by."""
+    import gen_tree_lane_baked as gen
+    from test_env_golden_forms_gpu import SPLIT_PART_OF_JOINT
+    from test_tree_lane_gen import check_split, host_accel, host_split_accel
+    desc = parked_tree_robot().get_description()
+    assert list(desc.parent) == [-1, -1, -1]
+    rng = np.random.default_rng(5)
+    q = rng.uniform(-3, 3, (16, 3)).astype(np.float32); qd = rng.uniform(-0.5, 0.5, (16, 3)).astype(np.float32)
+    sp = rng.uniform(-0.3, 0.3, (16, desc.n_t)).astype(np.float32)
+    accel, _ = host_accel(desc, "parked_forest")
+    assert np.abs(H * accel(q, qd, sp)).max() < 1e-12
+    for form, name, parts in ((0, "env_per_lane_split", 3), (1, "env_per_lane_split2", 2)):
+        max_parts, word = gen.library_split_form(form)
+        split, info = host_split_accel(desc, "parked_forest%d" % form, max_parts, word)
+        qdd, mismatches = split(q, qd, sp)
+        assert mismatches == 0 and np.abs(H * qdd).max() < 1e-12
+        assert info["n_parts"] == parts and tuple(info["part_of_joint"]) == SPLIT_PART_OF_JOINT[name]
+        assert (info["n_helpers"] >= 1) == (form == 0)
+    # (and the split forms on a robot that does accelerate: the same tendon routing at full strength, gravity on)
+    spec = desc.to_dict()
+    for j in spec["joints"]:
+        j["armature"], j["damping"] = 0.05, 0.3
+    for t in spec["tendons"]:
+        t["f_max"] = 10.0
+    spec["gravity"] = [0.0, 0.0, -9.81]
+    live = RobotDescription(spec)
+    assert check_split(live, "live_forest", max_parts=gen.library_split_form(0)[0], max_helpers=gen.library_split_form(0)[1])["n_helpers"] >= 1
 
 
 def _fixture():
