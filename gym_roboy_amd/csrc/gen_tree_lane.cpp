@@ -86,3 +86,22 @@ extern "C" int rb_gen_tree_lane_split_form(int form, int *max_parts, int *max_he
     *max_helpers = f.max_helpers | f.helper_share << 8 | int(f.two_sweeps) << 16 | int(f.share_trunk) << 18;
     return RB_OK;
 }
+
+// what the library hands to hiprtc for the kernel of `kind` (0 = step, 1 = env step; integ: 0 = Euler, 1 = RK4) of generated form
+// `form` (tree_lane_gen.hpp: FORM_LANE, FORM_SPLIT, FORM_SPLIT2) of a robot: writes the source to `path`, the program's name and the
+// kernel's name expression to `program` / `kernel` (buffers of `cap` bytes)
+extern "C" int rb_gen_tree_jit_source(const rb_robot_desc *d, int form, int integ, int kind, const char *path, char *program, char *kernel, int cap) {
+    if (form < 0 || form >= rblg::N_FORMS) return RB_EINVAL;
+    rblg::FormText g;
+    std::string err;
+    if (int rc = rblg::generate_form(d, form, g, err)) { std::fprintf(stderr, "rb_gen_tree_jit_source: %s\n", err.c_str()); return rc; }
+    const rblg::JitSource j = rblg::jit_source(form, g.text, g.lds, integ, kind);
+    if (int(j.program.size()) >= cap || int(j.kernel.size()) >= cap) return RB_EINVAL;
+    FILE *f = std::fopen(path, "w");
+    if (!f) return RB_EINVAL;
+    std::fputs(j.src.c_str(), f);
+    std::fclose(f);
+    std::snprintf(program, size_t(cap), "%s", j.program.c_str());
+    std::snprintf(kernel, size_t(cap), "%s", j.kernel.c_str());
+    return RB_OK;
+}

@@ -17,6 +17,8 @@
 enum : int { CLS_BALL8 = RB_CLASS_BALL8, CLS_BALLX = RB_CLASS_BALLX, CLS_TREE = RB_CLASS_TREE };
 enum : int { ENTRY_STEP = RB_ENTRY_STEP, ENTRY_ENV = RB_ENTRY_ENV_STEP, ENTRY_FUSED = RB_ENTRY_FUSED_ROLLOUT };
 enum : int { SRC_KERNARG = RB_SPEC_NONE, SRC_TABLE = RB_SPEC_TABLE, SRC_JIT = RB_SPEC_JIT };
+constexpr int F_LANE = RB_KERNEL_ENV_PER_LANE, F_OCTET = RB_KERNEL_TENDON_PER_LANE, F_WAVE = RB_KERNEL_ENV_PER_WAVE, F_SPLIT = RB_KERNEL_ENV_PER_LANE_SPLIT,
+              F_PAIR = RB_KERNEL_LANE_PAIR, F_SPLIT2 = RB_KERNEL_ENV_PER_LANE_SPLIT2;
 
 struct Key {
     int cls, entry, form, integ, block, src, variant;
@@ -180,25 +182,6 @@ inline rbe::TreeEnvArgs tree_env_args(rb_sim *s, const Launch &L) {
                             s->d_ep_sum + i0, s->d_ep_cnt + i0, s->d_infeas_n + i0, s->tree_host.dev.h, s->tree_host.dev.nsub, L.cnt,
                             s->seed, uint64_t(s->env0) + uint64_t(i0), s->n};
 }
-// a hiprtc-built joint-tree kernel: step kernels take (q, qd, feas, act, act_scale, h, nsub, n), env kernels one TreeEnvArgs
-inline int launch_tree_module(rb_sim *s, const Launch &L, hipFunction_t fn, bool env, unsigned groups, unsigned threads, size_t lds) {
-    if (env) {
-        rbe::TreeEnvArgs ka = tree_env_args(s, L);
-        void *args[] = {&ka};
-        RB_HIP(hipModuleLaunchKernel(fn, groups, 1, 1, threads, 1, 1, unsigned(lds), L.stream, args, nullptr));
-    } else {
-        float *q = s->d_q + size_t(L.i0) * s->n_q, *qd = s->d_qd + size_t(L.i0) * s->n_q;
-        uint32_t *feas = s->d_feas + L.i0;
-        const float *act = L.act + size_t(L.i0) * s->n_t;
-        float scale = L.act_scale, hh = s->tree_host.dev.h;
-        int ns = s->tree_host.dev.nsub;
-        long nn = L.cnt;
-        void *args[] = {&q, &qd, &feas, &act, &scale, &hh, &ns, &nn};
-        RB_HIP(hipModuleLaunchKernel(fn, groups, 1, 1, threads, 1, 1, unsigned(lds), L.stream, args, nullptr));
-    }
-    return RB_OK;
-}
-
 // octets of lanes per link, robot tables staged in LDS (robots without generated code)
 template <int INTEG, bool SP, bool ENV>
 int l_tree_aba(rb_sim *s, const Launch &L) {
@@ -219,7 +202,7 @@ int l_tree_aba(rb_sim *s, const Launch &L) {
 template <int INTEG, bool ENV>
 int l_tree_lane(rb_sim *s, const Launch &L) {
     const unsigned waves = blocks_for(L.cnt, 64);
-    const size_t lds = rblg::lane_lds_bytes_per_wave(s->lane_gen);
+    const size_t lds = s->form(F_LANE).gen.lds;
     if constexpr (ENV) {
         const rbe::TreeEnvArgs ka = tree_env_args(s, L);
         hipLaunchKernelGGL(rbl_baked::tree_lane_env_step<INTEG>, dim3(waves), dim3(64), lds, L.stream, ka);
@@ -229,28 +212,19 @@ int l_tree_lane(rb_sim *s, const Launch &L) {
     }
     return RB_OK;
 }
-template <bool ENV>
-int l_tree_lane_jit(rb_sim *s, const Launch &L) {
-    return launch_tree_module(s, L, (ENV ? s->lane_env_k : s->lane_step_k).fn, ENV, blocks_for(L.cnt, 64), 64, rblg::lane_lds_bytes_per_wave(s->lane_gen));
-}
 // the split form: one workgroup of n_parts (+ helper) waves per 64 envs (whole batches)
 template <int INTEG, bool ENV>
 int l_tree_split(rb_sim *s, const Launch &L) {
-    const unsigned groups = blocks_for(s->n, 64), threads = 64u * unsigned(s->split_gen.n_parts + s->split_gen.n_helpers);
-    const size_t lds = split_lds_bytes(s->split_gen);
+    const rblg::FormText &g = s->form(F_SPLIT).gen;
+    const unsigned groups = blocks_for(s->n, 64);
     if constexpr (ENV) {
         const rbe::TreeEnvArgs ka = tree_env_args(s, L);
-        hipLaunchKernelGGL(rbl_split_baked::tree_split_env_step<INTEG>, dim3(groups), dim3(threads), lds, L.stream, ka);
+        hipLaunchKernelGGL(rbl_split_baked::tree_split_env_step<INTEG>, dim3(groups), dim3(g.threads), g.lds, L.stream, ka);
     } else {
-        hipLaunchKernelGGL(rbl_split_baked::tree_split_step<INTEG>, dim3(groups), dim3(threads), lds, L.stream, s->d_q, s->d_qd, s->d_feas, L.act, L.act_scale,
+        hipLaunchKernelGGL(rbl_split_baked::tree_split_step<INTEG>, dim3(groups), dim3(g.threads), g.lds, L.stream, s->d_q, s->d_qd, s->d_feas, L.act, L.act_scale,
                            s->tree_host.dev.h, s->tree_host.dev.nsub, s->n);
     }
     return RB_OK;
-}
-template <bool ENV>
-int l_tree_split_jit(rb_sim *s, const Launch &L) {
-    return launch_tree_module(s, L, (ENV ? s->split_env_k : s->split_step_k).fn, ENV, blocks_for(s->n, 64),
-                              64u * unsigned(s->split_gen.n_parts + s->split_gen.n_helpers), split_lds_bytes(s->split_gen));
 }
 // the lean two-part split form: two part waves per 64 envs, two workgroups per CU (whole batches; instances: roboy_sim_split2.hip)
 template <int INTEG, bool ENV>
@@ -259,15 +233,30 @@ int l_tree_split2(rb_sim *s, const Launch &L) {
     else rbs2::launch_step(INTEG, blocks_for(s->n, 64), L.stream, s->d_q, s->d_qd, s->d_feas, L.act, L.act_scale, s->tree_host.dev.h, s->tree_host.dev.nsub, s->n);
     return RB_OK;
 }
-template <bool ENV>
-int l_tree_split2_jit(rb_sim *s, const Launch &L) {
-    return launch_tree_module(s, L, (ENV ? s->split2_env_k : s->split2_step_k).fn, ENV, blocks_for(s->n, 64), 64u * unsigned(s->split2_gen.n_parts),
-                              split_lean_lds_bytes(s->split2_gen));
+// the hiprtc-built kernels of generated form FORM (F_LANE, F_SPLIT, F_SPLIT2), one workgroup per 64 envs (the split forms: whole
+// batches, L.cnt = s->n): step kernels take (q, qd, feas, act, act_scale, h, nsub, n), env kernels one TreeEnvArgs
+template <int FORM, bool ENV>
+int l_tree_jit(rb_sim *s, const Launch &L) {
+    const rblj::TreeForm &f = s->form(FORM);
+    const unsigned groups = blocks_for(L.cnt, 64), threads = f.gen.threads, lds = unsigned(f.gen.lds);
+    if constexpr (ENV) {
+        rbe::TreeEnvArgs ka = tree_env_args(s, L);
+        void *args[] = {&ka};
+        RB_HIP(hipModuleLaunchKernel(f.env.fn, groups, 1, 1, threads, 1, 1, lds, L.stream, args, nullptr));
+    } else {
+        float *q = s->d_q + size_t(L.i0) * s->n_q, *qd = s->d_qd + size_t(L.i0) * s->n_q;
+        uint32_t *feas = s->d_feas + L.i0;
+        const float *act = L.act + size_t(L.i0) * s->n_t;
+        float scale = L.act_scale, hh = s->tree_host.dev.h;
+        int ns = s->tree_host.dev.nsub;
+        long nn = L.cnt;
+        void *args[] = {&q, &qd, &feas, &act, &scale, &hh, &ns, &nn};
+        RB_HIP(hipModuleLaunchKernel(f.step.fn, groups, 1, 1, threads, 1, 1, lds, L.stream, args, nullptr));
+    }
+    return RB_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------- the table
-constexpr int F_LANE = RB_KERNEL_ENV_PER_LANE, F_OCTET = RB_KERNEL_TENDON_PER_LANE, F_WAVE = RB_KERNEL_ENV_PER_WAVE, F_SPLIT = RB_KERNEL_ENV_PER_LANE_SPLIT,
-              F_PAIR = RB_KERNEL_LANE_PAIR, F_SPLIT2 = RB_KERNEL_ENV_PER_LANE_SPLIT2;
 constexpr int EU = RB_EULER, RK = RB_RK4;
 // unroll factors of the large-batch env-per-lane instances (roboy_sim.hip: RB_BIG_UNROLL_*, RB_BAKED_UNROLL_*)
 constexpr int UBE = RB_BAKED_UNROLL_EULER, UBR = RB_BAKED_UNROLL_RK4, UKE = RB_BIG_UNROLL_EULER, UKR = RB_BIG_UNROLL_RK4;
@@ -359,26 +348,26 @@ const Row TABLE[] = {
     {{CLS_TREE, ENTRY_STEP, F_LANE, RK, 64, SRC_TABLE, 0}, true, l_tree_lane<1, false>},
     {{CLS_TREE, ENTRY_ENV, F_LANE, EU, 64, SRC_TABLE, 0}, true, l_tree_lane<0, true>},
     {{CLS_TREE, ENTRY_ENV, F_LANE, RK, 64, SRC_TABLE, 0}, true, l_tree_lane<1, true>},
-    {{CLS_TREE, ENTRY_STEP, F_LANE, EU, 64, SRC_JIT, 0}, true, l_tree_lane_jit<false>},
-    {{CLS_TREE, ENTRY_STEP, F_LANE, RK, 64, SRC_JIT, 0}, true, l_tree_lane_jit<false>},
-    {{CLS_TREE, ENTRY_ENV, F_LANE, EU, 64, SRC_JIT, 0}, true, l_tree_lane_jit<true>},
-    {{CLS_TREE, ENTRY_ENV, F_LANE, RK, 64, SRC_JIT, 0}, true, l_tree_lane_jit<true>},
+    {{CLS_TREE, ENTRY_STEP, F_LANE, EU, 64, SRC_JIT, 0}, true, l_tree_jit<F_LANE, false>},
+    {{CLS_TREE, ENTRY_STEP, F_LANE, RK, 64, SRC_JIT, 0}, true, l_tree_jit<F_LANE, false>},
+    {{CLS_TREE, ENTRY_ENV, F_LANE, EU, 64, SRC_JIT, 0}, true, l_tree_jit<F_LANE, true>},
+    {{CLS_TREE, ENTRY_ENV, F_LANE, RK, 64, SRC_JIT, 0}, true, l_tree_jit<F_LANE, true>},
     {{CLS_TREE, ENTRY_STEP, F_SPLIT, EU, 0, SRC_TABLE, 0}, false, l_tree_split<0, false>},
     {{CLS_TREE, ENTRY_STEP, F_SPLIT, RK, 0, SRC_TABLE, 0}, false, l_tree_split<1, false>},
     {{CLS_TREE, ENTRY_ENV, F_SPLIT, EU, 0, SRC_TABLE, 0}, false, l_tree_split<0, true>},
     {{CLS_TREE, ENTRY_ENV, F_SPLIT, RK, 0, SRC_TABLE, 0}, false, l_tree_split<1, true>},
-    {{CLS_TREE, ENTRY_STEP, F_SPLIT, EU, 0, SRC_JIT, 0}, false, l_tree_split_jit<false>},
-    {{CLS_TREE, ENTRY_STEP, F_SPLIT, RK, 0, SRC_JIT, 0}, false, l_tree_split_jit<false>},
-    {{CLS_TREE, ENTRY_ENV, F_SPLIT, EU, 0, SRC_JIT, 0}, false, l_tree_split_jit<true>},
-    {{CLS_TREE, ENTRY_ENV, F_SPLIT, RK, 0, SRC_JIT, 0}, false, l_tree_split_jit<true>},
+    {{CLS_TREE, ENTRY_STEP, F_SPLIT, EU, 0, SRC_JIT, 0}, false, l_tree_jit<F_SPLIT, false>},
+    {{CLS_TREE, ENTRY_STEP, F_SPLIT, RK, 0, SRC_JIT, 0}, false, l_tree_jit<F_SPLIT, false>},
+    {{CLS_TREE, ENTRY_ENV, F_SPLIT, EU, 0, SRC_JIT, 0}, false, l_tree_jit<F_SPLIT, true>},
+    {{CLS_TREE, ENTRY_ENV, F_SPLIT, RK, 0, SRC_JIT, 0}, false, l_tree_jit<F_SPLIT, true>},
     {{CLS_TREE, ENTRY_STEP, F_SPLIT2, EU, 0, SRC_TABLE, 0}, false, l_tree_split2<0, false>},
     {{CLS_TREE, ENTRY_STEP, F_SPLIT2, RK, 0, SRC_TABLE, 0}, false, l_tree_split2<1, false>},
     {{CLS_TREE, ENTRY_ENV, F_SPLIT2, EU, 0, SRC_TABLE, 0}, false, l_tree_split2<0, true>},
     {{CLS_TREE, ENTRY_ENV, F_SPLIT2, RK, 0, SRC_TABLE, 0}, false, l_tree_split2<1, true>},
-    {{CLS_TREE, ENTRY_STEP, F_SPLIT2, EU, 0, SRC_JIT, 0}, false, l_tree_split2_jit<false>},
-    {{CLS_TREE, ENTRY_STEP, F_SPLIT2, RK, 0, SRC_JIT, 0}, false, l_tree_split2_jit<false>},
-    {{CLS_TREE, ENTRY_ENV, F_SPLIT2, EU, 0, SRC_JIT, 0}, false, l_tree_split2_jit<true>},
-    {{CLS_TREE, ENTRY_ENV, F_SPLIT2, RK, 0, SRC_JIT, 0}, false, l_tree_split2_jit<true>},
+    {{CLS_TREE, ENTRY_STEP, F_SPLIT2, EU, 0, SRC_JIT, 0}, false, l_tree_jit<F_SPLIT2, false>},
+    {{CLS_TREE, ENTRY_STEP, F_SPLIT2, RK, 0, SRC_JIT, 0}, false, l_tree_jit<F_SPLIT2, false>},
+    {{CLS_TREE, ENTRY_ENV, F_SPLIT2, EU, 0, SRC_JIT, 0}, false, l_tree_jit<F_SPLIT2, true>},
+    {{CLS_TREE, ENTRY_ENV, F_SPLIT2, RK, 0, SRC_JIT, 0}, false, l_tree_jit<F_SPLIT2, true>},
 };
 constexpr int N_ROWS = int(sizeof(TABLE) / sizeof(TABLE[0]));
 
@@ -430,8 +419,8 @@ inline int robot_class(const rb_sim *s) { return s->tree ? CLS_TREE : (s->ntx ? 
 inline int abilities(const rb_sim *s) {
     int a = 0;
     if (!s->tree && !s->ntx) a |= s->pair_ok ? NEED_MIRROR : NEED_NO_MIRROR;
-    if (s->tree && s->split_ok && s->split_baked) a |= NEED_SPLIT_TABLE;
-    if (s->tree && s->split2_ok && s->split2_baked) a |= NEED_SPLIT2_TABLE;
+    if (s->tree && s->form(F_SPLIT).baked) a |= NEED_SPLIT_TABLE;
+    if (s->tree && s->form(F_SPLIT2).baked) a |= NEED_SPLIT2_TABLE;
     if (s->tree && tree_wants_lane_auto(s)) a |= NEED_LANE;
     return a;
 }
@@ -457,26 +446,14 @@ inline int resolve_form(rb_sim *s, int entry, bool build, std::string *why) {
         if (entry == ENTRY_STEP) return s->kernel;                       // rb_select_kernel keeps it: the choice, or AUTO's for the plain step
         return s->kernel_choice != RB_KERNEL_AUTO ? s->kernel_choice : auto_form(s, ENTRY_ENV);
     }
-    int form = s->kernel_choice != RB_KERNEL_AUTO ? s->kernel_choice : auto_form(s, entry);
-    if (form == F_SPLIT2) {
-        if (s->split2_baked) return F_SPLIT2;
-        rblj::Kernel &k = kind ? s->split2_env_k : s->split2_step_k;
-        if (k.state == 1 || (build && build_split_kernel(s, true, kind))) return F_SPLIT2;
-        if (why) *why = "lean split kernel not available: " + k.why;
-        return -1;                                                       // an explicit choice that cannot be served is an error, not a fallback
+    const int form = s->kernel_choice != RB_KERNEL_AUTO ? s->kernel_choice : auto_form(s, entry);
+    if (form == F_WAVE) return F_WAVE;
+    if (tree_form_ready(s, form, kind, build)) return form;
+    if (form == F_SPLIT2) {                                              // an explicit choice that cannot be served is an error, not a fallback
+        if (why) *why = "lean split kernel not available: " + s->form(F_SPLIT2).kernel(kind).why;
+        return -1;
     }
-    if (form == F_SPLIT) {
-        if (s->split_baked) return F_SPLIT;
-        rblj::Kernel &k = kind ? s->split_env_k : s->split_step_k;
-        // (the plain step's kernel is built by rb_select_kernel; the env step's by rb_env_configure or here)
-        if (k.state == 1 || (build && kind == 1 && build_split_kernel(s, false, 1))) return F_SPLIT;
-        form = tree_wants_lane(s) ? F_LANE : F_WAVE;
-    }
-    if (form == F_LANE) {
-        if (s->lane_baked) return F_LANE;
-        if (tree_wants_lane(s) && (build ? lane_kernel(s, kind) : (kind ? &s->lane_env_k : &s->lane_step_k))->state == 1) return F_LANE;
-        return F_WAVE;
-    }
+    if (form == F_SPLIT && tree_wants_lane(s) && tree_form_ready(s, F_LANE, kind, build)) return F_LANE;
     return F_WAVE;
 }
 
@@ -486,8 +463,7 @@ inline bool resolve(rb_sim *s, int entry, bool build, Key &k, std::string *why =
     k = Key{robot_class(s), entry, form, s->integrator == RB_EULER ? EU : RK, 0, SRC_KERNARG, 0};
     if (s->tree) {
         if (form == F_WAVE) { k.variant = s->tree_host.dev.single_pass != 0 ? 1 : 0; return true; }
-        const bool table = form == F_LANE ? s->lane_baked : (form == F_SPLIT ? s->split_baked : s->split2_baked);
-        k.src = table ? SRC_TABLE : SRC_JIT;
+        k.src = s->form(form).baked ? SRC_TABLE : SRC_JIT;
         k.block = form == F_LANE ? 64 : 0;
         return true;
     }

@@ -465,21 +465,15 @@ struct rb_sim {
     rbt::TreeHost tree_host;
     uint32_t *d_tree_words = nullptr;   // the robot tables, staged into LDS by every workgroup
     int tree_waves = 1;                 // waves per workgroup
-    // env-per-lane form of the joint-tree kernels (tree_lane.hpp): the text generated for this robot, whether it is
-    // the text the library's ahead-of-time instances were compiled from, and the hiprtc-built kernels otherwise
-    rblg::Generated lane_gen;
-    bool lane_ok = false;               // lane_gen is valid (the generator supports the robot)
-    bool lane_baked = false;
-    rblj::Kernel lane_step_k, lane_env_k;
-    // the split form of the same (tree_lane_split.hpp): several waves per group of 64 envs, for small batches
-    rblg::SplitGenerated split_gen;
-    bool split_ok = false, split_baked = false;
-    rblj::Kernel split_step_k, split_env_k;
-    // ... and its lean two-part form (two workgroups per CU): the ahead-of-time instances of roboy_sim_split2.hip for the committed
-    // upper body, hiprtc-built ones for any other robot that has a split plan (on request: rb_select_kernel(6))
-    rblg::SplitGenerated split2_gen;
-    bool split2_ok = false, split2_baked = false;
-    rblj::Kernel split2_step_k, split2_env_k;
+    // the generated forms of the joint-tree kernels (tree_lane_gen.hpp), by rblg::FORM_*: one wave per 64 envs (tree_lane.hpp), and
+    // the split forms (tree_lane_split.hpp: several waves per group of 64 envs, for small batches) - five waves, or the lean two-part
+    // form (two workgroups per CU).  Ahead-of-time instances for the committed upper body, hiprtc-built kernels for any other robot
+    rblj::TreeForm forms[rblg::N_FORMS];
+    static int form_index(int kernel) {      // RB_KERNEL_ENV_PER_LANE, _SPLIT or _SPLIT2
+        return kernel == RB_KERNEL_ENV_PER_LANE_SPLIT ? rblg::FORM_SPLIT : kernel == RB_KERNEL_ENV_PER_LANE_SPLIT2 ? rblg::FORM_SPLIT2 : rblg::FORM_LANE;
+    }
+    rblj::TreeForm &form(int kernel) { return forms[form_index(kernel)]; }
+    const rblj::TreeForm &form(int kernel) const { return forms[form_index(kernel)]; }
     GoalBox box;
     hipStream_t own_stream = nullptr, stream = nullptr;
     static constexpr int MAX_CHAINS = 4;
@@ -564,72 +558,31 @@ int jit_level() {      // ROBOY_SIM_JIT: 0 = never, 1 (default) = from the batch
 
 // AUTO's own condition for the one-wave-per-64-envs form of the joint-tree kernels: instances at hand, or worth building
 bool tree_wants_lane_auto(const rb_sim *s) {
-    if (!s->tree || !s->lane_ok) return false;
-    if (s->lane_baked) return true;
+    const rblj::TreeForm &f = s->form(RB_KERNEL_ENV_PER_LANE);
+    if (!s->tree || !f.ok) return false;
+    if (f.baked) return true;
     const int lvl = jit_level();
-    return s->lane_gen.max_live <= RB_TREE_LANE_MAX_LIVE && (lvl == 2 || (lvl == 1 && s->n >= RB_TREE_JIT_BATCH));
+    return f.gen.max_live <= RB_TREE_LANE_MAX_LIVE && (lvl == 2 || (lvl == 1 && s->n >= RB_TREE_JIT_BATCH));
 }
 // may this handle run that form?  (an explicit choice, AUTO's condition, or as what the split forms degrade to)
 bool tree_wants_lane(const rb_sim *s) {
-    if (!s->tree || !s->lane_ok || s->kernel_choice == RB_KERNEL_ENV_PER_WAVE) return false;
+    if (!s->tree || !s->form(RB_KERNEL_ENV_PER_LANE).ok || s->kernel_choice == RB_KERNEL_ENV_PER_WAVE) return false;
     return s->kernel_choice == RB_KERNEL_ENV_PER_LANE || tree_wants_lane_auto(s);
 }
 
-bool tree_wants_split(const rb_sim *s);      // (defined behind the dispatch table: AUTO's rules decide)
-bool tree_wants_split2(const rb_sim *s);
-// the lean layout's formula (tree_lane_split.hpp, RBL_LEAN): q | qd | goal, the exchange area over the action / observation image, flags
-size_t split_lean_lds_bytes(const rblg::SplitGenerated &g) {
-    const int img = 3 * g.n_q + (3 * g.n_q > g.n_t ? 3 * g.n_q : g.n_t);
-    int shared = g.x_buffers * g.x_slots > img - 3 * g.n_q ? g.x_buffers * g.x_slots : img - 3 * g.n_q;
-    if (shared < 4 * g.n_q) shared = 4 * g.n_q;
-    return size_t(3 * g.n_q + shared + 3 * g.n_parts + 1) * 64 * 4;
-}
-size_t split_lds_bytes(const rblg::SplitGenerated &g) {      // the formula of tree_lane_split.hpp: SP_LDS_BYTES
-    const int img = 3 * g.n_q + (3 * g.n_q > g.n_t ? 3 * g.n_q : g.n_t);
-    return size_t(img + g.x_buffers * g.x_slots + g.n_parts * (g.part_lds + 2 * g.n_q) + 3 * g.n_parts + 1 + (g.n_helpers > 0 ? g.n_q : 0)) * 64 * 4;
-}
-// the hiprtc-built split kernels of a robot without ahead-of-time instances (explicit choice only): the five-wave form, or (lean) the
-// lean two-part form; kind: 0 = step, 1 = env step
-bool build_split_kernel(rb_sim *s, bool lean, int kind) {
-    rblj::Kernel &k = lean ? (kind == 0 ? s->split2_step_k : s->split2_env_k) : (kind == 0 ? s->split_step_k : s->split_env_k);
-    if (k.state != 0) return k.state == 1;
-    if (capturing(s)) return false;                      // try again outside the capture
-    if (hipSetDevice(s->device) != hipSuccess) { k.state = -1; k.why = "hipSetDevice failed"; return false; }
-    const std::string form = lean ? "split2" : "split", ns = "rbl_jit_" + form;
-    const size_t lds = lean ? split_lean_lds_bytes(s->split2_gen) : split_lds_bytes(s->split_gen);
-    // (the static_assert: the host's LDS formula - what the launch asks for - must be the kernels' layout)
-    const std::string src = "#include \"tree_lane_defs.hpp\"\n#define RBL_NS " + ns + "\n" + (lean ? "#define RBL_LEAN 1\n" : "") +
-                            (lean ? s->split2_gen : s->split_gen).text + "#include \"tree_lane_split.hpp\"\n" +
-                            "static_assert(" + ns + "::SP_LDS_BYTES == " + std::to_string(lds) + ", \"host and kernel LDS layouts differ\");\n";
-    const std::string name = ns + (kind == 0 ? "::tree_split_step<" : "::tree_split_env_step<") + (s->integrator == RB_EULER ? "0>" : "1>");
-    const char *names[1] = {name.c_str()};
-    hipFunction_t *slots[1] = {&k.fn};
-    k.state = rbj::compile_and_load(src, ("roboy_tree_" + form + "_jit.hip").c_str(), names, 1, k.mod, slots, k.why) ? 1 : -1;
-    if (k.state == 1 && lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) != hipSuccess) {
-        k.state = -1; k.why = std::string("LDS of the ") + (lean ? "lean " : "") + "split kernel not granted";
-    }
-    return k.state == 1;
-}
-
-// kind: 0 = step, 1 = env step.  The kernel to launch, or nullptr for the ahead-of-time instances / the octet kernels.
-rblj::Kernel *lane_kernel(rb_sim *s, int kind) {
-    rblj::Kernel &k = kind == 0 ? s->lane_step_k : s->lane_env_k;
-    if (k.state == 0 && !s->lane_baked && tree_wants_lane(s) && !capturing(s) && hipSetDevice(s->device) == hipSuccess) {
-        if (!rblj::build(s->lane_gen, kind, s->integrator == RB_EULER ? 0 : 1, k)) s->jit_why = k.why;
-        else {
-            // a workgroup is one wave; more than 64 KiB of dynamic LDS (robots with many joints) has to be granted
-            const size_t lds = rblg::lane_lds_bytes_per_wave(s->lane_gen);
-            if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)) != hipSuccess) {
-                k.state = -1; s->jit_why = k.why = "LDS region of the lane kernel not granted";
-            }
-        }
-    }
-    return &k;
+// Is generated form `kernel` (RB_KERNEL_ENV_PER_LANE, _SPLIT, _SPLIT2) at hand for `kind` (0 = step, 1 = env step)?  Its ahead-of-time
+// instances, or its hiprtc-built kernel - which `build` = true builds if it has not been tried yet, never during a stream capture.
+bool tree_form_ready(rb_sim *s, int kernel, int kind, bool build) {
+    rblj::TreeForm &f = s->form(kernel);
+    rblj::Kernel &k = f.kernel(kind);
+    if (f.baked || k.state == 1) return true;
+    if (build && f.ok && k.state == 0 && !capturing(s))
+        return rblj::build(s->device, rb_sim::form_index(kernel), f.gen, s->integrator == RB_EULER ? 0 : 1, kind, k);
+    return false;
 }
 void maybe_jit(rb_sim *s) {
     if (s->params) return;                        // the parameter kernels are ahead of time (and a later call builds after rb_params_disable)
-    if (s->tree) { if (tree_wants_lane(s) && !s->lane_baked) (void)lane_kernel(s, 0); return; }
+    if (s->tree) { if (tree_wants_lane(s)) (void)tree_form_ready(s, RB_KERNEL_ENV_PER_LANE, 0, true); return; }
     if (s->jit_state != 0) return;
     if (s->ntx || s->baked || s->n <= RB_SMALL_BATCH || !rbj::enabled() || jit_level() == 0) { s->jit_state = -1; return; }
     if (capturing(s)) return;                     // try again outside the capture
@@ -688,19 +641,14 @@ inline unsigned chain_event_flags() {
 #endif
 #include "roboy_dispatch.hpp"
 
-// does this handle run the split form (several waves per 64 envs)?  An explicit choice, or AUTO's rule (ahead-of-time instances
-// and a batch small enough that its waves still find a SIMD each) ...
-bool tree_wants_split(const rb_sim *s) {
-    if (!s->tree || !s->split_ok) return false;
-    if (s->kernel_choice == RB_KERNEL_ENV_PER_LANE_SPLIT) return true;
-    return s->kernel_choice == RB_KERNEL_AUTO && auto_form(s, ENTRY_STEP) == F_SPLIT;
-}
-// ... or the lean two-part split form?  An explicit choice (any robot with a split plan: hiprtc), or AUTO between the five-wave
-// form's batch and a wave on every SIMD where ahead-of-time instances exist
-bool tree_wants_split2(const rb_sim *s) {
-    if (!s->tree || !s->split2_ok) return false;
-    if (s->kernel_choice == RB_KERNEL_ENV_PER_LANE_SPLIT2) return true;      // (rb_select_kernel has built the kernels of a robot without instances)
-    return s->kernel_choice == RB_KERNEL_AUTO && auto_form(s, ENTRY_STEP) == F_SPLIT2;
+// does this handle run split form `kernel`: F_SPLIT (five waves per 64 envs) or F_SPLIT2 (the lean two-part form)?  An explicit choice
+// (any robot with a split plan: rb_select_kernel has built the kernels of a robot without instances), or AUTO's rules: the five-wave
+// form while its waves still find a SIMD each, the lean form from there up to a wave on every SIMD - both where ahead-of-time
+// instances exist
+bool tree_wants_split(const rb_sim *s, int kernel) {
+    if (!s->tree || !s->form(kernel).ok) return false;
+    if (s->kernel_choice == kernel) return true;
+    return s->kernel_choice == RB_KERNEL_AUTO && auto_form(s, ENTRY_STEP) == kernel;
 }
 
 // kernel forms that step a sub-range of the batch (shifted pointers, own env count): what chains and the rb_*_range_dev entry points
@@ -919,24 +867,21 @@ int rb_create(const rb_robot_desc *robot, int64_t n_envs, int integrator, double
         rc = rbt::tree_build(robot, step_size, n_substeps, s->tree_host, why_tree);
         if (rc == RB_OK) {
             s->tree = true;
-            std::string why_gen;
-            s->lane_ok = rblg::generate(robot, true, s->lane_gen, why_gen) == RB_OK;
-            s->lane_baked = s->lane_ok && s->lane_gen.hash == RBL_TEXT_HASH && rblg::lane_lds_slots(s->lane_gen) == rbl_baked::LDS_SLOTS;
-            s->split_ok = rblg::generate_split(robot, rblg::SPLIT_FORM, s->split_gen, why_gen) == RB_OK && split_lds_bytes(s->split_gen) <= 160 * 1024;
-            if (!s->split_ok && rblg::SPLIT_FORM.max_helpers > 0)        // (the exchange area of the helper form does not fit: the three-barrier-less form)
-                s->split_ok = rblg::generate_split(robot, rblg::SPLIT_FORM.max_parts, s->split_gen, why_gen, 0) == RB_OK;
-            // (... and the host's LDS formula is the kernels': a launch with less LDS than tree_lane_split.hpp lays out would write past it)
-            s->split_baked = s->split_ok && s->split_gen.hash == RBL_SPLIT_TEXT_HASH && s->split_gen.n_parts == RBL_NPARTS &&
-                             s->split_gen.n_helpers == RBL_NHELPERS && split_lds_bytes(s->split_gen) == size_t(rbl_split_baked::SP_LDS_BYTES);
-            // the lean two-part form: only if the text generated for THIS robot is the text the second translation unit was compiled from
-            if (s->split_ok) {
-                std::string why2;
-                s->split2_ok = rblg::generate_split(robot, rblg::SPLIT2_FORM, s->split2_gen, why2) == RB_OK &&
-                               split_lean_lds_bytes(s->split2_gen) <= 160 * 1024;
-                s->split2_baked = s->split2_ok && robot->n_q == rbs2::n_q() && robot->n_t == rbs2::n_t() && s->split2_gen.hash == rbs2::text_hash() &&
-                                  s->split2_gen.n_parts == rbs2::n_parts() && split_lean_lds_bytes(s->split2_gen) == rbs2::lds_bytes();
-                if (!s->split2_ok) s->split2_gen = rblg::SplitGenerated();
+            // the generated forms (the lean two-part form only for robots the five-wave form serves) ...
+            for (int f = 0; f < rblg::N_FORMS; ++f) {
+                std::string why_gen;
+                s->forms[f].ok = (f != rblg::FORM_SPLIT2 || s->forms[rblg::FORM_SPLIT].ok) &&
+                                 rblg::generate_form(robot, f, s->forms[f].gen, why_gen) == RB_OK;
             }
+            // ... and which of them the ahead-of-time instances serve: the text they were compiled from, in the layout the launch
+            // asks LDS for (less LDS than the kernels lay out would be written past)
+            rblj::TreeForm &lane = s->forms[rblg::FORM_LANE], &split = s->forms[rblg::FORM_SPLIT], &split2 = s->forms[rblg::FORM_SPLIT2];
+            lane.baked = lane.ok && lane.gen.hash == RBL_TEXT_HASH && lane.gen.lds == size_t(rbl_baked::LDS_BYTES_PER_WAVE);
+            split.baked = split.ok && split.gen.hash == RBL_SPLIT_TEXT_HASH && split.gen.n_parts == RBL_NPARTS &&
+                          split.gen.n_helpers == RBL_NHELPERS && split.gen.lds == size_t(rbl_split_baked::SP_LDS_BYTES);
+            // (the lean form's instances are the second translation unit's: its text and layout are asked for)
+            split2.baked = split2.ok && robot->n_q == rbs2::n_q() && robot->n_t == rbs2::n_t() && split2.gen.hash == rbs2::text_hash() &&
+                           split2.gen.n_parts == rbs2::n_parts() && split2.gen.lds == rbs2::lds_bytes();
         }
         else why = "not a ball-joint robot (" + why + ") and not a supported joint tree (" + why_tree + ")";
     }
@@ -1008,7 +953,7 @@ int rb_create(const rb_robot_desc *robot, int64_t n_envs, int integrator, double
         RB_TREE_ATTR((rbt::tree_tendon_state<rbt::TREE_E, true>)); RB_TREE_ATTR((rbt::tree_tendon_state<rbt::TREE_E, false>));
         RB_TRY(hipMalloc(&s->d_ts_lconst, sizeof(float) * s->ts_tree_lconst.size()));
         RB_TRY(hipMemcpy(s->d_ts_lconst, s->ts_tree_lconst.data(), sizeof(float) * s->ts_tree_lconst.size(), hipMemcpyHostToDevice));
-        if (s->split_baked) {
+        if (s->form(RB_KERNEL_ENV_PER_LANE_SPLIT).baked) {
             RB_TREE_ATTR(rbl_split_baked::tree_split_step<0>); RB_TREE_ATTR(rbl_split_baked::tree_split_step<1>);
             RB_TREE_ATTR(rbl_split_baked::tree_split_env_step<0>); RB_TREE_ATTR(rbl_split_baked::tree_split_env_step<1>);
         }
@@ -1034,8 +979,7 @@ void rb_destroy(rb_sim *s) {
     (void)drain(s);
     for (auto &kv : s->graphs) kv.second.destroy();
     rbj::unload(s->jit);
-    rblj::unload(s->lane_step_k); rblj::unload(s->lane_env_k); rblj::unload(s->split_step_k); rblj::unload(s->split_env_k);
-    rblj::unload(s->split2_step_k); rblj::unload(s->split2_env_k);
+    for (rblj::TreeForm &f : s->forms) rblj::unload(f);
     (void)hipFree(s->d_q); (void)hipFree(s->d_qd); (void)hipFree(s->d_feas);
     (void)hipFree(s->d_goal_count); (void)hipFree(s->d_rows); (void)hipFree(s->d_u8); (void)hipFree(s->d_ten);
     (void)hipFree(s->d_tree_words); (void)hipFree(s->d_ts_lconst); (void)hipFree(s->d_ts_out);
@@ -1124,12 +1068,14 @@ void rb_jit_cache_stats(int64_t *hits, int64_t *compiles, int64_t *stores) {
 int rb_specialization(rb_sim *s) {
     if (check(s)) return -1;
     if (s->tree) {
-        if (tree_wants_split2(s)) return s->split2_baked ? RB_SPEC_TABLE : (s->split2_step_k.state == 1 ? RB_SPEC_JIT : RB_SPEC_NONE);
-        if (tree_wants_split(s)) return s->split_baked ? RB_SPEC_TABLE : (s->split_step_k.state == 1 ? RB_SPEC_JIT : RB_SPEC_NONE);
-        if (!tree_wants_lane(s)) { g_err = s->lane_ok ? "the octet kernels are selected (batch below the build threshold, or by choice)" : "no generator for this robot"; return RB_SPEC_NONE; }
-        if (s->lane_baked) return RB_SPEC_TABLE;
-        if (lane_kernel(s, 0)->state == 1) return RB_SPEC_JIT;
-        g_err = s->lane_step_k.why;
+        const int form = tree_wants_split(s, F_SPLIT2) ? F_SPLIT2 : tree_wants_split(s, F_SPLIT) ? F_SPLIT : F_LANE;
+        if (form == F_LANE && !tree_wants_lane(s)) {
+            g_err = s->form(F_LANE).ok ? "the octet kernels are selected (batch below the build threshold, or by choice)" : "no generator for this robot";
+            return RB_SPEC_NONE;
+        }
+        if (s->form(form).baked) return RB_SPEC_TABLE;
+        if (tree_form_ready(s, form, 0, true)) return RB_SPEC_JIT;
+        g_err = s->form(form).step.why;
         return RB_SPEC_NONE;
     }
     if (s->baked) return RB_SPEC_TABLE;
@@ -1143,38 +1089,28 @@ int rb_select_kernel(rb_sim *s, int kernel) {
     if (check(s)) return RB_EINVAL;
     // validate first: a refused request leaves the handle as it was (kernel_choice, rb_info, the graph cache)
     if (kernel < RB_KERNEL_AUTO || kernel > RB_KERNEL_ENV_PER_LANE_SPLIT2) return fail(RB_EINVAL, "unknown kernel variant");
-    if (kernel == RB_KERNEL_ENV_PER_LANE_SPLIT2 && !(s->tree && s->split2_ok))
+    const bool generated = kernel == RB_KERNEL_ENV_PER_LANE || kernel == RB_KERNEL_ENV_PER_LANE_SPLIT || kernel == RB_KERNEL_ENV_PER_LANE_SPLIT2;
+    if ((kernel == RB_KERNEL_ENV_PER_LANE_SPLIT || kernel == RB_KERNEL_ENV_PER_LANE_SPLIT2) && !(s->tree && s->form(kernel).ok))
         return fail(RB_EUNSUPPORTED, "no split form for this robot (a ball-joint robot, a serial chain, or branches tied together by tendons)");
     if (kernel == RB_KERNEL_LANE_PAIR && !(s->pair_ok && !s->tree && !s->ntx))
         return fail(RB_EUNSUPPORTED, "the two-lanes-per-env form needs an 8-tendon ball-joint robot with a mirror plane (tendons in mirror-image pairs, "
                                      "principal-axis inertia, symmetric joint limits)");
-    if (kernel == RB_KERNEL_ENV_PER_LANE_SPLIT && !(s->tree && s->split_ok))
-        return fail(RB_EUNSUPPORTED, "no split form for this robot (a ball-joint robot, a serial chain, or branches tied together by tendons)");
     if (s->tree) {
         if (kernel == RB_KERNEL_TENDON_PER_LANE) return fail(RB_EUNSUPPORTED, "joint-tree robots have no tendon-per-lane kernel");
-        if (kernel == RB_KERNEL_ENV_PER_LANE && !s->lane_ok) return fail(RB_EUNSUPPORTED, "no env-per-lane kernel can be generated for this robot");
+        if (kernel == RB_KERNEL_ENV_PER_LANE && !s->form(kernel).ok) return fail(RB_EUNSUPPORTED, "no env-per-lane kernel can be generated for this robot");
         const int before = s->kernel_choice;
-        s->kernel_choice = kernel;           // lane_kernel() / tree_wants_*() read it; restored on every failure below
-        if (kernel == RB_KERNEL_ENV_PER_LANE && !s->lane_baked) {
-            // an explicit choice builds the step kernel now (and fails loudly if that is not possible)
-            if (capturing(s)) { s->kernel_choice = before; return fail(RB_EINVAL, "the env-per-lane kernels cannot be built during a stream capture"); }
-            if (lane_kernel(s, 0)->state != 1) {
+        s->kernel_choice = kernel;           // tree_wants_*() read it; restored on every failure below
+        if (generated && !s->form(kernel).baked) {
+            // an explicit choice of a generated form builds its step kernel now (and fails loudly if that is not possible)
+            static const char *const NAME[rblg::N_FORMS] = {"env-per-lane kernel", "split-form kernel", "lean split-form kernel"};
+            static const char *const CAPTURED[rblg::N_FORMS] = {"the env-per-lane kernels cannot be built during a stream capture",
+                                                                "the split-form kernel cannot be built during a stream capture",
+                                                                "the lean split-form kernel cannot be built during a stream capture"};
+            const int f = rb_sim::form_index(kernel);
+            if (capturing(s)) { s->kernel_choice = before; return fail(RB_EINVAL, CAPTURED[f]); }
+            if (!tree_form_ready(s, kernel, 0, true)) {
                 s->kernel_choice = before;
-                return fail(RB_EUNSUPPORTED, "env-per-lane kernel not available: " + s->lane_step_k.why);
-            }
-        }
-        if (kernel == RB_KERNEL_ENV_PER_LANE_SPLIT2 && !s->split2_baked) {
-            if (capturing(s)) { s->kernel_choice = before; return fail(RB_EINVAL, "the lean split-form kernel cannot be built during a stream capture"); }
-            if (!build_split_kernel(s, true, 0)) {
-                s->kernel_choice = before;
-                return fail(RB_EUNSUPPORTED, "lean split-form kernel not available: " + s->split2_step_k.why);
-            }
-        }
-        if (kernel == RB_KERNEL_ENV_PER_LANE_SPLIT && !s->split_baked) {
-            if (capturing(s)) { s->kernel_choice = before; return fail(RB_EINVAL, "the split-form kernel cannot be built during a stream capture"); }
-            if (!build_split_kernel(s, false, 0)) {
-                s->kernel_choice = before;
-                return fail(RB_EUNSUPPORTED, "split-form kernel not available: " + s->split_step_k.why);
+                return fail(RB_EUNSUPPORTED, std::string(NAME[f]) + " not available: " + s->form(kernel).step.why);
             }
         }
         int rc = drop_graphs(s);             // graphs captured with another variant must not be replayed
@@ -1493,8 +1429,7 @@ int rb_env_configure(rb_sim *s, const rb_env_config *cfg) {
     s->env_ready = true;
     // the run-time specialised kernels are built here, outside any capture a caller may wrap around its first step
     maybe_jit(s);
-    if (s->tree && tree_wants_lane(s) && !s->lane_baked) (void)lane_kernel(s, 1);
-    if (s->tree && tree_wants_split(s) && !s->split_baked) (void)build_split_kernel(s, false, 1);
+    if (s->tree) (void)resolve_form(s, ENTRY_ENV, /*build=*/true, nullptr);      // (the env step's kernel of the generated form it runs)
     return rb_env_reset_dev(s, nullptr);
 }
 

@@ -1,7 +1,7 @@
 // roboy_sim_split2.hip - second translation unit of libroboy_sim.so: the lean two-part split kernels of the committed upper body
 // (tree_lane_split.hpp with RBL_LEAN = 1 around tree_lane_split2_baked.hpp; interface: tree_lane_split2.hpp).  For batches between
 // "one five-wave workgroup per CU" (16 384 envs) and "a wave on every SIMD" (65 536): two part waves per 64 envs, two workgroups per
-// CU, every wave alone on its SIMD - 32 768 envs in one generation (roboy_sim.hip: tree_wants_split2).
+// CU, every wave alone on its SIMD - 32 768 envs in one generation (roboy_sim.hip: tree_wants_split).
 #include <hip/hip_runtime.h>
 
 #include "tree_lane_split2.hpp"

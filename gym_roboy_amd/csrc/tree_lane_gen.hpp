@@ -1434,5 +1434,71 @@ inline int lane_lds_slots(const Generated &g) {
     return (g.lds_slots > stage ? g.lds_slots : stage) + 2 * g.n_q;
 }
 inline size_t lane_lds_bytes_per_wave(const Generated &g) { return size_t(lane_lds_slots(g)) * 64 * 4; }
+// ... and dynamic LDS bytes of a workgroup of the split kernels (tree_lane_split.hpp: SP_LDS_BYTES) in the five-wave layout ...
+inline size_t split_lds_bytes(const SplitGenerated &g) {
+    const int img = 3 * g.n_q + (3 * g.n_q > g.n_t ? 3 * g.n_q : g.n_t);
+    return size_t(img + g.x_buffers * g.x_slots + g.n_parts * (g.part_lds + 2 * g.n_q) + 3 * g.n_parts + 1 + (g.n_helpers > 0 ? g.n_q : 0)) * 64 * 4;
+}
+// ... and in the lean one (RBL_LEAN): q | qd | goal, the exchange area over the action / observation image, flags
+inline size_t split_lean_lds_bytes(const SplitGenerated &g) {
+    const int img = 3 * g.n_q + (3 * g.n_q > g.n_t ? 3 * g.n_q : g.n_t);
+    int shared = g.x_buffers * g.x_slots > img - 3 * g.n_q ? g.x_buffers * g.x_slots : img - 3 * g.n_q;
+    if (shared < 4 * g.n_q) shared = 4 * g.n_q;
+    return size_t(3 * g.n_q + shared + 3 * g.n_parts + 1) * 64 * 4;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The generated forms the library runs for a robot: one wave per 64 envs (tree_lane.hpp), the five-wave split form and the lean
+// two-part split form (tree_lane_split.hpp).  What it generates in each, and the source hiprtc builds a kernel of it from - the
+// one statement of both, for roboy_sim.hip (rb_create, tree_lane_jit.hpp) and for the CPU tests (gen_tree_lane.cpp).
+enum : int { FORM_LANE = 0, FORM_SPLIT = 1, FORM_SPLIT2 = 2, N_FORMS = 3 };
+
+struct FormText {
+    std::string text;            // the generated header
+    uint64_t hash = 0;           // FNV-1a of the text (the ahead-of-time instances run where it is theirs)
+    size_t lds = 0;              // dynamic LDS of a workgroup: what a launch asks for
+    unsigned threads = 0;        // threads of a workgroup
+    int n_parts = 0, n_helpers = 0;   // the split forms' part and helper waves
+    int max_live = 0;            // the one-wave form: Generated::max_live (what AUTO's build condition reads)
+};
+
+// RB_OK, or why the robot has no such form (no split plan; more LDS than a CU's 160 KiB)
+inline int generate_form(const rb_robot_desc *d, int form, FormText &out, std::string &err) {
+    out = FormText();
+    if (form == FORM_LANE) {
+        Generated g;
+        if (int rc = generate(d, true, g, err)) return rc;
+        out.text = g.text; out.hash = g.hash; out.max_live = g.max_live;
+        out.lds = lane_lds_bytes_per_wave(g); out.threads = 64;
+        return RB_OK;
+    }
+    const bool lean = form == FORM_SPLIT2;
+    const auto lds = [lean](const SplitGenerated &g) { return lean ? split_lean_lds_bytes(g) : split_lds_bytes(g); };
+    SplitGenerated g;
+    int rc = generate_split(d, lean ? SPLIT2_FORM : SPLIT_FORM, g, err);
+    if (rc == RB_OK && lds(g) > 160 * 1024) { rc = RB_EUNSUPPORTED; err = "the split form's LDS exceeds the 160 KiB of a CU"; }
+    if (rc != RB_OK && !lean && SPLIT_FORM.max_helpers > 0)          // (the exchange area of the helper form does not fit: the helper-less form)
+        rc = generate_split(d, SPLIT_FORM.max_parts, g, err, 0);
+    if (rc) return rc;
+    out.text = g.text; out.hash = g.hash; out.n_parts = g.n_parts; out.n_helpers = g.n_helpers;
+    out.lds = lds(g); out.threads = 64u * unsigned(g.n_parts + g.n_helpers);
+    return RB_OK;
+}
+
+// What hiprtc compiles for the kernel of `kind` (0 = step, 1 = env step; integ: 0 = Euler, 1 = RK4) of a form: the program's source
+// and name, and the kernel's name expression.  The static_assert holds the launch's LDS (`lds`) to the kernels' own layout: a launch
+// with less LDS than they lay out would write past it.
+struct JitSource { std::string src, program, kernel; };
+inline JitSource jit_source(int form, const std::string &text, size_t lds, int integ, int kind) {
+    const bool lane = form == FORM_LANE, lean = form == FORM_SPLIT2;
+    const std::string name = lane ? "lane" : lean ? "split2" : "split", sfx = lane ? "" : "_" + name, ns = "rbl_jit" + sfx;
+    JitSource j;
+    j.src = "#include \"tree_lane_defs.hpp\"\n#define RBL_NS rbl_jit" + sfx + "\n" + (lean ? "#define RBL_LEAN 1\n" : "") + text +
+            (lane ? "#include \"tree_lane.hpp\"\n" : "#include \"tree_lane_split.hpp\"\n") + "static_assert(" + ns +
+            (lane ? "::LDS_BYTES_PER_WAVE == " : "::SP_LDS_BYTES == ") + std::to_string(lds) + ", \"host and kernel LDS layouts differ\");\n";
+    j.program = "roboy_tree_" + name + "_jit.hip";
+    j.kernel = ns + (lane ? "::tree_lane_" : "::tree_split_") + (kind == 0 ? "step<" : "env_step<") + (integ ? "1>" : "0>");
+    return j;
+}
 
 }  // namespace rblg

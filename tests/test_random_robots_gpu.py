@@ -425,3 +425,40 @@ def test_fused_env_layer_of_the_hiprtc_built_lane_and_split_kernels_matches_host
     st = vec.stats()
     assert st["n_env_steps"] == 16 * n and st["n_episodes"] == n_done
     vec.close(); stepper.close()
+
+
+@pytest.mark.gpu
+def test_first_env_step_of_the_hiprtc_built_lean_split_form_may_be_captured():
+    """rb_env_configure builds the env-step kernel of the generated form the handle runs, the lean two-part split form included: a
+    robot without its ahead-of-time instances, pinned to RB_KERNEL_ENV_PER_LANE_SPLIT2, takes its FIRST env step inside a stream
+    capture (torch.cuda.graph around RoboyVecEnv.step) - where nothing can be built - and the graph's replays step like eager steps,
+    bit for bit."""
+    import ctypes
+    import torch
+    from gym_roboy_amd import _native as nat
+    from gym_roboy_amd.envs.vec_env import RoboyVecEnv
+    robot, desc = random_tree_robot(4)
+    n = 130
+    captured, eager = (RoboyVecEnv(robot, n, seed=5) for _ in range(2))
+    for vec in (captured, eager):
+        vec.sim.select_kernel(6)                                           # builds the step kernel only
+        nat.check(vec.sim._lib.rb_env_configure(vec.sim.handle, ctypes.byref(vec._cfg)))
+        vec.reset()
+    act = torch.zeros((n, desc.n_t), device="cuda")
+    stream = torch.cuda.Stream()
+    captured.set_stream(stream.cuda_stream)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=stream):
+        obs, rew, done, _ = captured.step(act)                             # the handle's first env step
+    rng = np.random.default_rng(3)
+    for _ in range(4):
+        a = torch.from_numpy(rng.uniform(-1, 1, (n, desc.n_t)).astype(np.float32)).cuda()
+        act.copy_(a)
+        g.replay()
+        e_obs, e_rew, e_done, _ = eager.step(a)
+        torch.cuda.synchronize()
+        assert torch.equal(obs, e_obs) and torch.equal(rew, e_rew) and torch.equal(done, e_done)
+    assert captured.sim.info()["kernel"] == 6 and captured.sim.specialization() == "jit"
+    del g
+    captured.close(); eager.close()

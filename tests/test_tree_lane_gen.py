@@ -209,38 +209,45 @@ def _hiprtc_compile(src, name, exprs):
     return rc, log, size.value
 
 
+def _jit_source(desc, tag, form, integrator, kind):
+    """(source, program name, kernel name expression) the library hands to hiprtc for this kernel (csrc/tree_lane_gen.hpp: jit_source)."""
+    import gen_tree_lane_baked as gen
+    os.makedirs(BUILD, exist_ok=True)
+    path = os.path.join(BUILD, "jit_%s.hip" % tag)
+    program, kernel = gen.jit_source(desc, form, integrator, kind, path)
+    return open(path).read(), program, kernel
+
+
 def test_hiprtc_builds_the_kernels_of_a_random_robot():
-    """What rblj::build (csrc/tree_lane_jit.hpp) hands to hiprtc at run time, compiled here for gfx950: the run-time
-    compiler has no standard headers, so every name the kernels use must come from rtc_compat.hpp."""
+    """What the library hands to hiprtc at run time (csrc/tree_lane_jit.hpp: rblj::build) for the one-wave form and the five-wave split
+    form of random robots, compiled here for gfx950: the run-time compiler has no standard headers, so every name the kernels use must
+    come from rtc_compat.hpp; and the source's static_assert holds the launch's LDS to the kernels' own layout."""
     import gen_tree_lane_baked as gen
     from gym_roboy_amd.envs.robots import RobotDescription
     from random_robots import random_tree_spec
-    hdr = os.path.join(BUILD, "lane_rtc.hpp")
-    gen.generate(RobotDescription(random_tree_spec(3)), hdr)
-    text = open(hdr).read()
-    text = text[:text.rindex("#define RBL_TEXT_HASH")]
-    src = '#include "tree_lane_defs.hpp"\n#define RBL_NS rbl_jit\n' + text + '#include "tree_lane.hpp"\n'
-    for kern in ("rbl_jit::tree_lane_step<1>", "rbl_jit::tree_lane_env_step<0>"):
-        rc, log, size = _hiprtc_compile(src, "roboy_tree_lane_jit.hip", [kern])
-        assert rc == 0, log[:2000]
-        assert size > 10000
+    for form, seed in ((gen.FORM_LANE, 3), (gen.FORM_SPLIT, 5)):
+        desc = RobotDescription(random_tree_spec(seed))
+        for integrator, kind in ((1, 0), (0, 1)):
+            src, program, kern = _jit_source(desc, "rtc_%d_%d" % (form, kind), form, integrator, kind)
+            rc, log, size = _hiprtc_compile(src, program, [kern])
+            assert rc == 0, log[:2000]
+            assert size > 10000
 
 
 def test_hiprtc_builds_the_lean_split_kernels_of_a_random_robot():
-    """What build_split_kernel (csrc/roboy_sim.hip) hands to hiprtc for rb_select_kernel(6) on a robot without ahead-of-time
-    instances: the two-part split text behind `#define RBL_LEAN 1` - parking slots in registers, exchange area over the row
-    image (tree_lane_split.hpp) - compiled here for gfx950."""
+    """What the library hands to hiprtc for rb_select_kernel(6) on a robot without ahead-of-time instances: the two-part split text
+    behind `#define RBL_LEAN 1` - parking slots in registers, exchange area over the row image (tree_lane_split.hpp) - compiled here
+    for gfx950."""
     import gen_tree_lane_baked as gen
     from gym_roboy_amd.envs.robots import RobotDescription
     from random_robots import random_tree_spec
-    hdr = os.path.join(BUILD, "lane_split2_rtc.hpp")
-    info = gen.generate_split(RobotDescription(random_tree_spec(5)), hdr, *gen.library_split_form(1))
+    desc = RobotDescription(random_tree_spec(5))
+    info = gen.generate_split(desc, os.path.join(BUILD, "lane_split2_rtc.hpp"), *gen.library_split_form(1))
     assert info["n_parts"] == 2 and info["n_helpers"] == 0
-    text = open(hdr).read()
-    text = text[:text.rindex("#define RBL_SPLIT_TEXT_HASH")]
-    src = '#include "tree_lane_defs.hpp"\n#define RBL_NS rbl_jit_split2\n#define RBL_LEAN 1\n' + text + '#include "tree_lane_split.hpp"\n'
-    for kern in ("rbl_jit_split2::tree_split_step<1>", "rbl_jit_split2::tree_split_env_step<0>"):
-        rc, log, size = _hiprtc_compile(src, "roboy_tree_split2_jit.hip", [kern])
+    for integrator, kind in ((1, 0), (0, 1)):
+        src, program, kern = _jit_source(desc, "rtc_split2_%d" % kind, gen.FORM_SPLIT2, integrator, kind)
+        assert "#define RBL_LEAN 1\n" in src and program == "roboy_tree_split2_jit.hip"
+        rc, log, size = _hiprtc_compile(src, program, [kern])
         assert rc == 0, log[:2000]
         assert size > 10000
 
@@ -436,13 +443,11 @@ def test_device_definitions_accept_every_pair_constant_shape_the_generator_write
     import gen_tree_lane_baked as gen
     from gym_roboy_amd.envs.robots import RobotDescription
     from random_robots import random_mirrored_spec
-    hdr = os.path.join(BUILD, "lane_rtc_mirrored_%d.hpp" % seed)
-    gen.generate(RobotDescription(random_mirrored_spec(seed, n_branch=3 + seed, n_t_branch=3 + seed)), hdr)
-    text = open(hdr).read()
+    desc = RobotDescription(random_mirrored_spec(seed, n_branch=3 + seed, n_t_branch=3 + seed))
+    text, program, kern = _jit_source(desc, "rtc_mirrored_%d" % seed, gen.FORM_LANE, 0, 0)
     assert "RBL_K2(" in text and "rbl_f2" in text
-    text = text[:text.rindex("#define RBL_TEXT_HASH")]
     for mode in (0, 1):
-        src = '#define RBL_K2_SPLIT %d\n#include "tree_lane_defs.hpp"\n#define RBL_NS rbl_jit\n' % mode + text + '#include "tree_lane.hpp"\n'
-        rc, log, size = _hiprtc_compile(src, "roboy_tree_lane_jit.hip", ["rbl_jit::tree_lane_step<0>"])
+        src = '#define RBL_K2_SPLIT %d\n' % mode + text
+        rc, log, size = _hiprtc_compile(src, program, [kern])
         assert rc == 0, log[:3000]
         assert size > 10000

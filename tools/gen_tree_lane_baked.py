@@ -77,6 +77,21 @@ def generate_split(desc, path, max_parts=4, max_helpers=0, helper_share=0, two_s
             "helper_stmt": helper_stmt.value}
 
 
+FORM_LANE, FORM_SPLIT, FORM_SPLIT2 = 0, 1, 2          # the library's generated forms (csrc/tree_lane_gen.hpp: FORM_*)
+
+
+def jit_source(desc, form, integrator, kind, path):
+    """Write to `path` the source the library hands to hiprtc for the kernel `kind` (0: step, 1: env step) of `desc` in generated
+    form `form` (FORM_*) with `integrator` (0: Euler, 1: RK4); returns (program name, kernel name expression)."""
+    lib = load_generator()
+    program, kernel = ctypes.create_string_buffer(256), ctypes.create_string_buffer(256)
+    rc = lib.rb_gen_tree_jit_source(ctypes.byref(desc.as_c_struct()), int(form), int(integrator), int(kind), path.encode(), program,
+                                    kernel, 256)
+    if rc:
+        raise RuntimeError("rb_gen_tree_jit_source failed: %d" % rc)
+    return program.value.decode(), kernel.value.decode()
+
+
 if __name__ == "__main__":
     from gym_roboy_amd.envs.robots import UpperBodyRobot
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gym_roboy_amd", "csrc", "tree_lane_baked.hpp")
