@@ -47,6 +47,15 @@ struct SpLds {
     __device__ __forceinline__ float operator()(int k) const { return col[k * stride]; }
 };
 
+// activation offsets: the first KEEP in registers, the rest as an LDS column ([NT8 - KEEP][BLOCK] floats, lane-contiguous rows)
+template <int KEEP>
+struct SpSplit {
+    const float *reg;
+    const float *col;   // &lds[0][threadIdx.x]
+    int stride;         // BLOCK
+    __device__ __forceinline__ float operator()(int k) const { return k < KEEP ? reg[k] : col[(k - KEEP) * stride]; }
+};
+
 // set-point -> activation offset, per tendon: act_scale * ksg_k, multiplied out on the host once per launch
 // (on the device the product of two kernarg scalars costs a v_mov and a v_mul per lane and tendon)
 struct Scale8 { float v[NT8]; };
@@ -127,7 +136,15 @@ msj_step_env_per_lane_rs(const Const8 c_arg, float *__restrict__ q, float *__res
     const float a[NT8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
 #pragma unroll
     for (int k = 0; k < NT8; ++k) u[k] = a[k] * us.v[k];
-    const bool ok = rb::MsjModel<float, NT8>::template step_rs<INTEG>(c, qq, vv, u);
+    // The tendons in pairs (msj_math.hpp: tendon_pair).  The pair form holds 3 registers more than one tendon at a time, and the
+    // kernel stays in the 64-register class by parking the LAST pair's two activation offsets in LDS (2 KB per workgroup) - one
+    // ds_read2 per stage, issued at the head of that pair and waited for a routing later.  Each lane reads back only what it wrote:
+    // no barrier.  (All eight parked: 4 reads per stage, half of the gain gone - profiles/r7_a/README.md.)
+    constexpr int KEEP = NT8 - 2;
+    __shared__ float lds_u[NT8 - KEEP][BLOCK];
+#pragma unroll
+    for (int k = KEEP; k < NT8; ++k) lds_u[k - KEEP][le] = u[k];
+    const bool ok = rb::MsjModel<float, NT8>::template step_rs_paired<INTEG>(c, qq, vv, SpSplit<KEEP>{u, &lds_u[0][le], BLOCK});
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(qq[j]), wg_rsrc(q + j * n + env0, live * 4), off, 0, 0);

@@ -519,7 +519,9 @@ struct MsjModel {
     }
 
     // All NT tendons written out one after the other, each behind a scheduling barrier (device): one tendon's temporaries
-    // at a time.  The acceleration of the "rolled stages" form (RS) of the kernels, below.
+    // at a time.  The acceleration of the "rolled stages" form (RS) of the fused env kernels and of env_params.hpp's twin; the
+    // step kernel msj_step_env_per_lane_rs takes the tendons in pairs instead (AccelPaired, below: the same results, about 5 % less
+    // time at four waves per SIMD - DESIGN.md section 7).
     struct AccelPinned {
         const C &c;
         const T *u;          // activation offsets (prescale() of the set-points)
@@ -536,12 +538,110 @@ struct MsjModel {
             rigid_body(c, f, qd, tx, ty, tz, qdd);
         }
     };
+
+    // ---- two tendons in flight ------------------------------------------------------------------------------------------
+    // tendon() + tendon_force() cut at the transcendentals (routing | rsqrt | strain, two exp2 | activation, force-velocity
+    // quotient, rcp | torque), so that the pieces of two tendons can be issued in turn.  Every expression is the one of tendon() /
+    // tendon_force(), term for term: tests/test_accel_paired.py holds the two forms bit-equal on the host, and the kernels give the
+    // same bytes with either (profiles/r7_a/README.md).
+    struct Routing { T d2, mx, my, mz; };
+    static RB_HD Routing routing(const Frame &f, const MsjTendon<T> &t) {
+        const T ax = f.r00 * t.A[0] + f.r10 * t.A[1] + f.r20 * t.A[2];
+        const T ay = f.r01 * t.A[0] + f.r11 * t.A[1] + f.r21 * t.A[2];
+        const T az = f.r02 * t.A[0] + f.r12 * t.A[1] + f.r22 * t.A[2];
+        Routing r;
+        r.d2 = ax * t.B2[0] + (ay * t.B2[1] + (az * t.B2[2] + t.ab2));
+        r.mx = ay * t.Bv[2] - az * t.Bv[1];
+        r.my = az * t.Bv[0] - ax * t.Bv[2];
+        r.mz = ax * t.Bv[1] - ay * t.Bv[0];
+        return r;
+    }
+    // behind rsqrt(d2): rate and strain, the two exponentials issued
+    struct Strain { T v, es, fl, pe; };
+    static RB_HD Strain strain(const C &c, const Frame &f, const MsjTendon<T> &t, const Routing &r, T inv) {
+        Strain s;
+        s.v = (f.wx * r.mx + f.wy * r.my + f.wz * r.mz) * inv;
+        s.es = (r.d2 * inv) * t.il0s + t.elcs;
+        s.fl = Fast<T>::exp2(-(s.es * s.es));
+        s.pe = Fast<T>::exp2(c.pe_k2s * s.es);
+        return s;
+    }
+    // activation and the force-velocity quotient's two halves: act * f_L * num and 1 / den
+    struct Hill { T afn, rden; };
+    static RB_HD Hill hill(const C &c, const Strain &s, T u) {
+        const T act = tclamp(c.kps * s.es - u, T(0), T(1));
+        const T vp = tmax(s.v, T(0)), p = tclamp(s.v + T(1), T(0), T(1));
+        const T num = c.fv_c1l * vp + p;
+        const T den = c.fv_c2l * vp + (c.fv_c2s * p + c.fv_k);
+        Hill h;
+        h.rden = Fast<T>::rcp(den);
+        h.afn = (act * s.fl) * num;
+        return h;
+    }
+    static RB_HD void torque(const C &c, const MsjTendon<T> &t, const Routing &r, T inv, const Strain &s, const Hill &h,
+                             T &tx, T &ty, T &tz) {
+        const T fpe = tmax(s.pe * c.inv_pe_den - c.inv_pe_den, T(0));
+        const T Fs = (t.fmaxv * inv) * (h.afn * h.rden + fpe);
+        tx -= Fs * r.mx; ty -= Fs * r.my; tz -= Fs * r.mz;
+    }
+    // the compiler's scheduler keeps what stands between two of these between them (device; nothing on the host)
+    static RB_HD void pin() {
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+    }
+    // Tendons a and b, a's torque summed first, b one piece behind a: b's routing stands behind a's rsqrt, b's strain beside a's
+    // activation, b's activation beside a's torque.  Staggered like this the pair holds 3 registers more than one tendon (both
+    // abreast: 6 more, and no faster - profiles/r7_a/README.md).
+    static RB_HD void tendon_pair(const C &c, const Frame &f, const MsjTendon<T> &ta, const MsjTendon<T> &tb, T ua, T ub,
+                                  T &tx, T &ty, T &tz) {
+        const Routing ra = routing(f, ta);
+        pin();
+        const T ia = Fast<T>::rsqrt(ra.d2);
+        const Routing rb_ = routing(f, tb);
+        pin();
+        const T ib = Fast<T>::rsqrt(rb_.d2);
+        const Strain sa = strain(c, f, ta, ra, ia);
+        pin();
+        const Hill ha = hill(c, sa, ua);
+        const Strain sb = strain(c, f, tb, rb_, ib);
+        pin();
+        torque(c, ta, ra, ia, sa, ha, tx, ty, tz);
+        const Hill hb = hill(c, sb, ub);
+        pin();
+        torque(c, tb, rb_, ib, sb, hb, tx, ty, tz);
+        pin();
+    }
+    // AccelPinned with the tendons taken two at a time (tendon_pair): the same sums in the same order.
+    // SP: source of the activation offsets, sp(k) (register array or LDS column), read at the head of each pair.
+    template <typename SP>
+    struct AccelPaired {
+        const C &c;
+        const SP &sp;
+        RB_HD void operator()(const T q[3], const T qd[3], T qdd[3]) const {
+            static_assert(NT % 2 == 0, "tendons in pairs");
+            const Frame f = frame(q, qd);
+            T tx = T(0), ty = T(0), tz = T(0);
+#pragma unroll
+            for (int k = 0; k < NT; k += 2) {
+                const T ua = sp(k), ub = sp(k + 1);
+                tendon_pair(c, f, c.ten[k], c.ten[k + 1], ua, ub, tx, ty, tz);
+            }
+            rigid_body(c, f, qd, tx, ty, tz, qdd);
+        }
+    };
     // RS: the integrator's stages as a rolled loop over running sums (integrate_acc), the tendons written out inside it
-    // (AccelPinned).  UNROLL = RS in the kernels' template arguments selects it.
+    // (AccelPinned, or AccelPaired through step_rs_paired).  UNROLL = RS in the kernels' template arguments selects it.
     static constexpr int RS = 9;
     template <int INTEG>
     static RB_HD bool step_rs(const C &c, T q[3], T qd[3], const T u[NT]) {
         return integrate_acc<INTEG>(c, q, qd, AccelPinned{c, u});
+    }
+
+    // step_rs with the tendons in pairs and the activation offsets from sp(k)
+    template <int INTEG, typename SP>
+    static RB_HD bool step_rs_paired(const C &c, T q[3], T qd[3], const SP &sp) {
+        return integrate_acc<INTEG>(c, q, qd, AccelPaired<SP>{c, sp});
     }
 
     // sp(k): activation offset of tendon k (prescale() of its set-point)
