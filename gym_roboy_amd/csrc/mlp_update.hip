@@ -7,7 +7,13 @@
 //   rp_clip_adam_dev   clip_grad_norm_ + Adam.step over the flat gradient vector of rp_ppo_grad_dev and a parameter
 //                      buffer of the same layout: one workgroup, two passes over ~10^4 floats
 // The reference's consumer is stable_baselines' PPO2 (train_parallel.py:28-31); torch's optimiser is the statement these
-// kernels are tested against (tests/test_policy_gpu.py).
+// kernels are tested against (tests/test_policy_gpu.py); tests/test_policy_scale_gpu.py holds them against the float64 statements of
+// oracle/policy_ref.py where the small cases do not reach: rp_adv_stats_dev with all STAT_BLOCKS blocks (more than 522 240 samples: the
+// last block sums 256 partials), constant and far-from-zero advantages, repeated calls on one scratch; rp_clip_adam_dev's grad_scale
+// (applied BEFORE the entropy bonus: the mean over ranks of gradients that each carry it), the slots it must neither read nor write,
+// a zero gradient, norms on both sides of the bound, step numbers up to 100 000.  The exploration noise those tests restate bit for
+// bit (csrc/mlp_policy.hip): Philox4x32-10, key = seed, counter = (sample id low, high, step + step base, 2 << 8 | block), action j =
+// component j & 3 of block j >> 2, Box-Muller on words (0, 1) and (2, 3) with u1 = ((w >> 8) + 1) / 2^24, u2 = (w >> 8) / 2^24.
 #include <hip/hip_runtime.h>
 
 #include "../../include/roboy_policy.h"
