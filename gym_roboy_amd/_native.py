@@ -128,6 +128,9 @@ SIGNATURES = {
     "rb_params_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p)]),
     "rb_params_set_ranges": (ctypes.c_int, [_sim, _fp, _fp, ctypes.c_int]),
     "rb_params_sample_dev": (ctypes.c_int, [_sim, _vp]),
+    "rb_env_obs_configure": (ctypes.c_int, [_sim, ctypes.c_uint32, _fp]),
+    "rb_env_obs_dim": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_int32)]),
+    "rb_env_obs_count": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

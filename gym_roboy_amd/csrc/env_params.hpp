@@ -218,66 +218,75 @@ struct RedrawParams {
     }
 };
 
+// The body as text, for the reason and with the conventions of RB_MSJ_ENV_STEP_BODY (msj_kernels.hpp): env_obs.hpp's parameter kernels
+// expand it with their extension for OX; by-value arguments c_arg, a, pa; template parameters INTEG, BLOCK, CONST, BK by name.
+#define RB_MSJ_PARAMS_ENV_STEP_BODY(OX) \
+    constexpr bool X = std::is_same<CONST, ConstX>::value;                                                                          \
+    const float *__restrict__ q = a.q, *__restrict__ qd = a.qd, *__restrict__ goal = a.goal, *__restrict__ act = a.act;             \
+    const float *par = pa.par;        /* (not restrict: the redraw behind the step writes the planes) */                            \
+    const long n = a.n, cnt = a.cnt;                                                                                                \
+    const float slope = a.e.slope, act_hi = a.e.act_hi;                                                                             \
+    const CONST &c = rbk::robot_consts<BK>(c_arg);                                                                                  \
+    const long i = long(blockIdx.x) * BLOCK + threadIdx.x;                                                                          \
+    if (i >= cnt) return;                                                                                                           \
+    float qq[3], vv[3], gg[3];                                                                                                      \
+    _Pragma("unroll")                                                                                                               \
+    for (int j = 0; j < 3; ++j) { qq[j] = q[j * n + i]; vv[j] = qd[j * n + i]; gg[j] = goal[j * n + i]; }                           \
+    /* clamp, slope * (x - in_high) + out_high with two roundings (roboy_env.py:157-158), + the env's offset, -> activation offset  */ \
+    auto setpoint = [&](float x, float o) { return rbe::mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi) + o; };    \
+    BodyScale bs;                                                                                                                   \
+    bool ok;                                                                                                                        \
+    rbk::HeldOffsets held{nullptr, nullptr, 1};                                                                                     \
+    constexpr bool IN_LDS = !BK;                                                                                                    \
+    float u[NT8], fs[NT8];                                                                                                          \
+    if constexpr (X) {                                                                                                              \
+        __shared__ float lds[2 * NTX][BLOCK];                                                                                       \
+        const int nt = c.nt;                                                                                                        \
+        const float *row = act + i * nt;                                                                                            \
+        for (int k = 0; k < nt; ++k) {                                                                                              \
+            lds[k][threadIdx.x] = setpoint(row[k], par[(nt + k) * n + i]) * c.ten[k].ksg;                                           \
+            lds[NTX + k][threadIdx.x] = par[k * n + i];                                                                             \
+        }                                                                                                                           \
+        bs.ms = par[2 * nt * n + i];                                                                                                \
+    _Pragma("unroll")                                                                                                               \
+        for (int j = 0; j < 3; ++j) bs.ds[j] = par[(2 * nt + 1 + j) * n + i];                                                       \
+        ok = rb::MsjModel<float, NTX>::template integrate_acc<INTEG>(c, qq, vv, AccelScaledLds<NTX, true>{c, &lds[0][threadIdx.x], BLOCK, bs}); \
+        held = rbk::HeldOffsets{&lds[0][threadIdx.x], &lds[NTX][threadIdx.x], BLOCK};                                               \
+    } else {                                                                                                                        \
+        const float4 a0 = reinterpret_cast<const float4 *>(act)[2 * i];                                                             \
+        const float4 a1 = reinterpret_cast<const float4 *>(act)[2 * i + 1];                                                         \
+        const float av[NT8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};                                                     \
+    _Pragma("unroll")                                                                                                               \
+        for (int k = 0; k < NT8; ++k) {                                                                                             \
+            fs[k] = par[k * n + i];                                                                                                 \
+            u[k] = setpoint(av[k], par[(NT8 + k) * n + i]) * c.ten[k].ksg;                                                          \
+        }                                                                                                                           \
+        bs.ms = par[2 * NT8 * n + i];                                                                                               \
+    _Pragma("unroll")                                                                                                               \
+        for (int j = 0; j < 3; ++j) bs.ds[j] = par[(2 * NT8 + 1 + j) * n + i];                                                      \
+        if constexpr (BK) {                                                                                                         \
+            ok = rb::MsjModel<float, NT8>::template integrate_acc<INTEG>(c, qq, vv, AccelScaled<NT8>{c, u, fs, bs});                \
+            held = rbk::HeldOffsets{u, fs, 1};                                                                                      \
+        } else {                                                                                                                    \
+            __shared__ float lds[2 * NT8][BLOCK];                                                                                   \
+    _Pragma("unroll")                                                                                                               \
+            for (int k = 0; k < NT8; ++k) { lds[k][threadIdx.x] = u[k]; lds[NT8 + k][threadIdx.x] = fs[k]; }                        \
+            ok = rb::MsjModel<float, NT8>::template integrate_acc<INTEG>(c, qq, vv, AccelScaledLds<NT8, false>{c, &lds[0][threadIdx.x], BLOCK, bs}); \
+            held = rbk::HeldOffsets{&lds[0][threadIdx.x], &lds[NT8][threadIdx.x], BLOCK};                                           \
+        }                                                                                                                           \
+    }                                                                                                                               \
+    if constexpr (BK) {                                                                                                             \
+        rbk::env_account(&a, i, qq, vv, gg, ok, RedrawParams<const ParamArgs *>{&pa}, (OX).template policy<IN_LDS>(&a, &pa, c, held, i)); \
+    } else {                                                                                                                        \
+        const rbk::msj_env_kernarg_ptr la = rbk::late_env_args(rbk::msj_env_args_offset(int(sizeof(CONST))));                       \
+        const param_kernarg_ptr lp = (param_kernarg_ptr)((const __attribute__((address_space(4))) char *)la - rbk::msj_env_args_offset(int(sizeof(CONST))) + \
+                                                         param_args_offset(int(sizeof(CONST))));                                    \
+        rbk::env_account(la, i, qq, vv, gg, ok, RedrawParams<param_kernarg_ptr>{lp}, (OX).template policy<IN_LDS>(la, lp, c, held, i)); \
+    }
 template <int INTEG, int BLOCK, typename CONST, bool BK>
 __global__ void __launch_bounds__(BLOCK)
 msj_params_env_step(const CONST c_arg, const MsjEnvArgs a, const ParamArgs pa) {
-    constexpr bool X = std::is_same<CONST, ConstX>::value;                 // run-time tendon count
-    const float *__restrict__ q = a.q, *__restrict__ qd = a.qd, *__restrict__ goal = a.goal, *__restrict__ act = a.act;
-    const float *par = pa.par;        // (not restrict: the redraw behind the step writes the planes)
-    const long n = a.n, cnt = a.cnt;
-    const float slope = a.e.slope, act_hi = a.e.act_hi;
-    const CONST &c = rbk::robot_consts<BK>(c_arg);
-    const long i = long(blockIdx.x) * BLOCK + threadIdx.x;
-    if (i >= cnt) return;
-    float qq[3], vv[3], gg[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { qq[j] = q[j * n + i]; vv[j] = qd[j * n + i]; gg[j] = goal[j * n + i]; }
-    // clamp, slope * (x - in_high) + out_high with two roundings (roboy_env.py:157-158), + the env's offset, -> activation offset
-    auto setpoint = [&](float x, float o) { return rbe::mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi) + o; };
-    BodyScale bs;
-    bool ok;
-    if constexpr (X) {
-        __shared__ float lds[2 * NTX][BLOCK];
-        const int nt = c.nt;
-        const float *row = act + i * nt;
-        for (int k = 0; k < nt; ++k) {
-            lds[k][threadIdx.x] = setpoint(row[k], par[(nt + k) * n + i]) * c.ten[k].ksg;
-            lds[NTX + k][threadIdx.x] = par[k * n + i];
-        }
-        bs.ms = par[2 * nt * n + i];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) bs.ds[j] = par[(2 * nt + 1 + j) * n + i];
-        ok = rb::MsjModel<float, NTX>::template integrate_acc<INTEG>(c, qq, vv, AccelScaledLds<NTX, true>{c, &lds[0][threadIdx.x], BLOCK, bs});
-    } else {
-        float u[NT8], fs[NT8];
-        const float4 a0 = reinterpret_cast<const float4 *>(act)[2 * i];
-        const float4 a1 = reinterpret_cast<const float4 *>(act)[2 * i + 1];
-        const float av[NT8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-        for (int k = 0; k < NT8; ++k) {
-            fs[k] = par[k * n + i];
-            u[k] = setpoint(av[k], par[(NT8 + k) * n + i]) * c.ten[k].ksg;
-        }
-        bs.ms = par[2 * NT8 * n + i];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) bs.ds[j] = par[(2 * NT8 + 1 + j) * n + i];
-        if constexpr (BK) {
-            ok = rb::MsjModel<float, NT8>::template integrate_acc<INTEG>(c, qq, vv, AccelScaled<NT8>{c, u, fs, bs});
-        } else {
-            __shared__ float lds[2 * NT8][BLOCK];
-#pragma unroll
-            for (int k = 0; k < NT8; ++k) { lds[k][threadIdx.x] = u[k]; lds[NT8 + k][threadIdx.x] = fs[k]; }
-            ok = rb::MsjModel<float, NT8>::template integrate_acc<INTEG>(c, qq, vv, AccelScaledLds<NT8, false>{c, &lds[0][threadIdx.x], BLOCK, bs});
-        }
-    }
-    if constexpr (BK) {
-        rbk::env_account(&a, i, qq, vv, gg, ok, RedrawParams<const ParamArgs *>{&pa});
-    } else {
-        const rbk::msj_env_kernarg_ptr la = rbk::late_env_args(rbk::msj_env_args_offset(int(sizeof(CONST))));
-        const param_kernarg_ptr lp = (param_kernarg_ptr)((const __attribute__((address_space(4))) char *)la - rbk::msj_env_args_offset(int(sizeof(CONST))) +
-                                                         param_args_offset(int(sizeof(CONST))));
-        rbk::env_account(la, i, qq, vv, gg, ok, RedrawParams<param_kernarg_ptr>{lp});
-    }
+    RB_MSJ_PARAMS_ENV_STEP_BODY(rbk::NoObsExt{})
 }
 
 }  // namespace rbp

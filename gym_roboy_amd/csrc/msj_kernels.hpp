@@ -343,12 +343,29 @@ struct NoDoneHook {
     __device__ __forceinline__ void operator()(long, uint64_t, uint64_t, int) const {}
 };
 
+// How env_account stores the env's observation: the reference's row [q, qd, goal] at a stride of nine floats, or (env_obs.hpp) that
+// row with tendon columns behind it at the handle's own stride.  Called as write_obs(obs, i, o, qq, vv, reset) with the state the
+// row reports (after the reset handling) and reset = the env was done and auto-reset by this step.
+struct PlainObs {
+    // 36-byte observation record: two 16-byte stores and one dword (dword-aligned
+    // vector stores are legal for global memory) instead of nine strided dwords
+    static __device__ __forceinline__ void store9(float *orow, const float (&o)[9]) {
+        typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+        *reinterpret_cast<f4u *>(orow) = f4u{o[0], o[1], o[2], o[3]};
+        *reinterpret_cast<f4u *>(orow + 4) = f4u{o[4], o[5], o[6], o[7]};
+        orow[8] = o[8];
+    }
+    __device__ __forceinline__ void operator()(float *obs, long i, const float (&o)[9], const float (&)[3], const float (&)[3], bool) const {
+        store9(obs + i * 9, o);
+    }
+};
+
 // What RoboyEnv.step does around the simulator's answer for env i of this launch (qq, vv: the new state; gg: the env's goal; ok:
 // feasible): reward, done, episode accounting, goal redraw / reset on done, and every row back.  Shared by the env-per-lane
 // kernel and the two-lanes-per-env kernel (whose even lanes call it).
-template <typename ARGS, typename HOOK = NoDoneHook>      // ARGS: const MsjEnvArgs * (the argument itself) or msj_env_kernarg_ptr (the late view of it)
+template <typename ARGS, typename HOOK = NoDoneHook, typename OBS = PlainObs>      // ARGS: const MsjEnvArgs * (the argument itself) or msj_env_kernarg_ptr (the late view of it)
 __device__ __forceinline__ void env_account(ARGS a, long i, float (&qq)[3], float (&vv)[3], float (&gg)[3], bool ok,
-                                            const HOOK &on_done = HOOK{}) {
+                                            const HOOK &on_done = HOOK{}, const OBS &write_obs = OBS{}) {
     EnvParams e;                  // (field by field: the source may live in the constant address space)
     e.vel_penalty = a->e.vel_penalty; e.bonus = a->e.bonus; e.max_len = a->e.max_len; e.auto_reset = a->e.auto_reset;
     e.penalty = a->e.penalty; e.bonus_val = a->e.bonus_val;
@@ -411,64 +428,85 @@ __device__ __forceinline__ void env_account(ARGS a, long i, float (&qq)[3], floa
 #pragma unroll
     for (int j = 0; j < 3; ++j) { q[j * n + i] = qq[j]; qd[j * n + i] = vv[j]; }
     feas[i] = fz; step_num[i] = sn; ep_ret[i] = ret;
-    // 36-byte observation record: two 16-byte stores and one dword (dword-aligned
-    // vector stores are legal for global memory) instead of nine strided dwords
-    typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-    float *orow = obs + i * 9;
-    *reinterpret_cast<f4u *>(orow) = f4u{o[0], o[1], o[2], o[3]};
-    *reinterpret_cast<f4u *>(orow + 4) = f4u{o[4], o[5], o[6], o[7]};
-    orow[8] = o[8];
+    write_obs(obs, i, o, qq, vv, dn && e.auto_reset);
     reward[i] = r; done[i] = dn ? 1u : 0u;
 }
 
-// UNROLL = 0: run-time tendon count (ConstX, c.nt tendons, action rows of c.nt floats)
+// The activation offsets a lane stepped with, for the observation policy behind the step: u[k * stride] is tendon k's - the lane's
+// registers (stride 1) or its LDS column (stride BLOCK); fs likewise the force scales of the parameter form (env_params.hpp)
+struct HeldOffsets { float *u, *fs; int stride; };
+// The fused env step without an extension of the observation: env_account's own row.  An extension (env_obs.hpp: ObsExt) makes
+// the policy from the launch's late argument pointer, the robot's constants and the held offsets (IN_LDS: they are an LDS column).
+struct NoObsExt {
+    template <bool IN_LDS, typename ARGS, typename CONST>
+    __device__ __forceinline__ PlainObs policy(ARGS, const CONST &, const HeldOffsets &, long) const { return PlainObs{}; }
+    template <bool IN_LDS, typename ARGS, typename PA, typename CONST>      // the parameter form (env_params.hpp: PA views its ParamArgs)
+    __device__ __forceinline__ PlainObs policy(ARGS, PA, const CONST &, const HeldOffsets &, long) const { return PlainObs{}; }
+};
+
+// The body of the fused env step, as text: a kernel reads its by-value arguments (c_arg, a) in place in the kernel-argument segment,
+// and a function between the kernel and this code - arguments by reference or by value - makes the compiler load them another way
+// (wider or narrower scalar loads, other registers: 18 kernel instances came out different).  So the kernels of env_obs.hpp, which are
+// this step with tendon columns behind it, expand the same text with their extension for OX.  Uses the kernel's template parameters
+// INTEG, BLOCK, UNROLL (0: run-time tendon count - ConstX, c.nt tendons, action rows of c.nt floats), CONST and BK by name, and its
+// arguments c_arg and a; comments inside are block comments (a line comment would swallow the continuation).
+#define RB_MSJ_ENV_STEP_BODY(OX) \
+    /* a.n: the handle's envs = the stride of the state / goal / statistics planes; a.cnt: the envs of THIS launch - all of them,  */ \
+    /* or a sub-range (rb_env_step_range_dev: every pointer then points at the range's first env, a.env0 is its global id)          */ \
+    const float *__restrict__ q = a.q, *__restrict__ qd = a.qd, *__restrict__ goal = a.goal, *__restrict__ act = a.act;             \
+    const long n = a.n, cnt = a.cnt;                                                                                                \
+    const float slope = a.e.slope, act_hi = a.e.act_hi;                                                                             \
+    const CONST &c = robot_consts<BK>(c_arg);                                                                                       \
+    const long i = long(blockIdx.x) * BLOCK + threadIdx.x;                                                                          \
+    if (i >= cnt) return;                                                                                                           \
+    float qq[3], vv[3], gg[3];                                                                                                      \
+    _Pragma("unroll")                                                                                                               \
+    for (int j = 0; j < 3; ++j) { qq[j] = q[j * n + i]; vv[j] = qd[j * n + i]; gg[j] = goal[j * n + i]; }                           \
+    /* the reference asserts the action lies in [-1,1] (roboy_env.py:52); a batched kernel cannot raise, so it clamps.  Then        */ \
+    /* slope * (x - in_high) + out_high, each op rounded (roboy_env.py:157-158)                                                     */ \
+    auto rescale = [&](float x) { return mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi); };                       \
+    bool ok;                                                                                                                        \
+    HeldOffsets held{nullptr, nullptr, 1};                                                                                          \
+    constexpr bool IN_LDS = UNROLL != RS && UNROLL < NT8;                                                                           \
+    float sp[NT8];                                                                                                                  \
+    if constexpr (UNROLL == 0) {                                                                                                    \
+        __shared__ float lds_sp[NTX][BLOCK];                                                                                        \
+        const int nt = c.nt;                                                                                                        \
+        const float *row = act + i * nt;                                                                                            \
+        for (int k = 0; k < nt; ++k) lds_sp[k][threadIdx.x] = rescale(row[k]) * c.ten[k].ksg;                                       \
+        ok = rb::MsjModel<float, NTX>::template step_sp<INTEG, 0>(c, qq, vv, SpLds{&lds_sp[0][threadIdx.x], BLOCK});                \
+        held = HeldOffsets{&lds_sp[0][threadIdx.x], nullptr, BLOCK};                                                                \
+    } else {                                                                                                                        \
+    held.u = sp;                                                                                                                    \
+    const float4 a0 = reinterpret_cast<const float4 *>(act)[2 * i];                                                                 \
+    const float4 a1 = reinterpret_cast<const float4 *>(act)[2 * i + 1];                                                             \
+    const float av[NT8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};                                                         \
+    _Pragma("unroll")                                                                                                               \
+    for (int k = 0; k < NT8; ++k) sp[k] = rescale(av[k]) * c.ten[k].ksg;                                                            \
+    if (UNROLL == RS) {                                                                                                             \
+        ok = rb::MsjModel<float, NT8>::template step_rs<INTEG>(c, qq, vv, sp);                                                      \
+    } else if (UNROLL >= NT8) {                                                                                                     \
+        ok = rb::MsjModel<float, NT8>::template step_sp<INTEG, UNROLL>(c, qq, vv, rb::SpArray<float, NT8>{sp});                     \
+    } else {                                                                                                                        \
+        /* rolled tendon loop: the set-points are indexed at run time, keep them as an LDS column (as msj_step_env_per_lane does);  */ \
+        /* each lane reads back only what it wrote                                                                                  */ \
+        __shared__ float lds_sp[NT8][BLOCK];                                                                                        \
+    _Pragma("unroll")                                                                                                               \
+        for (int k = 0; k < NT8; ++k) lds_sp[k][threadIdx.x] = sp[k];                                                               \
+        ok = rb::MsjModel<float, NT8>::template step_sp<INTEG, UNROLL>(c, qq, vv, SpLds{&lds_sp[0][threadIdx.x], BLOCK});           \
+        held = HeldOffsets{&lds_sp[0][threadIdx.x], nullptr, BLOCK};                                                                \
+    }                                                                                                                               \
+    }                                                                                                                               \
+    if constexpr (BK) {                                                                                                             \
+        env_account(&a, i, qq, vv, gg, ok, NoDoneHook{}, (OX).template policy<IN_LDS>(&a, c, held, i));                             \
+    } else {                                                                                                                        \
+        const msj_env_kernarg_ptr la = late_env_args(msj_env_args_offset(int(sizeof(CONST))));                                      \
+        env_account(la, i, qq, vv, gg, ok, NoDoneHook{}, (OX).template policy<IN_LDS>(la, c, held, i));                             \
+    }
 template <int INTEG, int BLOCK, int UNROLL, typename CONST = Const8, bool BK = false>
 __global__ void __launch_bounds__(BLOCK)
 msj_env_step_kernel(const CONST c_arg, const MsjEnvArgs a) {
-    // a.n: the handle's envs = the stride of the state / goal / statistics planes; a.cnt: the envs of THIS launch - all of them, or a
-    // sub-range (rb_env_step_range_dev: every pointer then points at the range's first env, a.env0 is its global id)
-    const float *__restrict__ q = a.q, *__restrict__ qd = a.qd, *__restrict__ goal = a.goal, *__restrict__ act = a.act;
-    const long n = a.n, cnt = a.cnt;
-    const float slope = a.e.slope, act_hi = a.e.act_hi;
-    const CONST &c = robot_consts<BK>(c_arg);
-    const long i = long(blockIdx.x) * BLOCK + threadIdx.x;
-    if (i >= cnt) return;
-    float qq[3], vv[3], gg[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { qq[j] = q[j * n + i]; vv[j] = qd[j * n + i]; gg[j] = goal[j * n + i]; }
-    // the reference asserts the action lies in [-1,1] (roboy_env.py:52); a batched kernel
-    // cannot raise, so it clamps.  Then slope * (x - in_high) + out_high, each op rounded
-    // (roboy_env.py:157-158)
-    auto rescale = [&](float x) { return mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi); };
-    bool ok;
-    if constexpr (UNROLL == 0) {
-        __shared__ float lds_sp[NTX][BLOCK];
-        const int nt = c.nt;
-        const float *row = act + i * nt;
-        for (int k = 0; k < nt; ++k) lds_sp[k][threadIdx.x] = rescale(row[k]) * c.ten[k].ksg;
-        ok = rb::MsjModel<float, NTX>::template step_sp<INTEG, 0>(c, qq, vv, SpLds{&lds_sp[0][threadIdx.x], BLOCK});
-    } else {
-    float sp[NT8];
-    const float4 a0 = reinterpret_cast<const float4 *>(act)[2 * i];
-    const float4 a1 = reinterpret_cast<const float4 *>(act)[2 * i + 1];
-    const float av[NT8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-#pragma unroll
-    for (int k = 0; k < NT8; ++k) sp[k] = rescale(av[k]) * c.ten[k].ksg;   // set-point -> activation offset
-    if (UNROLL == RS) {
-        ok = rb::MsjModel<float, NT8>::template step_rs<INTEG>(c, qq, vv, sp);
-    } else if (UNROLL >= NT8) {
-        ok = rb::MsjModel<float, NT8>::template step_sp<INTEG, UNROLL>(c, qq, vv, rb::SpArray<float, NT8>{sp});
-    } else {
-        // rolled tendon loop: the set-points are indexed at run time, keep them as an LDS column
-        // (as msj_step_env_per_lane does); each lane reads back only what it wrote
-        __shared__ float lds_sp[NT8][BLOCK];
-#pragma unroll
-        for (int k = 0; k < NT8; ++k) lds_sp[k][threadIdx.x] = sp[k];
-        ok = rb::MsjModel<float, NT8>::template step_sp<INTEG, UNROLL>(c, qq, vv, SpLds{&lds_sp[0][threadIdx.x], BLOCK});
-    }
-    }
-    if constexpr (BK) env_account(&a, i, qq, vv, gg, ok);
-    else env_account(late_env_args(msj_env_args_offset(int(sizeof(CONST)))), i, qq, vv, gg, ok);
+    RB_MSJ_ENV_STEP_BODY(NoObsExt{})
 }
 
 

@@ -245,6 +245,12 @@ struct MsjModel {
     // The readout twin of tendon() + tendon_force(): the same routing and muscle arithmetic, but the tendon's length, rate,
     // activation and force in physical units instead of its torque.  `u` is the activation offset (prescale()).
     static RB_HD TendonReading<T> tendon_state(const C &c, const Frame &f, const MsjTendon<T> &t, const TendonUnits<T> &pu, T u) {
+        return tendon_state_sel(c, f, t, pu, u, true);
+    }
+    // tendon_state with the force optional (want_force false: force 0, its two exponentials and the reciprocal are not evaluated):
+    // the fused env step's tendon columns (env_obs.hpp) evaluate only the channels their mask selects
+    static RB_HD TendonReading<T> tendon_state_sel(const C &c, const Frame &f, const MsjTendon<T> &t, const TendonUnits<T> &pu, T u,
+                                                   bool want_force) {
         const T ax = f.r00 * t.A[0] + f.r10 * t.A[1] + f.r20 * t.A[2];
         const T ay = f.r01 * t.A[0] + f.r11 * t.A[1] + f.r21 * t.A[2];
         const T az = f.r02 * t.A[0] + f.r12 * t.A[1] + f.r22 * t.A[2];
@@ -257,17 +263,20 @@ struct MsjModel {
         const T dl = d2 * inv;                                          // |d|, the moving segment
         const T es = dl * t.il0s + t.elcs;
         const T act = tclamp(c.kps * es - u, T(0), T(1));
-        const T fl = Fast<T>::exp2(-(es * es));
-        const T vp = tmax(v, T(0)), p = tclamp(v + T(1), T(0), T(1));
-        const T num = c.fv_c1l * vp + p;
-        const T den = c.fv_c2l * vp + (c.fv_c2s * p + c.fv_k);
-        const T rden = Fast<T>::rcp(den);
-        const T fpe = tmax(Fast<T>::exp2(c.pe_k2s * es) * c.inv_pe_den - c.inv_pe_den, T(0));
         TendonReading<T> r;
         r.length = dl + pu.lc;
         r.rate = v * pu.vl0;
         r.activation = act;
-        r.force = pu.fmax * ((act * fl) * num * rden + fpe);
+        r.force = T(0);
+        if (want_force) {
+            const T fl = Fast<T>::exp2(-(es * es));
+            const T vp = tmax(v, T(0)), p = tclamp(v + T(1), T(0), T(1));
+            const T num = c.fv_c1l * vp + p;
+            const T den = c.fv_c2l * vp + (c.fv_c2s * p + c.fv_k);
+            const T rden = Fast<T>::rcp(den);
+            const T fpe = tmax(Fast<T>::exp2(c.pe_k2s * es) * c.inv_pe_den - c.inv_pe_den, T(0));
+            r.force = pu.fmax * ((act * fl) * num * rden + fpe);
+        }
         return r;
     }
 

@@ -493,8 +493,16 @@ inline const Row *row_for(rb_sim *s, int entry, bool build, std::string *why = n
 
 // every launch of the library's three entry kinds
 // a handle with per-env parameters enabled (rb_params_enable) launches the kernels of env_params.hpp instead of its row
+// a handle with tendon channels in its observation (rb_env_obs_configure) launches the kernels of env_obs.hpp for the env-step entry
 int params_launch(rb_sim *s, int entry, const Launch &L);      // (roboy_sim.hip)
+int obs_launch(rb_sim *s, const Launch &L);
 inline int dispatch(rb_sim *s, int entry, const Launch &L) {
+    if (entry == ENTRY_ENV && s->obs_mask) {
+        const int rc = obs_launch(s, L);
+        if (rc) return rc;
+        RB_HIP(hipGetLastError());
+        return RB_OK;
+    }
     if (s->params) {
         const int rc = params_launch(s, entry, L);
         if (rc) return rc;

@@ -45,6 +45,7 @@
 #include "tree_lane_split2.hpp"      // the lean two-part split instances: a translation unit of their own (roboy_sim_split2.hip)
 #include "tendon_state.hpp"           // the tendon-state readout (rb_tendon_state_dev)
 #include "env_params.hpp"             // per-env physical parameters (rb_params_*)
+#include "env_obs.hpp"                // tendon channels in the fused env step's observation (rb_env_obs_*)
 
 namespace {
 
@@ -531,6 +532,11 @@ struct rb_sim {
     uint32_t *d_param_draws = nullptr;
     std::vector<float> param_ranges;
     bool param_resample = false;
+    // tendon channels in the env step's observation (env_obs.hpp; rb_env_obs_*): while the mask is set, the env-step entry launches
+    // the extended kernels - the nominal or the parameter form - instead of the dispatch table's row / the parameter kernel
+    int obs_mask = 0;
+    float obs_scale[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    int obs_dim() const { return 3 * n_q + rbo::n_channels(obs_mask) * n_t; }
 };
 
 namespace {
@@ -792,6 +798,60 @@ int params_launch_integ(rb_sim *s, int entry, const Launch &L) {
     }
     return fail(RB_EUNSUPPORTED, "per-env parameters have no fused-rollout kernel (rb_params_disable first)");
 }
+// ---- tendon channels in the observation (env_obs.hpp): what dispatch() launches for the env-step entry while a mask is set ----
+// dynamic LDS of an extended env-step launch: the rows of its 256 envs, where they fit beside the instance's own columns (0: per-lane stores)
+size_t obs_stage_bytes(const rb_sim *s) {
+    const size_t columns = (s->baked ? 0 : s->ntx ? 4 * 256 * NTX : 4 * 256 * NT8) * (s->params ? 2 : 1);
+    const size_t rows = size_t(4) * 256 * s->obs_dim();
+    return columns + rows <= 65536 ? rows : 0;
+}
+template <int NT>
+rbo::ObsArgs<NT> obs_args(const rb_sim *s, bool staged = false) {
+    rbo::ObsArgs<NT> oa;
+    oa.mask = s->obs_mask; oa.obs_dim = s->obs_dim(); oa.staged = staged ? 1 : 0; oa.pad_ = 0;
+    for (int c = 0; c < 4; ++c) oa.scale[c] = s->obs_scale[c];
+    for (int k = 0; k < NT; ++k) oa.units[k] = s->ts_units.u[k];
+    return oa;
+}
+template <int INTEG>
+int obs_launch_integ(rb_sim *s, const Launch &L) {
+    constexpr int B = 256;
+    const size_t lds = obs_stage_bytes(s);
+    const dim3 grid(blocks_for(L.cnt, B)), block(B);
+    MsjEnvArgs a = msj_env_args(s, L);
+    a.obs = L.obs + L.i0 * s->obs_dim();                 // the row stride is the handle's obs_dim
+    constexpr int UB = INTEG == 0 ? UBE : UBR, UK = INTEG == 0 ? UKE : UKR;     // the unroll factors of the large-batch env-per-lane rows
+    if (s->params) {
+        const rbp::ParamArgs pa{s->d_params + L.i0, s->d_param_draws + L.i0, s->d_param_ranges, s->n, s->n_params, s->param_resample ? 1 : 0};
+        if (s->ntx)
+            hipLaunchKernelGGL((rbo::msj_obs_params_env_step<INTEG, B, ConstX, false>), grid, block, lds, L.stream, s->cx, a, pa, obs_args<NTX>(s, lds != 0));
+        else if (s->baked)
+            hipLaunchKernelGGL((rbo::msj_obs_params_env_step<INTEG, B, Const8, true>), grid, block, lds, L.stream, s->c8, a, pa, obs_args<NT8>(s, lds != 0));
+        else
+            hipLaunchKernelGGL((rbo::msj_obs_params_env_step<INTEG, B, Const8, false>), grid, block, lds, L.stream, s->c8, a, pa, obs_args<NT8>(s, lds != 0));
+    } else if (s->ntx) {
+        hipLaunchKernelGGL((rbo::msj_obs_env_step<INTEG, B, 0, ConstX, false>), grid, block, lds, L.stream, s->cx, a, obs_args<NTX>(s, lds != 0));
+    } else if (s->baked) {
+        hipLaunchKernelGGL((rbo::msj_obs_env_step<INTEG, B, UB, Const8, true>), grid, block, lds, L.stream, s->c8, a, obs_args<NT8>(s, lds != 0));
+    } else {
+        hipLaunchKernelGGL((rbo::msj_obs_env_step<INTEG, B, UK, Const8, false>), grid, block, lds, L.stream, s->c8, a, obs_args<NT8>(s, lds != 0));
+    }
+    return RB_OK;
+}
+int obs_launch(rb_sim *s, const Launch &L) {
+    if (L.cnt <= 0) return RB_OK;
+    return s->integrator == RB_EULER ? obs_launch_integ<0>(s, L) : obs_launch_integ<1>(s, L);
+}
+// rb_env_reset_dev's observation rows on such a handle: the state the reset kernel has just written, every set-point 0
+void obs_rows_launch(rb_sim *s, float *d_obs) {
+    const dim3 grid(blocks_for(s->n, 256)), block(256);
+    const float *par = s->params ? s->d_params : nullptr;
+    if (s->ntx)
+        hipLaunchKernelGGL((rbo::msj_obs_rows<256, ConstX>), grid, block, 0, s->stream, s->cx, obs_args<NTX>(s), s->d_q, s->d_qd, s->d_goal, par, d_obs, s->n);
+    else
+        hipLaunchKernelGGL((rbo::msj_obs_rows<256, Const8>), grid, block, 0, s->stream, s->c8, obs_args<NT8>(s), s->d_q, s->d_qd, s->d_goal, par, d_obs, s->n);
+}
+
 int params_launch(rb_sim *s, int entry, const Launch &L) {
     if (L.cnt <= 0) return RB_OK;
     return s->integrator == RB_EULER ? params_launch_integ<0>(s, entry, L) : params_launch_integ<1>(s, entry, L);
@@ -1444,8 +1504,42 @@ int rb_env_reset_dev(rb_sim *s, float *d_obs) {
     else
         hipLaunchKernelGGL(env_reset_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream,
                            s->box, s->d_q, s->d_qd, s->d_feas, s->d_goal, s->d_step_num, s->d_ep_ret,
-                           s->d_goal_count, d_obs, s->n, s->seed, uint64_t(s->env0));
+                           s->d_goal_count, s->obs_mask ? nullptr : d_obs, s->n, s->seed, uint64_t(s->env0));
     RB_HIP(hipGetLastError());
+    if (s->obs_mask && d_obs) {               // rows of obs_dim floats: the tendon columns at the zero pose, every set-point 0
+        obs_rows_launch(s, d_obs);
+        RB_HIP(hipGetLastError());
+    }
+    return RB_OK;
+}
+
+// ---- tendon channels in the fused env step's observation (env_obs.hpp) ----
+int32_t rb_env_obs_count(int32_t n_q, int32_t n_t, uint32_t channel_mask) {
+    if (n_q < 0 || n_t < 0 || (channel_mask & ~uint32_t(RB_OBS_ALL))) return -1;
+    return 3 * n_q + rbo::n_channels(int(channel_mask)) * n_t;
+}
+int rb_env_obs_configure(rb_sim *s, uint32_t channel_mask, const float *scale) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
+    if (channel_mask & ~uint32_t(RB_OBS_ALL)) return fail(RB_EINVAL, "unknown bits in the channel mask (RB_OBS_LENGTH | RB_OBS_RATE | RB_OBS_ACTIVATION | RB_OBS_FORCE)");
+    if (scale)
+        for (int c = 0; c < 4; ++c)
+            if (!std::isfinite(scale[c])) return fail(RB_EINVAL, "channel scales must be finite");
+    if (s->tree && channel_mask)
+        return fail(RB_EUNSUPPORTED, "tendon channels in the observation are built for ball-joint robots (1-16 tendons); a joint tree's readout is "
+                                     "rb_tendon_state_dev");
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);                       // nothing in flight may still write rows of the old width
+    if (rc) return rc;
+    rc = drop_graphs(s);
+    if (rc) return rc;
+    s->obs_mask = int(channel_mask);
+    for (int c = 0; c < 4; ++c) s->obs_scale[c] = scale ? scale[c] : 1.0f;
+    return RB_OK;
+}
+int rb_env_obs_dim(rb_sim *s, int32_t *obs_dim) {
+    if (check(s) || !obs_dim) return fail(RB_EINVAL, "null argument");
+    *obs_dim = s->obs_dim();
     return RB_OK;
 }
 
@@ -1518,7 +1612,7 @@ int rb_range_capable(rb_sim *s) {
     // builds what a launch would build (outside captures), then asks the table: bit 0 = the step's row takes sub-ranges, bit 1 = the env step's
     maybe_jit(s);
     const Row *step = row_for(s, ENTRY_STEP, true), *env = row_for(s, ENTRY_ENV, s->env_ready);
-    return (step && step->ranges ? 1 : 0) | (env && env->ranges ? 2 : 0);
+    return (step && step->ranges ? 1 : 0) | (s->obs_mask || (env && env->ranges) ? 2 : 0);     // (env_obs.hpp's kernels take sub-ranges)
 }
 
 static int stats_launch(rb_sim *s, double *d_out2) {
@@ -1661,6 +1755,8 @@ int rb_dispatch_current(rb_sim *s, int entry, rb_dispatch_row *out) {
     if (entry < ENTRY_STEP || entry > ENTRY_FUSED) return fail(RB_EINVAL, "unknown entry kind");
     if (entry == ENTRY_FUSED && (s->tree || s->ntx)) return fail(RB_EUNSUPPORTED, "fused rollout is built for 8-tendon ball-joint robots");
     if (s->params) return fail(RB_EUNSUPPORTED, "per-env parameters are enabled: the parameter kernels (env_params.hpp) are not rows of the dispatch table");
+    if (entry == ENTRY_ENV && s->obs_mask)
+        return fail(RB_EUNSUPPORTED, "tendon channels are set (rb_env_obs_configure): the extended env-step kernels (env_obs.hpp) are not rows of the dispatch table");
     RB_HIP(hipSetDevice(s->device));
     if (entry != ENTRY_ENV || s->env_ready) maybe_jit(s);
     std::string why;

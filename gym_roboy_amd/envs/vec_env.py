@@ -13,7 +13,8 @@ one returned).
 
 ``step`` takes actions ``[N, n_t]`` in ``[-1, 1]`` either as a numpy array
 (copied to the device) or as a CUDA ``torch.Tensor`` (used in place), and
-returns ``(obs [N, 3 n_q], reward [N], done [N], infos)`` of the same kind.
+returns ``(obs [N, obs_dim], reward [N], done [N], infos)`` of the same kind;
+``obs_dim`` is ``3 n_q``, or ``3 n_q + C n_t`` with ``tendon_obs`` (C channels).
 """
 import ctypes
 
@@ -27,6 +28,31 @@ from .simulations.hip_simulation_client import HipBatchSimulation
 
 _IN_SLAB = object()      # RoboyVecEnv._last_actions: the last step's numpy actions, uploaded into the action slab
 
+# tendon channels of the observation, in row order, with their bits (rb_obs_channel) and physical bounds
+TENDON_OBS_CHANNELS = ("length", "rate", "activation", "force")
+_TENDON_OBS_BOUNDS = {"length": (0.0, np.inf), "rate": (-np.inf, np.inf), "activation": (0.0, 1.0), "force": (0.0, np.inf)}
+
+
+def tendon_obs_mask(channels) -> int:
+    """Channel names (any order, no repeats) -> the mask of ``rb_env_obs_configure``."""
+    names = [channels] if isinstance(channels, str) else list(channels)
+    unknown = [c for c in names if c not in TENDON_OBS_CHANNELS]
+    if unknown or len(set(names)) != len(names):
+        raise ValueError("tendon_obs takes distinct names out of %s, got %r" % (TENDON_OBS_CHANNELS, channels))
+    return sum(1 << TENDON_OBS_CHANNELS.index(c) for c in names)
+
+
+def tendon_obs_scales(scale) -> np.ndarray:
+    """``{"force": 1/400, ...}`` (or None) -> the four finite fp32 scales in channel order, 1 where not given."""
+    out = np.ones(4, np.float32)
+    for k, v in dict(scale or {}).items():
+        if k not in TENDON_OBS_CHANNELS:
+            raise ValueError("tendon_obs_scale: unknown channel %r" % (k,))
+        out[TENDON_OBS_CHANNELS.index(k)] = v
+    if not np.all(np.isfinite(out)):
+        raise ValueError("tendon_obs_scale must be finite")
+    return out
+
 
 class RoboyVecEnv:
 
@@ -35,9 +61,13 @@ class RoboyVecEnv:
                  is_agent_getting_bonus_for_reaching_goal: bool = True,
                  auto_reset: bool = True, integrator="euler", n_substeps: int = 1,
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
-                 randomization=None):
+                 randomization=None, tendon_obs=None, tendon_obs_scale=None):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
-        ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself."""
+        ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
+        ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
+        ``[q, qd, goal, then n_t values per channel in that fixed order]``, the tendons' state at the reported state under the actions
+        just applied (ball-joint robots); ``tendon_obs_scale``: ``{channel: factor}``, default 1 (m, m/s, [0, 1], N).
+        Combines with ``randomization``."""
         self.robot = robot
         self.num_envs = int(num_envs)
         self.sim = HipBatchSimulation(robot, num_envs, integrator=integrator, n_substeps=n_substeps,
@@ -69,9 +99,26 @@ class RoboyVecEnv:
                 raise NotImplementedError("fused env layer expects uniform per-joint boxes")
         self._cfg = cfg
         nat.check(self.sim._lib.rb_env_configure(self.sim.handle, ctypes.byref(cfg)))
+        self.tendon_obs = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
+        self.tendon_obs_scale = tendon_obs_scales(tendon_obs_scale)
+        self.obs_dim = 3 * self.n_q
+        if self.tendon_obs:
+            # before anything is captured into a graph: the extended kernels replace the handle's env-step kernels from here on
+            nat.check(self.sim._lib.rb_env_obs_configure(self.sim.handle, tendon_obs_mask(self.tendon_obs), nat.fptr(self.tendon_obs_scale)))
+            dim = ctypes.c_int32()
+            nat.check(self.sim._lib.rb_env_obs_dim(self.sim.handle, ctypes.byref(dim)))
+            self.obs_dim = int(dim.value)
+            lo, hi = [self.observation_space.low], [self.observation_space.high]
+            for c in self.tendon_obs:
+                b = np.sort(np.float32(_TENDON_OBS_BOUNDS[c]) * self.tendon_obs_scale[TENDON_OBS_CHANNELS.index(c)]) \
+                    if self.tendon_obs_scale[TENDON_OBS_CHANNELS.index(c)] != 0 else np.zeros(2, np.float32)
+                lo.append(np.full(self.n_t, b[0], np.float32))
+                hi.append(np.full(self.n_t, b[1], np.float32))
+            self.observation_space = spaces.Box(low=np.concatenate(lo), high=np.concatenate(hi), dtype="float32")
+            assert self.observation_space.shape == (self.obs_dim,)
         n = self.num_envs
         self._d_act = self.sim.malloc(4 * n * self.n_t)
-        self._d_obs = self.sim.malloc(4 * n * 3 * self.n_q)
+        self._d_obs = self.sim.malloc(4 * n * self.obs_dim)
         self._d_rew = self.sim.malloc(4 * n)
         self._d_done = self.sim.malloc(4 * n)
         self._pending_actions = None
@@ -92,7 +139,7 @@ class RoboyVecEnv:
             self.sim.sample_params()
         nat.check(self.sim._lib.rb_env_reset_dev(self.sim.handle, ctypes.c_void_p(self._d_obs)))
         self.sim.synchronize()
-        return self.sim.download(self._d_obs, (self.num_envs, 3 * self.n_q))
+        return self.sim.download(self._d_obs, (self.num_envs, self.obs_dim))
 
     def set_goal(self, goal_q, step_num=None):
         """Overwrite every env's goal ``[N, n_q]`` (and episode step counter ``[N]``): the
@@ -116,12 +163,12 @@ class RoboyVecEnv:
         self._last_actions = _IN_SLAB
         self.sim.synchronize()
         n = self.num_envs
-        return (self.sim.download(self._d_obs, (n, 3 * self.n_q)),
+        return (self.sim.download(self._d_obs, (n, self.obs_dim)),
                 self.sim.download(self._d_rew, (n,)),
                 self.sim.download(self._d_done, (n,), np.uint32).astype(bool), [{}] * n)
 
     def step_dev(self, d_act, d_obs, d_rew, d_done):
-        """Raw device-pointer form: asynchronous on the simulation's stream."""
+        """Raw device-pointer form: asynchronous on the simulation's stream.  ``d_obs`` holds ``num_envs * obs_dim`` floats."""
         nat.check(self.sim._lib.rb_env_step_dev(
             self.sim.handle, ctypes.c_void_p(d_act), ctypes.c_void_p(d_obs),
             ctypes.c_void_p(d_rew), ctypes.c_void_p(d_done)))
@@ -146,7 +193,7 @@ class RoboyVecEnv:
         # run on torch's current stream so the policy's kernels and the env
         # step are ordered without a host sync
         self.set_stream(torch.cuda.current_stream(actions.device).cuda_stream)
-        obs = torch.empty((n, 3 * self.n_q), dtype=torch.float32, device=actions.device)
+        obs = torch.empty((n, self.obs_dim), dtype=torch.float32, device=actions.device)
         rew = torch.empty((n,), dtype=torch.float32, device=actions.device)
         done = torch.empty((n,), dtype=torch.int32, device=actions.device)
         self.step_dev(actions.data_ptr(), obs.data_ptr(), rew.data_ptr(), done.data_ptr())

@@ -342,6 +342,14 @@ def average_gradients(module, dist=None):
             off += n
 
 
+def _tendon_obs_of(env):
+    """What a checkpoint records about the env's observation (RoboyVecEnv's tendon channels and their scales): a policy only
+    makes sense on the observation it was trained on.  An env without the option - or an older checkpoint - has no channels."""
+    channels = tuple(getattr(env, "tendon_obs", ()) or ())
+    scale = [float(x) for x in getattr(env, "tendon_obs_scale", (1.0, 1.0, 1.0, 1.0))] if channels else [1.0] * 4
+    return {"channels": list(channels), "scale": scale}
+
+
 def _fused_kernels_apply(policy, obs_dim, act_dim):
     """MlpPolicy's shape (two hidden layers of 64 units per net) in dimensions the kernels of include/roboy_policy.h
     support, and the library is there."""
@@ -679,10 +687,13 @@ class PPO:
     def save(self, path):
         opt = self._fadam.state_dict() if self._fgrad is not None else self.opt.state_dict()
         torch.save({"policy": self.policy.state_dict(), "optimizer": opt, "num_timesteps": self.num_timesteps,
-                    "epoch": self._epoch}, path)
+                    "epoch": self._epoch, "tendon_obs": _tendon_obs_of(self.env)}, path)
 
     def load(self, path):
         ck = torch.load(path, map_location=self.device)
+        if ck.get("tendon_obs", _tendon_obs_of(None)) != _tendon_obs_of(self.env):
+            raise ValueError("the checkpoint was trained on the observation %r, this env gives %r (RoboyVecEnv's tendon_obs / "
+                             "tendon_obs_scale)" % (ck.get("tendon_obs", _tendon_obs_of(None)), _tendon_obs_of(self.env)))
         self.policy.load_state_dict(ck["policy"])      # copies in place: the views of the fused optimiser's flat buffer stay valid
         fused_ck = isinstance(ck["optimizer"], dict) and ck["optimizer"].get("fused_adam", False)
         if self._fgrad is not None and fused_ck:

@@ -33,7 +33,14 @@ def main(argv=None):
     ap.add_argument("--torch-policy", action="store_true",
                     help="policy step and minibatch gradient through torch (autograd, rocBLAS) instead of the fused "
                          "matrix-core kernels of include/roboy_policy.h")
+    ap.add_argument("--tendon-obs", default="", metavar="CHANNELS",
+                    help="comma-separated tendon channels appended to the observation, out of length,rate,activation,force "
+                         "(e.g. length,force: 25 columns for MsjRobot); stored in the checkpoint")
+    ap.add_argument("--tendon-obs-scale", default="", metavar="CHANNEL=FACTOR,...",
+                    help="factor per channel, default 1 (m, m/s, [0,1], N), e.g. force=0.0025,length=4")
     args = ap.parse_args(argv)
+    tendon_obs = tuple(c for c in args.tendon_obs.split(",") if c)
+    tendon_obs_scale = {k: float(v) for k, v in (item.split("=", 1) for item in args.tendon_obs_scale.split(",") if item)}
 
     import torch
     from .envs.robots import MsjRobot
@@ -59,7 +66,7 @@ def main(argv=None):
         os.makedirs(results, exist_ok=True)
 
     env = RoboyVecEnv(MsjRobot(), args.num_envs, seed=args.seed, device=local_rank,
-                      env_id_offset=rank * args.num_envs)
+                      env_id_offset=rank * args.num_envs, tendon_obs=tendon_obs or None, tendon_obs_scale=tendon_obs_scale or None)
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,

@@ -39,18 +39,41 @@ def main(argv=None):
     from .envs.simulations import HipSimulationClient
     from .ppo import MlpPolicy
 
-    env = RoboyEnv(simulation_client=HipSimulationClient(robot=MsjRobot()))
-    policy = MlpPolicy(env.observation_space.shape[0], env.action_space.shape[0])
-    policy.load_state_dict(torch.load(args.model, map_location="cpu")["policy"])
+    ck = torch.load(args.model, map_location="cpu")
+    tendon_obs = ck.get("tendon_obs", {}).get("channels", [])
+    if tendon_obs:
+        # trained with tendon channels in the observation (train_parallel --tendon-obs): the same row comes from a RoboyVecEnv of
+        # one env, which resets itself on done and returns the reset observation
+        from .envs.vec_env import TENDON_OBS_CHANNELS, RoboyVecEnv
+        vec = RoboyVecEnv(MsjRobot(), 1, tendon_obs=tendon_obs, tendon_obs_scale=dict(zip(TENDON_OBS_CHANNELS, ck["tendon_obs"]["scale"])))
+        reset = lambda: vec.reset()[0]
+
+        def step(a):
+            o, r, d, _ = vec.step(a[None])
+            return o[0], float(r[0]), False
+        n_obs, n_act = vec.observation_space.shape[0], vec.action_space.shape[0]
+    else:
+        env = RoboyEnv(simulation_client=HipSimulationClient(robot=MsjRobot()))
+        reset = env.reset
+
+        def step(a):
+            o, r, d, _ = env.step(a)
+            return o, r, d
+        n_obs, n_act = env.observation_space.shape[0], env.action_space.shape[0]
+    policy = MlpPolicy(n_obs, n_act)
+    if ck["policy"]["pi.0.weight"].shape[1] != n_obs:
+        raise SystemExit("%s holds a policy over %d observation columns, this env gives %d: it was not written by this "
+                         "train_parallel" % (args.model, ck["policy"]["pi.0.weight"].shape[1], n_obs))
+    policy.load_state_dict(ck["policy"])
     logger = Logger(args.pause)
-    obs = env.reset()
-    for step in range(args.steps):
+    obs = reset()
+    for i in range(args.steps):
         with torch.no_grad():
             action, _, _ = policy.act(torch.as_tensor(obs, dtype=torch.float32)[None], deterministic=True)
-        obs, reward, done, _ = env.step(np.clip(action[0].numpy(), -1.0, 1.0).astype(np.float32))
-        logger.log(step, reward)
+        obs, reward, done = step(np.clip(action[0].numpy(), -1.0, 1.0).astype(np.float32))
+        logger.log(i, reward)
         if done:
-            obs = env.reset()
+            obs = reset()
     return logger.total
 
 

@@ -335,6 +335,40 @@ int rb_params_ptr(rb_sim *sim, float **d_params, uint32_t **d_draws);
 int rb_params_set_ranges(rb_sim *sim, const float *lo, const float *hi, int resample_on_reset);
 int rb_params_sample_dev(rb_sim *sim, const uint8_t *d_mask);
 
+/* ---- tendon channels in the fused env step's observation (ABI 6, additive) ----
+ * Ball-joint robots (1..16 tendons) only; a joint tree is refused with RB_EUNSUPPORTED.  With a channel mask set, the rows that
+ * rb_env_step_dev, rb_env_step_range_dev and rb_env_reset_dev write are
+ *   [q (n_q), qd (n_q), goal (n_q), then per selected channel in the order length, rate, activation, force: n_t values],
+ * obs_dim = 3 n_q + C n_t floats (C = the number of selected channels; MsjRobot with length and force: 25), row stride obs_dim: the
+ * caller's observation array holds n_envs * obs_dim floats, and rb_env_step_range_dev applies first_env * obs_dim to it.  The first
+ * 3 n_q columns and every other output of the step are what they are without the mask.
+ * The tendon columns are the quantities of the tendon state readout above (m, m/s, [0, 1], N) at the state the row reports, under
+ * the set-points the step has just applied, held, and - on a handle with per-env parameters - under the parameters the env's NEXT
+ * step will use: what that step's first acceleration evaluation sees if the action is repeated.  On a handle without parameters
+ * that is what rb_tendon_state_dev returns behind the step for the same actions under RB_SP_ENV; an env that was done and
+ * auto-reset reports the zero pose under the last actions, with resample_on_reset under its REDRAWN parameters.  rb_env_reset_dev
+ * writes the columns of the zero pose with every set-point 0 (plus the env's set-point offset, on a handle with parameters).
+ * Each channel is multiplied by its scale (scale[4] in channel order, NULL = ones; one rounded fp32 multiply, no shift).
+ * While a mask is set, the env-step entries launch the extended kernels (csrc/env_obs.hpp), one env per lane in the nominal or the
+ * parameter form, whatever rb_select_kernel chose, and rb_dispatch_current refuses RB_ENTRY_ENV_STEP with RB_EUNSUPPORTED; the
+ * step entries are untouched.
+ *   configure: needs rb_env_configure; mask 0 switches the extension off (the handle's own kernels again); evicts the cached
+ *              rollout graphs; RB_EINVAL for unknown bits and for a scale that is not finite.
+ *   obs_dim:   the row width of the handle as configured (3 n_q without a mask).
+ *   obs_count: 3 n_q + popcount(mask) n_t, without a handle or a device; -1 for unknown bits or negative counts.
+ * RB_ABI_VERSION is still 6 (nothing that existed changed), so the number does not tell a consumer whether these three functions
+ * are there: look the symbol up (dlsym of the configure function) before relying on them. */
+enum rb_obs_channel {
+    RB_OBS_LENGTH = 1,
+    RB_OBS_RATE = 2,
+    RB_OBS_ACTIVATION = 4,
+    RB_OBS_FORCE = 8,
+    RB_OBS_ALL = 15
+};
+int rb_env_obs_configure(rb_sim *sim, uint32_t channel_mask, const float *scale);
+int rb_env_obs_dim(rb_sim *sim, int32_t *obs_dim);
+int32_t rb_env_obs_count(int32_t n_q, int32_t n_t, uint32_t channel_mask);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
