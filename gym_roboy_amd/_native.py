@@ -77,6 +77,15 @@ class EnvConfig(ctypes.Structure):
                 ("goal_angle_tol", ctypes.c_float), ("goal_vel_tol", ctypes.c_float)]
 
 
+RB_IO_MAX_DELAY = 7
+
+
+class EnvIoConfig(ctypes.Structure):
+    """rb_env_io_config: sensor-noise standard deviations and the action-delay range of the fused env step"""
+    _fields_ = [("sigma_q", ctypes.c_float), ("sigma_qd", ctypes.c_float), ("sigma_tendon", ctypes.c_float * 4),
+                ("delay_lo", ctypes.c_int32), ("delay_hi", ctypes.c_int32), ("resample_on_reset", ctypes.c_int32), ("_pad", ctypes.c_int32)]
+
+
 _vp = ctypes.c_void_p
 _fp = ctypes.POINTER(ctypes.c_float)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -131,6 +140,10 @@ SIGNATURES = {
     "rb_env_obs_configure": (ctypes.c_int, [_sim, ctypes.c_uint32, _fp]),
     "rb_env_obs_dim": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_int32)]),
     "rb_env_obs_count": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32]),
+    "rb_env_io_configure": (ctypes.c_int, [_sim, ctypes.POINTER(EnvIoConfig)]),
+    "rb_env_io_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                     ctypes.POINTER(ctypes.c_int32)]),
+    "rb_env_io_sample_delay_dev": (ctypes.c_int, [_sim, _vp]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

@@ -52,12 +52,17 @@ template <typename CONST> struct NtOf { static constexpr int N = std::is_same<CO
 
 // What the parameter form's policy needs to hold an auto-reset env's columns under its redrawn parameters: the action row and the
 // planes again.  Nominal form: nothing (the offsets do not depend on the episode).
+// (NOISY: the type also has noise(row, obs_dim, i), called with the lane's finished row where it has just been written - its LDS row
+// or its row of the observation array - before the row leaves; MAYBE_EMPTY: the mask may be 0, nine columns and no tendon evaluated.
+// Both are env_io.hpp's.)
 struct NoRefresh {
+    static constexpr bool NOISY = false, MAYBE_EMPTY = false;
     template <bool WRITTEN_OUT, typename CONST>
     __device__ __forceinline__ void run(const CONST &, const HeldOffsets &, int, long) const {}
 };
 template <typename ARGS, typename PA>
 struct ParamRefresh {
+    static constexpr bool NOISY = false, MAYBE_EMPTY = false;
     ARGS a;
     PA pa;
     template <bool WRITTEN_OUT, typename CONST>
@@ -112,6 +117,7 @@ struct TendonObs {
         } else {
             rbk::PlainObs::store9(row, o);
         }
+        if constexpr (REFRESH::MAYBE_EMPTY) { if (!mask) return; }
         const float s_len = ox->scale[0], s_rate = ox->scale[1], s_act = ox->scale[2], s_force = ox->scale[3];
         const bool want_force = (mask & CH_FORCE) != 0;
         const typename M::Frame f = M::frame(qq, vv);
@@ -150,6 +156,7 @@ struct TendonObs {
         if (PARAMS && reset) refresh.template run<WRITTEN_OUT>(c, held, nt, i);
         if (!ox->staged) {                        // (wave-uniform: the rows do not fit into LDS beside the step's columns)
             write_row<false>(obs + i * od, o, qq, vv, nt);
+            if constexpr (REFRESH::NOISY) refresh.noise(obs + i * od, od, i);
             return;
         }
         // The wave's 64 rows are one contiguous run of 256 obs_dim bytes, 16-byte aligned (a launch starts at a multiple of 256
@@ -160,6 +167,7 @@ struct TendonObs {
         const int lane = int(threadIdx.x) & 63, wave = int(threadIdx.x) >> 6;
         float *wrow = obs_stage + wave * 64 * od;
         write_row<true>(wrow + lane * od, o, qq, vv, nt);
+        if constexpr (REFRESH::NOISY) refresh.noise(wrow + lane * od, od, i);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (one wave: LDS instructions execute in issue order)
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -174,7 +182,7 @@ struct TendonObs {
     }
 };
 
-// The extension the env-step bodies take in NoObsExt's place.  BK: the robot's constants are literals, the ObsArgs argument is read
+// The extension the env-step bodies take in NoObsExt's place (action row and episode-end hook as NoObsExt's).  BK: the robot's constants are literals, the ObsArgs argument is read
 // directly; otherwise through the late pointer, OFF bytes behind the launch's MsjEnvArgs.
 template <int NT, bool BK, int OFF>
 struct ObsExt {
@@ -184,12 +192,15 @@ struct ObsExt {
         if constexpr (BK) return direct;
         else return (const __attribute__((address_space(4))) ObsArgs<NT> *)((kernarg_bytes)la + OFF);
     }
-    template <bool IN_LDS, typename ARGS, typename CONST>
-    __device__ __forceinline__ auto policy(ARGS la, const CONST &c, const HeldOffsets &held, long i) const {
+    __device__ __forceinline__ rbk::HandedRow applied(const uint32_t *, const float *act, long i, int nt) const { return rbk::HandedRow{act + i * nt}; }
+    template <typename ARGS, typename HOOK>
+    __device__ __forceinline__ HOOK done_hook(ARGS, const HOOK &h) const { return h; }
+    template <bool IN_LDS, typename ARGS, typename AP, typename CONST>
+    __device__ __forceinline__ auto policy(ARGS la, const AP &, const CONST &c, const HeldOffsets &held, long i) const {
         return TendonObs<CONST, decltype(view(la)), BK && !IN_LDS, false, NoRefresh>{c, view(la), held, NoRefresh{}, la->cnt - (i - (long(threadIdx.x) & 63))};
     }
-    template <bool IN_LDS, typename ARGS, typename PA, typename CONST>
-    __device__ __forceinline__ auto policy(ARGS la, PA pa, const CONST &c, const HeldOffsets &held, long i) const {
+    template <bool IN_LDS, typename ARGS, typename PA, typename AP, typename CONST>
+    __device__ __forceinline__ auto policy(ARGS la, PA pa, const AP &, const CONST &c, const HeldOffsets &held, long i) const {
         return TendonObs<CONST, decltype(view(la)), BK && !IN_LDS, true, ParamRefresh<ARGS, PA>>{c, view(la), held, ParamRefresh<ARGS, PA>{la, pa}, la->cnt - (i - (long(threadIdx.x) & 63))};
     }
 };

@@ -233,7 +233,8 @@ struct RedrawParams {
     _Pragma("unroll")                                                                                                               \
     for (int j = 0; j < 3; ++j) { qq[j] = q[j * n + i]; vv[j] = qd[j * n + i]; gg[j] = goal[j * n + i]; }                           \
     /* clamp, slope * (x - in_high) + out_high with two roundings (roboy_env.py:157-158), + the env's offset, -> activation offset  */ \
-    auto setpoint = [&](float x, float o) { return rbe::mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi) + o; };    \
+    decltype((OX).applied(a.step_num, act, i, 0)) ap{};        /* the row the lane steps with: named where each branch reads it */ \
+    auto setpoint = [&](float x, float o) { return (ap.rest ? 0.0f : rbe::mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi)) + o; }; \
     BodyScale bs;                                                                                                                   \
     bool ok;                                                                                                                        \
     rbk::HeldOffsets held{nullptr, nullptr, 1};                                                                                     \
@@ -242,7 +243,8 @@ struct RedrawParams {
     if constexpr (X) {                                                                                                              \
         __shared__ float lds[2 * NTX][BLOCK];                                                                                       \
         const int nt = c.nt;                                                                                                        \
-        const float *row = act + i * nt;                                                                                            \
+        ap = (OX).applied(a.step_num, act, i, nt);                                                                                  \
+        const float *row = ap.row;                                                                                                  \
         for (int k = 0; k < nt; ++k) {                                                                                              \
             lds[k][threadIdx.x] = setpoint(row[k], par[(nt + k) * n + i]) * c.ten[k].ksg;                                           \
             lds[NTX + k][threadIdx.x] = par[k * n + i];                                                                             \
@@ -253,8 +255,9 @@ struct RedrawParams {
         ok = rb::MsjModel<float, NTX>::template integrate_acc<INTEG>(c, qq, vv, AccelScaledLds<NTX, true>{c, &lds[0][threadIdx.x], BLOCK, bs}); \
         held = rbk::HeldOffsets{&lds[0][threadIdx.x], &lds[NTX][threadIdx.x], BLOCK};                                               \
     } else {                                                                                                                        \
-        const float4 a0 = reinterpret_cast<const float4 *>(act)[2 * i];                                                             \
-        const float4 a1 = reinterpret_cast<const float4 *>(act)[2 * i + 1];                                                         \
+        ap = (OX).applied(a.step_num, act, i, NT8);                                                                                 \
+        const float4 a0 = reinterpret_cast<const float4 *>(ap.row)[0];                                                              \
+        const float4 a1 = reinterpret_cast<const float4 *>(ap.row)[1];                                                              \
         const float av[NT8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};                                                     \
     _Pragma("unroll")                                                                                                               \
         for (int k = 0; k < NT8; ++k) {                                                                                             \
@@ -276,12 +279,12 @@ struct RedrawParams {
         }                                                                                                                           \
     }                                                                                                                               \
     if constexpr (BK) {                                                                                                             \
-        rbk::env_account(&a, i, qq, vv, gg, ok, RedrawParams<const ParamArgs *>{&pa}, (OX).template policy<IN_LDS>(&a, &pa, c, held, i)); \
+        rbk::env_account(&a, i, qq, vv, gg, ok, (OX).done_hook(&a, RedrawParams<const ParamArgs *>{&pa}), (OX).template policy<IN_LDS>(&a, &pa, ap, c, held, i)); \
     } else {                                                                                                                        \
         const rbk::msj_env_kernarg_ptr la = rbk::late_env_args(rbk::msj_env_args_offset(int(sizeof(CONST))));                       \
         const param_kernarg_ptr lp = (param_kernarg_ptr)((const __attribute__((address_space(4))) char *)la - rbk::msj_env_args_offset(int(sizeof(CONST))) + \
                                                          param_args_offset(int(sizeof(CONST))));                                    \
-        rbk::env_account(la, i, qq, vv, gg, ok, RedrawParams<param_kernarg_ptr>{lp}, (OX).template policy<IN_LDS>(la, lp, c, held, i)); \
+        rbk::env_account(la, i, qq, vv, gg, ok, (OX).done_hook(la, RedrawParams<param_kernarg_ptr>{lp}), (OX).template policy<IN_LDS>(la, lp, ap, c, held, i)); \
     }
 template <int INTEG, int BLOCK, typename CONST, bool BK>
 __global__ void __launch_bounds__(BLOCK)

@@ -435,21 +435,32 @@ __device__ __forceinline__ void env_account(ARGS a, long i, float (&qq)[3], floa
 // The activation offsets a lane stepped with, for the observation policy behind the step: u[k * stride] is tendon k's - the lane's
 // registers (stride 1) or its LDS column (stride BLOCK); fs likewise the force scales of the parameter form (env_params.hpp)
 struct HeldOffsets { float *u, *fs; int stride; };
-// The fused env step without an extension of the observation: env_account's own row.  An extension (env_obs.hpp: ObsExt) makes
-// the policy from the launch's late argument pointer, the robot's constants and the held offsets (IN_LDS: they are an LDS column).
+// The action row a lane steps with, as the extension's applied() names it: `row` is read like the caller's row, `rest` says that the
+// step takes the rest command instead (every set-point 0 m: env_io.hpp, an env whose delayed command lies before its episode)
+struct HandedRow { const float *row; static constexpr bool rest = false; };
+// The fused env step without an extension: the caller's action row, the body's own hook, env_account's own row.  An extension
+// (env_obs.hpp: ObsExt; env_io.hpp: IoExt) makes the policy from the launch's late argument pointer, the row that was applied, the
+// robot's constants and the held offsets (IN_LDS: they are an LDS column).
 struct NoObsExt {
-    template <bool IN_LDS, typename ARGS, typename CONST>
-    __device__ __forceinline__ PlainObs policy(ARGS, const CONST &, const HeldOffsets &, long) const { return PlainObs{}; }
-    template <bool IN_LDS, typename ARGS, typename PA, typename CONST>      // the parameter form (env_params.hpp: PA views its ParamArgs)
-    __device__ __forceinline__ PlainObs policy(ARGS, PA, const CONST &, const HeldOffsets &, long) const { return PlainObs{}; }
+    // the action row that drives env i's step: the one the caller handed in (env_io.hpp: a row of the env's history, or the rest command)
+    __device__ __forceinline__ HandedRow applied(const uint32_t *, const float *act, long i, int nt) const { return HandedRow{act + i * nt}; }
+    // env_account's episode-end hook: the body's own (env_io.hpp: the delay's redraw behind it)
+    template <typename ARGS, typename HOOK>
+    __device__ __forceinline__ HOOK done_hook(ARGS, const HOOK &h) const { return h; }
+    template <bool IN_LDS, typename ARGS, typename AP, typename CONST>
+    __device__ __forceinline__ PlainObs policy(ARGS, const AP &, const CONST &, const HeldOffsets &, long) const { return PlainObs{}; }
+    template <bool IN_LDS, typename ARGS, typename PA, typename AP, typename CONST>      // the parameter form (env_params.hpp: PA views its ParamArgs)
+    __device__ __forceinline__ PlainObs policy(ARGS, PA, const AP &, const CONST &, const HeldOffsets &, long) const { return PlainObs{}; }
 };
 
 // The body of the fused env step, as text: a kernel reads its by-value arguments (c_arg, a) in place in the kernel-argument segment,
 // and a function between the kernel and this code - arguments by reference or by value - makes the compiler load them another way
 // (wider or narrower scalar loads, other registers: 18 kernel instances came out different).  So the kernels of env_obs.hpp, which are
-// this step with tendon columns behind it, expand the same text with their extension for OX.  Uses the kernel's template parameters
-// INTEG, BLOCK, UNROLL (0: run-time tendon count - ConstX, c.nt tendons, action rows of c.nt floats), CONST and BK by name, and its
-// arguments c_arg and a; comments inside are block comments (a line comment would swallow the continuation).
+// this step with tendon columns behind it, and of env_io.hpp expand the same text with their extension for OX, which names the action
+// row a lane steps with (applied(): called where each branch reads the row - in front of the branches the ConstX instances came out
+// with other registers), wraps the episode-end hook (done_hook()) and makes the observation policy (policy()).  Uses the kernel's
+// template parameters INTEG, BLOCK, UNROLL (0: run-time tendon count - ConstX, c.nt tendons, action rows of c.nt floats), CONST and BK
+// by name, and its arguments c_arg and a; comments inside are block comments (a line comment would swallow the continuation).
 #define RB_MSJ_ENV_STEP_BODY(OX) \
     /* a.n: the handle's envs = the stride of the state / goal / statistics planes; a.cnt: the envs of THIS launch - all of them,  */ \
     /* or a sub-range (rb_env_step_range_dev: every pointer then points at the range's first env, a.env0 is its global id)          */ \
@@ -464,7 +475,8 @@ struct NoObsExt {
     for (int j = 0; j < 3; ++j) { qq[j] = q[j * n + i]; vv[j] = qd[j * n + i]; gg[j] = goal[j * n + i]; }                           \
     /* the reference asserts the action lies in [-1,1] (roboy_env.py:52); a batched kernel cannot raise, so it clamps.  Then        */ \
     /* slope * (x - in_high) + out_high, each op rounded (roboy_env.py:157-158)                                                     */ \
-    auto rescale = [&](float x) { return mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi); };                       \
+    decltype((OX).applied(a.step_num, act, i, 0)) ap{};        /* the row the lane steps with: named where each branch reads it */ \
+    auto rescale = [&](float x) { return ap.rest ? 0.0f : mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi); };      \
     bool ok;                                                                                                                        \
     HeldOffsets held{nullptr, nullptr, 1};                                                                                          \
     constexpr bool IN_LDS = UNROLL != RS && UNROLL < NT8;                                                                           \
@@ -472,14 +484,16 @@ struct NoObsExt {
     if constexpr (UNROLL == 0) {                                                                                                    \
         __shared__ float lds_sp[NTX][BLOCK];                                                                                        \
         const int nt = c.nt;                                                                                                        \
-        const float *row = act + i * nt;                                                                                            \
+        ap = (OX).applied(a.step_num, act, i, nt);                                                                                  \
+        const float *row = ap.row;                                                                                                  \
         for (int k = 0; k < nt; ++k) lds_sp[k][threadIdx.x] = rescale(row[k]) * c.ten[k].ksg;                                       \
         ok = rb::MsjModel<float, NTX>::template step_sp<INTEG, 0>(c, qq, vv, SpLds{&lds_sp[0][threadIdx.x], BLOCK});                \
         held = HeldOffsets{&lds_sp[0][threadIdx.x], nullptr, BLOCK};                                                                \
     } else {                                                                                                                        \
     held.u = sp;                                                                                                                    \
-    const float4 a0 = reinterpret_cast<const float4 *>(act)[2 * i];                                                                 \
-    const float4 a1 = reinterpret_cast<const float4 *>(act)[2 * i + 1];                                                             \
+    ap = (OX).applied(a.step_num, act, i, NT8);                                                                                     \
+    const float4 a0 = reinterpret_cast<const float4 *>(ap.row)[0];                                                                  \
+    const float4 a1 = reinterpret_cast<const float4 *>(ap.row)[1];                                                                  \
     const float av[NT8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};                                                         \
     _Pragma("unroll")                                                                                                               \
     for (int k = 0; k < NT8; ++k) sp[k] = rescale(av[k]) * c.ten[k].ksg;                                                            \
@@ -498,10 +512,10 @@ struct NoObsExt {
     }                                                                                                                               \
     }                                                                                                                               \
     if constexpr (BK) {                                                                                                             \
-        env_account(&a, i, qq, vv, gg, ok, NoDoneHook{}, (OX).template policy<IN_LDS>(&a, c, held, i));                             \
+        env_account(&a, i, qq, vv, gg, ok, (OX).done_hook(&a, NoDoneHook{}), (OX).template policy<IN_LDS>(&a, ap, c, held, i));     \
     } else {                                                                                                                        \
         const msj_env_kernarg_ptr la = late_env_args(msj_env_args_offset(int(sizeof(CONST))));                                      \
-        env_account(la, i, qq, vv, gg, ok, NoDoneHook{}, (OX).template policy<IN_LDS>(la, c, held, i));                             \
+        env_account(la, i, qq, vv, gg, ok, (OX).done_hook(la, NoDoneHook{}), (OX).template policy<IN_LDS>(la, ap, c, held, i));     \
     }
 template <int INTEG, int BLOCK, int UNROLL, typename CONST = Const8, bool BK = false>
 __global__ void __launch_bounds__(BLOCK)

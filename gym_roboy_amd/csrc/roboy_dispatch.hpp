@@ -497,7 +497,7 @@ inline const Row *row_for(rb_sim *s, int entry, bool build, std::string *why = n
 int params_launch(rb_sim *s, int entry, const Launch &L);      // (roboy_sim.hip)
 int obs_launch(rb_sim *s, const Launch &L);
 inline int dispatch(rb_sim *s, int entry, const Launch &L) {
-    if (entry == ENTRY_ENV && s->obs_mask) {
+    if (entry == ENTRY_ENV && (s->obs_mask || s->io)) {      // (obs_launch: the io kernels while rb_env_io_configure holds)
         const int rc = obs_launch(s, L);
         if (rc) return rc;
         RB_HIP(hipGetLastError());

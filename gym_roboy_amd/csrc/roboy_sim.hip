@@ -46,6 +46,7 @@
 #include "tendon_state.hpp"           // the tendon-state readout (rb_tendon_state_dev)
 #include "env_params.hpp"             // per-env physical parameters (rb_params_*)
 #include "env_obs.hpp"                // tendon channels in the fused env step's observation (rb_env_obs_*)
+#include "env_io.hpp"                 // per-env action latency and sensor noise in the fused env step (rb_env_io_*)
 
 namespace {
 
@@ -537,6 +538,13 @@ struct rb_sim {
     int obs_mask = 0;
     float obs_scale[4] = {1.0f, 1.0f, 1.0f, 1.0f};
     int obs_dim() const { return 3 * n_q + rbo::n_channels(obs_mask) * n_t; }
+    // action latency and sensor noise of the env step (env_io.hpp; rb_env_io_*): while configured, the env-step entry launches the io
+    // kernels - nominal or parameter form, with or without channels.  Planes [n] each; the ring [io_slots][n][n_t] only with delay_hi > 0
+    bool io = false;
+    rb_env_io_config io_cfg = {};
+    uint32_t *d_io_delay = nullptr, *d_io_draws = nullptr, *d_io_rows = nullptr;
+    float *d_io_hist = nullptr;
+    int io_slots = 0;
 };
 
 namespace {
@@ -800,9 +808,9 @@ int params_launch_integ(rb_sim *s, int entry, const Launch &L) {
 }
 // ---- tendon channels in the observation (env_obs.hpp): what dispatch() launches for the env-step entry while a mask is set ----
 // dynamic LDS of an extended env-step launch: the rows of its 256 envs, where they fit beside the instance's own columns (0: per-lane stores)
-size_t obs_stage_bytes(const rb_sim *s) {
-    const size_t columns = (s->baked ? 0 : s->ntx ? 4 * 256 * NTX : 4 * 256 * NT8) * (s->params ? 2 : 1);
-    const size_t rows = size_t(4) * 256 * s->obs_dim();
+size_t obs_stage_bytes(const rb_sim *s, int block = 256) {
+    const size_t columns = (s->baked ? 0 : s->ntx ? 4 * block * NTX : 4 * block * NT8) * (s->params ? 2 : 1);
+    const size_t rows = size_t(4) * block * s->obs_dim();
     return columns + rows <= 65536 ? rows : 0;
 }
 template <int NT>
@@ -838,8 +846,73 @@ int obs_launch_integ(rb_sim *s, const Launch &L) {
     }
     return RB_OK;
 }
+// ---- action latency and sensor noise (env_io.hpp): what dispatch() launches for the env-step entry while rb_env_io_configure holds ----
+// first: the launch's first env (the planes and the ring inside each slot are shifted by it)
+rbio::IoArgs io_args(const rb_sim *s, long first) {
+    rbio::IoArgs io;
+    std::memset(&io, 0, sizeof(io));
+    const rb_env_io_config &cfg = s->io_cfg;
+    io.delay = s->d_io_delay + first; io.delay_draws = s->d_io_draws + first; io.rows = s->d_io_rows + first;
+    io.hist = s->d_io_hist ? s->d_io_hist + first * s->n_t : nullptr;
+    io.slot_stride = long(s->n) * s->n_t;
+    io.slot_mask = s->io_slots ? s->io_slots - 1 : 0;
+    io.delay_lo = cfg.delay_lo; io.delay_hi = cfg.delay_hi; io.resample = cfg.resample_on_reset ? 1 : 0;
+    // row positions: q, qd, (goal: never), then the selected channels in row order, each sigma in the units the column reports (x scale)
+    const int nq = s->n_q;
+    for (int j = 0; j < nq; ++j) { io.colsig[j] = cfg.sigma_q; io.colsig[nq + j] = cfg.sigma_qd; }
+    int col = 3 * nq;
+    for (int ch = 0; ch < 4; ++ch)
+        if (s->obs_mask >> ch & 1)
+            for (int k = 0; k < s->n_t; ++k) io.colsig[col++] = cfg.sigma_tendon[ch] * s->obs_scale[ch];
+    for (int c = 0; c < col; ++c)
+        if (io.colsig[c] != 0.0f) io.noise_blocks |= 1u << (c >> 2);
+    return io;
+}
+template <int INTEG>
+int io_launch_integ(rb_sim *s, const Launch &L) {
+    constexpr int B = 256;
+    MsjEnvArgs a = msj_env_args(s, L);
+    a.obs = L.obs + L.i0 * s->obs_dim();
+    const rbio::IoArgs io = io_args(s, L.i0);
+    // An io kernel is the text of the kernel it stands in for.  Without parameters and channels that is the table's env-per-lane
+    // row, which for MsjRobot's baked constants at small batches is the 64-thread instance with tendons AND integrator stages written
+    // out - another summation order of the RK4 stages than the large-batch text (rolled stages): a configuration of zeros steps like
+    // no configuration there too.  (Kernarg constants: the large-batch text's rolled tendon loop adds the same terms in the same order
+    // as the written-out 64-thread row, and that row has no scalar register to spare - with the io arguments it would spill.)
+    if (!s->params && !s->obs_mask && s->baked && s->n <= RB_SMALL_BATCH) {
+        const size_t lds = obs_stage_bytes(s, 64);
+        hipLaunchKernelGGL((rbio::msj_io_env_step<INTEG, 64, 8, Const8, true>), dim3(blocks_for(L.cnt, 64)), dim3(64), lds, L.stream, s->c8, a,
+                           obs_args<NT8>(s, lds != 0), io);
+        return RB_OK;
+    }
+    const size_t lds = obs_stage_bytes(s);
+    const dim3 grid(blocks_for(L.cnt, B)), block(B);
+    constexpr int UB = INTEG == 0 ? UBE : UBR, UK = INTEG == 0 ? UKE : UKR;
+    if (s->params) {
+        const rbp::ParamArgs pa{s->d_params + L.i0, s->d_param_draws + L.i0, s->d_param_ranges, s->n, s->n_params, s->param_resample ? 1 : 0};
+        if (s->ntx)
+            hipLaunchKernelGGL((rbio::msj_io_params_env_step<INTEG, B, ConstX, false>), grid, block, lds, L.stream, s->cx, a, pa, obs_args<NTX>(s, lds != 0), io);
+        else if (s->baked)
+            hipLaunchKernelGGL((rbio::msj_io_params_env_step<INTEG, B, Const8, true>), grid, block, lds, L.stream, s->c8, a, pa, obs_args<NT8>(s, lds != 0), io);
+        else
+            hipLaunchKernelGGL((rbio::msj_io_params_env_step<INTEG, B, Const8, false>), grid, block, lds, L.stream, s->c8, a, pa, obs_args<NT8>(s, lds != 0), io);
+    } else if (s->ntx) {
+        hipLaunchKernelGGL((rbio::msj_io_env_step<INTEG, B, 0, ConstX, false>), grid, block, lds, L.stream, s->cx, a, obs_args<NTX>(s, lds != 0), io);
+    } else if (s->baked) {
+        hipLaunchKernelGGL((rbio::msj_io_env_step<INTEG, B, UB, Const8, true>), grid, block, lds, L.stream, s->c8, a, obs_args<NT8>(s, lds != 0), io);
+    } else {
+        hipLaunchKernelGGL((rbio::msj_io_env_step<INTEG, B, UK, Const8, false>), grid, block, lds, L.stream, s->c8, a, obs_args<NT8>(s, lds != 0), io);
+    }
+    return RB_OK;
+}
+void io_free(rb_sim *s) {
+    (void)hipFree(s->d_io_delay); (void)hipFree(s->d_io_draws); (void)hipFree(s->d_io_rows); (void)hipFree(s->d_io_hist);
+    s->d_io_delay = nullptr; s->d_io_draws = nullptr; s->d_io_rows = nullptr; s->d_io_hist = nullptr;
+    s->io = false; s->io_slots = 0;
+}
 int obs_launch(rb_sim *s, const Launch &L) {
     if (L.cnt <= 0) return RB_OK;
+    if (s->io) return s->integrator == RB_EULER ? io_launch_integ<0>(s, L) : io_launch_integ<1>(s, L);
     return s->integrator == RB_EULER ? obs_launch_integ<0>(s, L) : obs_launch_integ<1>(s, L);
 }
 // rb_env_reset_dev's observation rows on such a handle: the state the reset kernel has just written, every set-point 0
@@ -1047,6 +1120,7 @@ void rb_destroy(rb_sim *s) {
     (void)hipFree(s->d_goal); (void)hipFree(s->d_ep_ret); (void)hipFree(s->d_ep_sum); (void)hipFree(s->d_ep_cnt);
     (void)hipFree(s->d_step_num); (void)hipFree(s->d_infeas_n); (void)hipFree(s->d_stats);
     params_free(s);
+    io_free(s);
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1510,6 +1584,13 @@ int rb_env_reset_dev(rb_sim *s, float *d_obs) {
         obs_rows_launch(s, d_obs);
         RB_HIP(hipGetLastError());
     }
+    if (s->io && d_obs) {                     // sensor readings too: the rows' noise, in place (the episode restarts, the history needs nothing)
+        const rbio::IoArgs io = io_args(s, 0);
+        if (io.noise_blocks) {
+            hipLaunchKernelGGL(rbio::io_noise_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, s->obs_dim(), io, s->n, s->seed, uint64_t(s->env0));
+            RB_HIP(hipGetLastError());
+        }
+    }
     return RB_OK;
 }
 
@@ -1537,6 +1618,64 @@ int rb_env_obs_configure(rb_sim *s, uint32_t channel_mask, const float *scale) {
     for (int c = 0; c < 4; ++c) s->obs_scale[c] = scale ? scale[c] : 1.0f;
     return RB_OK;
 }
+// ---- per-env action latency and sensor noise in the fused env step (env_io.hpp) ----
+int rb_env_io_configure(rb_sim *s, const rb_env_io_config *cfg) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
+    if (cfg) {
+        const float sig[6] = {cfg->sigma_q, cfg->sigma_qd, cfg->sigma_tendon[0], cfg->sigma_tendon[1], cfg->sigma_tendon[2], cfg->sigma_tendon[3]};
+        for (float v : sig)
+            if (!std::isfinite(v) || v < 0.0f) return fail(RB_EINVAL, "sensor-noise standard deviations must be finite and >= 0");
+        if (cfg->delay_lo < 0 || cfg->delay_lo > cfg->delay_hi || cfg->delay_hi > RB_IO_MAX_DELAY)
+            return fail(RB_EINVAL, "action delay: 0 <= delay_lo <= delay_hi <= RB_IO_MAX_DELAY");
+        if (s->tree)
+            return fail(RB_EUNSUPPORTED, "action latency and sensor noise are built for ball-joint robots (1-16 tendons); joint trees have none");
+    }
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);                       // nothing in flight may still use the planes or the ring
+    if (rc) return rc;
+    rc = drop_graphs(s);
+    if (rc) return rc;
+    io_free(s);
+    if (!cfg) return RB_OK;
+    const size_t n = size_t(s->n);
+    RB_HIP(hipMalloc(&s->d_io_delay, sizeof(uint32_t) * n));
+    RB_HIP(hipMalloc(&s->d_io_draws, sizeof(uint32_t) * n));
+    RB_HIP(hipMalloc(&s->d_io_rows, sizeof(uint32_t) * n));
+    RB_HIP(hipMemsetAsync(s->d_io_draws, 0, sizeof(uint32_t) * n, s->stream));
+    RB_HIP(hipMemsetAsync(s->d_io_rows, 0, sizeof(uint32_t) * n, s->stream));
+    s->io_slots = 0;
+    if (cfg->delay_hi > 0) {
+        s->io_slots = 1;
+        while (s->io_slots <= cfg->delay_hi) s->io_slots *= 2;
+        const size_t bytes = sizeof(float) * size_t(s->io_slots) * n * size_t(s->n_t);
+        RB_HIP(hipMalloc(&s->d_io_hist, bytes));
+        RB_HIP(hipMemsetAsync(s->d_io_hist, 0, bytes, s->stream));
+    }
+    s->io_cfg = *cfg;
+    s->io = true;
+    return rb_env_io_sample_delay_dev(s, nullptr);      // draw 0 of every env
+}
+int rb_env_io_ptr(rb_sim *s, uint32_t **d_delay, uint32_t **d_delay_draws, uint32_t **d_rows, float **d_history, int32_t *slots) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->io) return fail(RB_EINVAL, "no io configuration (rb_env_io_configure)");
+    if (d_delay) *d_delay = s->d_io_delay;
+    if (d_delay_draws) *d_delay_draws = s->d_io_draws;
+    if (d_rows) *d_rows = s->d_io_rows;
+    if (d_history) *d_history = s->d_io_hist;
+    if (slots) *slots = s->io_slots;
+    return RB_OK;
+}
+int rb_env_io_sample_delay_dev(rb_sim *s, const uint8_t *d_mask) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->io) return fail(RB_EINVAL, "no io configuration (rb_env_io_configure)");
+    RB_HIP(hipSetDevice(s->device));
+    hipLaunchKernelGGL(rbio::io_sample_delay, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->d_io_delay, s->d_io_draws, d_mask,
+                       s->io_cfg.delay_lo, s->io_cfg.delay_hi, long(s->n), s->seed, uint64_t(s->env0));
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
+
 int rb_env_obs_dim(rb_sim *s, int32_t *obs_dim) {
     if (check(s) || !obs_dim) return fail(RB_EINVAL, "null argument");
     *obs_dim = s->obs_dim();
@@ -1612,7 +1751,7 @@ int rb_range_capable(rb_sim *s) {
     // builds what a launch would build (outside captures), then asks the table: bit 0 = the step's row takes sub-ranges, bit 1 = the env step's
     maybe_jit(s);
     const Row *step = row_for(s, ENTRY_STEP, true), *env = row_for(s, ENTRY_ENV, s->env_ready);
-    return (step && step->ranges ? 1 : 0) | (s->obs_mask || (env && env->ranges) ? 2 : 0);     // (env_obs.hpp's kernels take sub-ranges)
+    return (step && step->ranges ? 1 : 0) | (s->obs_mask || s->io || (env && env->ranges) ? 2 : 0);     // (env_obs.hpp's and env_io.hpp's kernels take sub-ranges)
 }
 
 static int stats_launch(rb_sim *s, double *d_out2) {
@@ -1755,6 +1894,8 @@ int rb_dispatch_current(rb_sim *s, int entry, rb_dispatch_row *out) {
     if (entry < ENTRY_STEP || entry > ENTRY_FUSED) return fail(RB_EINVAL, "unknown entry kind");
     if (entry == ENTRY_FUSED && (s->tree || s->ntx)) return fail(RB_EUNSUPPORTED, "fused rollout is built for 8-tendon ball-joint robots");
     if (s->params) return fail(RB_EUNSUPPORTED, "per-env parameters are enabled: the parameter kernels (env_params.hpp) are not rows of the dispatch table");
+    if (entry == ENTRY_ENV && s->io)
+        return fail(RB_EUNSUPPORTED, "an io configuration is set (rb_env_io_configure): the io env-step kernels (env_io.hpp) are not rows of the dispatch table");
     if (entry == ENTRY_ENV && s->obs_mask)
         return fail(RB_EUNSUPPORTED, "tendon channels are set (rb_env_obs_configure): the extended env-step kernels (env_obs.hpp) are not rows of the dispatch table");
     RB_HIP(hipSetDevice(s->device));

@@ -237,6 +237,33 @@ class HipBatchSimulation:
             nat.check(self._lib.rb_params_sample_dev(self._h, ctypes.c_void_p(self._d_param_mask)))
         self.synchronize()
 
+    # -- action latency and sensor noise of the fused env step (rb_env_io_*; ball-joint robots) -----
+    def configure_io(self, cfg):
+        """``cfg``: a ``_native.EnvIoConfig``, or None to switch the extension off.  Needs the env layer configured; resets the
+        delay plane, the counters and the action history."""
+        nat.check(self._lib.rb_env_io_configure(self._h, None if cfg is None else ctypes.byref(cfg)))
+
+    def io_ptrs(self) -> dict:
+        """device pointers: 'delay', 'delay_draws', 'rows' ([N] uint32 each), 'history' ([slots][N][n_t] float32 or None), 'slots'"""
+        p = [ctypes.c_void_p() for _ in range(4)]
+        slots = ctypes.c_int32()
+        nat.check(self._lib.rb_env_io_ptr(self._h, *[ctypes.byref(x) for x in p], ctypes.byref(slots)))
+        return dict(zip(("delay", "delay_draws", "rows", "history"), (x.value for x in p)), slots=int(slots.value))
+
+    def sample_io_delay(self, mask=None):
+        """Redraw the action delay of the masked envs (``mask`` [N] bool, None = all) from the configured range; synchronous."""
+        if mask is None:
+            nat.check(self._lib.rb_env_io_sample_delay_dev(self._h, None))
+        else:
+            m = np.ascontiguousarray(mask, dtype=np.uint8)
+            if m.shape != (self.n_envs,):
+                raise ValueError("mask must have shape (%d,)" % self.n_envs)
+            if self._d_param_mask is None:
+                self._d_param_mask = self.malloc(self.n_envs)
+            self.upload(self._d_param_mask, m)
+            nat.check(self._lib.rb_env_io_sample_delay_dev(self._h, ctypes.c_void_p(self._d_param_mask)))
+        self.synchronize()
+
     # -- device-pointer interface (no host copies) ------------------------
     def state_ptrs(self):
         q, qd, f = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()

@@ -54,6 +54,39 @@ def tendon_obs_scales(scale) -> np.ndarray:
     return out
 
 
+SENSOR_NOISE_KEYS = ("q", "qd") + TENDON_OBS_CHANNELS
+
+
+def sensor_noise_sigmas(sensor_noise, tendon_obs=()) -> np.ndarray:
+    """``{"q": 0.01, "force": 2.0, ...}`` (or None) -> six fp32 standard deviations ``[q, qd, length, rate, activation, force]``
+    in physical units, 0 where not given.  Keys: ``q``, ``qd`` and the channel names; a channel must be one of ``tendon_obs``."""
+    out = np.zeros(6, np.float32)
+    for k, v in dict(sensor_noise or {}).items():
+        if k not in SENSOR_NOISE_KEYS:
+            raise ValueError("sensor_noise: unknown key %r (takes %s)" % (k, SENSOR_NOISE_KEYS))
+        if k in TENDON_OBS_CHANNELS and k not in tuple(tendon_obs or ()):
+            raise ValueError("sensor_noise: channel %r is not in tendon_obs" % (k,))
+        if not np.isfinite(v) or v < 0:
+            raise ValueError("sensor_noise[%r] must be finite and >= 0" % (k,))
+        out[SENSOR_NOISE_KEYS.index(k)] = v
+    return out
+
+
+def action_delay_range(action_delay):
+    """``2`` -> ``(2, 2, False)``, ``(0, 3)`` -> ``(0, 3, True)`` (a range is redrawn on auto-reset), None -> ``(0, 0, False)``"""
+    if action_delay is None:
+        return 0, 0, False
+    if isinstance(action_delay, (int, np.integer)):
+        lo = hi = int(action_delay)
+        ranged = False
+    else:
+        lo, hi = (int(x) for x in action_delay)
+        ranged = True
+    if not 0 <= lo <= hi <= nat.RB_IO_MAX_DELAY:
+        raise ValueError("action_delay: 0 <= lo <= hi <= %d, got %r" % (nat.RB_IO_MAX_DELAY, action_delay))
+    return lo, hi, ranged
+
+
 class RoboyVecEnv:
 
     def __init__(self, robot: RoboyRobot, num_envs: int, seed: int = 0,
@@ -61,13 +94,22 @@ class RoboyVecEnv:
                  is_agent_getting_bonus_for_reaching_goal: bool = True,
                  auto_reset: bool = True, integrator="euler", n_substeps: int = 1,
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
-                 randomization=None, tendon_obs=None, tendon_obs_scale=None):
+                 randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
         ``[q, qd, goal, then n_t values per channel in that fixed order]``, the tendons' state at the reported state under the actions
         just applied (ball-joint robots); ``tendon_obs_scale``: ``{channel: factor}``, default 1 (m, m/s, [0, 1], N).
-        Combines with ``randomization``."""
+        Combines with ``randomization``.
+        ``sensor_noise``: ``{"q": 0.01, "qd": 0.05, "length": 5e-4, "force": 2.0}`` - Gaussian noise on the reported columns, standard
+        deviations in physical units (rad, rad/s, m, m/s, activation, N; a channel must be in ``tendon_obs``); the goal columns,
+        reward, done and the state are exact, and nothing is clipped to ``observation_space``, which is unchanged.
+        ``action_delay``: an int ``d`` - every step is driven by the action handed in ``d`` steps earlier in the same episode (the rest
+        command, every set-point 0, before that) - or a pair ``(lo, hi)``: each env draws its own delay, again at every auto-reset.
+        At most 7.  Both combine with ``randomization`` and ``tendon_obs``; ball-joint robots."""
+        obs_names = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
+        sig = sensor_noise_sigmas(sensor_noise, obs_names)               # (bad options: before anything is allocated)
+        d_lo, d_hi, ranged = action_delay_range(action_delay)
         self.robot = robot
         self.num_envs = int(num_envs)
         self.sim = HipBatchSimulation(robot, num_envs, integrator=integrator, n_substeps=n_substeps,
@@ -132,6 +174,17 @@ class RoboyVecEnv:
             # before anything is captured into a graph: the parameter kernels replace the handle's step kernels from here on
             self.sim.enable_params()
             self.sim.set_param_ranges(randomization, resample_on_reset=True)
+        self.sensor_noise = dict(sensor_noise or {})
+        self.action_delay = None if action_delay is None else ((d_lo, d_hi) if ranged else d_lo)
+        self._io = bool(sig.any() or d_hi > 0)
+        if self._io:
+            # after tendon_obs and randomization, before anything is captured into a graph: the io kernels replace the env-step kernels
+            io = nat.EnvIoConfig()
+            io.sigma_q, io.sigma_qd = float(sig[0]), float(sig[1])
+            for c in range(4):
+                io.sigma_tendon[c] = float(sig[2 + c])
+            io.delay_lo, io.delay_hi, io.resample_on_reset = d_lo, d_hi, int(ranged)
+            self.sim.configure_io(io)
 
     # ------------------------------------------------------------------
     def reset(self):
@@ -283,6 +336,24 @@ class RoboyVecEnv:
 
     def stats_dev(self, d_out8: int, reset: bool = False):
         nat.check(self.sim._lib.rb_env_stats_dev(self.sim.handle, ctypes.c_void_p(d_out8), int(reset)))
+
+    def get_action_delay(self) -> np.ndarray:
+        """Every env's action delay ``[N]`` (steps); needs ``sensor_noise`` or ``action_delay``."""
+        if not self._io:
+            raise RuntimeError("this RoboyVecEnv has no action delay (action_delay=None)")
+        self.sim.synchronize()
+        return self.sim.download(self.sim.io_ptrs()["delay"], (self.num_envs,), np.uint32).astype(np.int64)
+
+    def set_action_delay(self, delay):
+        """Overwrite every env's delay ``[N]``: integers in ``[0, hi]`` of the configured ``action_delay``."""
+        if not self._io:
+            raise RuntimeError("this RoboyVecEnv has no action delay (action_delay=None)")
+        d = np.asarray(delay)
+        hi = action_delay_range(self.action_delay)[1]
+        if d.shape != (self.num_envs,) or np.any(d < 0) or np.any(d > hi) or np.any(d != np.floor(d)):
+            raise ValueError("delay must be %d integers in [0, %d]" % (self.num_envs, hi))
+        self.sim.synchronize()
+        self.sim.upload(self.sim.io_ptrs()["delay"], np.ascontiguousarray(d, dtype=np.uint32))
 
     def get_params(self) -> dict:
         """Every env's physical parameters (``HipBatchSimulation.get_params``); needs ``randomization``."""

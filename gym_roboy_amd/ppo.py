@@ -350,6 +350,14 @@ def _tendon_obs_of(env):
     return {"channels": list(channels), "scale": scale}
 
 
+def _env_io_of(env):
+    """What a checkpoint records about the conditions the policy was trained under (RoboyVecEnv's sensor_noise and action_delay):
+    not part of the observation's layout, so a checkpoint loads on any env - playback (visualize_agent) reads them back."""
+    delay = getattr(env, "action_delay", None)
+    return {"sensor_noise": {k: float(v) for k, v in dict(getattr(env, "sensor_noise", None) or {}).items()},
+            "action_delay": list(delay) if isinstance(delay, tuple) else delay}
+
+
 def _fused_kernels_apply(policy, obs_dim, act_dim):
     """MlpPolicy's shape (two hidden layers of 64 units per net) in dimensions the kernels of include/roboy_policy.h
     support, and the library is there."""
@@ -687,7 +695,7 @@ class PPO:
     def save(self, path):
         opt = self._fadam.state_dict() if self._fgrad is not None else self.opt.state_dict()
         torch.save({"policy": self.policy.state_dict(), "optimizer": opt, "num_timesteps": self.num_timesteps,
-                    "epoch": self._epoch, "tendon_obs": _tendon_obs_of(self.env)}, path)
+                    "epoch": self._epoch, "tendon_obs": _tendon_obs_of(self.env), "env_io": _env_io_of(self.env)}, path)
 
     def load(self, path):
         ck = torch.load(path, map_location=self.device)

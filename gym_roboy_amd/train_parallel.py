@@ -38,7 +38,18 @@ def main(argv=None):
                          "(e.g. length,force: 25 columns for MsjRobot); stored in the checkpoint")
     ap.add_argument("--tendon-obs-scale", default="", metavar="CHANNEL=FACTOR,...",
                     help="factor per channel, default 1 (m, m/s, [0,1], N), e.g. force=0.0025,length=4")
+    ap.add_argument("--sensor-noise", default="", metavar="KEY=SIGMA,...",
+                    help="Gaussian noise on the observation: standard deviations in physical units for q, qd and the selected tendon "
+                         "channels, e.g. q=0.01,qd=0.05,force=2; stored in the checkpoint")
+    ap.add_argument("--action-delay", default="", metavar="D | LO:HI",
+                    help="steps by which every action acts late (at most 7): one number, or a range each env draws from at every "
+                         "episode start, e.g. 0:3; stored in the checkpoint")
     args = ap.parse_args(argv)
+    sensor_noise = {k: float(v) for k, v in (item.split("=", 1) for item in args.sensor_noise.split(",") if item)}
+    action_delay = None
+    if args.action_delay:
+        parts = [int(x) for x in args.action_delay.split(":")]
+        action_delay = parts[0] if len(parts) == 1 else (parts[0], parts[1])
     tendon_obs = tuple(c for c in args.tendon_obs.split(",") if c)
     tendon_obs_scale = {k: float(v) for k, v in (item.split("=", 1) for item in args.tendon_obs_scale.split(",") if item)}
 
@@ -66,7 +77,8 @@ def main(argv=None):
         os.makedirs(results, exist_ok=True)
 
     env = RoboyVecEnv(MsjRobot(), args.num_envs, seed=args.seed, device=local_rank,
-                      env_id_offset=rank * args.num_envs, tendon_obs=tendon_obs or None, tendon_obs_scale=tendon_obs_scale or None)
+                      env_id_offset=rank * args.num_envs, tendon_obs=tendon_obs or None, tendon_obs_scale=tendon_obs_scale or None,
+                      sensor_noise=sensor_noise or None, action_delay=action_delay)
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,

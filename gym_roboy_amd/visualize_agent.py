@@ -41,11 +41,18 @@ def main(argv=None):
 
     ck = torch.load(args.model, map_location="cpu")
     tendon_obs = ck.get("tendon_obs", {}).get("channels", [])
-    if tendon_obs:
-        # trained with tendon channels in the observation (train_parallel --tendon-obs): the same row comes from a RoboyVecEnv of
-        # one env, which resets itself on done and returns the reset observation
+    env_io = ck.get("env_io", {})
+    sensor_noise, action_delay = env_io.get("sensor_noise") or None, env_io.get("action_delay")
+    if isinstance(action_delay, list):
+        action_delay = tuple(action_delay)
+    if tendon_obs or sensor_noise or action_delay:
+        # trained with tendon channels in the observation (train_parallel --tendon-obs), sensor noise or an action delay
+        # (--sensor-noise, --action-delay): the same row, under the same conditions, comes from a RoboyVecEnv of one env, which resets
+        # itself on done and returns the reset observation.  RoboyEnv, one env stepped from the host, offers neither noise nor delay.
         from .envs.vec_env import TENDON_OBS_CHANNELS, RoboyVecEnv
-        vec = RoboyVecEnv(MsjRobot(), 1, tendon_obs=tendon_obs, tendon_obs_scale=dict(zip(TENDON_OBS_CHANNELS, ck["tendon_obs"]["scale"])))
+        scale = dict(zip(TENDON_OBS_CHANNELS, ck["tendon_obs"]["scale"])) if tendon_obs else None
+        vec = RoboyVecEnv(MsjRobot(), 1, tendon_obs=tendon_obs or None, tendon_obs_scale=scale, sensor_noise=sensor_noise,
+                          action_delay=action_delay)
         reset = lambda: vec.reset()[0]
 
         def step(a):

@@ -369,6 +369,56 @@ int rb_env_obs_configure(rb_sim *sim, uint32_t channel_mask, const float *scale)
 int rb_env_obs_dim(rb_sim *sim, int32_t *obs_dim);
 int32_t rb_env_obs_count(int32_t n_q, int32_t n_t, uint32_t channel_mask);
 
+/* ---- per-env action latency and sensor noise in the fused env step (ABI 6, additive) ----
+ * Ball-joint robots (1..16 tendons) only; a joint tree is refused with RB_EUNSUPPORTED.  Opt-in per handle; composes with per-env
+ * parameters and with tendon channels (either, both or neither, a channel mask of 0 included).
+ * Latency.  Env i has an integer delay d_i in [0, RB_IO_MAX_DELAY], a uint32 plane [n_envs] the caller may read and write.  With k the
+ * episode step a launch computes (the env's step counter on entry: 1 behind a reset or an auto-reset), the step is driven by the action row the caller passed at
+ * episode step k - d_i of the same episode, clamped and rescaled like a direct one; while k - d_i < 1 by the rest command: every
+ * set-point 0 m, plus the env's set-point offset on a handle with parameters - what the env-reset rows' tendon columns assume.
+ * Everything behind the step sees the command that was applied: the tendon columns ("the set-points just applied, held") and the
+ * parameter form's columns of an auto-reset env.  The rows are kept in a device ring history[S][n_envs][n_t] of raw action rows,
+ * S the smallest power of two above delay_hi; every step stores the row it was handed into slot k mod S, an env with 0 < d_i < k
+ * reads slot (k - d_i) mod S.  No ring exists and the delay plane is not read with delay_hi = 0.  An auto-reset clears nothing (k
+ * restarts at 1); without auto_reset the counter and the history run on.  The ring is indexed by the step counter: a caller that
+ * rewrites the counters (the step_num argument of the set-goal call) steps with whatever those slots hold.  A delay written into
+ * the plane by hand must not exceed delay_hi.
+ * Delay draws: Philox4x32-10 stream 5.  Draw m of the env with global id g is word 0 of the generator at counter (g low, g high, m,
+ * 5 << 8) and key (seed low, seed high): d = delay_lo + (((word >> 8) * (delay_hi - delay_lo + 1)) >> 24), in integers.  m is the
+ * env's own draw counter (a uint32 plane), advanced by one per draw; independent of sharding (env_id_offset).  configure draws every
+ * env once.  With resample_on_reset the fused env step redraws d_i on done with auto_reset, where the goal and the parameters are
+ * redrawn: the episode that ended used the old delay, the new episode uses the new one.
+ * Sensor noise.  Standard deviations in physical units, finite and >= 0: sigma_q (the n_q angle columns), sigma_qd (the n_q
+ * velocity columns), sigma_tendon[4] per tendon channel in channel order (m, m/s, activation, N); the goal columns are never
+ * noised.  A noised column reports (value + sigma z) x its channel scale, evaluated as one fused multiply-add on the scaled value.
+ * Reward, done, state, statistics, goal and parameter redraws use the true state: with noise on and off they are bit-identical.
+ * Row number r of the env with global id g takes for the column at row position c (0 .. obs_dim-1, goal columns counted) component
+ * c & 3 of block c >> 2 of the generator at counter (g low, g high, r, 4 << 8 | block), Box-Muller on the pairs (0,1) and (2,3):
+ * u1 = ((w >> 8) + 1) / 2^24, u2 = (w >> 8) / 2^24, z = sqrt(-2 ln u1) cos(2 pi u2) for the even component, sin for the odd.
+ * r is a per-env uint32 row counter, zeroed by configure and advanced by one for every row the env-step or the env-reset entry
+ * writes for that env while any sigma is set (an auto-reset row is still one row per step).  The env-reset rows are noised too.
+ * Nothing is clipped to an observation box.
+ * While configured, the env-step entries (step, step-range, reset) run the io kernels (csrc/env_io.hpp), one env per lane in the
+ * nominal or the parameter form, whatever rb_select_kernel chose, and rb_dispatch_current refuses RB_ENTRY_ENV_STEP with
+ * RB_EUNSUPPORTED; the plain step entries are untouched.  A sub-range shifts the history by first_env n_t inside each slot (slot
+ * stride n_envs n_t floats) and the three planes by first_env.
+ *   configure:        needs rb_env_configure; drains the handle's streams and evicts the cached rollout graphs; calling it again
+ *                     resets planes, counters and ring; NULL switches it off (buffers freed, the handle's previous kernels again).
+ *                     RB_EINVAL for a negative or non-finite sigma or a delay range outside 0 <= lo <= hi <= RB_IO_MAX_DELAY.
+ *   ptr:              the device planes (delay, delay draw counters, row counters), the ring (NULL without one) and its slot
+ *                     count S (0 without one); any output may be NULL.  Asynchronous users order on the handle's stream.
+ *   sample_delay_dev: redraws the envs with d_mask[i] != 0 (d_mask: device [n_envs], NULL = all), asynchronous on the handle's stream.
+ * RB_ABI_VERSION is still 6, for the reason given above: look the configure function up before relying on these three. */
+#define RB_IO_MAX_DELAY 7
+typedef struct rb_env_io_config {
+    float sigma_q, sigma_qd, sigma_tendon[4];
+    int32_t delay_lo, delay_hi;          /* 0 <= lo <= hi <= RB_IO_MAX_DELAY */
+    int32_t resample_on_reset, _pad;
+} rb_env_io_config;
+int rb_env_io_configure(rb_sim *sim, const rb_env_io_config *cfg);
+int rb_env_io_ptr(rb_sim *sim, uint32_t **d_delay, uint32_t **d_delay_draws, uint32_t **d_rows, float **d_history, int32_t *slots);
+int rb_env_io_sample_delay_dev(rb_sim *sim, const uint8_t *d_mask);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
