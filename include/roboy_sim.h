@@ -242,7 +242,12 @@ int rb_env_reset_dev(rb_sim *sim, float *d_obs /* [n_envs][3 n_q] */);
  * (gym_roboy/envs/tests/test_roboy_env.py:62-66,172-176); lets a caller replay recorded
  * (state, goal, counter) triples through rb_env_step_dev. */
 int rb_env_set_goal(rb_sim *sim, const float *goal_q, const uint32_t *step_num /* [n_envs] or NULL */);
-int rb_env_step_dev(rb_sim *sim, const float *d_act /* [n_envs][n_t] in [-1,1] */,
+/* Actions: the reference asserts that an action lies in [-1, 1] (roboy_env.py:52); a batched kernel cannot raise, so every kernel
+ * form of the fused env step clamps every non-NaN action to [-1, 1] itself before rescaling it into the set-point box of
+ * rb_env_configure, +-inf included: an action outside the box gives, bit for bit, what its clipped value gives (a policy's raw
+ * Gaussian samples may be handed in as they are; tests/test_action_box_gpu.py pins this for every form).  NaN is the caller's to
+ * avoid: what a NaN action does is not specified. */
+int rb_env_step_dev(rb_sim *sim, const float *d_act /* [n_envs][n_t], clamped to [-1,1] */,
                     float *d_obs, float *d_reward, uint32_t *d_done);
 /* ---- sub-ranges: envs [first_env, first_env + n_envs) on a stream of the caller's choice ----
  * The per-step entry points above launch ONCE per step over the whole batch - which, for a large batch, leaves the launch
@@ -295,7 +300,7 @@ int rb_env_stats_dev(rb_sim *sim, double *d_stats8, int reset);
  * synchronises. */
 enum rb_setpoint_mode {
     RB_SP_SCALED = 0,   /* set-point = act_scale * act (the plain step's convention)                                          */
-    RB_SP_ENV = 1       /* the env layer's rescale of act in [-1, 1] into the action box (needs rb_env_configure)             */
+    RB_SP_ENV = 1       /* the env layer's rescale into the action box (needs rb_env_configure): non-NaN act clamped to [-1, 1] */
 };
 int rb_tendon_state_dev(rb_sim *sim, const float *d_act, int sp_mode, float act_scale,
                         float *d_length, float *d_rate, float *d_activation, float *d_force);

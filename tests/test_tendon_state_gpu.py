@@ -5,6 +5,7 @@ two set-point modes, the NULL conventions, the torch path and the single-env / v
 import numpy as np
 import pytest
 
+from action_box_util import outside, wide_actions
 from conftest import random_states
 from gym_roboy_amd import _native as nat
 
@@ -172,7 +173,9 @@ def test_env_mode_equals_scaled_mode_with_host_rescaled_set_points(which):
     env = RoboyVecEnv(robot, n)
     q, qd, _ = random_states(desc, n, 8)
     env.sim.set_state(q, qd)
-    act = np.random.default_rng(9).uniform(-1.0, 1.0, (n, desc.n_t)).astype(np.float32)
+    # actions from U(-2, 2) with +-1, their neighbours outside the box, +-1e30, +-inf and -0.0 planted: RB_SP_ENV clamps to [-1, 1]
+    act = wide_actions(n, desc.n_t, 1, 9)[0]
+    assert np.mean(outside(act)) > 0.4
     box = robot.get_action_space()
     lo, hi = np.float32(box.low[0]), np.float32(box.high[0])
     slope = np.float32(hi - lo) / np.float32(2.0)                    # the library's fp32 rescale, two roundings
