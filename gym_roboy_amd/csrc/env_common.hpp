@@ -14,6 +14,13 @@ __device__ __forceinline__ float mul_then_add(float a, float b, float c) {
     const float p = a * b;
     return p + c;
 }
+// An action -> its tendon set-point, the ONE place of every fused env-step kernel form.  The reference asserts that the action lies
+// in the box [-1, 1] (roboy_env.py:52); a batched kernel cannot raise, so it clamps.  Then slope * (x - in_high) + out_high with
+// in_high = 1, each operation rounded (roboy_env.py:157-158).
+__device__ __forceinline__ float clip_action(float x) { return fminf(fmaxf(x, -1.0f), 1.0f); }
+__device__ __forceinline__ float action_setpoint(float slope, float x, float act_hi) {
+    return mul_then_add(slope, clip_action(x) - 1.0f, act_hi);
+}
 __device__ __forceinline__ float goal_value(float lo, float hi, uint32_t u) {
     return mul_then_add(hi - lo, rb::u01(u), lo);
 }

@@ -4,7 +4,8 @@
 // table: while a handle has an io configuration, dispatch() launches these kernels for the env-step entry instead of the handle's row,
 // env_params.hpp's kernel or env_obs.hpp's.  The kernels ARE the env-step bodies - RB_MSJ_ENV_STEP_BODY, RB_MSJ_PARAMS_ENV_STEP_BODY -
 // expanded with an extension that varies the two places the bodies leave open: the action row a lane steps with (applied()) and
-// env_account's observation policy (and, for the delay's redraw, the episode-end hook).  One env per lane, 256-thread groups.
+// env_account's observation policy (and, for the delay's redraw, the episode-end hook).  One env per lane, 256-thread groups - but
+// for MsjRobot's baked constants without parameters and channels up to RB_SMALL_BATCH envs: 64-thread groups, as the row it stands in for.
 //
 // Latency: env i steps episode step k with the row its caller handed in at step k - d_i of the same episode, d_i = delay[i] in
 // [0, MAX_DELAY]; k = step_num[i] on entry, which a reset and an auto-reset leave at 1 (env_account's sn is k + 1: the counter
@@ -142,23 +143,7 @@ struct AppliedRefresh : RowNoise<ARGS> {
     AppliedRow ap;
     template <bool WRITTEN_OUT, typename CONST>
     __device__ __forceinline__ void run(const CONST &c, const HeldOffsets &h, int nt, long i) const {
-        const float slope = this->a->e.slope, act_hi = this->a->e.act_hi;
-        const float *act = ap.row;
-        const bool rest = ap.rest;
-        const float *par = pa->par;
-        const long n = pa->n;
-        auto one = [&](int k) {             // the step's own products (RB_MSJ_PARAMS_ENV_STEP_BODY: setpoint)
-            const float sp = (rest ? 0.0f : rbe::mul_then_add(slope, fminf(fmaxf(act[k], -1.0f), 1.0f) - 1.0f, act_hi)) + par[(nt + k) * n + i];
-            h.u[k * h.stride] = sp * c.ten[k].ksg;
-            h.fs[k * h.stride] = par[k * n + i];
-        };
-        if constexpr (WRITTEN_OUT) {
-#pragma unroll
-            for (int k = 0; k < NT8; ++k) one(k);
-        } else {
-#pragma unroll 1
-            for (int k = 0; k < nt; ++k) one(k);
-        }
+        rbo::refresh_held<WRITTEN_OUT>(c, h, nt, i, this->a->e.slope, this->a->e.act_hi, ap.row, ap.rest, pa->par, pa->n);
     }
 };
 

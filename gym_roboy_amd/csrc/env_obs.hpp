@@ -4,7 +4,8 @@
 // table: while a handle has a channel mask set, dispatch() launches these kernels for the env-step entry instead of the handle's row
 // (or instead of env_params.hpp's kernel, on a handle with parameters enabled).  The kernels ARE the env-step bodies of
 // msj_kernels.hpp / env_params.hpp - RB_MSJ_ENV_STEP_BODY, RB_MSJ_PARAMS_ENV_STEP_BODY - expanded with an observation policy for
-// env_account: one env per lane at every batch size, 256-thread groups.
+// env_account: one env per lane, 256-thread groups at every batch size (the policy itself takes any group size: env_io.hpp has a
+// 64-thread instance).
 //
 // Row: [q (3), qd (3), goal (3), then per selected channel in the order length, rate, activation, force: n_t values], obs_dim =
 // 9 + C n_t floats, rows dword-aligned only.  The tendon columns are MsjModel::tendon_state at the state the row reports, under the
@@ -60,6 +61,19 @@ struct NoRefresh {
     template <bool WRITTEN_OUT, typename CONST>
     __device__ __forceinline__ void run(const CONST &, const HeldOffsets &, int, long) const {}
 };
+// The refresh itself: env i's held offsets and force scales again from the planes par[.][n], under `row` (or the rest command) - the
+// step's own products (RB_MSJ_PARAMS_ENV_STEP_BODY: setpoint)
+template <bool WRITTEN_OUT, typename CONST>
+__device__ __forceinline__ void refresh_held(const CONST &c, const HeldOffsets &h, int nt, long i, float slope, float act_hi, const float *row, bool rest,
+                                             const float *par, long n) {
+    const int trips = WRITTEN_OUT ? NT8 : nt;
+#pragma unroll WRITTEN_OUT ? NT8 : 1        // (written out, the offsets are in registers: every index a constant)
+    for (int k = 0; k < trips; ++k) {
+        const float sp = (rest ? 0.0f : rbe::action_setpoint(slope, row[k], act_hi)) + par[(nt + k) * n + i];
+        h.u[k * h.stride] = sp * c.ten[k].ksg;
+        h.fs[k * h.stride] = par[k * n + i];
+    }
+}
 template <typename ARGS, typename PA>
 struct ParamRefresh {
     static constexpr bool NOISY = false, MAYBE_EMPTY = false;
@@ -67,22 +81,7 @@ struct ParamRefresh {
     PA pa;
     template <bool WRITTEN_OUT, typename CONST>
     __device__ __forceinline__ void run(const CONST &c, const HeldOffsets &h, int nt, long i) const {
-        const float slope = a->e.slope, act_hi = a->e.act_hi;
-        const float *act = a->act + i * nt;
-        const float *par = pa->par;
-        const long n = pa->n;
-        auto one = [&](int k) {             // the step's own products (RB_MSJ_PARAMS_ENV_STEP_BODY: setpoint)
-            const float sp = rbe::mul_then_add(slope, fminf(fmaxf(act[k], -1.0f), 1.0f) - 1.0f, act_hi) + par[(nt + k) * n + i];
-            h.u[k * h.stride] = sp * c.ten[k].ksg;
-            h.fs[k * h.stride] = par[k * n + i];
-        };
-        if constexpr (WRITTEN_OUT) {        // (offsets in registers: every index a constant)
-#pragma unroll
-            for (int k = 0; k < NT8; ++k) one(k);
-        } else {
-#pragma unroll 1
-            for (int k = 0; k < nt; ++k) one(k);
-        }
+        refresh_held<WRITTEN_OUT>(c, h, nt, i, a->e.slope, a->e.act_hi, a->act + i * nt, false, pa->par, pa->n);
     }
 };
 

@@ -232,9 +232,9 @@ struct RedrawParams {
     float qq[3], vv[3], gg[3];                                                                                                      \
     _Pragma("unroll")                                                                                                               \
     for (int j = 0; j < 3; ++j) { qq[j] = q[j * n + i]; vv[j] = qd[j * n + i]; gg[j] = goal[j * n + i]; }                           \
-    /* clamp, slope * (x - in_high) + out_high with two roundings (roboy_env.py:157-158), + the env's offset, -> activation offset  */ \
+    /* action -> set-point (rbe::action_setpoint) or the rest command, + the env's offset; times ksg: the activation offset         */ \
     decltype((OX).applied(a.step_num, act, i, 0)) ap{};        /* the row the lane steps with: named where each branch reads it */ \
-    auto setpoint = [&](float x, float o) { return (ap.rest ? 0.0f : rbe::mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi)) + o; }; \
+    auto setpoint = [&](float x, float o) { return (ap.rest ? 0.0f : rbe::action_setpoint(slope, x, act_hi)) + o; };                            \
     BodyScale bs;                                                                                                                   \
     bool ok;                                                                                                                        \
     rbk::HeldOffsets held{nullptr, nullptr, 1};                                                                                     \

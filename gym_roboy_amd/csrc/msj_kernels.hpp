@@ -473,10 +473,9 @@ struct NoObsExt {
     float qq[3], vv[3], gg[3];                                                                                                      \
     _Pragma("unroll")                                                                                                               \
     for (int j = 0; j < 3; ++j) { qq[j] = q[j * n + i]; vv[j] = qd[j * n + i]; gg[j] = goal[j * n + i]; }                           \
-    /* the reference asserts the action lies in [-1,1] (roboy_env.py:52); a batched kernel cannot raise, so it clamps.  Then        */ \
-    /* slope * (x - in_high) + out_high, each op rounded (roboy_env.py:157-158)                                                     */ \
+    /* action -> set-point: rbe::action_setpoint (env_common.hpp), or the rest command                                              */ \
     decltype((OX).applied(a.step_num, act, i, 0)) ap{};        /* the row the lane steps with: named where each branch reads it */ \
-    auto rescale = [&](float x) { return ap.rest ? 0.0f : mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi); };      \
+    auto rescale = [&](float x) { return ap.rest ? 0.0f : rbe::action_setpoint(slope, x, act_hi); };                                \
     bool ok;                                                                                                                        \
     HeldOffsets held{nullptr, nullptr, 1};                                                                                          \
     constexpr bool IN_LDS = UNROLL != RS && UNROLL < NT8;                                                                           \
@@ -548,9 +547,9 @@ msj_env_step_mirror_pairs(const Const8 c_arg, const PairMap pm, const MsjEnvArgs
     const __amdgpu_buffer_rsrc_t ra = wg_rsrc(act + wg0 * NT8, live * NT8 * 4);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        // clamp, slope * (x - in_high) + out_high with two roundings (roboy_env.py:157-158), then set-point -> activation offset
+        // action -> set-point (rbe::action_setpoint), then set-point -> activation offset
         const float x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(ra, off * NT8 + pm.a[k] + oddi * pm.d[k], 0, 0));
-        u[k] = mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi) * c.ten[k].ksg;
+        u[k] = rbe::action_setpoint(slope, x, act_hi) * c.ten[k].ksg;
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {

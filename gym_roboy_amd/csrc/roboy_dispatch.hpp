@@ -491,30 +491,25 @@ inline const Row *row_for(rb_sim *s, int entry, bool build, std::string *why = n
     return r;
 }
 
+// Is this handle's launch of `entry` served by the extension kernels and not by a row of the table?  Every entry while per-env
+// parameters are enabled (rb_params_enable: env_params.hpp), the env step while tendon channels (rb_env_obs_configure: env_obs.hpp)
+// or an io configuration (rb_env_io_configure: env_io.hpp) are set.  Those kernels take sub-ranges.
+inline bool extension_serves(const rb_sim *s, int entry) { return s->params || (entry == ENTRY_ENV && (s->obs_mask || s->io)); }
+int extension_launch(rb_sim *s, int entry, const Launch &L);      // (roboy_sim.hip)
+
 // every launch of the library's three entry kinds
-// a handle with per-env parameters enabled (rb_params_enable) launches the kernels of env_params.hpp instead of its row
-// a handle with tendon channels in its observation (rb_env_obs_configure) launches the kernels of env_obs.hpp for the env-step entry
-int params_launch(rb_sim *s, int entry, const Launch &L);      // (roboy_sim.hip)
-int obs_launch(rb_sim *s, const Launch &L);
 inline int dispatch(rb_sim *s, int entry, const Launch &L) {
-    if (entry == ENTRY_ENV && (s->obs_mask || s->io)) {      // (obs_launch: the io kernels while rb_env_io_configure holds)
-        const int rc = obs_launch(s, L);
-        if (rc) return rc;
-        RB_HIP(hipGetLastError());
-        return RB_OK;
+    int rc;
+    if (extension_serves(s, entry)) {
+        rc = extension_launch(s, entry, L);
+    } else {
+        std::string why;
+        const Row *r = row_for(s, entry, true, &why);
+        if (!r) return fail(RB_EUNSUPPORTED, why);
+        if (!r->ranges && !(L.i0 == 0 && L.cnt == s->n)) return fail(RB_EUNSUPPORTED, "this kernel form steps whole batches only (rb_range_capable)");
+        if (s->tree) s->kernel = r->key.form;                            // what rb_info reports for joint trees: the form last launched
+        rc = r->launch(s, L);
     }
-    if (s->params) {
-        const int rc = params_launch(s, entry, L);
-        if (rc) return rc;
-        RB_HIP(hipGetLastError());
-        return RB_OK;
-    }
-    std::string why;
-    const Row *r = row_for(s, entry, true, &why);
-    if (!r) return fail(RB_EUNSUPPORTED, why);
-    if (!r->ranges && !(L.i0 == 0 && L.cnt == s->n)) return fail(RB_EUNSUPPORTED, "this kernel form steps whole batches only (rb_range_capable)");
-    if (s->tree) s->kernel = r->key.form;                                // what rb_info reports for joint trees: the form last launched
-    const int rc = r->launch(s, L);
     if (rc) return rc;
     RB_HIP(hipGetLastError());
     return RB_OK;

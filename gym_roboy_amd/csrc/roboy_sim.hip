@@ -12,9 +12,11 @@
 // for the robot (tree_lane_gen.hpp, tree_lane.hpp: the committed upper body ahead of
 // time, other robots by hiprtc) or, without that specialisation, two envs per wave,
 // eight lanes per link, working set in LDS (tree_aba.hpp).  DESIGN.md §4-§5.
-// Which kernel instance a call launches is ONE table (roboy_dispatch.hpp, included below): 98 rows keyed by robot class / entry kind /
-// kernel form / integrator / workgroup size / constants source / variant, RB_KERNEL_AUTO's thresholds as a list of rules; this file
-// holds the kernels that are not in a header of their own, the handle, the availability predicates and the C ABI.
+// Which kernel instance a call launches is ONE table (roboy_dispatch.hpp, included below): rows keyed by robot class / entry kind /
+// kernel form / integrator / workgroup size / constants source / variant, RB_KERNEL_AUTO's thresholds as a list of rules - but for a
+// handle with per-env parameters, tendon channels or an io configuration, whose kernels (env_params.hpp, env_obs.hpp, env_io.hpp) one
+// launch path below chooses (extension_launch).  This file holds the kernels that are not in a header of their own, the handle, the
+// availability predicates and the C ABI.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -222,20 +224,23 @@ struct AccelOneTendon {
     }
 };
 
+// XCD-aware block -> env-group map of the two kernels below.  A wave touches only 32 bytes of each
+// state plane, so four consecutive waves share every 128-byte line; workgroups
+// are dealt round-robin over the 8 XCDs (private L2s), which made each line
+// travel to four L2s (PMC: 2.5x the algorithmic read bytes).  Blocks that share
+// an XCD (equal blockIdx % 8) now take one contiguous range of env groups
+// (bijective form of cdna_hip_programming.md T1; affects traffic only).
+__device__ __forceinline__ unsigned xcd_block() {
+    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7u, qn = nb >> 3, rn = nb & 7u;
+    return (xcd < rn ? xcd * (qn + 1u) : rn * (qn + 1u) + (xcd - rn) * qn) + (blockIdx.x >> 3);
+}
+
 template <int INTEG>
 __global__ void __launch_bounds__(64)
 msj_step_tendon_per_lane(const Const8 c, const rb::MsjTendon<float> *__restrict__ ten,
                          float *__restrict__ q, float *__restrict__ qd, uint32_t *__restrict__ feas,
                          const float *__restrict__ act, float act_scale, long n) {
-    // XCD-aware block -> env-group map.  A wave touches only 32 bytes of each
-    // state plane, so four consecutive waves share every 128-byte line; workgroups
-    // are dealt round-robin over the 8 XCDs (private L2s), which made each line
-    // travel to four L2s (PMC: 2.5x the algorithmic read bytes).  Blocks that share
-    // an XCD (equal blockIdx % 8) now take one contiguous range of env groups
-    // (bijective form of cdna_hip_programming.md T1; affects traffic only).
-    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7u, qn = nb >> 3, rn = nb & 7u;
-    const unsigned blk = (xcd < rn ? xcd * (qn + 1u) : rn * (qn + 1u) + (xcd - rn) * qn) + (blockIdx.x >> 3);
-    const long t = long(blk) * 64 + threadIdx.x;
+    const long t = long(xcd_block()) * 64 + threadIdx.x;
     const int k = threadIdx.x & 7;
     long e = t >> 3;
     const bool live = e < n;          // whole 8-lane groups are live or not; dead groups
@@ -266,17 +271,15 @@ msj_env_step_tendon_per_lane(const Const8 c, const rb::MsjTendon<float> *__restr
     const float *__restrict__ q = a.q, *__restrict__ qd = a.qd, *__restrict__ goal = a.goal, *__restrict__ act = a.act;
     const long n = a.n, cnt = a.cnt;
     const float slope = a.e.slope, act_hi = a.e.act_hi;
-    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7u, qn = nb >> 3, rn = nb & 7u;      // XCD-aware block -> env-group map (above)
-    const unsigned blk = (xcd < rn ? xcd * (qn + 1u) : rn * (qn + 1u) + (xcd - rn) * qn) + (blockIdx.x >> 3);
-    const long t = long(blk) * 64 + threadIdx.x;
+    const long t = long(xcd_block()) * 64 + threadIdx.x;
     const int k = threadIdx.x & 7;
     long e = t >> 3;
     const bool live = e < cnt;
     if (!live) e = cnt - 1;           // dead groups shadow the last env so every DPP partner is active
     const rb::MsjTendon<float> rec = ten[k];
-    // clamp, slope * (x - in_high) + out_high with two roundings (roboy_env.py:157-158), then set-point -> activation offset
+    // action -> set-point (rbe::action_setpoint), then set-point -> activation offset
     const float x = act[e * NT8 + k];
-    const float spk = rbk::mul_then_add(slope, fminf(fmaxf(x, -1.0f), 1.0f) - 1.0f, act_hi) * rec.ksg;
+    const float spk = rbe::action_setpoint(slope, x, act_hi) * rec.ksg;
     float qq[3], vv[3], gg[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) { qq[j] = q[j * n + e]; vv[j] = qd[j * n + e]; gg[j] = goal[j * n + e]; }
@@ -668,7 +671,7 @@ bool tree_wants_split(const rb_sim *s, int kernel) {
 // kernel forms that step a sub-range of the batch (shifted pointers, own env count): what chains and the rb_*_range_dev entry points
 // need.  A pure query: the row of what is at hand, no build (rb_rollout_dev / rb_step_range_dev / rb_range_capable build first).
 bool range_capable(const rb_sim *s) {
-    if (s->params) return true;                 // the parameter kernels take sub-ranges
+    if (extension_serves(s, ENTRY_STEP)) return true;
     const Row *r = row_for(const_cast<rb_sim *>(s), ENTRY_STEP, /*build=*/false);
     return r && r->ranges;
 }
@@ -775,39 +778,8 @@ int drop_graphs(rb_sim *s) {
     return RB_OK;
 }
 
-// ---- per-env physical parameters (env_params.hpp): what dispatch() launches while they are enabled ----
-template <int INTEG>
-int params_launch_integ(rb_sim *s, int entry, const Launch &L) {
-    constexpr int B = 256;
-    const unsigned blocks = blocks_for(L.cnt, B);
-    float *par = s->d_params + L.i0;
-    if (entry == ENTRY_STEP) {
-        float *q = s->d_q + L.i0, *qd = s->d_qd + L.i0;
-        uint32_t *feas = s->d_feas + L.i0;
-        const float *act = L.act + size_t(L.i0) * s->n_t;
-        if (s->ntx)
-            hipLaunchKernelGGL((rbp::msj_params_step_nt<INTEG, B>), dim3(blocks), dim3(B), 0, L.stream, s->cx, q, qd, feas, act, L.act_scale, par, s->n, L.cnt);
-        else if (s->baked)
-            hipLaunchKernelGGL((rbp::msj_params_step<INTEG, B, true>), dim3(blocks), dim3(B), 0, L.stream, s->c8, q, qd, feas, act, scale8(s, L.act_scale), par, s->n, L.cnt);
-        else
-            hipLaunchKernelGGL((rbp::msj_params_step<INTEG, B, false>), dim3(blocks), dim3(B), 0, L.stream, s->c8, q, qd, feas, act, scale8(s, L.act_scale), par, s->n, L.cnt);
-        return RB_OK;
-    }
-    if (entry == ENTRY_ENV) {
-        const MsjEnvArgs a = msj_env_args(s, L);
-        const rbp::ParamArgs pa{par, s->d_param_draws + L.i0, s->d_param_ranges, s->n, s->n_params, s->param_resample ? 1 : 0};
-        if (s->ntx)
-            hipLaunchKernelGGL((rbp::msj_params_env_step<INTEG, B, ConstX, false>), dim3(blocks), dim3(B), 0, L.stream, s->cx, a, pa);
-        else if (s->baked)
-            hipLaunchKernelGGL((rbp::msj_params_env_step<INTEG, B, Const8, true>), dim3(blocks), dim3(B), 0, L.stream, s->c8, a, pa);
-        else
-            hipLaunchKernelGGL((rbp::msj_params_env_step<INTEG, B, Const8, false>), dim3(blocks), dim3(B), 0, L.stream, s->c8, a, pa);
-        return RB_OK;
-    }
-    return fail(RB_EUNSUPPORTED, "per-env parameters have no fused-rollout kernel (rb_params_disable first)");
-}
-// ---- tendon channels in the observation (env_obs.hpp): what dispatch() launches for the env-step entry while a mask is set ----
-// dynamic LDS of an extended env-step launch: the rows of its 256 envs, where they fit beside the instance's own columns (0: per-lane stores)
+// ---- tendon channels in the observation (env_obs.hpp): the arguments of a launch while a mask is set ----
+// dynamic LDS of an extended env-step launch: the rows of its workgroup's envs, where they fit beside the instance's own columns (0: per-lane stores)
 size_t obs_stage_bytes(const rb_sim *s, int block = 256) {
     const size_t columns = (s->baked ? 0 : s->ntx ? 4 * block * NTX : 4 * block * NT8) * (s->params ? 2 : 1);
     const size_t rows = size_t(4) * block * s->obs_dim();
@@ -821,32 +793,7 @@ rbo::ObsArgs<NT> obs_args(const rb_sim *s, bool staged = false) {
     for (int k = 0; k < NT; ++k) oa.units[k] = s->ts_units.u[k];
     return oa;
 }
-template <int INTEG>
-int obs_launch_integ(rb_sim *s, const Launch &L) {
-    constexpr int B = 256;
-    const size_t lds = obs_stage_bytes(s);
-    const dim3 grid(blocks_for(L.cnt, B)), block(B);
-    MsjEnvArgs a = msj_env_args(s, L);
-    a.obs = L.obs + L.i0 * s->obs_dim();                 // the row stride is the handle's obs_dim
-    constexpr int UB = INTEG == 0 ? UBE : UBR, UK = INTEG == 0 ? UKE : UKR;     // the unroll factors of the large-batch env-per-lane rows
-    if (s->params) {
-        const rbp::ParamArgs pa{s->d_params + L.i0, s->d_param_draws + L.i0, s->d_param_ranges, s->n, s->n_params, s->param_resample ? 1 : 0};
-        if (s->ntx)
-            hipLaunchKernelGGL((rbo::msj_obs_params_env_step<INTEG, B, ConstX, false>), grid, block, lds, L.stream, s->cx, a, pa, obs_args<NTX>(s, lds != 0));
-        else if (s->baked)
-            hipLaunchKernelGGL((rbo::msj_obs_params_env_step<INTEG, B, Const8, true>), grid, block, lds, L.stream, s->c8, a, pa, obs_args<NT8>(s, lds != 0));
-        else
-            hipLaunchKernelGGL((rbo::msj_obs_params_env_step<INTEG, B, Const8, false>), grid, block, lds, L.stream, s->c8, a, pa, obs_args<NT8>(s, lds != 0));
-    } else if (s->ntx) {
-        hipLaunchKernelGGL((rbo::msj_obs_env_step<INTEG, B, 0, ConstX, false>), grid, block, lds, L.stream, s->cx, a, obs_args<NTX>(s, lds != 0));
-    } else if (s->baked) {
-        hipLaunchKernelGGL((rbo::msj_obs_env_step<INTEG, B, UB, Const8, true>), grid, block, lds, L.stream, s->c8, a, obs_args<NT8>(s, lds != 0));
-    } else {
-        hipLaunchKernelGGL((rbo::msj_obs_env_step<INTEG, B, UK, Const8, false>), grid, block, lds, L.stream, s->c8, a, obs_args<NT8>(s, lds != 0));
-    }
-    return RB_OK;
-}
-// ---- action latency and sensor noise (env_io.hpp): what dispatch() launches for the env-step entry while rb_env_io_configure holds ----
+// ---- action latency and sensor noise (env_io.hpp): the argument of a launch while rb_env_io_configure holds ----
 // first: the launch's first env (the planes and the ring inside each slot are shifted by it)
 rbio::IoArgs io_args(const rb_sim *s, long first) {
     rbio::IoArgs io;
@@ -868,52 +815,10 @@ rbio::IoArgs io_args(const rb_sim *s, long first) {
         if (io.colsig[c] != 0.0f) io.noise_blocks |= 1u << (c >> 2);
     return io;
 }
-template <int INTEG>
-int io_launch_integ(rb_sim *s, const Launch &L) {
-    constexpr int B = 256;
-    MsjEnvArgs a = msj_env_args(s, L);
-    a.obs = L.obs + L.i0 * s->obs_dim();
-    const rbio::IoArgs io = io_args(s, L.i0);
-    // An io kernel is the text of the kernel it stands in for.  Without parameters and channels that is the table's env-per-lane
-    // row, which for MsjRobot's baked constants at small batches is the 64-thread instance with tendons AND integrator stages written
-    // out - another summation order of the RK4 stages than the large-batch text (rolled stages): a configuration of zeros steps like
-    // no configuration there too.  (Kernarg constants: the large-batch text's rolled tendon loop adds the same terms in the same order
-    // as the written-out 64-thread row, and that row has no scalar register to spare - with the io arguments it would spill.)
-    if (!s->params && !s->obs_mask && s->baked && s->n <= RB_SMALL_BATCH) {
-        const size_t lds = obs_stage_bytes(s, 64);
-        hipLaunchKernelGGL((rbio::msj_io_env_step<INTEG, 64, 8, Const8, true>), dim3(blocks_for(L.cnt, 64)), dim3(64), lds, L.stream, s->c8, a,
-                           obs_args<NT8>(s, lds != 0), io);
-        return RB_OK;
-    }
-    const size_t lds = obs_stage_bytes(s);
-    const dim3 grid(blocks_for(L.cnt, B)), block(B);
-    constexpr int UB = INTEG == 0 ? UBE : UBR, UK = INTEG == 0 ? UKE : UKR;
-    if (s->params) {
-        const rbp::ParamArgs pa{s->d_params + L.i0, s->d_param_draws + L.i0, s->d_param_ranges, s->n, s->n_params, s->param_resample ? 1 : 0};
-        if (s->ntx)
-            hipLaunchKernelGGL((rbio::msj_io_params_env_step<INTEG, B, ConstX, false>), grid, block, lds, L.stream, s->cx, a, pa, obs_args<NTX>(s, lds != 0), io);
-        else if (s->baked)
-            hipLaunchKernelGGL((rbio::msj_io_params_env_step<INTEG, B, Const8, true>), grid, block, lds, L.stream, s->c8, a, pa, obs_args<NT8>(s, lds != 0), io);
-        else
-            hipLaunchKernelGGL((rbio::msj_io_params_env_step<INTEG, B, Const8, false>), grid, block, lds, L.stream, s->c8, a, pa, obs_args<NT8>(s, lds != 0), io);
-    } else if (s->ntx) {
-        hipLaunchKernelGGL((rbio::msj_io_env_step<INTEG, B, 0, ConstX, false>), grid, block, lds, L.stream, s->cx, a, obs_args<NTX>(s, lds != 0), io);
-    } else if (s->baked) {
-        hipLaunchKernelGGL((rbio::msj_io_env_step<INTEG, B, UB, Const8, true>), grid, block, lds, L.stream, s->c8, a, obs_args<NT8>(s, lds != 0), io);
-    } else {
-        hipLaunchKernelGGL((rbio::msj_io_env_step<INTEG, B, UK, Const8, false>), grid, block, lds, L.stream, s->c8, a, obs_args<NT8>(s, lds != 0), io);
-    }
-    return RB_OK;
-}
 void io_free(rb_sim *s) {
     (void)hipFree(s->d_io_delay); (void)hipFree(s->d_io_draws); (void)hipFree(s->d_io_rows); (void)hipFree(s->d_io_hist);
     s->d_io_delay = nullptr; s->d_io_draws = nullptr; s->d_io_rows = nullptr; s->d_io_hist = nullptr;
     s->io = false; s->io_slots = 0;
-}
-int obs_launch(rb_sim *s, const Launch &L) {
-    if (L.cnt <= 0) return RB_OK;
-    if (s->io) return s->integrator == RB_EULER ? io_launch_integ<0>(s, L) : io_launch_integ<1>(s, L);
-    return s->integrator == RB_EULER ? obs_launch_integ<0>(s, L) : obs_launch_integ<1>(s, L);
 }
 // rb_env_reset_dev's observation rows on such a handle: the state the reset kernel has just written, every set-point 0
 void obs_rows_launch(rb_sim *s, float *d_obs) {
@@ -925,9 +830,79 @@ void obs_rows_launch(rb_sim *s, float *d_obs) {
         hipLaunchKernelGGL((rbo::msj_obs_rows<256, Const8>), grid, block, 0, s->stream, s->c8, obs_args<NT8>(s), s->d_q, s->d_qd, s->d_goal, par, d_obs, s->n);
 }
 
-int params_launch(rb_sim *s, int entry, const Launch &L) {
+// ---- what dispatch() launches where extension_serves() (roboy_dispatch.hpp): the kernels of env_params.hpp, env_obs.hpp, env_io.hpp ----
+// The constants an instance is compiled for, chosen here and nowhere else: f(the constants object, BK as a type) with BK = the
+// constants are MsjRobot's literals (msj_baked.hpp), the object then only fills the argument's place
+template <typename F>
+int with_consts(const rb_sim *s, F &&f) {
+    if (s->ntx) return f(s->cx, std::false_type{});
+    if (s->baked) return f(s->c8, std::true_type{});
+    return f(s->c8, std::false_type{});
+}
+rbp::ParamArgs param_args(const rb_sim *s, const Launch &L) {
+    return rbp::ParamArgs{s->d_params + L.i0, s->d_param_draws + L.i0, s->d_param_ranges, s->n, s->n_params, s->param_resample ? 1 : 0};
+}
+// the plain step under parameters: three argument lists of their own
+template <int INTEG>
+int params_step_launch(rb_sim *s, const Launch &L) {
+    constexpr int B = 256;
+    const dim3 grid(blocks_for(L.cnt, B)), block(B);
+    float *q = s->d_q + L.i0, *qd = s->d_qd + L.i0, *par = s->d_params + L.i0;
+    uint32_t *feas = s->d_feas + L.i0;
+    const float *act = L.act + size_t(L.i0) * s->n_t;
+    return with_consts(s, [&](const auto &c, auto bk) {
+        if constexpr (std::is_same<std::decay_t<decltype(c)>, ConstX>::value)
+            hipLaunchKernelGGL((rbp::msj_params_step_nt<INTEG, B>), grid, block, 0, L.stream, c, q, qd, feas, act, L.act_scale, par, s->n, L.cnt);
+        else
+            hipLaunchKernelGGL((rbp::msj_params_step<INTEG, B, decltype(bk)::value>), grid, block, 0, L.stream, c, q, qd, feas, act, scale8(s, L.act_scale), par, s->n, L.cnt);
+        return RB_OK;
+    });
+}
+// The env step of a handle with any combination of parameters, channels and io: the env-step body with the extension of the last
+// header that applies (io over channels over none), in its parameter form where parameters are enabled.
+template <int INTEG>
+int ext_env_launch(rb_sim *s, const Launch &L) {
+    MsjEnvArgs a = msj_env_args(s, L);
+    a.obs = L.obs + L.i0 * s->obs_dim();                 // the row stride is the handle's obs_dim (9 without channels)
+    const bool par = s->params, io = s->io, rows = io || s->obs_mask;       // rows: TendonObs writes them (env_obs.hpp)
+    return with_consts(s, [&](const auto &c, auto bk) {
+        using CONST = std::decay_t<decltype(c)>;
+        constexpr bool BK = decltype(bk)::value;
+        constexpr int NT = rbo::NtOf<CONST>::N;
+        // the unroll factors of the large-batch env-per-lane rows (0: run-time tendon count)
+        constexpr int U = NT == NTX ? 0 : BK ? (INTEG == 0 ? UBE : UBR) : (INTEG == 0 ? UKE : UKR);
+        // An io kernel is the text of the kernel it stands in for.  Without parameters and channels that is the table's env-per-lane
+        // row, which for MsjRobot's baked constants at small batches is the 64-thread instance with tendons AND integrator stages written
+        // out - another summation order of the RK4 stages than the large-batch text (rolled stages): a configuration of zeros steps like
+        // no configuration there too.  (Kernarg constants: the large-batch text's rolled tendon loop adds the same terms in the same order
+        // as the written-out 64-thread row, and that row has no scalar register to spare - with the io arguments it would spill.)
+        const bool small = BK && io && !par && !s->obs_mask && s->n <= RB_SMALL_BATCH;
+        const int B = small ? 64 : 256;
+        const size_t lds = rows ? obs_stage_bytes(s, B) : 0;
+        const rbo::ObsArgs<NT> oa = obs_args<NT>(s, lds != 0);
+        auto go = [&](auto kernel, const auto &...behind) {      // every instance takes (constants, MsjEnvArgs, ...)
+            hipLaunchKernelGGL(kernel, dim3(blocks_for(L.cnt, B)), dim3(B), lds, L.stream, c, a, behind...);
+            return RB_OK;
+        };
+        auto io_step = [&](auto block, auto unroll) {
+            return go(rbio::msj_io_env_step<INTEG, decltype(block)::value, decltype(unroll)::value, CONST, BK>, oa, io_args(s, L.i0));
+        };
+        if (par && io) return go(rbio::msj_io_params_env_step<INTEG, 256, CONST, BK>, param_args(s, L), oa, io_args(s, L.i0));
+        if (io) {
+            if constexpr (BK) if (small) return io_step(std::integral_constant<int, 64>{}, std::integral_constant<int, 8>{});
+            return io_step(std::integral_constant<int, 256>{}, std::integral_constant<int, U>{});
+        }
+        if (par && rows) return go(rbo::msj_obs_params_env_step<INTEG, 256, CONST, BK>, param_args(s, L), oa);
+        if (rows) return go(rbo::msj_obs_env_step<INTEG, 256, U, CONST, BK>, oa);
+        return go(rbp::msj_params_env_step<INTEG, 256, CONST, BK>, param_args(s, L));
+    });
+}
+int extension_launch(rb_sim *s, int entry, const Launch &L) {
     if (L.cnt <= 0) return RB_OK;
-    return s->integrator == RB_EULER ? params_launch_integ<0>(s, entry, L) : params_launch_integ<1>(s, entry, L);
+    const bool euler = s->integrator == RB_EULER;
+    if (entry == ENTRY_STEP) return euler ? params_step_launch<0>(s, L) : params_step_launch<1>(s, L);
+    if (entry == ENTRY_ENV) return euler ? ext_env_launch<0>(s, L) : ext_env_launch<1>(s, L);
+    return fail(RB_EUNSUPPORTED, "per-env parameters have no fused-rollout kernel (rb_params_disable first)");
 }
 void params_free(rb_sim *s) {
     (void)hipFree(s->d_params); (void)hipFree(s->d_param_draws); (void)hipFree(s->d_param_ranges);
@@ -1747,11 +1722,15 @@ int rb_step_range_dev(rb_sim *s, int64_t first_env, int64_t n_envs, void *hip_st
 }
 int rb_range_capable(rb_sim *s) {
     if (check(s)) return -1;
-    if (s->params) return 3;                 // the parameter kernels take sub-ranges (step and env step)
-    // builds what a launch would build (outside captures), then asks the table: bit 0 = the step's row takes sub-ranges, bit 1 = the env step's
+    // builds what a launch would build (outside captures), then asks the table - or the extension kernels, which take sub-ranges:
+    // bit 0 = the step, bit 1 = the env step
     maybe_jit(s);
-    const Row *step = row_for(s, ENTRY_STEP, true), *env = row_for(s, ENTRY_ENV, s->env_ready);
-    return (step && step->ranges ? 1 : 0) | (s->obs_mask || s->io || (env && env->ranges) ? 2 : 0);     // (env_obs.hpp's and env_io.hpp's kernels take sub-ranges)
+    auto ranges = [s](int entry, bool build) {
+        if (extension_serves(s, entry)) return true;
+        const Row *r = row_for(s, entry, build);
+        return r && r->ranges;
+    };
+    return (ranges(ENTRY_STEP, true) ? 1 : 0) | (ranges(ENTRY_ENV, s->env_ready) ? 2 : 0);
 }
 
 static int stats_launch(rb_sim *s, double *d_out2) {
@@ -1893,11 +1872,11 @@ int rb_dispatch_current(rb_sim *s, int entry, rb_dispatch_row *out) {
     if (check(s) || !out) return fail(RB_EINVAL, "null argument");
     if (entry < ENTRY_STEP || entry > ENTRY_FUSED) return fail(RB_EINVAL, "unknown entry kind");
     if (entry == ENTRY_FUSED && (s->tree || s->ntx)) return fail(RB_EUNSUPPORTED, "fused rollout is built for 8-tendon ball-joint robots");
-    if (s->params) return fail(RB_EUNSUPPORTED, "per-env parameters are enabled: the parameter kernels (env_params.hpp) are not rows of the dispatch table");
-    if (entry == ENTRY_ENV && s->io)
-        return fail(RB_EUNSUPPORTED, "an io configuration is set (rb_env_io_configure): the io env-step kernels (env_io.hpp) are not rows of the dispatch table");
-    if (entry == ENTRY_ENV && s->obs_mask)
-        return fail(RB_EUNSUPPORTED, "tendon channels are set (rb_env_obs_configure): the extended env-step kernels (env_obs.hpp) are not rows of the dispatch table");
+    if (extension_serves(s, entry))
+        return fail(RB_EUNSUPPORTED,
+                    s->params ? "per-env parameters are enabled: the parameter kernels (env_params.hpp) are not rows of the dispatch table"
+                    : s->io   ? "an io configuration is set (rb_env_io_configure): the io env-step kernels (env_io.hpp) are not rows of the dispatch table"
+                              : "tendon channels are set (rb_env_obs_configure): the extended env-step kernels (env_obs.hpp) are not rows of the dispatch table");
     RB_HIP(hipSetDevice(s->device));
     if (entry != ENTRY_ENV || s->env_ready) maybe_jit(s);
     std::string why;

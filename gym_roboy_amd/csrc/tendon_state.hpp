@@ -38,7 +38,7 @@ template <int NT> struct Units { rb::TendonUnits<float> u[NT]; };
 
 // activation offset of one tendon from its action (ksg: the tendon's set-point -> activation factor), rounded here as in the step
 __device__ __forceinline__ float offset_of(const SetPoints &sp, float a, float ksg) {
-    const float u = sp.mode == RB_SP_ENV ? rbe::mul_then_add(sp.slope, fminf(fmaxf(a, -1.0f), 1.0f) - 1.0f, sp.act_hi) * ksg
+    const float u = sp.mode == RB_SP_ENV ? rbe::action_setpoint(sp.slope, a, sp.act_hi) * ksg
                                          : a * (sp.scale * ksg);
     return rbe::rounded_here(u);
 }

@@ -792,9 +792,7 @@ tree_env_step_aba(const TreeDev tg, const rbe::EnvParams ep, const rbe::GoalBox 
         int e, k;
         split<E>(it, tg.n_t, e, k);
         const long env = env0 + e < n ? env0 + e : n - 1;
-        // clamp to the action box, then slope * (x - in_high) + out_high with two roundings (roboy_env.py:157-158)
-        const float x = fminf(fmaxf(act[env * tg.n_t + k], -1.0f), 1.0f);
-        (c.env(e) + tg.o_SPU)[k] = rbe::mul_then_add(ep.slope, x - 1.0f, ep.act_hi) * c.tf(tg.o_tendon + k * TENDON_REC + 2);
+        (c.env(e) + tg.o_SPU)[k] = rbe::action_setpoint(ep.slope, act[env * tg.n_t + k], ep.act_hi) * c.tf(tg.o_tendon + k * TENDON_REC + 2);
     }
     tree_integrate<INTEG, E, SP>(c, qj, vj, ok);
     // publish the per-joint terms: W region, [0..nq) flags, [nq..2nq) dq^2, [2nq..3nq) qd^2  (6 n_cr >= ... not guaranteed:

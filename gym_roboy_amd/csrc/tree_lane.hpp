@@ -317,9 +317,7 @@ tree_lane_env_step(const rbe::TreeEnvArgs a) {
     }
 #pragma unroll
     for (int k = 0; k < RBL_NT; ++k) {
-        // clamp to the action box, then slope * (x - in_high) + out_high with two roundings (roboy_env.py:157-158)
-        const float x = fminf(fmaxf(spu[k], -1.0f), 1.0f);
-        spu[k] = rbe::rounded_here(rbe::mul_then_add(slope, x - 1.0f, act_hi) * KSG[k]);
+        spu[k] = rbe::rounded_here(rbe::action_setpoint(slope, spu[k], act_hi) * KSG[k]);
     }
     const bool ok = lane_step<INTEG>(L, spu, h, nsub, qq, vv);
     RBL_LANE_STAMP(2);

@@ -290,9 +290,7 @@ __device__ __forceinline__ void split_wave(float *lds, int lane, int live, float
     for (int k = 0; k < RBL_NT; ++k) {
         const float a = img[OA + row * RBL_NT + k];
         if (env_layer) {
-            // clamp to the action box, then slope * (x - in_high) + out_high with two roundings (roboy_env.py:157-158)
-            const float x = fminf(fmaxf(a, -1.0f), 1.0f);
-            spu[k] = rbe::rounded_here(rbe::mul_then_add(ep->slope, x - 1.0f, ep->act_hi) * KSG[k]);
+            spu[k] = rbe::rounded_here(rbe::action_setpoint(ep->slope, a, ep->act_hi) * KSG[k]);
         } else {
             spu[k] = rbe::rounded_here((a * act_scale) * KSG[k]);
         }
@@ -346,8 +344,7 @@ __device__ __forceinline__ void split_helper(float *lds, int lane, int live, flo
     for (int k = 0; k < RBL_NT; ++k) {
         const float a = img[OA + row * RBL_NT + k];
         if (env_layer) {
-            const float x = fminf(fmaxf(a, -1.0f), 1.0f);
-            spu[k] = rbe::rounded_here(rbe::mul_then_add(ep->slope, x - 1.0f, ep->act_hi) * KSG[k]);
+            spu[k] = rbe::rounded_here(rbe::action_setpoint(ep->slope, a, ep->act_hi) * KSG[k]);
         } else {
             spu[k] = rbe::rounded_here((a * act_scale) * KSG[k]);
         }
