@@ -8,7 +8,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
-RP_ABI_VERSION = 2
+RP_ABI_VERSION = 3
 
 
 class MlpParams(ctypes.Structure):
@@ -39,6 +39,19 @@ SIGNATURES = {
     "rp_grad_form": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "rp_act_dev": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
                                   ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    # running observation normalisation: the two kernels with `const float *d_norm, float clip`, the statistics' two launches
+    "rp_act_norm_dev": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
+                                       ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                       ctypes.c_float, ctypes.c_void_p]),
+    "rp_ppo_grad_norm_dev": (ctypes.c_int, [ctypes.c_void_p] * 9 + [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                            ctypes.c_float, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
+    "rp_obs_moments_scratch_doubles": (ctypes.c_int64, []),
+    "rp_obs_moments_blocks": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int]),
+    "rp_obs_moments_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "rp_obs_norm_merge_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
 }
 
 

@@ -111,6 +111,35 @@ __device__ __forceinline__ void mfma_stream(const float *w, const B0 &b0, const 
     }
 }
 
+// ---- running observation normalisation (include/roboy_policy.h) ----
+// Every observation operand of the policy kernels goes through obs_operand(): with NORM the column value enters the network as
+// med3((x - mean) * rstd, -clip, clip), the difference and the product each rounded once to fp32 (nothing contracts them), so that a
+// numpy / torch fp32 restatement reproduces the operand bit for bit; without NORM it is the value itself and the code is what it was.
+// The statistics norm = float[2][obs_dim] (mean, rstd) never take LDS: where the column is wave-uniform (the K loop of layer 1: column
+// 2 s + half) they come as scalar loads through the constant address space - no vector register, and no vmcnt wait behind the
+// prefetching gradient kernel's LDS-DMA traffic; where the column is the lane's (the dW1 operand) one lane holds its column's pair.
+template <bool NORM>
+__device__ __forceinline__ float obs_operand(float x, float mean, float rstd, float clip) {
+    if (!NORM) return x;
+    return __builtin_amdgcn_fmed3f(__fmul_rn(__fsub_rn(x, mean), rstd), -clip, clip);
+}
+typedef const __attribute__((address_space(4))) float *norm_ptr;
+__device__ __forceinline__ norm_ptr norm_of(const float *norm) { return (norm_ptr)norm; }
+// the pair of column min(k, obs_dim - 1) (columns past the observation - the bias column, padding - never use it)
+__device__ __forceinline__ void norm_at(norm_ptr norm, int obs_dim, int k, float &mean, float &rstd) {
+    const int kk = k < obs_dim ? k : obs_dim - 1;
+    mean = norm[kk];
+    rstd = norm[obs_dim + kk];
+}
+// the pair of column 2 s + half of a layer-1 K step: two uniform loads per row and a select
+__device__ __forceinline__ void norm_of_step(norm_ptr norm, int obs_dim, int s, int half, float &mean, float &rstd) {
+    float m0, r0, m1, r1;
+    norm_at(norm, obs_dim, 2 * s, m0, r0);
+    norm_at(norm, obs_dim, 2 * s + 1, m1, r1);
+    mean = half ? m1 : m0;
+    rstd = half ? r1 : r0;
+}
+
 // offsets of one net's parameters inside its gradient vector (torch layout)
 struct GOff { int w1, b1, w2, b2, w3, b3, ls, loss; };
 __host__ __device__ inline GOff goff_of(int obs_dim, int n_out) {

@@ -58,7 +58,7 @@ int cu_count(int dev) {
 }
 
 namespace {
-constexpr int GRANT_KERNELS = 8, GRANT_DEVICES = 64;
+constexpr int GRANT_KERNELS = 18, GRANT_DEVICES = 64;        // 0 .. 8, and + 9 for the normalising instance of each
 std::mutex g_grant_mutex;
 size_t g_granted[GRANT_KERNELS][GRANT_DEVICES];            // bytes granted so far (0: the default 64 KB)
 }
@@ -94,8 +94,11 @@ using namespace rpd;
 // y[q][t]: output row tile q (only q < ot computed), column tile t, brought back to one sample per lane.
 // The two nets run one after the other so that a wave stays within 256 registers (two waves per SIMD: at one wave
 // per SIMD the tanh passes - 2 quarter-rate instructions per element - issue at less than half their rate).
+// NORM: the observation operands are normalised as they are fetched (mlp_common.hpp: obs_operand) - the only site of this kernel.
+template <bool NORM>
 __device__ __forceinline__ void net_forward(const float *lds, const Layout &L, int net, int ot, int lane, float onehot,
-                                            const float *x0, const float *x1, int obs_dim, f32x16 (&y)[2][2]) {
+                                            const float *x0, const float *x1, int obs_dim, f32x16 (&y)[2][2],
+                                            const float *norm = nullptr, float clip = 0.0f) {
     const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const int half = lane >> 5;
     f32x16 h1[HT][2];
@@ -105,8 +108,13 @@ __device__ __forceinline__ void net_forward(const float *lds, const Layout &L, i
     const float *w1 = lds + L.o_l1 + (net * HT) * L.k1s * 64 + lane;
     for (int s = 0; s < L.k1s; ++s) {
         const int k = 2 * s + half;
-        const float b0 = k < obs_dim ? x0[k] : (k == obs_dim ? 1.0f : 0.0f);
-        const float b1 = k < obs_dim ? x1[k] : (k == obs_dim ? 1.0f : 0.0f);
+        float b0 = k < obs_dim ? x0[k] : (k == obs_dim ? 1.0f : 0.0f);
+        float b1 = k < obs_dim ? x1[k] : (k == obs_dim ? 1.0f : 0.0f);
+        if (NORM) {
+            float mu, rs;
+            norm_of_step(norm_of(norm), obs_dim, s, half, mu, rs);
+            if (k < obs_dim) { b0 = obs_operand<true>(b0, mu, rs, clip); b1 = obs_operand<true>(b1, mu, rs, clip); }
+        }
 #pragma unroll
         for (int m = 0; m < HT; ++m) {
             const float a = w1[(m * L.k1s + s) * 64];
@@ -167,80 +175,11 @@ __device__ __forceinline__ void net_forward(const float *lds, const Layout &L, i
     }
 }
 
-__global__ void __launch_bounds__(256, 2)
-mlp_act_kernel(const float *__restrict__ packed, const float *__restrict__ obs, float *__restrict__ act,
-               float *__restrict__ logp, float *__restrict__ value, float *__restrict__ mean_out, long n, int obs_dim,
-               int act_dim, uint64_t seed, uint64_t sample_offset, uint32_t step, const uint32_t *__restrict__ step_base,
-               int deterministic) {
-    extern __shared__ float4 lds4[];
-    if (step_base) step += *step_base;
-    float *lds = reinterpret_cast<float *>(lds4);
-    const Layout L = layout_of(obs_dim, act_dim);
-    for (int k = threadIdx.x; k < L.total / 4; k += blockDim.x) lds4[k] = reinterpret_cast<const float4 *>(packed)[k];
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const int col = lane & 31, half = lane >> 5;
-    const float onehot = half ? 0.0f : 1.0f;
-    const long n_tiles = (n + 63) / 64;
-    // work item = (tile, net): the two nets of a tile share nothing but the observation, so they go to different
-    // waves - twice the items, half the dependent MFMA chain per item (what a small batch waits for: 4 096 samples are
-    // 64 tiles for 1 024 SIMDs)
-    for (long item = long(blockIdx.x) * nw + wave; item < 2 * n_tiles; item += long(gridDim.x) * nw) {
-        const long tile = item >> 1;
-        long s0 = tile * 64 + col, s1 = s0 + 32;                    // this lane's samples in column tile 0 / 1
-        s0 = s0 < n ? s0 : n - 1; s1 = s1 < n ? s1 : n - 1;         // past the end: shadow the last sample
-        const float *x0 = obs + s0 * obs_dim, *x1 = obs + s1 * obs_dim;
-        const long i = tile * 64 + lane;
-        const bool live = i < n;
-        f32x16 ypi[2][2];
-        if (item & 1) {                                              // the value net
-            net_forward(lds, L, 1, 1, lane, onehot, x0, x1, obs_dim, ypi);
-            if (live) value[i] = ypi[0][0][0];                       // row 0 of its output tile
-            continue;
-        }
-        net_forward(lds, L, 0, L.ot_pi, lane, onehot, x0, x1, obs_dim, ypi);    // the action-mean net
-        // ---- epilogue: this lane's sample ----
-        float lp = -0.91893853320467274f * float(act_dim);          // -1/2 log(2 pi) per dimension
-        float *arow = act + (live ? i : 0) * act_dim, *mrow = mean_out ? mean_out + (live ? i : 0) * act_dim : nullptr;
-        const uint64_t gid = sample_offset + uint64_t(i);
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int hh = 0; hh < 2; ++hh) {
-                    // rows 32 q + 8 g + 4 hh + (0..3): one Philox block gives their four normals
-                    const int j0 = 32 * q + 8 * g + 4 * hh;
-                    if (j0 < act_dim) {
-                        float eps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                        if (!deterministic) {
-                            const rb::Philox4 u = rb::philox_draw(seed, gid, step, STREAM_POLICY, uint32_t(j0 >> 2));
-#pragma unroll
-                            for (int pr = 0; pr < 2; ++pr) {           // Box-Muller on (u1 in (0,1], u2 in [0,1))
-                                const float u1 = float((u.v[2 * pr] >> 8) + 1u) * (1.0f / 16777216.0f);
-                                const float u2 = rb::u01(u.v[2 * pr + 1]);
-                                const float rad = __builtin_amdgcn_sqrtf(-2.0f * __logf(u1));
-                                float sn, cs;
-                                __sincosf(6.2831853071795865f * u2, &sn, &cs);
-                                eps[2 * pr] = rad * cs; eps[2 * pr + 1] = rad * sn;
-                            }
-                        }
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) {
-                            const int j = j0 + c;
-                            if (j < act_dim) {
-                                const float mu = hh ? ypi[q][1][4 * g + c] : ypi[q][0][4 * g + c];
-                                const float ls = lds[L.o_logstd + j];
-                                const float a = mu + __expf(ls) * eps[c];
-                                lp -= 0.5f * eps[c] * eps[c] + ls;
-                                if (live) { arow[j] = a; if (mrow) mrow[j] = mu; }
-                            }
-                        }
-                    }
-                }
-        if (live) logp[i] = lp;
-    }
-}
+// the two instances of one kernel text: without normalisation and with it
+#define RP_NORM 0
+#include "mlp_act_kernel.inc"
+#define RP_NORM 1
+#include "mlp_act_kernel.inc"
 
 }  // namespace
 
@@ -298,6 +237,14 @@ int rp_pack(const rp_mlp_params *p, int obs_dim, int act_dim, float *out) {
 int rp_act_dev(const float *d_packed, const float *d_obs, float *d_act, float *d_logp, float *d_value, float *d_mean,
                int64_t n, int obs_dim, int act_dim, uint64_t seed, uint64_t sample_offset, uint32_t step,
                const uint32_t *d_step_base, int deterministic, void *stream) {
+    return rp_act_norm_dev(d_packed, d_obs, d_act, d_logp, d_value, d_mean, n, obs_dim, act_dim, seed, sample_offset, step, d_step_base,
+                           deterministic, nullptr, 0.0f, stream);
+}
+
+int rp_act_norm_dev(const float *d_packed, const float *d_obs, float *d_act, float *d_logp, float *d_value, float *d_mean,
+                    int64_t n, int obs_dim, int act_dim, uint64_t seed, uint64_t sample_offset, uint32_t step,
+                    const uint32_t *d_step_base, int deterministic, const float *d_norm, float clip, void *stream) {
+    if (d_norm && !(clip > 0.0f)) return fail(RP_EINVAL, "clip must be > 0");
     if (!d_packed || !d_obs || !d_act || !d_logp || !d_value) return fail(RP_EINVAL, "null argument");
     if (n < 1) return fail(RP_EINVAL, "n must be >= 1");
     if (rp_packed_floats(obs_dim, act_dim) < 0) return RP_EUNSUPPORTED;
@@ -307,16 +254,23 @@ int rp_act_dev(const float *d_packed, const float *d_obs, float *d_act, float *d
     hipError_t e = hipSuccess;
     int dev = 0;
     DeviceScope scope(d_packed); if (scope.rc) return scope.rc; dev = scope.dev;          // the blob's device is the device of the call
-    if (int rc = grant_lds(reinterpret_cast<const void *>(&mlp_act_kernel), 0, dev, lds)) return rc;   // per kernel and device
+    // per kernel and device (kernel ids 0 and 9: mlp_train.hip has 1 .. 8)
+    if (int rc = d_norm ? grant_lds(reinterpret_cast<const void *>(&mlp_act_norm_kernel), 9, dev, lds)
+                        : grant_lds(reinterpret_cast<const void *>(&mlp_act_kernel), 0, dev, lds)) return rc;
     const int n_cu = cu_count(dev);
     const long n_tiles = (n + 63) / 64;
     // 4 waves per workgroup (one per SIMD), two workgroups per CU, persistent over tiles; 6-wave workgroups spread
     // unevenly over the 4 SIMDs and were slower (107 against 78 us at 262 144 samples)
     long blocks = (2 * n_tiles + 3) / 4;             // items = (tile, net)
     if (blocks > 2 * n_cu) blocks = 2 * n_cu;
-    hipLaunchKernelGGL(mlp_act_kernel, dim3(unsigned(blocks)), dim3(256), lds, static_cast<hipStream_t>(stream), d_packed,
-                       d_obs, d_act, d_logp, d_value, d_mean, long(n), obs_dim, act_dim, seed, sample_offset, step,
-                       d_step_base, deterministic);
+    if (d_norm)
+        hipLaunchKernelGGL(mlp_act_norm_kernel, dim3(unsigned(blocks)), dim3(256), lds, static_cast<hipStream_t>(stream), d_packed,
+                           d_obs, d_act, d_logp, d_value, d_mean, long(n), obs_dim, act_dim, seed, sample_offset, step,
+                           d_step_base, deterministic, d_norm, clip);
+    else
+        hipLaunchKernelGGL(mlp_act_kernel, dim3(unsigned(blocks)), dim3(256), lds, static_cast<hipStream_t>(stream), d_packed,
+                           d_obs, d_act, d_logp, d_value, d_mean, long(n), obs_dim, act_dim, seed, sample_offset, step,
+                           d_step_base, deterministic);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(RP_EHIP, std::string("mlp_act_kernel: ") + hipGetErrorString(e));
     return RP_OK;

@@ -4,6 +4,8 @@
 //                      Feistel network on the next even power of two), instead of torch.randperm's sort of n keys
 //   rp_adv_stats_dev   mean and 1 / (std + 1e-8) of the minibatch's advantages (gathered through the index), which
 //                      rp_ppo_grad_dev then applies per sample: no gathered / normalised copy is materialised
+//   rp_obs_moments_dev, rp_obs_norm_merge_dev   the running observation statistics (ppo.py: ObsNorm): shifted fp64 column sums of a
+//                      rollout in one pass, and Chan's merge of them into (mean, var, count) + the float form the kernels read
 //   rp_clip_adam_dev   clip_grad_norm_ + Adam.step over the flat gradient vector of rp_ppo_grad_dev and a parameter
 //                      buffer of the same layout: one workgroup, two passes over ~10^4 floats
 // The reference's consumer is stable_baselines' PPO2 (train_parallel.py:28-31); torch's optimiser is the statement these
@@ -104,6 +106,104 @@ adv_stats_kernel(const float *__restrict__ adv, const long long *__restrict__ in
     }
 }
 
+// ---- running observation statistics ----
+// Column sums of obs [rows][obs_dim] around a shift, in fp64.  A workgroup takes RPB = 256 / obs_dim whole rows per pass: thread t <
+// RPB * obs_dim reads element t of that contiguous span (coalesced) and owns column t % obs_dim for the whole launch; the grid strides
+// over the spans, four loads in flight per thread.  Then per workgroup: the RPB partial sums of a column in row order; the last
+// workgroup (ticket, as adv_stats_kernel) adds the workgroups' partials in block order.  Every sum has one fixed order.
+constexpr int MOM_BLOCKS = 1024, MOM_ROWS_PER_THREAD = 8;
+__global__ void __launch_bounds__(256)
+obs_moments_kernel(const float *__restrict__ obs, long long rows, int obs_dim, const double *__restrict__ shift, double *scratch,
+                   double *__restrict__ sums) {
+    __shared__ double sh[2][256];
+    __shared__ bool last;
+    const int rpb = 256 / obs_dim, t = threadIdx.x;
+    const bool active = t < rpb * obs_dim;
+    const int c = t % obs_dim, r = t / obs_dim;
+    const double sft = active && shift ? shift[c] : 0.0;
+    double s = 0.0, ss = 0.0;
+    if (active) {
+        const long long step = (long long)gridDim.x * rpb;
+        long long row = (long long)blockIdx.x * rpb + r;
+        for (; row + 3 * step < rows; row += 4 * step) {
+            const float x0 = obs[row * obs_dim + c], x1 = obs[(row + step) * obs_dim + c];
+            const float x2 = obs[(row + 2 * step) * obs_dim + c], x3 = obs[(row + 3 * step) * obs_dim + c];
+            const double d0 = double(x0) - sft, d1 = double(x1) - sft, d2 = double(x2) - sft, d3 = double(x3) - sft;
+            s += d0; ss += d0 * d0; s += d1; ss += d1 * d1; s += d2; ss += d2 * d2; s += d3; ss += d3 * d3;
+        }
+        for (; row < rows; row += step) {
+            const double d = double(obs[row * obs_dim + c]) - sft;
+            s += d; ss += d * d;
+        }
+    }
+    sh[0][t] = s; sh[1][t] = ss;
+    __syncthreads();
+    const int nq = 2 * obs_dim;                             // outputs: q < obs_dim the sum of column q, then the squares
+    double *mine = scratch + (long long)blockIdx.x * nq;
+    if (t < nq) {
+        const int w = t >= obs_dim, cc = t - w * obs_dim;
+        double v = 0.0;
+        for (int rr = 0; rr < rpb; ++rr) v += sh[w][rr * obs_dim + cc];
+        mine[t] = v;
+    }
+    unsigned int *ticket = reinterpret_cast<unsigned int *>(scratch + (long long)MOM_BLOCKS * 2 * RP_MAX_OBS);
+    // hand-off as in adv_stats_kernel - stores -> agent-scope release -> vmcnt(0) -> ticket; the last block acquires - but the partials
+    // are stored by several waves here, so every wave releases its own stores before the barrier in front of the ticket
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (t == 0) {
+        last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    }
+    __syncthreads();
+    if (!last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (t < nq) {
+        double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
+        int b = 0;
+        for (; b + 3 < int(gridDim.x); b += 4) {
+            v0 += __hip_atomic_load(scratch + (long long)b * nq + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            v1 += __hip_atomic_load(scratch + (long long)(b + 1) * nq + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            v2 += __hip_atomic_load(scratch + (long long)(b + 2) * nq + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            v3 += __hip_atomic_load(scratch + (long long)(b + 3) * nq + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        for (; b < int(gridDim.x); ++b) v0 += __hip_atomic_load(scratch + (long long)b * nq + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sums[1 + t] = (v0 + v1) + (v2 + v3);
+    }
+    if (t == 0) {
+        sums[0] = double(rows);
+        *ticket = 0u;                                      // ready for the next launch (same stream: ordered behind this one)
+    }
+}
+
+// Chan's merge of the shifted sums (shift = the state's mean, so the batch mean's offset from it IS sum / n) into the state; one
+// workgroup, a thread per column
+__global__ void __launch_bounds__(128)
+obs_norm_merge_kernel(double *state, const double *__restrict__ sums, int obs_dim, double eps, float *__restrict__ norm) {
+    const int c = threadIdx.x;
+    const double n = sums[0], count = state[2 * obs_dim];
+    if (!(n > 0.0)) return;                                 // (uniform: every thread reads the same two values)
+    const double tot = count + n;
+    if (c < obs_dim) {
+        const double S = sums[1 + c], SS = sums[1 + obs_dim + c];
+        const double delta = S / n;                         // batch mean - running mean
+        double m2b = SS - S * delta;                        // the batch's sum of squares around its own mean
+        m2b = m2b > 0.0 ? m2b : 0.0;
+        const double mean = state[c] + delta * (n / tot);
+        const double var = (state[obs_dim + c] * count + m2b + delta * delta * (count * n / tot)) / tot;
+        state[c] = mean;
+        state[obs_dim + c] = var;
+        norm[c] = float(mean);
+        norm[obs_dim + c] = float(1.0 / sqrt(var + eps));
+    }
+    __syncthreads();                                        // every thread has read the count
+    if (c == 0) state[2 * obs_dim] = tot;
+}
+
 // ---- gradient clipping by global norm + Adam, one workgroup ----
 struct AdamArgs {
     float *p, *m, *v;
@@ -183,6 +283,39 @@ int rp_adv_stats_dev(const float *d_adv, const int64_t *d_index, int64_t batch, 
                        reinterpret_cast<const long long *>(d_index), (long long)batch, d_scratch, d_stats2);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RP_EHIP, std::string("adv_stats_kernel: ") + hipGetErrorString(e));
+    return RP_OK;
+}
+
+int64_t rp_obs_moments_scratch_doubles(void) { return int64_t(MOM_BLOCKS) * 2 * RP_MAX_OBS + 1; }
+
+int64_t rp_obs_moments_blocks(int64_t rows, int obs_dim) {
+    if (rows < 1 || obs_dim < 1 || obs_dim > RP_MAX_OBS) return fail(RP_EINVAL, "need rows >= 1 and 1 <= obs_dim <= 95");
+    const int64_t per_block = int64_t(256 / obs_dim) * MOM_ROWS_PER_THREAD;       // at least eight rows per thread
+    const int64_t blocks = (rows + per_block - 1) / per_block;
+    return blocks < MOM_BLOCKS ? blocks : MOM_BLOCKS;
+}
+
+int rp_obs_moments_dev(const float *d_obs, int64_t rows, int obs_dim, const double *d_shift, double *d_sums, double *d_scratch,
+                       void *stream) {
+    if (!d_obs || !d_sums || !d_scratch) return fail(RP_EINVAL, "null argument");
+    const int64_t blocks = rp_obs_moments_blocks(rows, obs_dim);
+    if (blocks < 0) return int(blocks);
+    DeviceScope scope(d_obs); if (scope.rc) return scope.rc;
+    hipLaunchKernelGGL(obs_moments_kernel, dim3(unsigned(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), d_obs,
+                       (long long)rows, obs_dim, d_shift, d_scratch, d_sums);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RP_EHIP, std::string("obs_moments_kernel: ") + hipGetErrorString(e));
+    return RP_OK;
+}
+
+int rp_obs_norm_merge_dev(double *d_state, const double *d_sums, int obs_dim, double eps, float *d_norm, void *stream) {
+    if (!d_state || !d_sums || !d_norm) return fail(RP_EINVAL, "null argument");
+    if (obs_dim < 1 || obs_dim > RP_MAX_OBS) return fail(RP_EINVAL, "need 1 <= obs_dim <= 95");
+    if (!(eps >= 0.0)) return fail(RP_EINVAL, "eps must be >= 0");
+    DeviceScope scope(d_state); if (scope.rc) return scope.rc;
+    hipLaunchKernelGGL(obs_norm_merge_kernel, dim3(1), dim3(128), 0, static_cast<hipStream_t>(stream), d_state, d_sums, obs_dim, eps, d_norm);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RP_EHIP, std::string("obs_norm_merge_kernel: ") + hipGetErrorString(e));
     return RP_OK;
 }
 

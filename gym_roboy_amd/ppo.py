@@ -25,6 +25,12 @@ is all-reduced once per minibatch.  At 262 144 envs a PPO iteration goes from 49
 (rollout + update, torch: ~40 memory-bound passes over [8.4 M x 64] activations per minibatch) to
 11 ms + 0.11 s.  ``fused_policy=False, fused_update=False`` select the torch path, which is what
 the kernels are tested against.
+
+``normalize_obs=True`` keeps a running mean / variance of every observation column (``ObsNorm``: what stable-baselines calls
+``VecNormalize``, for the observation) and feeds the networks ``clip((obs - mean) / sqrt(var + eps))``.  The fused kernels
+normalise as they fetch their operands (``rp_act_norm_dev``, ``rp_ppo_grad_norm_dev``): the rollout buffers keep the raw
+observation and no normalised copy is ever written.  The statistics are frozen through a rollout and the update on it and merged
+with that rollout's moments after the update's last minibatch.
 """
 import math
 
@@ -32,9 +38,129 @@ import torch
 from torch import nn
 
 
+class ObsNorm:
+    """Running per-column mean / variance of the observation and the form the networks apply.
+
+    State (float64): ``state`` = [mean (obs_dim), var (obs_dim, population), count].  The form the kernels read (float32):
+    ``norm`` [2, obs_dim] = mean, rstd = 1 / sqrt(var + eps) - the identity (0, 1) while count == 0.  A column value enters the
+    network as ``min(max((x - mean) * rstd, -clip), clip)``, difference and product each rounded once to float32 (``apply``; the
+    kernels compute the same bits).  ``update(rows)`` merges the moments of a [rows, obs_dim] float32 batch (Chan's parallel
+    formula over sums taken around the current mean); the tensors are updated in place, so a captured launch that holds
+    ``norm``'s address sees the new statistics on its next replay.  Not an ``nn.Module``: nothing here is a parameter or a
+    buffer of the policy."""
+
+    def __init__(self, obs_dim, device="cpu", clip=10.0, eps=1e-8):
+        self.obs_dim, self.device, self.clip, self.eps = int(obs_dim), torch.device(device), float(clip), float(eps)
+        if not self.clip > 0.0:
+            raise ValueError("clip must be > 0")
+        self.state = torch.zeros(2 * self.obs_dim + 1, dtype=torch.float64, device=self.device)
+        self.norm = torch.zeros(2, self.obs_dim, dtype=torch.float32, device=self.device)
+        self._reset()
+        self._native = None
+
+    def _reset(self):
+        self.state.zero_(); self.state[self.obs_dim:2 * self.obs_dim] = 1.0
+        self.norm[0] = 0.0; self.norm[1] = 1.0
+
+    mean = property(lambda self: self.state[:self.obs_dim])
+    var = property(lambda self: self.state[self.obs_dim:2 * self.obs_dim])
+    count = property(lambda self: float(self.state[-1].item()))
+
+    def apply(self, obs):
+        """The normalised observation in ``obs``'s dtype (the torch statement of the kernels' operand fetch)."""
+        norm = self.norm.to(obs.dtype)
+        return ((obs - norm[0]) * norm[1]).clamp(-self.clip, self.clip)
+
+    def _lib(self):
+        if self._native is None:
+            import ctypes
+            from . import _policy_native as pn
+            lib = pn.load()
+            self._native = (pn, ctypes, lib)
+            self._scratch = torch.zeros(int(lib.rp_obs_moments_scratch_doubles()), dtype=torch.float64, device=self.device)
+            self._sums = torch.zeros(1 + 2 * self.obs_dim, dtype=torch.float64, device=self.device)
+        return self._native
+
+    @torch.no_grad()
+    def moments(self, rows):
+        """[rows, sum (x - mean), sum (x - mean)^2] (float64, 1 + 2 obs_dim) of a [rows, obs_dim] float32 batch around the running
+        mean: one HIP launch on a GPU, the torch float64 statement of the same sums on the CPU."""
+        if rows.dim() != 2 or rows.shape[1] != self.obs_dim or rows.dtype != torch.float32:
+            raise ValueError("expected float32 rows of %d columns, got %s %r" % (self.obs_dim, rows.dtype, tuple(rows.shape)))
+        if rows.device.type != "cuda":
+            d = rows.to(torch.float64) - self.mean.to(rows.device)
+            n = torch.tensor([float(rows.shape[0])], dtype=torch.float64, device=rows.device)
+            return torch.cat([n, d.sum(0), (d * d).sum(0)])
+        pn, c, lib = self._lib()
+        if rows.shape[0] == 0:
+            return self._sums.zero_()
+        rows = rows.contiguous()
+        pn.check(lib.rp_obs_moments_dev(c.c_void_p(rows.data_ptr()), int(rows.shape[0]), self.obs_dim, c.c_void_p(self.state.data_ptr()),
+                                        c.c_void_p(self._sums.data_ptr()), c.c_void_p(self._scratch.data_ptr()),
+                                        c.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)))
+        return self._sums
+
+    @torch.no_grad()
+    def merge(self, sums):
+        """Chan's merge of ``moments()`` sums (taken around the CURRENT mean) into the state, and the float form."""
+        if self.device.type == "cuda":
+            pn, c, lib = self._lib()
+            pn.check(lib.rp_obs_norm_merge_dev(c.c_void_p(self.state.data_ptr()), c.c_void_p(sums.data_ptr()), self.obs_dim, self.eps,
+                                               c.c_void_p(self.norm.data_ptr()), c.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            return
+        od = self.obs_dim
+        n, count = float(sums[0]), float(self.state[-1])
+        if not n > 0.0:
+            return
+        S, SS = sums[1:1 + od], sums[1 + od:]
+        tot = count + n
+        delta = S / n                                         # batch mean - running mean
+        m2b = (SS - S * delta).clamp_min(0.0)                 # the batch's sum of squares around its own mean
+        mean = self.mean + delta * (n / tot)
+        var = (self.var * count + m2b + delta * delta * (count * n / tot)) / tot
+        self.state[:od] = mean; self.state[od:2 * od] = var; self.state[-1] = tot
+        self.norm[0] = mean.to(torch.float32)
+        self.norm[1] = (1.0 / torch.sqrt(var + self.eps)).to(torch.float32)
+
+    @torch.no_grad()
+    def update(self, obs_rows, dist=None):
+        """Merge the moments of ``obs_rows`` [rows, obs_dim].  With several ranks the 1 + 2 obs_dim sums - taken around the same
+        mean on every rank, so they add - are all-reduced once (the device tensor under nccl, through the host under gloo, as
+        ``FusedAdam.step``): every rank then merges the same numbers and holds bit-identical statistics."""
+        sums = self.moments(obs_rows.to(self.device))
+        if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            if sums.device.type != "cuda" or dist.get_backend() == "nccl":
+                dist.all_reduce(sums)
+            else:
+                host = sums.cpu()
+                dist.all_reduce(host)
+                sums.copy_(host)
+        self.merge(sums)
+
+    def state_dict(self):
+        od = self.obs_dim
+        return {"mean": self.state[:od].clone(), "var": self.state[od:2 * od].clone(), "count": self.count,
+                "clip": self.clip, "eps": self.eps}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        od = self.obs_dim
+        if tuple(sd["mean"].shape) != (od,) or tuple(sd["var"].shape) != (od,):
+            raise ValueError("observation statistics of %d columns, this policy's observation has %d" % (sd["mean"].numel(), od))
+        self.clip, self.eps = float(sd["clip"]), float(sd["eps"])
+        self._reset()
+        if float(sd["count"]) > 0.0:
+            self.state[:od] = sd["mean"].to(self.device, torch.float64); self.state[od:2 * od] = sd["var"].to(self.device, torch.float64)
+            self.state[-1] = float(sd["count"])
+            self.norm[0] = self.mean.to(torch.float32)
+            self.norm[1] = (1.0 / torch.sqrt(self.var + self.eps)).to(torch.float32)
+
+
 class MlpPolicy(nn.Module):
     """Two tanh layers of 64 units for the policy and for the value function,
     diagonal Gaussian with a state-independent log-std (stable_baselines' MlpPolicy)."""
+
+    obs_norm = None        # an ObsNorm once set_obs_norm() was called: a plain attribute, not a parameter or buffer
 
     def __init__(self, obs_dim: int, act_dim: int, hidden: int = 64):
         super().__init__()
@@ -50,11 +176,21 @@ class MlpPolicy(nn.Module):
         nn.init.orthogonal_(self.pi[-1].weight, 0.01)
         nn.init.orthogonal_(self.vf[-1].weight, 1.0)
 
+    def set_obs_norm(self, obs_norm):
+        """An ``ObsNorm`` (or None): ``dist()`` and ``value()`` then see the normalised observation.  The statistics are neither
+        parameters nor buffers of the module (``state_dict()`` keeps its keys) and carry no gradient."""
+        self.obs_norm = obs_norm
+        return self
+
     def dist(self, obs):
+        if self.obs_norm is not None:
+            obs = self.obs_norm.apply(obs)
         # validate_args=False: the check reads a device flag back (a host sync per call)
         return torch.distributions.Normal(self.pi(obs), self.log_std.exp(), validate_args=False)
 
     def value(self, obs):
+        if self.obs_norm is not None:
+            obs = self.obs_norm.apply(obs)
         return self.vf(obs).squeeze(-1)
 
     @torch.no_grad()
@@ -94,6 +230,12 @@ def gae_fused(rewards, values, dones, last_value, gamma, lam, adv_out=None, ret_
     return adv, ret
 
 
+def _check_norm(norm, obs_dim, device):
+    if norm.obs_dim != obs_dim or norm.norm.device != device or norm.norm.dtype != torch.float32 or not norm.norm.is_contiguous():
+        raise ValueError("observation statistics of %d columns on %s, the kernel reads %d on %s"
+                         % (norm.obs_dim, norm.norm.device, obs_dim, device))
+
+
 class FusedPolicyStep:
     """``MlpPolicy.act`` as one kernel on the matrix cores (include/roboy_policy.h, csrc/mlp_policy.hip): observation
     -> action sample, log-probability, value, written straight into the rollout buffers.  The parameters stay torch
@@ -127,15 +269,23 @@ class FusedPolicyStep:
 
     @torch.no_grad()
     def act_into(self, obs, act, logp, val, step=0, packed=None, mean=None, sample_offset=0, deterministic=False,
-                 step_base=None):
-        """obs [n, obs_dim] (contiguous, fp32, cuda) -> act [n, act_dim], logp [n], val [n] (preallocated)."""
+                 step_base=None, norm=None):
+        """obs [n, obs_dim] (contiguous, fp32, cuda) -> act [n, act_dim], logp [n], val [n] (preallocated).
+        norm (an ``ObsNorm``, optional): the observation is normalised as the kernel fetches it (rp_act_norm_dev)."""
         c = self._ct
         packed = self.pack() if packed is None else packed
         ptr = lambda t: c.c_void_p(t.data_ptr()) if t is not None else None
-        self._pn.check(self._lib.rp_act_dev(
-            ptr(packed), ptr(obs), ptr(act), ptr(logp), ptr(val), ptr(mean), int(obs.shape[0]), self.obs_dim, self.act_dim,
-            self.seed, int(sample_offset), int(step), ptr(step_base), int(bool(deterministic)),
-            c.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)))
+        stream = c.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        if norm is None:
+            self._pn.check(self._lib.rp_act_dev(
+                ptr(packed), ptr(obs), ptr(act), ptr(logp), ptr(val), ptr(mean), int(obs.shape[0]), self.obs_dim, self.act_dim,
+                self.seed, int(sample_offset), int(step), ptr(step_base), int(bool(deterministic)), stream))
+        else:
+            _check_norm(norm, self.obs_dim, obs.device)
+            self._pn.check(self._lib.rp_act_norm_dev(
+                ptr(packed), ptr(obs), ptr(act), ptr(logp), ptr(val), ptr(mean), int(obs.shape[0]), self.obs_dim, self.act_dim,
+                self.seed, int(sample_offset), int(step), ptr(step_base), int(bool(deterministic)), ptr(norm.norm), float(norm.clip),
+                stream))
         return packed
 
 
@@ -188,11 +338,12 @@ class FusedPolicyGrad:
 
     @torch.no_grad()
     def run(self, obs, act, adv, logp_old, val_old, ret, cliprange, vf_coef, ent_coef, index=None, adv_stats=None,
-            entropy_grad=True):
+            entropy_grad=True, norm=None):
         """index (int64 [B], optional): minibatch sample i is row index[i] of obs / act / logp_old / val_old / ret
         (the whole rollout's tensors, no gathered copies).  adv: in minibatch order and normalised by the caller, or
         - with adv_stats (minibatch_adv_stats()) - the rollout's raw advantage, indexed like the rest and normalised
-        in the kernel.  entropy_grad=False leaves the entropy bonus of the log-std to FusedAdam.step()."""
+        in the kernel.  entropy_grad=False leaves the entropy bonus of the log-std to FusedAdam.step().  norm (an ``ObsNorm``,
+        optional): obs holds raw observations, normalised where the kernels fetch them (rp_ppo_grad_norm_dev)."""
         c = self._ct
         B = int(index.shape[0]) if (index is not None and adv_stats is not None) else int(adv.shape[0])
         flat = torch.cat([self._named[k].detach().reshape(-1) for k in self._pn.PARAM_ORDER] + [self._zero])
@@ -201,11 +352,18 @@ class FusedPolicyGrad:
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, device=obs.device)
         ptr = lambda t: c.c_void_p(t.data_ptr()) if t is not None else None
-        self._pn.check(self._lib.rp_ppo_grad_dev(
-            ptr(packed), ptr(obs), ptr(act), ptr(adv), ptr(adv_stats), ptr(logp_old), ptr(val_old), ptr(ret), ptr(index), B,
-            self.obs_dim, self.act_dim,
-            float(cliprange), float(vf_coef), ptr(self._g), ptr(self._ws),
-            c.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)))
+        stream = c.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        if norm is None:
+            self._pn.check(self._lib.rp_ppo_grad_dev(
+                ptr(packed), ptr(obs), ptr(act), ptr(adv), ptr(adv_stats), ptr(logp_old), ptr(val_old), ptr(ret), ptr(index), B,
+                self.obs_dim, self.act_dim,
+                float(cliprange), float(vf_coef), ptr(self._g), ptr(self._ws), stream))
+        else:
+            _check_norm(norm, self.obs_dim, obs.device)
+            self._pn.check(self._lib.rp_ppo_grad_norm_dev(
+                ptr(packed), ptr(obs), ptr(act), ptr(adv), ptr(adv_stats), ptr(logp_old), ptr(val_old), ptr(ret), ptr(index), B,
+                self.obs_dim, self.act_dim, float(cliprange), float(vf_coef), ptr(norm.norm), float(norm.clip), ptr(self._g),
+                ptr(self._ws), stream))
         if entropy_grad:
             self._views["log_std"] -= ent_coef        # entropy bonus of a state-independent log-std
         for name, p in self._named.items():
@@ -374,7 +532,7 @@ class PPO:
     def __init__(self, env, policy=None, n_steps=128, nminibatches=4, noptepochs=4, gamma=0.99, lam=0.95,
                  learning_rate=2.5e-4, cliprange=0.2, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5,
                  device="cuda", dist=None, reward_scale=1.0, seed=0, use_graphs=False, fused_policy=None,
-                 fused_update=None, rollout_chains=None):
+                 fused_update=None, rollout_chains=None, normalize_obs=False, clip_obs=10.0, obs_norm_prime=True):
         """fused_policy / fused_update: None = the fused MFMA kernels whenever they apply (a GPU, MlpPolicy's shape,
         dimensions the kernels support), True = insist, False = the torch path (the statement the kernels are
         tested against).
@@ -382,13 +540,21 @@ class PPO:
         step) launches over the two halves of the batch on two streams, joined in front of GAE (the sub-range entry points of
         include/roboy_sim.h: one half's launch gaps and load / store phases lie under the other half's kernels; the results do
         not depend on the split); 1 = one chain over the whole batch; None = two from ``CHAIN_BATCH`` envs on where the env's
-        kernel form steps sub-ranges and the policy is of MsjRobot's size."""
+        kernel form steps sub-ranges and the policy is of MsjRobot's size.
+        normalize_obs: running mean / variance normalisation of the observation (``ObsNorm``), clamped to +-clip_obs; the
+        statistics are frozen through a rollout and the update on it, then merged with that rollout's moments.  obs_norm_prime:
+        while no statistics exist, the first ``collect()`` runs one rollout under the identity for its moments alone (not
+        returned, not counted in ``num_timesteps``) and collects again."""
         self.env, self.dist, self.device = env, dist, torch.device(device)
         self._chains_arg = rollout_chains
         torch.manual_seed(seed)
         obs_dim = env.observation_space.shape[0]
         act_dim = env.action_space.shape[0]
         self.policy = (policy or MlpPolicy(obs_dim, act_dim)).to(self.device)
+        self.obs_norm = ObsNorm(obs_dim, self.device, clip=clip_obs) if normalize_obs else None
+        self._obs_norm_prime = bool(obs_norm_prime)
+        if self.obs_norm is not None or getattr(self.policy, "obs_norm", None) is not None:
+            self.policy.set_obs_norm(self.obs_norm)
         if dist is not None and dist.is_available() and dist.is_initialized():
             for p in self.policy.parameters():          # same initial weights on every rank
                 dist.broadcast(p.data, 0)
@@ -453,7 +619,7 @@ class PPO:
                 # straight into the rollout buffers; the env kernel clamps the action to its box itself.  The noise is keyed by
                 # the GLOBAL sample index (sample_offset): the same draw however the batch is cut
                 self._fused.act_into(b["obs"][t][lo:hi], b["act"][t][lo:hi], b["logp"][t][lo:hi], b["val"][t][lo:hi], step=t,
-                                     packed=packed, step_base=self._step_base, sample_offset=lo)
+                                     packed=packed, step_base=self._step_base, sample_offset=lo, norm=self.obs_norm)
                 if whole:
                     env.step_dev(b["act"][t].data_ptr(), b["obs"][t + 1].data_ptr(), b["rew_raw"][t].data_ptr(),
                                  b["done_i"][t].data_ptr())
@@ -524,7 +690,7 @@ class PPO:
             # first use of the GEMM library for these shapes (handle, workspace) must not fall into the capture
             self.policy.act(b["carry"]); self.policy.value(b["carry"])
             if self._fused is not None:       # its one-time launch configuration must not fall into the capture either
-                self._fused.act_into(b["carry"], b["act"][0], b["logp"][0], b["val"][0], deterministic=True)
+                self._fused.act_into(b["carry"], b["act"][0], b["logp"][0], b["val"][0], deterministic=True, norm=self.obs_norm)
         side.synchronize()
         self.rollout_chains = self._pick_chains(N)
         # thread-local capture mode: another thread of the process (RCCL's watchdog in a multi-rank run) may call into
@@ -581,6 +747,17 @@ class PPO:
                 "done": b["done"], "adv": b["adv"], "ret": b["ret"]}
 
     def collect(self):
+        if self.obs_norm is not None and self._obs_norm_prime:
+            self._obs_norm_prime = False                     # (asked once: the count is read back from the device)
+            if self.obs_norm.count == 0:
+                # priming: one rollout under the identity, for its moments alone
+                before = self.num_timesteps
+                roll = self._collect_rollout()
+                self.num_timesteps = before
+                self.obs_norm.update(roll["obs"].reshape(-1, roll["obs"].shape[-1]), self.dist)
+        return self._collect_rollout()
+
+    def _collect_rollout(self):
         if self.use_graphs:
             return self._collect_graph()
         env, T = self.env, self.n_steps
@@ -594,7 +771,7 @@ class PPO:
                 o = self._obs.contiguous()
                 a = torch.empty(N, self._fused.act_dim, device=self.device)
                 logp, v = torch.empty(N, device=self.device), torch.empty(N, device=self.device)
-                self._fused.act_into(o, a, logp, v, step=t, packed=packed, step_base=self._step_base)
+                self._fused.act_into(o, a, logp, v, step=t, packed=packed, step_base=self._step_base, norm=self.obs_norm)
             else:
                 a, logp, v = self.policy.act(self._obs)
             clipped = a.clamp(-1.0, 1.0).contiguous()        # the env's action box (roboy_env.py:31)
@@ -631,7 +808,7 @@ class PPO:
         gather the rollout's rows through idx and normalise the advantage per sample), clip + Adam."""
         stats = self._fgrad.minibatch_adv_stats(flat["adv"], idx)
         pg, vf = self._fgrad.run(flat["obs"], flat["act"], flat["adv"], flat["logp"], flat["val"], flat["ret"], self.cliprange,
-                                 self.vf_coef, self.ent_coef, index=idx, adv_stats=stats, entropy_grad=False)
+                                 self.vf_coef, self.ent_coef, index=idx, adv_stats=stats, entropy_grad=False, norm=self.obs_norm)
         scale = self._fadam.step(self.ent_coef, self.dist)          # all-reduces the gradient vector first when ranks > 1
         ent = (0.5 + 0.5 * math.log(2 * math.pi) + self.policy.log_std.detach()).sum()
         pg, vf = pg * scale, vf * scale                              # (the loss slots were summed over the ranks with the rest)
@@ -676,6 +853,9 @@ class PPO:
             perm = self._sample_order(n) if sample_orders is None else sample_orders[ep].contiguous()
             for s in range(0, n - mb + 1, mb):
                 out = self._minibatch_step(flat, perm[s:s + mb])
+        if self.obs_norm is not None:
+            # the statistics move only now: rollout and update saw the same ones (old and new log-probabilities of the same inputs)
+            self.obs_norm.update(flat["obs"], self.dist)
         if out is None:
             return {}
         loss, pg, vf, ent = out
@@ -695,13 +875,20 @@ class PPO:
     def save(self, path):
         opt = self._fadam.state_dict() if self._fgrad is not None else self.opt.state_dict()
         torch.save({"policy": self.policy.state_dict(), "optimizer": opt, "num_timesteps": self.num_timesteps,
-                    "epoch": self._epoch, "tendon_obs": _tendon_obs_of(self.env), "env_io": _env_io_of(self.env)}, path)
+                    "epoch": self._epoch, "tendon_obs": _tendon_obs_of(self.env), "env_io": _env_io_of(self.env),
+                    "obs_norm": self.obs_norm.state_dict() if self.obs_norm is not None else None}, path)
 
     def load(self, path):
         ck = torch.load(path, map_location=self.device)
         if ck.get("tendon_obs", _tendon_obs_of(None)) != _tendon_obs_of(self.env):
             raise ValueError("the checkpoint was trained on the observation %r, this env gives %r (RoboyVecEnv's tendon_obs / "
                              "tendon_obs_scale)" % (ck.get("tendon_obs", _tendon_obs_of(None)), _tendon_obs_of(self.env)))
+        if (ck.get("obs_norm") is not None) != (self.obs_norm is not None):      # (a checkpoint without the key: written without it)
+            raise ValueError("the checkpoint was trained %s observation normalisation, this agent runs %s it (PPO's normalize_obs)"
+                             % (("with", "without") if self.obs_norm is None else ("without", "with")))
+        if self.obs_norm is not None:
+            self.obs_norm.load_state_dict(ck["obs_norm"])
+            self._obs_norm_prime = self._obs_norm_prime and float(ck["obs_norm"]["count"]) == 0.0
         self.policy.load_state_dict(ck["policy"])      # copies in place: the views of the fused optimiser's flat buffer stay valid
         fused_ck = isinstance(ck["optimizer"], dict) and ck["optimizer"].get("fused_adam", False)
         if self._fgrad is not None and fused_ck:

@@ -44,6 +44,10 @@ def main(argv=None):
     ap.add_argument("--action-delay", default="", metavar="D | LO:HI",
                     help="steps by which every action acts late (at most 7): one number, or a range each env draws from at every "
                          "episode start, e.g. 0:3; stored in the checkpoint")
+    ap.add_argument("--normalize-obs", action="store_true",
+                    help="running mean / variance normalisation of the observation inside the policy kernels (what "
+                         "stable-baselines calls VecNormalize); the statistics are stored in the checkpoint")
+    ap.add_argument("--clip-obs", type=float, default=10.0, metavar="X", help="clamp of the normalised observation (default 10)")
     args = ap.parse_args(argv)
     sensor_noise = {k: float(v) for k, v in (item.split("=", 1) for item in args.sensor_noise.split(",") if item)}
     action_delay = None
@@ -82,7 +86,7 @@ def main(argv=None):
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,
-                fused_update=not args.torch_policy)
+                fused_update=not args.torch_policy, normalize_obs=args.normalize_obs, clip_obs=args.clip_obs)
     if os.path.exists(model_file):
         agent.load(model_file)                  # resume from the last backup
     for _ in range(args.rounds):

@@ -72,6 +72,11 @@ def main(argv=None):
         raise SystemExit("%s holds a policy over %d observation columns, this env gives %d: it was not written by this "
                          "train_parallel" % (args.model, ck["policy"]["pi.0.weight"].shape[1], n_obs))
     policy.load_state_dict(ck["policy"])
+    if ck.get("obs_norm") is not None:          # trained with PPO's normalize_obs: the policy reads the observation through them
+        from .ppo import ObsNorm
+        stats = ObsNorm(n_obs)
+        stats.load_state_dict(ck["obs_norm"])
+        policy.set_obs_norm(stats)
     logger = Logger(args.pause)
     obs = reset()
     for i in range(args.steps):

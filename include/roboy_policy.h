@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define RP_ABI_VERSION 2
+#define RP_ABI_VERSION 3
 #define RP_HIDDEN 64          /* units per hidden layer (stable_baselines' MlpPolicy) */
 #define RP_MAX_OBS 95         /* obs_dim + 1 (bias column) <= 96 */
 #define RP_MAX_ACT 64
@@ -112,6 +112,39 @@ int rp_adv_stats_dev(const float *d_adv, const int64_t *d_index, int64_t batch, 
 int rp_clip_adam_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int act_dim, float lr,
                      float beta1, float beta2, float eps, int64_t step, float max_grad_norm, float grad_scale, float ent_coef,
                      void *stream);
+/* ---- running observation normalisation (gym_roboy_amd/ppo.py: ObsNorm) ----
+ * State per observation column: mean, var and a shared count, float64 (d_state: double[2 * obs_dim + 1] = mean, var, count).
+ * The form the kernels read is d_norm = float[2][obs_dim]: row 0 mean, row 1 rstd = 1 / sqrt(var + eps); while count == 0 it is
+ * the identity (mean 0, rstd 1).  A column value enters the network as
+ *     x' = min(max((x - mean) * rstd, -clip), clip)
+ * with the difference and the product each rounded once to float32 (never contracted) and the clamp last, so that a numpy / torch
+ * float32 restatement reproduces the operand bit for bit; the bias column stays the constant 1; the statistics carry no gradient.
+ * The statistics take no LDS: every limit of the unnormalised entry points (rp_train_packed_floats, rp_grad_form) holds unchanged. */
+
+/* rp_act_dev with the observation normalised as it is fetched (the layer-1 operands: the kernel's only read of it).  d_norm == NULL
+ * launches rp_act_dev's kernel itself; clip > 0 (INFINITY: no clamp). */
+int rp_act_norm_dev(const float *d_packed, const float *d_obs, float *d_act, float *d_logp, float *d_value, float *d_mean,
+                    int64_t n, int obs_dim, int act_dim, uint64_t seed, uint64_t sample_offset, uint32_t step,
+                    const uint32_t *d_step_base, int deterministic, const float *d_norm, float clip, void *stream);
+/* rp_ppo_grad_dev on normalised observations, in all three forms rp_grad_form reports: the layer-1 forward operands AND the operands
+ * of dW1 += delta1 [obs | 1]^T are x'.  d_norm == NULL launches rp_ppo_grad_dev's kernels themselves. */
+int rp_ppo_grad_norm_dev(const float *d_packed_train, const float *d_obs, const float *d_act, const float *d_adv,
+                         const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
+                         const int64_t *d_index, int64_t batch, int obs_dim, int act_dim, float cliprange, float vf_coef,
+                         const float *d_norm, float clip, float *d_grad, float *d_workspace, void *stream);
+/* Shifted moments of obs [rows][obs_dim] (float32, contiguous): d_sums = double[1 + 2 * obs_dim] = {rows, sum_c (x - shift_c),
+ * sum_c (x - shift_c)^2}; d_shift: double[obs_dim] or NULL (= 0).  The shift is the current running mean (d_state's first obs_dim
+ * doubles), which is what rp_obs_norm_merge_dev assumes; sums of different ranks taken with the same shift add.  One launch, fp64
+ * accumulation in a fixed order (bit-reproducible run to run), no floating-point atomics.  d_scratch:
+ * rp_obs_moments_scratch_doubles() doubles, zeroed ONCE by the caller (the kernel leaves it ready for the next call).
+ * rp_obs_moments_blocks(): the grid of that launch - a workgroup takes 256 / obs_dim rows per pass of its grid-stride loop. */
+int64_t rp_obs_moments_scratch_doubles(void);
+int64_t rp_obs_moments_blocks(int64_t rows, int obs_dim);
+int rp_obs_moments_dev(const float *d_obs, int64_t rows, int obs_dim, const double *d_shift, double *d_sums, double *d_scratch,
+                       void *stream);
+/* Chan's parallel merge of d_sums (taken with shift = d_state's mean) into d_state = {mean, var (population), count}, and the float
+ * form d_norm = {mean, 1 / sqrt(var + eps)}.  rows == 0 (d_sums[0]) leaves everything unchanged.  One small launch. */
+int rp_obs_norm_merge_dev(double *d_state, const double *d_sums, int obs_dim, double eps, float *d_norm, void *stream);
 /* test hook: would a grant of lds_bytes of dynamic LDS be issued for (kernel id, device) now?  Records it. */
 int rp_debug_lds_grant_needed(int kernel_id, int dev, int64_t lds_bytes);
 /* which form of the gradient kernels rp_ppo_grad_dev launches for this policy: 2 = the small instance (obs_dim <= 31, up to 8
