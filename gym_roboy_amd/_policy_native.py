@@ -8,7 +8,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
-RP_ABI_VERSION = 3
+RP_ABI_VERSION = 4
 
 
 class MlpParams(ctypes.Structure):
@@ -52,6 +52,12 @@ SIGNATURES = {
                                           ctypes.c_void_p, ctypes.c_void_p]),
     "rp_obs_norm_merge_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
                                              ctypes.c_void_p]),
+    # running return normalisation of the reward: the rollout's tail as one launch
+    "rp_rollout_tail_scratch_doubles": (ctypes.c_int64, []),
+    "rp_rollout_tail_blocks": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int64]),
+    "rp_rollout_tail_dev": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                                           ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 7 +
+                                          [ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),
 }
 
 

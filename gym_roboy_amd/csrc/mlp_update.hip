@@ -6,6 +6,8 @@
 //                      rp_ppo_grad_dev then applies per sample: no gathered / normalised copy is materialised
 //   rp_obs_moments_dev, rp_obs_norm_merge_dev   the running observation statistics (ppo.py: ObsNorm): shifted fp64 column sums of a
 //                      rollout in one pass, and Chan's merge of them into (mean, var, count) + the float form the kernels read
+//   rp_rollout_tail_dev   the rollout's tail under running return normalisation of the reward (ppo.py: RewardNorm): reward scaling,
+//                      the discounted-return scan with its fp64 moments, the done conversion and GAE as one launch
 //   rp_clip_adam_dev   clip_grad_norm_ + Adam.step over the flat gradient vector of rp_ppo_grad_dev and a parameter
 //                      buffer of the same layout: one workgroup, two passes over ~10^4 floats
 // The reference's consumer is stable_baselines' PPO2 (train_parallel.py:28-31); torch's optimiser is the statement these
@@ -17,6 +19,7 @@
 // bit (csrc/mlp_policy.hip): Philox4x32-10, key = seed, counter = (sample id low, high, step + step base, 2 << 8 | block), action j =
 // component j & 3 of block j >> 2, Box-Muller on words (0, 1) and (2, 3) with u1 = ((w >> 8) + 1) / 2^24, u2 = (w >> 8) / 2^24.
 #include <hip/hip_runtime.h>
+
 
 #include "../../include/roboy_policy.h"
 #include "mlp_common.hpp"
@@ -204,6 +207,149 @@ obs_norm_merge_kernel(double *state, const double *__restrict__ sums, int obs_di
     if (c == 0) state[2 * obs_dim] = tot;
 }
 
+// ---- the rollout's tail with running return normalisation of the reward (ppo.py: RewardNorm) ----
+// One env per lane, [T][N] arrays indexed t * N + i (coalesced over i), two scans per lane:
+//   forward   r_s = fl32(rew_raw * scale);  R = gamma R + r_s in fp64;  d = R - shift joins S, SS;  R = 0 where done  (R: ret_carry)
+//   backward  gae_kernel's recurrence over r~ = med3(fl32(r_s * rstd), -clip, clip); writes rew, done (as float), adv, ret
+// TAIL_UNROLL steps' loads are issued before the first of them is used: a lane's scan is a serial chain, and the bytes in flight per
+// wave are what the loads of independent steps put there.  Then the fp64 sums as obs_moments_kernel hands them on: per wave by
+// shuffles, per workgroup in wave order to scratch, every wave releasing its own stores before the barrier in front of the ticket;
+// the last workgroup adds the workgroups' partials - thread k those of workgroups k, k + 256, ... in that order, then the same
+// shuffle / wave-order tree - so every sum has one fixed order.  A grid of at most TAIL_BLOCKS workgroups strides over the envs.
+constexpr int TAIL_BLOCKS = 4096, TAIL_UNROLL = 8;
+#define TAIL_ADDRESSING \
+    typedef __attribute__((address_space(1))) char *gchar; \
+    typedef __attribute__((address_space(1))) float *gfloat; \
+    typedef __attribute__((address_space(1))) int *gint; \
+    auto uni = [](const void *row) { \
+        const unsigned long long a = reinterpret_cast<unsigned long long>(row); \
+        const unsigned lo = __builtin_amdgcn_readfirstlane(unsigned(a)), hi = __builtin_amdgcn_readfirstlane(unsigned(a >> 32)); \
+        return reinterpret_cast<gchar>((unsigned long long)hi << 32 | lo); \
+    }; \
+    auto ldf = [&](const float *row, unsigned off) { return *reinterpret_cast<gfloat>(uni(row) + off); }; \
+    auto ldi = [&](const int *row, unsigned off) { return *reinterpret_cast<gint>(uni(row) + off); }; \
+    auto st = [&](float *row, unsigned off, float x) { *reinterpret_cast<gfloat>(uni(row) + off) = x; };
+// The fp64 sums of a workgroup of BS lanes, handed on as obs_moments_kernel does (see above); called once, by every lane.
+template <int BS>
+__device__ __forceinline__ void tail_reduce(double s, double ss, double *scratch, double *__restrict__ sums3, int T, long long n) {
+    __shared__ double sh[2][BS / 64];
+    __shared__ bool last;
+    const int tid = threadIdx.x;
+    auto wave_sum = [&](int q) { double v = sh[q][0]; for (int w = 1; w < BS / 64; ++w) v += sh[q][w]; return v; };
+    auto block_sum = [&]() {
+        for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off, 64); ss += __shfl_xor(ss, off, 64); }
+        if ((tid & 63) == 0) { sh[0][tid >> 6] = s; sh[1][tid >> 6] = ss; }
+        __syncthreads();
+    };
+    block_sum();
+    unsigned int *ticket = reinterpret_cast<unsigned int *>(scratch + 2 * TAIL_BLOCKS);
+    if (tid == 0) {
+        scratch[2 * blockIdx.x] = wave_sum(0);
+        scratch[2 * blockIdx.x + 1] = wave_sum(1);
+    }
+    // hand-off as in obs_moments_kernel: every wave releases its own stores (the partials above, and nothing of the arrays needs it)
+    // before the barrier in front of the ticket; the last workgroup acquires
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+    }
+    __syncthreads();
+    if (!last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    s = 0.0; ss = 0.0;
+    for (int b = tid; b < int(gridDim.x); b += BS) {
+        s += __hip_atomic_load(scratch + 2 * b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ss += __hip_atomic_load(scratch + 2 * b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();                                        // (thread 0 has read sh for its partial)
+    block_sum();
+    if (tid == 0) {
+        sums3[0] = double(T) * double(n);
+        sums3[1] = wave_sum(0);
+        sums3[2] = wave_sum(1);
+        *ticket = 0u;                                      // ready for the next launch (same stream: ordered behind this one)
+    }
+}
+
+__global__ void __launch_bounds__(256, 4)                  // four waves per SIMD: 262 144 envs are one resident grid of 1 024 workgroups
+rollout_tail_kernel(const float *__restrict__ rew_raw, const int *__restrict__ done_i, const float *__restrict__ val,
+                    const float *__restrict__ last_val, float scale, const float *__restrict__ norm2, float clip,
+                    const double *__restrict__ shift, double gamma, float lam, double *__restrict__ ret_carry, float *__restrict__ rew,
+                    float *__restrict__ done, float *__restrict__ adv, float *__restrict__ ret, double *__restrict__ sums3,
+                    double *scratch, int T, long long n) {
+    const float rstd = norm2 ? norm2[1] : 1.0f, gamma_f = float(gamma);
+    const double sft = shift ? shift[0] : 0.0;
+    double s = 0.0, ss = 0.0;
+    // Addresses: the base of a chunk's first row, t0 * n, is wave-uniform (a scalar pair per array and chunk); the lane adds one
+    // 32-bit byte offset per step of the chunk, 4 (u n + i), shared by all seven arrays (n < 2^26, checked by the caller: the offsets
+    // of TAIL_UNROLL rows fit 32 bits) - instead of a 64-bit register pair per array and step
+    const unsigned rowb = unsigned(n) * 4u;
+    // (the row base goes through readfirstlane: it stays a scalar pair, and the loop optimiser does not turn every (array, step) into
+    // a 64-bit induction pointer per lane of its own)
+    TAIL_ADDRESSING
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const unsigned boff = unsigned(i) * 4u;
+        double R = ret_carry[i];
+        int t = 0;
+        for (; t + TAIL_UNROLL <= T; t += TAIL_UNROLL) {
+            const long long row = (long long)t * n;
+            float r[TAIL_UNROLL]; int dn[TAIL_UNROLL];
+#pragma unroll
+            for (int u = 0; u < TAIL_UNROLL; ++u) { r[u] = ldf(rew_raw + row, boff + u * rowb); dn[u] = ldi(done_i + row, boff + u * rowb); }
+#pragma unroll
+            for (int u = 0; u < TAIL_UNROLL; ++u) {
+                R = gamma * R + double(__fmul_rn(r[u], scale));
+                const double d = R - sft;
+                s += d; ss += d * d;
+                R = dn[u] ? 0.0 : R;
+            }
+        }
+#pragma unroll 1
+        for (; t < T; ++t) {
+            const long long row = (long long)t * n;
+            R = gamma * R + double(__fmul_rn(ldf(rew_raw + row, boff), scale));
+            const double d = R - sft;
+            s += d; ss += d * d;
+            R = ldi(done_i + row, boff) ? 0.0 : R;
+        }
+        ret_carry[i] = R;
+
+        float next_value = last_val[i], lastgae = 0.0f;
+        auto step = [&](long long row, unsigned off, float rr, int dd, float v) {
+            const float rt = __builtin_amdgcn_fmed3f(__fmul_rn(__fmul_rn(rr, scale), rstd), -clip, clip);
+            const float df = float(dd), nonterminal = 1.0f - df;
+            const float delta = rt + gamma_f * next_value * nonterminal - v;
+            lastgae = delta + gamma_f * lam * nonterminal * lastgae;
+            st(rew + row, off, rt); st(done + row, off, df); st(adv + row, off, lastgae); st(ret + row, off, lastgae + v);
+            next_value = v;
+        };
+        t = T - 1;
+        for (; t - (TAIL_UNROLL - 1) >= 0; t -= TAIL_UNROLL) {
+            const long long row = (long long)(t - (TAIL_UNROLL - 1)) * n;      // the chunk's lowest row; step u is row TAIL_UNROLL - 1 - u of it
+            float r[TAIL_UNROLL], v[TAIL_UNROLL]; int dn[TAIL_UNROLL];
+#pragma unroll
+            for (int u = 0; u < TAIL_UNROLL; ++u) {
+                const unsigned off = boff + (TAIL_UNROLL - 1 - u) * rowb;
+                r[u] = ldf(rew_raw + row, off); dn[u] = ldi(done_i + row, off); v[u] = ldf(val + row, off);
+            }
+#pragma unroll
+            for (int u = 0; u < TAIL_UNROLL; ++u) step(row, boff + (TAIL_UNROLL - 1 - u) * rowb, r[u], dn[u], v[u]);
+        }
+#pragma unroll 1
+        for (; t >= 0; --t) {
+            const long long row = (long long)t * n;
+            step(row, boff, ldf(rew_raw + row, boff), ldi(done_i + row, boff), ldf(val + row, boff));
+        }
+    }
+    tail_reduce<256>(s, ss, scratch, sums3, T, n);
+}
+
 // ---- gradient clipping by global norm + Adam, one workgroup ----
 struct AdamArgs {
     float *p, *m, *v;
@@ -316,6 +462,35 @@ int rp_obs_norm_merge_dev(double *d_state, const double *d_sums, int obs_dim, do
     hipLaunchKernelGGL(obs_norm_merge_kernel, dim3(1), dim3(128), 0, static_cast<hipStream_t>(stream), d_state, d_sums, obs_dim, eps, d_norm);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RP_EHIP, std::string("obs_norm_merge_kernel: ") + hipGetErrorString(e));
+    return RP_OK;
+}
+
+int64_t rp_rollout_tail_scratch_doubles(void) { return 2 * int64_t(TAIL_BLOCKS) + 1; }
+
+int64_t rp_rollout_tail_blocks(int n_steps, int64_t n_envs) {
+    if (n_steps < 1 || n_envs < 1) return fail(RP_EINVAL, "n_steps and n_envs must be >= 1");
+    if (n_envs >= (int64_t(1) << 26)) return fail(RP_EUNSUPPORTED, "the rollout tail supports fewer than 2^26 envs");
+    const int64_t blocks = (n_envs + 255) / 256;
+    return blocks < TAIL_BLOCKS ? blocks : TAIL_BLOCKS;
+}
+
+int rp_rollout_tail_dev(const float *d_rew_raw, const int32_t *d_done_i, const float *d_val, const float *d_last_val, float reward_scale,
+                        const float *d_norm2, float clip, const double *d_shift, double gamma, double lam, double *d_ret_carry,
+                        float *d_rew, float *d_done, float *d_adv, float *d_ret, double *d_sums3, double *d_scratch, int n_steps,
+                        int64_t n_envs, void *stream) {
+    if (!d_rew_raw || !d_done_i || !d_val || !d_last_val || !d_ret_carry || !d_rew || !d_done || !d_adv || !d_ret || !d_sums3 || !d_scratch)
+        return fail(RP_EINVAL, "null argument");
+    const int64_t blocks = rp_rollout_tail_blocks(n_steps, n_envs);
+    if (blocks < 0) return int(blocks);
+    if (!(clip > 0.0f)) return fail(RP_EINVAL, "clip must be > 0");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(RP_EINVAL, "gamma must lie in [0, 1]");
+    DeviceScope scope(d_rew_raw); if (scope.rc) return scope.rc;
+    const int *di = reinterpret_cast<const int *>(d_done_i);
+    hipLaunchKernelGGL(rollout_tail_kernel, dim3(unsigned(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), d_rew_raw, di,
+                       d_val, d_last_val, reward_scale, d_norm2, clip, d_shift, gamma, float(lam), d_ret_carry, d_rew, d_done, d_adv,
+                       d_ret, d_sums3, d_scratch, n_steps, (long long)n_envs);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RP_EHIP, std::string("rollout_tail_kernel: ") + hipGetErrorString(e));
     return RP_OK;
 }
 

@@ -156,6 +156,146 @@ class ObsNorm:
             self.norm[1] = (1.0 / torch.sqrt(self.var + self.eps)).to(torch.float32)
 
 
+def _all_reduce_sums(sums, dist):
+    """Sum a small float64 tensor over the ranks: the device tensor under nccl, through the host under gloo."""
+    if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if sums.device.type != "cuda" or dist.get_backend() == "nccl":
+            dist.all_reduce(sums)
+        else:
+            host = sums.cpu()
+            dist.all_reduce(host)
+            sums.copy_(host)
+
+
+class RewardNorm:
+    """Running mean / variance of the discounted return and the reward scaling that follows from it: what
+    stable-baselines calls ``VecNormalize(norm_reward=True)``, the counterpart of ``ObsNorm``.
+
+    State (float64): ``state`` = [mean, var (population), count] of the discounted return; ``norm`` (float32 [2, 1]) = mean, rstd = 1 /
+    sqrt(var + eps) - the identity (0, 1) while count == 0; ``ret_carry`` (float64 [n_envs]) every env's running discounted return,
+    carried from one rollout into the next.  Per env and step: r_s = the scaled reward (float32), R = gamma R + r_s in float64,
+    d = R - mean joins the rollout's sums [n, S, SS], then R = 0 where the step ended an episode (``scan``).  The reward the agent
+    learns from is ``min(max(r_s * rstd, -clip), clip)``, the product rounded once to float32, the mean not subtracted (``apply``).
+    The statistics are frozen through a rollout; ``update(dist)`` merges its sums (Chan's formula, shift = the state's mean) after
+    an all-reduce over the ranks.  On a GPU ``tail()`` is the whole tail of a rollout - scan, scaling, done conversion, GAE - as one
+    launch (include/roboy_policy.h: rp_rollout_tail_dev)."""
+
+    def __init__(self, n_envs, gamma, device="cpu", clip=10.0, eps=1e-8):
+        self.n_envs, self.gamma, self.device = int(n_envs), float(gamma), torch.device(device)
+        self.clip, self.eps = float(clip), float(eps)
+        if not self.clip > 0.0:
+            raise ValueError("clip must be > 0")
+        if not 0.0 <= self.gamma <= 1.0:
+            raise ValueError("gamma must lie in [0, 1]")
+        z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=self.device)
+        self.state, self.norm, self.ret_carry, self.sums = z(3), z(2, 1, dtype=torch.float32), z(self.n_envs), z(3)
+        self._reset()
+        self._native = None
+
+    def _reset(self):
+        self.state.zero_(); self.state[1] = 1.0
+        self.norm[0] = 0.0; self.norm[1] = 1.0
+
+    mean = property(lambda self: self.state[0])
+    var = property(lambda self: self.state[1])
+    count = property(lambda self: float(self.state[2].item()))
+
+    def reset_returns(self, n_envs=None):
+        """The envs were reset: no return runs across that.  n_envs: the batch's size, where it was not known before."""
+        if n_envs is not None and int(n_envs) != self.n_envs:
+            self.n_envs = int(n_envs)
+            self.ret_carry = torch.zeros(self.n_envs, dtype=torch.float64, device=self.device)
+        self.ret_carry.zero_()
+
+    def apply(self, r_s):
+        """The reward GAE sees, from the scaled reward ``r_s`` (float32): the torch statement of the kernel's."""
+        return (r_s * self.norm[1, 0]).clamp(-self.clip, self.clip)
+
+    @torch.no_grad()
+    def scan(self, r_s, done):
+        """The forward scan of a [T, n_envs] rollout in float64: moves ``ret_carry`` on and leaves [n, S, SS] - the sums of the
+        T * n_envs returns around the running mean - in ``sums``.  No host synchronisation: it can be captured."""
+        if r_s.dim() != 2 or r_s.shape[1] != self.n_envs or r_s.dtype != torch.float32:
+            raise ValueError("expected float32 rewards of %d envs, got %s %r" % (self.n_envs, r_s.dtype, tuple(r_s.shape)))
+        R, mean = self.ret_carry, self.state[0]
+        S, SS = torch.zeros_like(mean), torch.zeros_like(mean)
+        for t in range(r_s.shape[0]):
+            R.mul_(self.gamma).add_(r_s[t].to(torch.float64))
+            d = R - mean
+            S = S + d.sum(); SS = SS + (d * d).sum()
+            R.masked_fill_(done[t] != 0, 0.0)
+        # (fill_ / copy_ between device tensors: assigning a Python number to an element is a host-to-device copy, which a capture refuses)
+        self.sums[0:1].fill_(float(r_s.numel())); self.sums[1:2].copy_(S.reshape(1)); self.sums[2:3].copy_(SS.reshape(1))
+        return self.sums
+
+    def _lib(self):
+        if self._native is None:
+            import ctypes
+            from . import _policy_native as pn
+            lib = pn.load()
+            self._native = (pn, ctypes, lib)
+            self._scratch = torch.zeros(int(lib.rp_rollout_tail_scratch_doubles()), dtype=torch.float64, device=self.device)
+        return self._native
+
+    @torch.no_grad()
+    def tail(self, rew_raw, done_i, val, last_val, reward_scale, lam, rew, done, adv, ret, ret_carry=None):
+        """One launch for the tail of a [T, n_envs] rollout (contiguous tensors on the GPU; done_i int32): ``scan`` on
+        fl32(rew_raw * reward_scale), then rew = ``apply`` of it, done = done_i as floats, adv / ret = GAE over rew."""
+        pn, c, lib = self._lib()
+        T, N = rew_raw.shape
+        if N != self.n_envs:
+            raise ValueError("a rollout of %d envs, these statistics carry the returns of %d" % (N, self.n_envs))
+        carry = self.ret_carry if ret_carry is None else ret_carry
+        ptr = lambda t: c.c_void_p(t.data_ptr())
+        pn.check(lib.rp_rollout_tail_dev(ptr(rew_raw), ptr(done_i), ptr(val), ptr(last_val), float(reward_scale), ptr(self.norm),
+                                         self.clip, ptr(self.state), self.gamma, float(lam), ptr(carry), ptr(rew), ptr(done), ptr(adv),
+                                         ptr(ret), ptr(self.sums), ptr(self._scratch), int(T), int(N),
+                                         c.c_void_p(torch.cuda.current_stream(rew_raw.device).cuda_stream)))
+
+    @torch.no_grad()
+    def merge(self, sums):
+        """Chan's merge of [n, S, SS] (taken around the CURRENT mean) into the state, and the float form."""
+        if self.device.type == "cuda":
+            pn, c, lib = self._lib()
+            pn.check(lib.rp_obs_norm_merge_dev(c.c_void_p(self.state.data_ptr()), c.c_void_p(sums.data_ptr()), 1, self.eps,
+                                               c.c_void_p(self.norm.data_ptr()), c.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            return
+        n, S, SS = float(sums[0]), float(sums[1]), float(sums[2])
+        count = float(self.state[2])
+        if not n > 0.0:
+            return
+        tot = count + n
+        delta = S / n                                         # batch mean - running mean
+        m2b = max(SS - S * delta, 0.0)                        # the batch's sum of squares around its own mean
+        mean = float(self.state[0]) + delta * (n / tot)
+        var = (float(self.state[1]) * count + m2b + delta * delta * (count * n / tot)) / tot
+        self.state[0] = mean; self.state[1] = var; self.state[2] = tot
+        self.norm[0] = torch.tensor(mean, dtype=torch.float64).to(torch.float32)
+        self.norm[1] = torch.tensor(1.0 / math.sqrt(var + self.eps), dtype=torch.float64).to(torch.float32)
+
+    @torch.no_grad()
+    def update(self, dist=None):
+        """Merge the last rollout's sums.  With several ranks the three doubles - taken around the same mean on every rank, so they
+        add - are all-reduced first, as ``ObsNorm.update``: every rank then holds bit-identical statistics."""
+        _all_reduce_sums(self.sums, dist)
+        self.merge(self.sums)
+
+    def state_dict(self):
+        return {"mean": float(self.state[0].item()), "var": float(self.state[1].item()), "count": self.count,
+                "clip": self.clip, "eps": self.eps, "gamma": self.gamma}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd):
+        if float(sd["gamma"]) != self.gamma:
+            raise ValueError("return statistics under gamma = %r, this agent discounts with %r" % (float(sd["gamma"]), self.gamma))
+        self.clip, self.eps = float(sd["clip"]), float(sd["eps"])
+        self._reset()
+        if float(sd["count"]) > 0.0:
+            self.state[0] = float(sd["mean"]); self.state[1] = float(sd["var"]); self.state[2] = float(sd["count"])
+            self.norm[0] = self.state[0].to(torch.float32)
+            self.norm[1] = (1.0 / torch.sqrt(self.state[1] + self.eps)).to(torch.float32)
+
+
 class MlpPolicy(nn.Module):
     """Two tanh layers of 64 units for the policy and for the value function,
     diagonal Gaussian with a state-independent log-std (stable_baselines' MlpPolicy)."""
@@ -532,7 +672,8 @@ class PPO:
     def __init__(self, env, policy=None, n_steps=128, nminibatches=4, noptepochs=4, gamma=0.99, lam=0.95,
                  learning_rate=2.5e-4, cliprange=0.2, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5,
                  device="cuda", dist=None, reward_scale=1.0, seed=0, use_graphs=False, fused_policy=None,
-                 fused_update=None, rollout_chains=None, normalize_obs=False, clip_obs=10.0, obs_norm_prime=True):
+                 fused_update=None, rollout_chains=None, normalize_obs=False, clip_obs=10.0, obs_norm_prime=True,
+                 normalize_reward=False, clip_reward=10.0, reward_norm_prime=True):
         """fused_policy / fused_update: None = the fused MFMA kernels whenever they apply (a GPU, MlpPolicy's shape,
         dimensions the kernels support), True = insist, False = the torch path (the statement the kernels are
         tested against).
@@ -544,7 +685,10 @@ class PPO:
         normalize_obs: running mean / variance normalisation of the observation (``ObsNorm``), clamped to +-clip_obs; the
         statistics are frozen through a rollout and the update on it, then merged with that rollout's moments.  obs_norm_prime:
         while no statistics exist, the first ``collect()`` runs one rollout under the identity for its moments alone (not
-        returned, not counted in ``num_timesteps``) and collects again."""
+        returned, not counted in ``num_timesteps``) and collects again.
+        normalize_reward: the scaled reward is divided by the running standard deviation of the discounted return and clamped to
+        +-clip_reward (``RewardNorm``); the statistics are frozen through a rollout and merged with its returns at the end of
+        ``collect()``.  reward_norm_prime: the same priming rollout, run while either set of statistics is empty."""
         self.env, self.dist, self.device = env, dist, torch.device(device)
         self._chains_arg = rollout_chains
         torch.manual_seed(seed)
@@ -593,6 +737,11 @@ class PPO:
         self.gamma, self.lam, self.cliprange = gamma, lam, cliprange
         self.ent_coef, self.vf_coef, self.max_grad_norm = ent_coef, vf_coef, max_grad_norm
         self.reward_scale = reward_scale
+        self.reward_norm = None
+        if normalize_reward:
+            self.reward_norm = RewardNorm(getattr(env, "num_envs", 0), gamma, self.device, clip=clip_reward)
+        self._reward_norm_prime = bool(reward_norm_prime)
+        self._rew_raw = None                  # the last rollout's raw reward (kept with normalize_reward: learn() reports it)
         self.num_timesteps = 0
         self._obs = None
 
@@ -633,7 +782,29 @@ class PPO:
             env.step_dev(clipped.data_ptr(), b["obs"][t + 1].data_ptr(), b["rew_raw"][t].data_ptr(),
                          b["done_i"][t].data_ptr())
 
+    def _rollout_tail_norm(self, b):
+        """``_rollout_tail`` under return normalisation of the reward: with the fused policy step everything behind the value of the
+        last observation is one launch (rp_rollout_tail_dev); otherwise the torch statement and ``gae``."""
+        T, rn = self.n_steps, self.reward_norm
+        if self._fused is not None:
+            self._step_base += T
+        with torch.no_grad():
+            last_value = self.policy.value(b["obs"][T])
+        if self._fused is not None:
+            rn.tail(b["rew_raw"], b["done_i"], b["val"], last_value.contiguous(), self.reward_scale, self.lam, b["rew"], b["done"],
+                    b["adv"], b["ret"])
+        else:
+            r_s = b["rew_raw"] * self.reward_scale
+            b["done"].copy_(b["done_i"].to(torch.float32))
+            rn.scan(r_s, b["done_i"])
+            b["rew"].copy_(rn.apply(r_s))
+            adv, ret = gae(b["rew"], b["val"], b["done"], last_value, self.gamma, self.lam)
+            b["adv"].copy_(adv); b["ret"].copy_(ret)
+        b["carry"].copy_(b["obs"][T])
+
     def _rollout_tail(self, b):
+        if self.reward_norm is not None:
+            return self._rollout_tail_norm(b)
         T = self.n_steps
         if self._fused is not None:
             self._step_base += T                                             # fresh noise on the next replay
@@ -677,6 +848,8 @@ class PPO:
         b = {"obs": z(T + 1, N, od), "act": z(T, N, ad), "logp": z(T, N), "val": z(T, N), "rew_raw": z(T, N),
              "rew": z(T, N), "done_i": z(T, N, dtype=torch.int32), "done": z(T, N), "adv": z(T, N), "ret": z(T, N),
              "carry": z(N, od)}
+        if self._obs is None and self.reward_norm is not None:
+            self.reward_norm.reset_returns(N)
         b["carry"].copy_(self._to_tensor(env.reset()) if self._obs is None else self._obs)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -691,6 +864,9 @@ class PPO:
             self.policy.act(b["carry"]); self.policy.value(b["carry"])
             if self._fused is not None:       # its one-time launch configuration must not fall into the capture either
                 self._fused.act_into(b["carry"], b["act"][0], b["logp"][0], b["val"][0], deterministic=True, norm=self.obs_norm)
+                if self.reward_norm is not None:  # nor the tail kernel's (on a copy of the returns: they must not move)
+                    self.reward_norm.tail(b["rew_raw"], b["done_i"], b["val"], b["val"][0], self.reward_scale, self.lam, b["rew"],
+                                          b["done"], b["adv"], b["ret"], ret_carry=self.reward_norm.ret_carry.clone())
         side.synchronize()
         self.rollout_chains = self._pick_chains(N)
         # thread-local capture mode: another thread of the process (RCCL's watchdog in a multi-rank run) may call into
@@ -743,18 +919,27 @@ class PPO:
             self.env.note_replayed_steps(T)
         self._obs = b["carry"]
         self.num_timesteps += T * b["carry"].shape[0]
+        if self.reward_norm is not None:
+            # behind the replay and outside the graph: the all-reduce and the merge of the rollout's return moments
+            self._rew_raw = b["rew_raw"]
+            self.reward_norm.update(self.dist)
         return {"obs": b["obs"][:T], "act": b["act"], "logp": b["logp"], "val": b["val"], "rew": b["rew"],
                 "done": b["done"], "adv": b["adv"], "ret": b["ret"]}
 
     def collect(self):
-        if self.obs_norm is not None and self._obs_norm_prime:
-            self._obs_norm_prime = False                     # (asked once: the count is read back from the device)
-            if self.obs_norm.count == 0:
-                # priming: one rollout under the identity, for its moments alone
+        ask_obs = self.obs_norm is not None and self._obs_norm_prime
+        ask_rew = self.reward_norm is not None and self._reward_norm_prime
+        if ask_obs or ask_rew:
+            self._obs_norm_prime = self._reward_norm_prime = False     # (asked once: the counts are read back from the device)
+            prime_obs = ask_obs and self.obs_norm.count == 0
+            if prime_obs or (ask_rew and self.reward_norm.count == 0):
+                # priming: one rollout under the identity, for its moments alone (one rollout serves both sets of statistics; the
+                # returns' moments are merged where every rollout's are, at the end of _collect_rollout)
                 before = self.num_timesteps
                 roll = self._collect_rollout()
                 self.num_timesteps = before
-                self.obs_norm.update(roll["obs"].reshape(-1, roll["obs"].shape[-1]), self.dist)
+                if prime_obs:
+                    self.obs_norm.update(roll["obs"].reshape(-1, roll["obs"].shape[-1]), self.dist)
         return self._collect_rollout()
 
     def _collect_rollout(self):
@@ -763,8 +948,11 @@ class PPO:
         env, T = self.env, self.n_steps
         if self._obs is None:
             self._obs = self._to_tensor(env.reset())
+            if self.reward_norm is not None:
+                self.reward_norm.reset_returns(self._obs.shape[0])
         N = self._obs.shape[0]
         buf = {k: [] for k in ("obs", "act", "logp", "val", "rew", "done")}
+        raw = []
         packed = self._fused.pack() if self._fused is not None else None
         for t in range(T):
             if self._fused is not None:
@@ -777,12 +965,21 @@ class PPO:
             clipped = a.clamp(-1.0, 1.0).contiguous()        # the env's action box (roboy_env.py:31)
             obs, rew, done, _ = env.step(clipped if self.device.type == "cuda" else clipped.cpu().numpy())
             buf["obs"].append(self._obs); buf["act"].append(a); buf["logp"].append(logp); buf["val"].append(v)
-            buf["rew"].append(self._to_tensor(rew) * self.reward_scale)
+            rew = self._to_tensor(rew)
+            if self.reward_norm is not None:
+                raw.append(rew)
+            buf["rew"].append(rew * self.reward_scale)
             buf["done"].append(self._to_tensor(done))
             self._obs = self._to_tensor(obs)
         if self._fused is not None:
             self._step_base += T
         roll = {k: torch.stack(v) for k, v in buf.items()}
+        if self.reward_norm is not None:
+            # the torch statement of the fused tail: the returns' scan on the scaled reward, the statistics frozen through it
+            self._rew_raw = torch.stack(raw)
+            self.reward_norm.scan(roll["rew"], roll["done"])
+            roll["rew"] = self.reward_norm.apply(roll["rew"])
+            self.reward_norm.update(self.dist)
         with torch.no_grad():
             last_value = self.policy.value(self._obs)
         roll["adv"], roll["ret"] = gae(roll["rew"], roll["val"], roll["done"], last_value, self.gamma, self.lam)
@@ -866,7 +1063,10 @@ class PPO:
         while self.num_timesteps < target:
             roll = self.collect()
             stats = self.update(roll)
-            stats["mean_reward"] = roll["rew"].mean().item() / self.reward_scale
+            if self.reward_norm is not None:     # the env's raw reward, not the normalised one the agent learns from
+                stats["mean_reward"] = self._rew_raw.mean().item()
+            else:
+                stats["mean_reward"] = roll["rew"].mean().item() / self.reward_scale
             stats["timesteps"] = self.num_timesteps
             if log:
                 log(stats)
@@ -876,7 +1076,8 @@ class PPO:
         opt = self._fadam.state_dict() if self._fgrad is not None else self.opt.state_dict()
         torch.save({"policy": self.policy.state_dict(), "optimizer": opt, "num_timesteps": self.num_timesteps,
                     "epoch": self._epoch, "tendon_obs": _tendon_obs_of(self.env), "env_io": _env_io_of(self.env),
-                    "obs_norm": self.obs_norm.state_dict() if self.obs_norm is not None else None}, path)
+                    "obs_norm": self.obs_norm.state_dict() if self.obs_norm is not None else None,
+                    "reward_norm": self.reward_norm.state_dict() if self.reward_norm is not None else None}, path)
 
     def load(self, path):
         ck = torch.load(path, map_location=self.device)
@@ -886,9 +1087,16 @@ class PPO:
         if (ck.get("obs_norm") is not None) != (self.obs_norm is not None):      # (a checkpoint without the key: written without it)
             raise ValueError("the checkpoint was trained %s observation normalisation, this agent runs %s it (PPO's normalize_obs)"
                              % (("with", "without") if self.obs_norm is None else ("without", "with")))
+        if (ck.get("reward_norm") is not None) != (self.reward_norm is not None):
+            raise ValueError("the checkpoint was trained %s reward normalisation, this agent runs %s it (PPO's normalize_reward)"
+                             % (("with", "without") if self.reward_norm is None else ("without", "with")))
         if self.obs_norm is not None:
             self.obs_norm.load_state_dict(ck["obs_norm"])
             self._obs_norm_prime = self._obs_norm_prime and float(ck["obs_norm"]["count"]) == 0.0
+        if self.reward_norm is not None:
+            self.reward_norm.load_state_dict(ck["reward_norm"])
+            self.reward_norm.reset_returns()                 # the running returns are not stored: they start afresh
+            self._reward_norm_prime = self._reward_norm_prime and float(ck["reward_norm"]["count"]) == 0.0
         self.policy.load_state_dict(ck["policy"])      # copies in place: the views of the fused optimiser's flat buffer stay valid
         fused_ck = isinstance(ck["optimizer"], dict) and ck["optimizer"].get("fused_adam", False)
         if self._fgrad is not None and fused_ck:

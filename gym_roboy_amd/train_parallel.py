@@ -48,6 +48,10 @@ def main(argv=None):
                     help="running mean / variance normalisation of the observation inside the policy kernels (what "
                          "stable-baselines calls VecNormalize); the statistics are stored in the checkpoint")
     ap.add_argument("--clip-obs", type=float, default=10.0, metavar="X", help="clamp of the normalised observation (default 10)")
+    ap.add_argument("--normalize-reward", action="store_true",
+                    help="divide the (scaled) reward by the running standard deviation of the discounted return (what "
+                         "stable-baselines calls VecNormalize(norm_reward=True)); the statistics are stored in the checkpoint")
+    ap.add_argument("--clip-reward", type=float, default=10.0, metavar="X", help="clamp of the normalised reward (default 10)")
     args = ap.parse_args(argv)
     sensor_noise = {k: float(v) for k, v in (item.split("=", 1) for item in args.sensor_noise.split(",") if item)}
     action_delay = None
@@ -86,7 +90,8 @@ def main(argv=None):
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,
-                fused_update=not args.torch_policy, normalize_obs=args.normalize_obs, clip_obs=args.clip_obs)
+                fused_update=not args.torch_policy, normalize_obs=args.normalize_obs, clip_obs=args.clip_obs,
+                normalize_reward=args.normalize_reward, clip_reward=args.clip_reward)
     if os.path.exists(model_file):
         agent.load(model_file)                  # resume from the last backup
     for _ in range(args.rounds):

@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define RP_ABI_VERSION 3
+#define RP_ABI_VERSION 4
 #define RP_HIDDEN 64          /* units per hidden layer (stable_baselines' MlpPolicy) */
 #define RP_MAX_OBS 95         /* obs_dim + 1 (bias column) <= 96 */
 #define RP_MAX_ACT 64
@@ -145,6 +145,27 @@ int rp_obs_moments_dev(const float *d_obs, int64_t rows, int obs_dim, const doub
 /* Chan's parallel merge of d_sums (taken with shift = d_state's mean) into d_state = {mean, var (population), count}, and the float
  * form d_norm = {mean, 1 / sqrt(var + eps)}.  rows == 0 (d_sums[0]) leaves everything unchanged.  One small launch. */
 int rp_obs_norm_merge_dev(double *d_state, const double *d_sums, int obs_dim, double eps, float *d_norm, void *stream);
+/* ---- running return normalisation of the reward (gym_roboy_amd/ppo.py: RewardNorm) ----
+ * The tail of a rollout as ONE launch: reward scaling, the discounted-return scan with its moments, the done conversion and GAE.
+ * Device pointers, [n_steps][n_envs] row-major.  Per env, forwards in time from R = d_ret_carry[i] (double, read and written back):
+ *     r_s = fl32(rew_raw_t * reward_scale);  R = gamma * R + r_s (float64);  d = R - shift joins S += d, SS += d * d;
+ *     then R = 0 where done_i_t != 0
+ * and backwards rp_gae_dev's recurrence (gamma, lam rounded to float32) over
+ *     r~_t = min(max(fl32(r_s * rstd), -clip), clip)
+ * - both products rounded once to float32, the clamp last, the mean NOT subtracted - writing d_rew = r~, d_done = done_i as 0 / 1
+ * floats, d_adv, d_ret.  d_norm2: float[2] = {mean, rstd} of the discounted return, NULL = the identity (rstd 1); clip > 0
+ * (INFINITY: no clamp); d_shift: one double, the statistics' running mean, NULL = 0; d_sums3 = double[3] = {n_steps * n_envs, S, SS},
+ * the layout rp_obs_norm_merge_dev merges with obs_dim = 1.  fp64 sums in one fixed order (bit-reproducible run to run), no
+ * floating-point atomics.  d_scratch: rp_rollout_tail_scratch_doubles() doubles, zeroed ONCE by the caller (the kernel leaves it
+ * ready for the next call).  rp_rollout_tail_blocks(): the grid of that launch - one env per lane, 256 per workgroup, at most
+ * 4 096 workgroups striding over the envs (n_envs < 2^26).  Null pointers, n_steps < 1, n_envs < 1, clip not > 0, gamma outside
+ * [0, 1]: RP_EINVAL. */
+int64_t rp_rollout_tail_scratch_doubles(void);
+int64_t rp_rollout_tail_blocks(int n_steps, int64_t n_envs);
+int rp_rollout_tail_dev(const float *d_rew_raw, const int32_t *d_done_i, const float *d_val, const float *d_last_val, float reward_scale,
+                        const float *d_norm2, float clip, const double *d_shift, double gamma, double lam, double *d_ret_carry,
+                        float *d_rew, float *d_done, float *d_adv, float *d_ret, double *d_sums3, double *d_scratch, int n_steps,
+                        int64_t n_envs, void *stream);
 /* test hook: would a grant of lds_bytes of dynamic LDS be issued for (kernel id, device) now?  Records it. */
 int rp_debug_lds_grant_needed(int kernel_id, int dev, int64_t lds_bytes);
 /* which form of the gradient kernels rp_ppo_grad_dev launches for this policy: 2 = the small instance (obs_dim <= 31, up to 8
