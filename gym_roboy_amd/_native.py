@@ -78,6 +78,7 @@ class EnvConfig(ctypes.Structure):
 
 
 RB_IO_MAX_DELAY = 7
+RB_DONE_NONE, RB_DONE_TERMINATED, RB_DONE_TRUNCATED = 0, 1, 2      # the done words while rb_env_done_kind_configure holds
 
 
 class EnvIoConfig(ctypes.Structure):
@@ -144,6 +145,8 @@ SIGNATURES = {
     "rb_env_io_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                      ctypes.POINTER(ctypes.c_int32)]),
     "rb_env_io_sample_delay_dev": (ctypes.c_int, [_sim, _vp]),
+    "rb_env_done_kind_configure": (ctypes.c_int, [_sim, ctypes.c_int]),
+    "rb_env_done_kind_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp)]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

@@ -8,7 +8,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
-RP_ABI_VERSION = 4
+RP_ABI_VERSION = 5
 
 
 class MlpParams(ctypes.Structure):
@@ -59,6 +59,9 @@ SIGNATURES = {
                                            ctypes.c_double, ctypes.c_double] + [ctypes.c_void_p] * 7 +
                                           [ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),
 }
+# the same tail with value bootstrapping where the done word is 2 (truncated): the same argument list
+SIGNATURES["rp_rollout_tail_boot_dev"] = SIGNATURES["rp_rollout_tail_dev"]
+
 
 
 def library_path():

@@ -277,78 +277,12 @@ __device__ __forceinline__ void tail_reduce(double s, double ss, double *scratch
     }
 }
 
-__global__ void __launch_bounds__(256, 4)                  // four waves per SIMD: 262 144 envs are one resident grid of 1 024 workgroups
-rollout_tail_kernel(const float *__restrict__ rew_raw, const int *__restrict__ done_i, const float *__restrict__ val,
-                    const float *__restrict__ last_val, float scale, const float *__restrict__ norm2, float clip,
-                    const double *__restrict__ shift, double gamma, float lam, double *__restrict__ ret_carry, float *__restrict__ rew,
-                    float *__restrict__ done, float *__restrict__ adv, float *__restrict__ ret, double *__restrict__ sums3,
-                    double *scratch, int T, long long n) {
-    const float rstd = norm2 ? norm2[1] : 1.0f, gamma_f = float(gamma);
-    const double sft = shift ? shift[0] : 0.0;
-    double s = 0.0, ss = 0.0;
-    // Addresses: the base of a chunk's first row, t0 * n, is wave-uniform (a scalar pair per array and chunk); the lane adds one
-    // 32-bit byte offset per step of the chunk, 4 (u n + i), shared by all seven arrays (n < 2^26, checked by the caller: the offsets
-    // of TAIL_UNROLL rows fit 32 bits) - instead of a 64-bit register pair per array and step
-    const unsigned rowb = unsigned(n) * 4u;
-    // (the row base goes through readfirstlane: it stays a scalar pair, and the loop optimiser does not turn every (array, step) into
-    // a 64-bit induction pointer per lane of its own)
-    TAIL_ADDRESSING
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const unsigned boff = unsigned(i) * 4u;
-        double R = ret_carry[i];
-        int t = 0;
-        for (; t + TAIL_UNROLL <= T; t += TAIL_UNROLL) {
-            const long long row = (long long)t * n;
-            float r[TAIL_UNROLL]; int dn[TAIL_UNROLL];
-#pragma unroll
-            for (int u = 0; u < TAIL_UNROLL; ++u) { r[u] = ldf(rew_raw + row, boff + u * rowb); dn[u] = ldi(done_i + row, boff + u * rowb); }
-#pragma unroll
-            for (int u = 0; u < TAIL_UNROLL; ++u) {
-                R = gamma * R + double(__fmul_rn(r[u], scale));
-                const double d = R - sft;
-                s += d; ss += d * d;
-                R = dn[u] ? 0.0 : R;
-            }
-        }
-#pragma unroll 1
-        for (; t < T; ++t) {
-            const long long row = (long long)t * n;
-            R = gamma * R + double(__fmul_rn(ldf(rew_raw + row, boff), scale));
-            const double d = R - sft;
-            s += d; ss += d * d;
-            R = ldi(done_i + row, boff) ? 0.0 : R;
-        }
-        ret_carry[i] = R;
-
-        float next_value = last_val[i], lastgae = 0.0f;
-        auto step = [&](long long row, unsigned off, float rr, int dd, float v) {
-            const float rt = __builtin_amdgcn_fmed3f(__fmul_rn(__fmul_rn(rr, scale), rstd), -clip, clip);
-            const float df = float(dd), nonterminal = 1.0f - df;
-            const float delta = rt + gamma_f * next_value * nonterminal - v;
-            lastgae = delta + gamma_f * lam * nonterminal * lastgae;
-            st(rew + row, off, rt); st(done + row, off, df); st(adv + row, off, lastgae); st(ret + row, off, lastgae + v);
-            next_value = v;
-        };
-        t = T - 1;
-        for (; t - (TAIL_UNROLL - 1) >= 0; t -= TAIL_UNROLL) {
-            const long long row = (long long)(t - (TAIL_UNROLL - 1)) * n;      // the chunk's lowest row; step u is row TAIL_UNROLL - 1 - u of it
-            float r[TAIL_UNROLL], v[TAIL_UNROLL]; int dn[TAIL_UNROLL];
-#pragma unroll
-            for (int u = 0; u < TAIL_UNROLL; ++u) {
-                const unsigned off = boff + (TAIL_UNROLL - 1 - u) * rowb;
-                r[u] = ldf(rew_raw + row, off); dn[u] = ldi(done_i + row, off); v[u] = ldf(val + row, off);
-            }
-#pragma unroll
-            for (int u = 0; u < TAIL_UNROLL; ++u) step(row, boff + (TAIL_UNROLL - 1 - u) * rowb, r[u], dn[u], v[u]);
-        }
-#pragma unroll 1
-        for (; t >= 0; --t) {
-            const long long row = (long long)t * n;
-            step(row, boff, ldf(rew_raw + row, boff), ldi(done_i + row, boff), ldf(val + row, boff));
-        }
-    }
-    tail_reduce<256>(s, ss, scratch, sums3, T, n);
-}
+// the kernel's text, once per instance: rollout_tail_kernel, and rollout_tail_boot_kernel whose done words are episode-end codes and
+// whose backward scan bootstraps the truncated steps
+#define RP_BOOT 0
+#include "rollout_tail_kernel.inc"
+#define RP_BOOT 1
+#include "rollout_tail_kernel.inc"
 
 // ---- gradient clipping by global norm + Adam, one workgroup ----
 struct AdamArgs {
@@ -389,6 +323,27 @@ clip_adam_kernel(const AdamArgs a) {
         a.m[i] = m; a.v[i] = v;
         a.p[i] -= step * m / (sqrtf(v) * isb2 + a.eps);     // torch.optim.Adam: denom = sqrt(v) / sqrt(bc2) + eps
     }
+}
+
+// the two instances of rollout_tail_kernel.inc share their argument list, their checks and their grid
+int rollout_tail_launch(decltype(&rollout_tail_kernel) kernel, const char *name, const float *d_rew_raw, const int32_t *d_done_i, const float *d_val, const float *d_last_val,
+                        float reward_scale, const float *d_norm2, float clip, const double *d_shift, double gamma, double lam,
+                        double *d_ret_carry, float *d_rew, float *d_done, float *d_adv, float *d_ret, double *d_sums3, double *d_scratch,
+                        int n_steps, int64_t n_envs, void *stream) {
+    if (!d_rew_raw || !d_done_i || !d_val || !d_last_val || !d_ret_carry || !d_rew || !d_done || !d_adv || !d_ret || !d_sums3 || !d_scratch)
+        return fail(RP_EINVAL, "null argument");
+    const int64_t blocks = rp_rollout_tail_blocks(n_steps, n_envs);
+    if (blocks < 0) return int(blocks);
+    if (!(clip > 0.0f)) return fail(RP_EINVAL, "clip must be > 0");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(RP_EINVAL, "gamma must lie in [0, 1]");
+    DeviceScope scope(d_rew_raw); if (scope.rc) return scope.rc;
+    const int *di = reinterpret_cast<const int *>(d_done_i);
+    hipLaunchKernelGGL(kernel, dim3(unsigned(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), d_rew_raw, di,
+                       d_val, d_last_val, reward_scale, d_norm2, clip, d_shift, gamma, float(lam), d_ret_carry, d_rew, d_done, d_adv,
+                       d_ret, d_sums3, d_scratch, n_steps, (long long)n_envs);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RP_EHIP, std::string(name) + ": " + hipGetErrorString(e));
+    return RP_OK;
 }
 
 }  // namespace
@@ -478,20 +433,16 @@ int rp_rollout_tail_dev(const float *d_rew_raw, const int32_t *d_done_i, const f
                         const float *d_norm2, float clip, const double *d_shift, double gamma, double lam, double *d_ret_carry,
                         float *d_rew, float *d_done, float *d_adv, float *d_ret, double *d_sums3, double *d_scratch, int n_steps,
                         int64_t n_envs, void *stream) {
-    if (!d_rew_raw || !d_done_i || !d_val || !d_last_val || !d_ret_carry || !d_rew || !d_done || !d_adv || !d_ret || !d_sums3 || !d_scratch)
-        return fail(RP_EINVAL, "null argument");
-    const int64_t blocks = rp_rollout_tail_blocks(n_steps, n_envs);
-    if (blocks < 0) return int(blocks);
-    if (!(clip > 0.0f)) return fail(RP_EINVAL, "clip must be > 0");
-    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(RP_EINVAL, "gamma must lie in [0, 1]");
-    DeviceScope scope(d_rew_raw); if (scope.rc) return scope.rc;
-    const int *di = reinterpret_cast<const int *>(d_done_i);
-    hipLaunchKernelGGL(rollout_tail_kernel, dim3(unsigned(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), d_rew_raw, di,
-                       d_val, d_last_val, reward_scale, d_norm2, clip, d_shift, gamma, float(lam), d_ret_carry, d_rew, d_done, d_adv,
-                       d_ret, d_sums3, d_scratch, n_steps, (long long)n_envs);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RP_EHIP, std::string("rollout_tail_kernel: ") + hipGetErrorString(e));
-    return RP_OK;
+    return rollout_tail_launch(rollout_tail_kernel, "rollout_tail_kernel", d_rew_raw, d_done_i, d_val, d_last_val, reward_scale, d_norm2, clip,
+                               d_shift, gamma, lam, d_ret_carry, d_rew, d_done, d_adv, d_ret, d_sums3, d_scratch, n_steps, n_envs, stream);
+}
+
+int rp_rollout_tail_boot_dev(const float *d_rew_raw, const int32_t *d_done_i, const float *d_val, const float *d_last_val, float reward_scale,
+                             const float *d_norm2, float clip, const double *d_shift, double gamma, double lam, double *d_ret_carry,
+                             float *d_rew, float *d_done, float *d_adv, float *d_ret, double *d_sums3, double *d_scratch, int n_steps,
+                             int64_t n_envs, void *stream) {
+    return rollout_tail_launch(rollout_tail_boot_kernel, "rollout_tail_boot_kernel", d_rew_raw, d_done_i, d_val, d_last_val, reward_scale, d_norm2,
+                               clip, d_shift, gamma, lam, d_ret_carry, d_rew, d_done, d_adv, d_ret, d_sums3, d_scratch, n_steps, n_envs, stream);
 }
 
 int rp_clip_adam_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int act_dim, float lr,

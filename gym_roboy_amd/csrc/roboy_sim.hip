@@ -420,6 +420,24 @@ stats_reduce_kernel(const double *ep_sum, const uint32_t *ep_cnt, const float *e
     if (threadIdx.x == 0) *ticket = 0u;       // ready for the next launch (same stream: ordered behind this kernel)
 }
 
+// Episode-end codes (rb_env_done_kind_*): behind an env-step kernel of any form, over the envs [i0, i1) it stepped.
+// An env that is done reached its goal iff its goal counter moved since its last episode end (`seen`); its done word becomes
+// RB_DONE_TERMINATED or RB_DONE_TRUNCATED.  Lanes that are not done read nothing but their done word.
+__global__ void __launch_bounds__(256)
+done_kind_kernel(uint32_t *__restrict__ done, const uint32_t *__restrict__ goals, uint32_t *__restrict__ seen,
+                 uint32_t *__restrict__ kind, long i0, long i1) {
+    const long i = i0 + long(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= i1) return;
+    uint32_t d = done[i];
+    if (d) {
+        const uint32_t g = goals[i];
+        d = g != seen[i] ? uint32_t(RB_DONE_TERMINATED) : uint32_t(RB_DONE_TRUNCATED);
+        done[i] = d;
+        seen[i] = g;
+    }
+    kind[i] = d;
+}
+
 __global__ void env_reset_kernel(const GoalBox box, float *q, float *qd, uint32_t *feas, float *goal,
                                  uint32_t *step_num, float *ep_ret, uint32_t *goal_count, float *obs,
                                  long n, uint64_t seed, uint64_t env0) {
@@ -548,6 +566,10 @@ struct rb_sim {
     uint32_t *d_io_delay = nullptr, *d_io_draws = nullptr, *d_io_rows = nullptr;
     float *d_io_hist = nullptr;
     int io_slots = 0;
+    // episode-end codes (rb_env_done_kind_*): while enabled, every env-step launch is followed by done_kind_kernel over its range.
+    // Planes [n] each: the goal counter d_ep_cnt[2n + i] as of env i's last episode end, and the last step's codes
+    bool done_kind = false;
+    uint32_t *d_done_seen = nullptr, *d_done_kind = nullptr;
 };
 
 namespace {
@@ -1096,6 +1118,7 @@ void rb_destroy(rb_sim *s) {
     (void)hipFree(s->d_step_num); (void)hipFree(s->d_infeas_n); (void)hipFree(s->d_stats);
     params_free(s);
     io_free(s);
+    (void)hipFree(s->d_done_seen); (void)hipFree(s->d_done_kind);
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1533,6 +1556,7 @@ int rb_env_configure(rb_sim *s, const rb_env_config *cfg) {
     }
     RB_HIP(hipMemsetAsync(s->d_ep_sum, 0, sizeof(double) * size_t(s->n) * 2, s->stream));
     RB_HIP(hipMemsetAsync(s->d_ep_cnt, 0, sizeof(uint32_t) * size_t(s->n) * 3, s->stream));
+    if (s->done_kind) RB_HIP(hipMemsetAsync(s->d_done_seen, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
     RB_HIP(hipMemsetAsync(s->d_infeas_n, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
     s->env_steps = 0.0;
     s->env_ready = true;
@@ -1558,6 +1582,10 @@ int rb_env_reset_dev(rb_sim *s, float *d_obs) {
     if (s->obs_mask && d_obs) {               // rows of obs_dim floats: the tendon columns at the zero pose, every set-point 0
         obs_rows_launch(s, d_obs);
         RB_HIP(hipGetLastError());
+    }
+    if (s->done_kind) {                       // a reset is no episode end: the next one is judged against the counters as they stand, and nothing is reported
+        RB_HIP(hipMemcpyAsync(s->d_done_seen, s->d_ep_cnt + 2 * size_t(s->n), sizeof(uint32_t) * size_t(s->n), hipMemcpyDeviceToDevice, s->stream));
+        RB_HIP(hipMemsetAsync(s->d_done_kind, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
     }
     if (s->io && d_obs) {                     // sensor readings too: the rows' noise, in place (the episode restarts, the history needs nothing)
         const rbio::IoArgs io = io_args(s, 0);
@@ -1651,6 +1679,34 @@ int rb_env_io_sample_delay_dev(rb_sim *s, const uint8_t *d_mask) {
     return RB_OK;
 }
 
+// ---- episode-end codes of the fused env step (done_kind_kernel) ----
+int rb_env_done_kind_configure(rb_sim *s, int enable) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);                       // nothing in flight may still write the planes
+    if (rc) return rc;
+    rc = drop_graphs(s);
+    if (rc) return rc;
+    s->done_kind = false;
+    (void)hipFree(s->d_done_seen); (void)hipFree(s->d_done_kind);
+    s->d_done_seen = nullptr; s->d_done_kind = nullptr;
+    if (!enable) return RB_OK;
+    const size_t plane = sizeof(uint32_t) * size_t(s->n);
+    RB_HIP(hipMalloc(&s->d_done_seen, plane));
+    RB_HIP(hipMalloc(&s->d_done_kind, plane));
+    RB_HIP(hipMemcpyAsync(s->d_done_seen, s->d_ep_cnt + 2 * size_t(s->n), plane, hipMemcpyDeviceToDevice, s->stream));
+    RB_HIP(hipMemsetAsync(s->d_done_kind, 0, plane, s->stream));
+    s->done_kind = true;
+    return RB_OK;
+}
+int rb_env_done_kind_ptr(rb_sim *s, uint32_t **d_kind) {
+    if (check(s) || !d_kind) return fail(RB_EINVAL, "null argument");
+    if (!s->done_kind) return fail(RB_EINVAL, "episode-end codes are not enabled (rb_env_done_kind_configure)");
+    *d_kind = s->d_done_kind;
+    return RB_OK;
+}
+
 int rb_env_obs_dim(rb_sim *s, int32_t *obs_dim) {
     if (check(s) || !obs_dim) return fail(RB_EINVAL, "null argument");
     *obs_dim = s->obs_dim();
@@ -1676,7 +1732,13 @@ int rb_env_set_goal(rb_sim *s, const float *goal_q, const uint32_t *step_num) {
 static int env_step_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done) {
     Launch L;
     L.i0 = i0; L.cnt = cnt; L.stream = stream; L.act = d_act; L.obs = d_obs; L.reward = d_reward; L.done = d_done;
-    return dispatch(s, ENTRY_ENV, L);
+    const int rc = dispatch(s, ENTRY_ENV, L);
+    if (rc != RB_OK || !s->done_kind) return rc;
+    // the episode-end codes of the range, behind whichever kernel stepped it (same stream)
+    hipLaunchKernelGGL(done_kind_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, d_done, s->d_ep_cnt + 2 * size_t(s->n),
+                       s->d_done_seen, s->d_done_kind, i0, i0 + cnt);
+    RB_HIP(hipGetLastError());
+    return RB_OK;
 }
 
 int rb_env_step_dev(rb_sim *s, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done) {
@@ -1751,6 +1813,7 @@ static int stats_reset(rb_sim *s) {
     if (s->env_ready) {
         RB_HIP(hipMemsetAsync(s->d_ep_sum, 0, sizeof(double) * size_t(s->n) * 2, s->stream));
         RB_HIP(hipMemsetAsync(s->d_ep_cnt, 0, sizeof(uint32_t) * size_t(s->n) * 3, s->stream));
+        if (s->done_kind) RB_HIP(hipMemsetAsync(s->d_done_seen, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
     }
     RB_HIP(hipMemsetAsync(s->d_infeas_n, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
     s->env_steps = 0.0;

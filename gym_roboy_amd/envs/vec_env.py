@@ -94,7 +94,8 @@ class RoboyVecEnv:
                  is_agent_getting_bonus_for_reaching_goal: bool = True,
                  auto_reset: bool = True, integrator="euler", n_substeps: int = 1,
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
-                 randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None):
+                 randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None,
+                 report_truncation: bool = False):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
@@ -106,7 +107,14 @@ class RoboyVecEnv:
         reward, done and the state are exact, and nothing is clipped to ``observation_space``, which is unchanged.
         ``action_delay``: an int ``d`` - every step is driven by the action handed in ``d`` steps earlier in the same episode (the rest
         command, every set-point 0, before that) - or a pair ``(lo, hi)``: each env draws its own delay, again at every auto-reset.
-        At most 7.  Both combine with ``randomization`` and ``tendon_obs``; ball-joint robots."""
+        At most 7.  Both combine with ``randomization`` and ``tendon_obs``; ball-joint robots.
+        ``report_truncation``: tell the episodes that ended at ``max_episode_length`` from those that reached their goal (DESIGN.md
+        §17; every robot, every kernel form, every option above).  ``step()`` returns ``done`` as bools as before, and
+        ``truncated()`` gives the last step's ``[N]`` bools: True where the time limit alone ended the episode (an env that
+        reaches its goal on its last permitted step is not truncated).  ``step_dev`` and ``step_range_dev`` then leave episode-end
+        CODES in ``d_done`` - 0 not done, 1 terminated, 2 truncated (``_native.RB_DONE_*``) - so ``done != 0`` is the done of an env
+        without the option.  The ``info`` dicts stay empty: a dict per env does not scale to 262 144 envs, so there is no
+        ``TimeLimit.truncated`` key."""
         obs_names = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
         sig = sensor_noise_sigmas(sensor_noise, obs_names)               # (bad options: before anything is allocated)
         d_lo, d_hi, ranged = action_delay_range(action_delay)
@@ -185,6 +193,11 @@ class RoboyVecEnv:
                 io.sigma_tendon[c] = float(sig[2 + c])
             io.delay_lo, io.delay_hi, io.resample_on_reset = d_lo, d_hi, int(ranged)
             self.sim.configure_io(io)
+        self.report_truncation = bool(report_truncation)
+        self._last_done_codes = None   # truncated(): the last torch step's int32 codes (None: the last step was not a torch step)
+        if self.report_truncation:
+            # before anything is captured into a graph: every env-step launch is followed by the small kernel that writes the codes
+            nat.check(self.sim._lib.rb_env_done_kind_configure(self.sim.handle, 1))
 
     # ------------------------------------------------------------------
     def reset(self):
@@ -214,6 +227,7 @@ class RoboyVecEnv:
         self.sim.upload(self._d_act, a)
         self.step_dev(self._d_act, self._d_obs, self._d_rew, self._d_done)
         self._last_actions = _IN_SLAB
+        self._last_done_codes = None
         self.sim.synchronize()
         n = self.num_envs
         return (self.sim.download(self._d_obs, (n, self.obs_dim)),
@@ -221,7 +235,8 @@ class RoboyVecEnv:
                 self.sim.download(self._d_done, (n,), np.uint32).astype(bool), [{}] * n)
 
     def step_dev(self, d_act, d_obs, d_rew, d_done):
-        """Raw device-pointer form: asynchronous on the simulation's stream.  ``d_obs`` holds ``num_envs * obs_dim`` floats."""
+        """Raw device-pointer form: asynchronous on the simulation's stream.  ``d_obs`` holds ``num_envs * obs_dim`` floats.
+        ``d_done``: ``num_envs`` uint32, 0 / 1 - with ``report_truncation`` the codes 0 / 1 (terminated) / 2 (truncated)."""
         nat.check(self.sim._lib.rb_env_step_dev(
             self.sim.handle, ctypes.c_void_p(d_act), ctypes.c_void_p(d_obs),
             ctypes.c_void_p(d_rew), ctypes.c_void_p(d_done)))
@@ -230,7 +245,8 @@ class RoboyVecEnv:
         """``step_dev`` for envs [first_env, first_env + n_envs) on the stream ``stream_ptr`` (None: the simulation's); the
         pointers are those of the WHOLE batch's arrays.  Disjoint ranges may be stepped concurrently on different streams
         (``rb_env_step_range_dev``): how a closed-loop caller overlaps one half's launch gaps and memory phases with the
-        other half's arithmetic (``gym_roboy_amd/ppo.py``)."""
+        other half's arithmetic (``gym_roboy_amd/ppo.py``).  With ``report_truncation`` the range's ``d_done`` words are the codes
+        0 / 1 / 2 as ``step_dev`` leaves them, written on the same stream."""
         nat.check(self.sim._lib.rb_env_step_range_dev(
             self.sim.handle, int(first_env), int(n_envs), ctypes.c_void_p(int(stream_ptr or 0)), ctypes.c_void_p(d_act),
             ctypes.c_void_p(d_obs), ctypes.c_void_p(d_rew), ctypes.c_void_p(d_done)))
@@ -251,7 +267,21 @@ class RoboyVecEnv:
         done = torch.empty((n,), dtype=torch.int32, device=actions.device)
         self.step_dev(actions.data_ptr(), obs.data_ptr(), rew.data_ptr(), done.data_ptr())
         self._last_actions = actions
+        self._last_done_codes = done if self.report_truncation else None
         return obs, rew, done.bool(), [{}] * n
+
+    def truncated(self):
+        """``[N]`` bools of the last step: True where the episode ended at the time limit without reaching its goal.  numpy after a
+        numpy step (or ``step_dev`` / ``step_range_dev``, read from the handle's code plane after a synchronisation), a CUDA tensor
+        after a torch step.  Needs ``report_truncation=True``."""
+        if not self.report_truncation:
+            raise RuntimeError("this RoboyVecEnv does not report truncation (report_truncation=False)")
+        if self._last_done_codes is not None:
+            return self._last_done_codes == nat.RB_DONE_TRUNCATED
+        kind = ctypes.c_void_p()
+        nat.check(self.sim._lib.rb_env_done_kind_ptr(self.sim.handle, ctypes.byref(kind)))
+        self.sim.synchronize()
+        return self.sim.download(kind.value, (self.num_envs,), np.uint32) == nat.RB_DONE_TRUNCATED
 
     def tendon_state(self, actions=None):
         """Per-tendon state of every env at its current state (``HipBatchSimulation.tendon_state``), the set-points formed

@@ -238,19 +238,22 @@ class RewardNorm:
         return self._native
 
     @torch.no_grad()
-    def tail(self, rew_raw, done_i, val, last_val, reward_scale, lam, rew, done, adv, ret, ret_carry=None):
+    def tail(self, rew_raw, done_i, val, last_val, reward_scale, lam, rew, done, adv, ret, ret_carry=None, boot=False, identity=False):
         """One launch for the tail of a [T, n_envs] rollout (contiguous tensors on the GPU; done_i int32): ``scan`` on
-        fl32(rew_raw * reward_scale), then rew = ``apply`` of it, done = done_i as floats, adv / ret = GAE over rew."""
+        fl32(rew_raw * reward_scale), then rew = ``apply`` of it, done = done_i as floats, adv / ret = GAE over rew.
+        boot: done_i holds episode-end codes (0 / 1 terminated / 2 truncated) and GAE bootstraps the truncated steps
+        (rp_rollout_tail_boot_dev, ``gae_boot``).  identity: the kernel runs without statistics (rstd 1, shift 0), whatever the state."""
         pn, c, lib = self._lib()
         T, N = rew_raw.shape
         if N != self.n_envs:
             raise ValueError("a rollout of %d envs, these statistics carry the returns of %d" % (N, self.n_envs))
         carry = self.ret_carry if ret_carry is None else ret_carry
         ptr = lambda t: c.c_void_p(t.data_ptr())
-        pn.check(lib.rp_rollout_tail_dev(ptr(rew_raw), ptr(done_i), ptr(val), ptr(last_val), float(reward_scale), ptr(self.norm),
-                                         self.clip, ptr(self.state), self.gamma, float(lam), ptr(carry), ptr(rew), ptr(done), ptr(adv),
-                                         ptr(ret), ptr(self.sums), ptr(self._scratch), int(T), int(N),
-                                         c.c_void_p(torch.cuda.current_stream(rew_raw.device).cuda_stream)))
+        fn = lib.rp_rollout_tail_boot_dev if boot else lib.rp_rollout_tail_dev
+        pn.check(fn(ptr(rew_raw), ptr(done_i), ptr(val), ptr(last_val), float(reward_scale), None if identity else ptr(self.norm),
+                    self.clip, None if identity else ptr(self.state), self.gamma, float(lam), ptr(carry), ptr(rew), ptr(done), ptr(adv),
+                    ptr(ret), ptr(self.sums), ptr(self._scratch), int(T), int(N),
+                    c.c_void_p(torch.cuda.current_stream(rew_raw.device).cuda_stream)))
 
     @torch.no_grad()
     def merge(self, sums):
@@ -355,6 +358,25 @@ def gae(rewards, values, dones, last_value, gamma, lam):
         adv[t] = last
         next_value = values[t]
     return adv, adv + values
+
+
+def gae_boot(rew, val, done_code, last_value, gamma, lam):
+    """``gae`` over episode-end codes (``done_code`` [T, N]: 0 not done, 1 terminated, 2 truncated - RoboyVecEnv's
+    ``report_truncation``): any non-zero code ends the episode as ``dones`` does in ``gae``, and a truncated step takes
+    ``rew + gamma * val`` for its reward - the value of the state the episode was cut at, so that the return the critic learns does not
+    collapse at a time limit the observation does not show.  The torch statement of rp_rollout_tail_boot_dev's recurrence."""
+    T = rew.shape[0]
+    adv = torch.zeros_like(rew)
+    last = torch.zeros_like(last_value)
+    next_value = last_value
+    for t in range(T - 1, -1, -1):
+        nonterminal = 1.0 - (done_code[t] != 0).to(rew.dtype)
+        r = torch.where(done_code[t] == 2, rew[t] + gamma * val[t], rew[t])
+        delta = r + gamma * next_value * nonterminal - val[t]
+        last = delta + gamma * lam * nonterminal * last
+        adv[t] = last
+        next_value = val[t]
+    return adv, adv + val
 
 
 def gae_fused(rewards, values, dones, last_value, gamma, lam, adv_out=None, ret_out=None):
@@ -673,7 +695,7 @@ class PPO:
                  learning_rate=2.5e-4, cliprange=0.2, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5,
                  device="cuda", dist=None, reward_scale=1.0, seed=0, use_graphs=False, fused_policy=None,
                  fused_update=None, rollout_chains=None, normalize_obs=False, clip_obs=10.0, obs_norm_prime=True,
-                 normalize_reward=False, clip_reward=10.0, reward_norm_prime=True):
+                 normalize_reward=False, clip_reward=10.0, reward_norm_prime=True, bootstrap_timeouts=False):
         """fused_policy / fused_update: None = the fused MFMA kernels whenever they apply (a GPU, MlpPolicy's shape,
         dimensions the kernels support), True = insist, False = the torch path (the statement the kernels are
         tested against).
@@ -688,7 +710,11 @@ class PPO:
         returned, not counted in ``num_timesteps``) and collects again.
         normalize_reward: the scaled reward is divided by the running standard deviation of the discounted return and clamped to
         +-clip_reward (``RewardNorm``); the statistics are frozen through a rollout and merged with its returns at the end of
-        ``collect()``.  reward_norm_prime: the same priming rollout, run while either set of statistics is empty."""
+        ``collect()``.  reward_norm_prime: the same priming rollout, run while either set of statistics is empty.
+        bootstrap_timeouts: an episode that ended at the env's time limit is not treated as if its return stopped there - GAE adds
+        gamma * V(last observation before the limit) to that step's reward (``gae_boot``).  Needs an env built with
+        ``report_truncation=True``.  With the fused policy step the rollout's tail is one launch (rp_rollout_tail_boot_dev), under
+        ``normalize_reward`` or not; the rollout dict gains ``"trunc"`` ([T, N] floats, 1 where the step was truncated)."""
         self.env, self.dist, self.device = env, dist, torch.device(device)
         self._chains_arg = rollout_chains
         torch.manual_seed(seed)
@@ -741,6 +767,17 @@ class PPO:
         if normalize_reward:
             self.reward_norm = RewardNorm(getattr(env, "num_envs", 0), gamma, self.device, clip=clip_reward)
         self._reward_norm_prime = bool(reward_norm_prime)
+        self.bootstrap_timeouts = bool(bootstrap_timeouts)
+        self._boot_tail = None                # the fused boot tail without normalize_reward: identity statistics, a private return carry
+        if self.bootstrap_timeouts:
+            if not getattr(env, "report_truncation", False):
+                raise ValueError("bootstrap_timeouts needs an env that tells truncated episodes from terminated ones: "
+                                 "RoboyVecEnv(report_truncation=True)")
+            if self._fused is not None and self.reward_norm is None:
+                self._boot_tail = RewardNorm(getattr(env, "num_envs", 0), gamma, self.device, clip=math.inf)
+        elif self.use_graphs and getattr(env, "report_truncation", False):
+            raise ValueError("an env built with report_truncation=True leaves episode-end codes (0 / 1 / 2) in the done words of "
+                             "step_dev, which the captured rollout reads as 0 / 1: pass bootstrap_timeouts=True or build the env without it")
         self._rew_raw = None                  # the last rollout's raw reward (kept with normalize_reward: learn() reports it)
         self.num_timesteps = 0
         self._obs = None
@@ -792,19 +829,46 @@ class PPO:
             last_value = self.policy.value(b["obs"][T])
         if self._fused is not None:
             rn.tail(b["rew_raw"], b["done_i"], b["val"], last_value.contiguous(), self.reward_scale, self.lam, b["rew"], b["done"],
-                    b["adv"], b["ret"])
+                    b["adv"], b["ret"], boot=self.bootstrap_timeouts)
         else:
             r_s = b["rew_raw"] * self.reward_scale
-            b["done"].copy_(b["done_i"].to(torch.float32))
+            b["done"].copy_(((b["done_i"] != 0) if self.bootstrap_timeouts else b["done_i"]).to(torch.float32))
             rn.scan(r_s, b["done_i"])
             b["rew"].copy_(rn.apply(r_s))
-            adv, ret = gae(b["rew"], b["val"], b["done"], last_value, self.gamma, self.lam)
+            if self.bootstrap_timeouts:
+                adv, ret = gae_boot(b["rew"], b["val"], b["done_i"], last_value, self.gamma, self.lam)
+            else:
+                adv, ret = gae(b["rew"], b["val"], b["done"], last_value, self.gamma, self.lam)
             b["adv"].copy_(adv); b["ret"].copy_(ret)
+        if self.bootstrap_timeouts:
+            b["trunc"].copy_((b["done_i"] == 2).to(torch.float32))
+        b["carry"].copy_(b["obs"][T])
+
+    def _rollout_tail_boot(self, b):
+        """``_rollout_tail`` with ``bootstrap_timeouts`` and without reward normalisation: with the fused policy step one launch
+        of rp_rollout_tail_boot_dev under identity statistics (its sums are discarded, its return carry is private); otherwise the
+        torch statements and ``gae_boot``."""
+        T = self.n_steps
+        if self._fused is not None:
+            self._step_base += T
+        with torch.no_grad():
+            last_value = self.policy.value(b["obs"][T])
+        if self._fused is not None:
+            self._boot_tail.tail(b["rew_raw"], b["done_i"], b["val"], last_value.contiguous(), self.reward_scale, self.lam, b["rew"],
+                                 b["done"], b["adv"], b["ret"], boot=True, identity=True)
+        else:
+            b["rew"].copy_(b["rew_raw"] * self.reward_scale)
+            b["done"].copy_((b["done_i"] != 0).to(torch.float32))
+            adv, ret = gae_boot(b["rew"], b["val"], b["done_i"], last_value, self.gamma, self.lam)
+            b["adv"].copy_(adv); b["ret"].copy_(ret)
+        b["trunc"].copy_((b["done_i"] == 2).to(torch.float32))
         b["carry"].copy_(b["obs"][T])
 
     def _rollout_tail(self, b):
         if self.reward_norm is not None:
             return self._rollout_tail_norm(b)
+        if self.bootstrap_timeouts:
+            return self._rollout_tail_boot(b)
         T = self.n_steps
         if self._fused is not None:
             self._step_base += T                                             # fresh noise on the next replay
@@ -848,8 +912,12 @@ class PPO:
         b = {"obs": z(T + 1, N, od), "act": z(T, N, ad), "logp": z(T, N), "val": z(T, N), "rew_raw": z(T, N),
              "rew": z(T, N), "done_i": z(T, N, dtype=torch.int32), "done": z(T, N), "adv": z(T, N), "ret": z(T, N),
              "carry": z(N, od)}
+        if self.bootstrap_timeouts:
+            b["trunc"] = z(T, N)
         if self._obs is None and self.reward_norm is not None:
             self.reward_norm.reset_returns(N)
+        if self._boot_tail is not None:
+            self._boot_tail.reset_returns(N)
         b["carry"].copy_(self._to_tensor(env.reset()) if self._obs is None else self._obs)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -866,7 +934,11 @@ class PPO:
                 self._fused.act_into(b["carry"], b["act"][0], b["logp"][0], b["val"][0], deterministic=True, norm=self.obs_norm)
                 if self.reward_norm is not None:  # nor the tail kernel's (on a copy of the returns: they must not move)
                     self.reward_norm.tail(b["rew_raw"], b["done_i"], b["val"], b["val"][0], self.reward_scale, self.lam, b["rew"],
-                                          b["done"], b["adv"], b["ret"], ret_carry=self.reward_norm.ret_carry.clone())
+                                          b["done"], b["adv"], b["ret"], ret_carry=self.reward_norm.ret_carry.clone(),
+                                          boot=self.bootstrap_timeouts)
+                elif self._boot_tail is not None:
+                    self._boot_tail.tail(b["rew_raw"], b["done_i"], b["val"], b["val"][0], self.reward_scale, self.lam, b["rew"],
+                                         b["done"], b["adv"], b["ret"], boot=True, identity=True)
         side.synchronize()
         self.rollout_chains = self._pick_chains(N)
         # thread-local capture mode: another thread of the process (RCCL's watchdog in a multi-rank run) may call into
@@ -923,8 +995,11 @@ class PPO:
             # behind the replay and outside the graph: the all-reduce and the merge of the rollout's return moments
             self._rew_raw = b["rew_raw"]
             self.reward_norm.update(self.dist)
-        return {"obs": b["obs"][:T], "act": b["act"], "logp": b["logp"], "val": b["val"], "rew": b["rew"],
+        roll = {"obs": b["obs"][:T], "act": b["act"], "logp": b["logp"], "val": b["val"], "rew": b["rew"],
                 "done": b["done"], "adv": b["adv"], "ret": b["ret"]}
+        if self.bootstrap_timeouts:
+            roll["trunc"] = b["trunc"]
+        return roll
 
     def collect(self):
         ask_obs = self.obs_norm is not None and self._obs_norm_prime
@@ -952,7 +1027,10 @@ class PPO:
                 self.reward_norm.reset_returns(self._obs.shape[0])
         N = self._obs.shape[0]
         buf = {k: [] for k in ("obs", "act", "logp", "val", "rew", "done")}
-        raw = []
+        raw, codes = [], []
+        boot = self.bootstrap_timeouts
+        if boot and self._fused is not None:
+            return self._collect_rollout_boot_fused()
         packed = self._fused.pack() if self._fused is not None else None
         for t in range(T):
             if self._fused is not None:
@@ -970,6 +1048,8 @@ class PPO:
                 raw.append(rew)
             buf["rew"].append(rew * self.reward_scale)
             buf["done"].append(self._to_tensor(done))
+            if boot:                                         # the codes: 0, 1 terminated, 2 truncated
+                codes.append(self._to_tensor(done, torch.int32) + self._to_tensor(env.truncated(), torch.int32))
             self._obs = self._to_tensor(obs)
         if self._fused is not None:
             self._step_base += T
@@ -982,7 +1062,48 @@ class PPO:
             self.reward_norm.update(self.dist)
         with torch.no_grad():
             last_value = self.policy.value(self._obs)
-        roll["adv"], roll["ret"] = gae(roll["rew"], roll["val"], roll["done"], last_value, self.gamma, self.lam)
+        if boot:
+            codes = torch.stack(codes)
+            roll["trunc"] = (codes == 2).to(torch.float32)
+            roll["adv"], roll["ret"] = gae_boot(roll["rew"], roll["val"], codes, last_value, self.gamma, self.lam)
+        else:
+            roll["adv"], roll["ret"] = gae(roll["rew"], roll["val"], roll["done"], last_value, self.gamma, self.lam)
+        self.num_timesteps += T * N
+        return roll
+
+    def _collect_rollout_boot_fused(self):
+        """The eager rollout with the fused policy step and ``bootstrap_timeouts``: the steps through ``env.step``, then the tail as
+        the graph modes run it - one launch of rp_rollout_tail_boot_dev over the stacked rollout - so that eager and captured
+        rollouts agree bit for bit."""
+        env, T = self.env, self.n_steps
+        N = self._obs.shape[0]
+        if self._boot_tail is not None and self._boot_tail.n_envs != N:
+            self._boot_tail.reset_returns(N)
+        z = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=self.device)
+        roll = {"obs": z(T, N, self._obs.shape[1]), "act": z(T, N, self._fused.act_dim), "logp": z(T, N), "val": z(T, N),
+                "rew": z(T, N), "done": z(T, N), "adv": z(T, N), "ret": z(T, N)}
+        rew_raw, codes = z(T, N), z(T, N, dtype=torch.int32)
+        packed = self._fused.pack()
+        for t in range(T):
+            roll["obs"][t].copy_(self._obs)
+            self._fused.act_into(roll["obs"][t], roll["act"][t], roll["logp"][t], roll["val"][t], step=t, packed=packed,
+                                 step_base=self._step_base, norm=self.obs_norm)
+            obs, rew, done, _ = env.step(roll["act"][t].clamp(-1.0, 1.0).contiguous())
+            rew_raw[t].copy_(rew)
+            codes[t].copy_(done.to(torch.int32) + env.truncated().to(torch.int32))
+            self._obs = obs
+        self._step_base += T
+        with torch.no_grad():
+            last_value = self.policy.value(self._obs).contiguous()
+        if self.reward_norm is not None:
+            self._rew_raw = rew_raw
+            self.reward_norm.tail(rew_raw, codes, roll["val"], last_value, self.reward_scale, self.lam, roll["rew"], roll["done"],
+                                  roll["adv"], roll["ret"], boot=True)
+            self.reward_norm.update(self.dist)
+        else:
+            self._boot_tail.tail(rew_raw, codes, roll["val"], last_value, self.reward_scale, self.lam, roll["rew"], roll["done"],
+                                 roll["adv"], roll["ret"], boot=True, identity=True)
+        roll["trunc"] = (codes == 2).to(torch.float32)
         self.num_timesteps += T * N
         return roll
 
@@ -1077,7 +1198,8 @@ class PPO:
         torch.save({"policy": self.policy.state_dict(), "optimizer": opt, "num_timesteps": self.num_timesteps,
                     "epoch": self._epoch, "tendon_obs": _tendon_obs_of(self.env), "env_io": _env_io_of(self.env),
                     "obs_norm": self.obs_norm.state_dict() if self.obs_norm is not None else None,
-                    "reward_norm": self.reward_norm.state_dict() if self.reward_norm is not None else None}, path)
+                    "reward_norm": self.reward_norm.state_dict() if self.reward_norm is not None else None,
+                    "bootstrap_timeouts": self.bootstrap_timeouts}, path)
 
     def load(self, path):
         ck = torch.load(path, map_location=self.device)

@@ -52,6 +52,9 @@ def main(argv=None):
                     help="divide the (scaled) reward by the running standard deviation of the discounted return (what "
                          "stable-baselines calls VecNormalize(norm_reward=True)); the statistics are stored in the checkpoint")
     ap.add_argument("--clip-reward", type=float, default=10.0, metavar="X", help="clamp of the normalised reward (default 10)")
+    ap.add_argument("--bootstrap-timeouts", action="store_true",
+                    help="episodes that end at the time limit bootstrap the value of their last observation in GAE instead of "
+                         "ending the return there (the env then reports truncation); recorded in the checkpoint")
     args = ap.parse_args(argv)
     sensor_noise = {k: float(v) for k, v in (item.split("=", 1) for item in args.sensor_noise.split(",") if item)}
     action_delay = None
@@ -86,12 +89,14 @@ def main(argv=None):
 
     env = RoboyVecEnv(MsjRobot(), args.num_envs, seed=args.seed, device=local_rank,
                       env_id_offset=rank * args.num_envs, tendon_obs=tendon_obs or None, tendon_obs_scale=tendon_obs_scale or None,
-                      sensor_noise=sensor_noise or None, action_delay=action_delay)
+                      sensor_noise=sensor_noise or None, action_delay=action_delay,
+                      report_truncation=args.bootstrap_timeouts)
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,
                 fused_update=not args.torch_policy, normalize_obs=args.normalize_obs, clip_obs=args.clip_obs,
-                normalize_reward=args.normalize_reward, clip_reward=args.clip_reward)
+                normalize_reward=args.normalize_reward, clip_reward=args.clip_reward,
+                bootstrap_timeouts=args.bootstrap_timeouts)
     if os.path.exists(model_file):
         agent.load(model_file)                  # resume from the last backup
     for _ in range(args.rounds):

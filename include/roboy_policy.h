@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define RP_ABI_VERSION 4
+#define RP_ABI_VERSION 5
 #define RP_HIDDEN 64          /* units per hidden layer (stable_baselines' MlpPolicy) */
 #define RP_MAX_OBS 95         /* obs_dim + 1 (bias column) <= 96 */
 #define RP_MAX_ACT 64
@@ -166,6 +166,21 @@ int rp_rollout_tail_dev(const float *d_rew_raw, const int32_t *d_done_i, const f
                         const float *d_norm2, float clip, const double *d_shift, double gamma, double lam, double *d_ret_carry,
                         float *d_rew, float *d_done, float *d_adv, float *d_ret, double *d_sums3, double *d_scratch, int n_steps,
                         int64_t n_envs, void *stream);
+/* ---- the same tail with value bootstrapping of truncated episodes (ABI 5; PPO(bootstrap_timeouts=True)) ----
+ * rp_rollout_tail_dev's argument list and launch; d_done_i carries episode-end codes (roboy_sim.h: RB_DONE_*): 0 none, 1 terminated
+ * (the goal was reached), 2 truncated (the time limit ended the episode).  Any non-zero code ends the episode exactly as above: the
+ * return scan's reset, GAE's mask, d_done written as 0 / 1 floats.  Where the code is 2 the backward recurrence takes
+ *     r^_t = fl32(r~_t + fl32(gamma32 * val_t))
+ * in place of r~_t - two roundings, no contraction - and is otherwise rp_rollout_tail_dev's: the return the critic is trained on
+ * no longer collapses at a moment the observation does not show.  val_t is the value of the last observation before the limit
+ * (the terminal observation itself is overwritten by the auto-reset row: the rl_games / Isaac Gym form).  d_rew still receives r~
+ * without the bootstrap, and the return scan with its fp64 moments does not see it.  With no code 2 anywhere every output is
+ * bit-equal to rp_rollout_tail_dev's.  A second instance of the same kernel text: rp_rollout_tail_dev's instruction stream is
+ * unchanged.  Same scratch, same grid, same argument errors. */
+int rp_rollout_tail_boot_dev(const float *d_rew_raw, const int32_t *d_done_i, const float *d_val, const float *d_last_val, float reward_scale,
+                             const float *d_norm2, float clip, const double *d_shift, double gamma, double lam, double *d_ret_carry,
+                             float *d_rew, float *d_done, float *d_adv, float *d_ret, double *d_sums3, double *d_scratch, int n_steps,
+                             int64_t n_envs, void *stream);
 /* test hook: would a grant of lds_bytes of dynamic LDS be issued for (kernel id, device) now?  Records it. */
 int rp_debug_lds_grant_needed(int kernel_id, int dev, int64_t lds_bytes);
 /* which form of the gradient kernels rp_ppo_grad_dev launches for this policy: 2 = the small instance (obs_dim <= 31, up to 8

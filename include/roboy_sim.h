@@ -424,6 +424,29 @@ int rb_env_io_configure(rb_sim *sim, const rb_env_io_config *cfg);
 int rb_env_io_ptr(rb_sim *sim, uint32_t **d_delay, uint32_t **d_delay_draws, uint32_t **d_rows, float **d_history, int32_t *slots);
 int rb_env_io_sample_delay_dev(rb_sim *sim, const uint8_t *d_mask);
 
+/* ---- episode-end codes: which episodes ended at the time limit ----
+ * The fused env step ends an episode when the goal is reached or when the episode is max_episode_length steps old, and reports
+ * both as done = 1.  While enabled, every env-step entry (rb_env_step_dev, rb_env_step_range_dev; every kernel form, both robot
+ * classes, every extension) is followed on the same stream, over the same envs, by one small kernel that rewrites the step's done
+ * words into codes: RB_DONE_NONE, RB_DONE_TERMINATED (the goal was reached) or RB_DONE_TRUNCATED (the time limit alone ended the
+ * episode).  Terminated wins: an env that reaches its goal on its last permitted step reads RB_DONE_TERMINATED.  `done != 0` is
+ * exactly the done of a handle without the option; observations, rewards, state and statistics are untouched.  A consumer that
+ * bootstraps the value of truncated episodes (rp_rollout_tail_boot_dev in roboy_policy.h) reads the codes from d_done.
+ * How: an env reached its goal iff its goal counter (the n_goal_reached term of rb_env_stats) moved since its last episode end;
+ * the handle keeps that counter's last seen value per env.  Enabling reads the counters as they stand; rb_env_configure and the
+ * reset of rb_env_stats / rb_env_stats_dev, which zero the counters, zero the seen values on the same stream, and rb_env_reset_dev
+ * re-reads them.  rb_rollout_fused_dev (the open-loop benchmark entry) reports no codes.
+ *   configure: needs rb_env_configure; drains the handle's streams and evicts the cached rollout graphs, so call it before a
+ *              caller captures env steps into a graph of its own.  enable = 0 frees the planes: the handle launches exactly what
+ *              it launched before.  Off by default.
+ *   ptr:       the last step's codes, a device plane [n_envs] (zero until the first step); RB_EINVAL while not enabled.
+ * RB_ABI_VERSION is still 6 (nothing that existed changed): look rb_env_done_kind_configure up before relying on it. */
+#define RB_DONE_NONE 0
+#define RB_DONE_TERMINATED 1
+#define RB_DONE_TRUNCATED 2
+int rb_env_done_kind_configure(rb_sim *sim, int enable);
+int rb_env_done_kind_ptr(rb_sim *sim, uint32_t **d_kind);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both

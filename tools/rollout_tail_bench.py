@@ -7,7 +7,8 @@ one process, alternating, with HIP events on torch's stream after warm-up.
 
 Variants per shape (262 144 x 128 and 4 096 x 128): the parent's tail TWICE (two graphs over buffers of their own: what separates them
 is the run-to-run spread the new launch is judged against), the one launch with identity statistics (null pointers) and with real
-ones (an rstd, a clamp, a shift).  One JSON line per shape: per variant the median, the smallest and the largest of the rounds'
+ones (an rstd, a clamp, a shift), and the bootstrapping instance (rp_rollout_tail_boot_dev; half of the dones truncated)
+with identity statistics - what PPO(bootstrap_timeouts=True) runs without normalize_reward - and with real ones.  One JSON line per shape: per variant the median, the smallest and the largest of the rounds'
 microseconds per replay, and the bytes per second of the nine array passes each variant makes (read rew_raw and done_i twice, val
 once; write rew, done, adv, ret) against the chip's 8 TB/s.  --iteration adds a whole PPO iteration (rollout + update) at 262 144 envs with
 the option off and on, timed as tools/policy_bench.py times it."""
@@ -84,21 +85,25 @@ def tail_shapes(args):
                 gae_fused(b["rew"], val, b["done"], last, GAMMA, LAM, b["adv"], b["ret"])
             return captured(run)
 
-        def fused(norm2, shift, clip):
+        code_i = torch.where((done_i != 0) & (torch.rand(T, N, device="cuda", generator=g) < 0.5), 2, done_i).to(torch.int32)
+
+        def fused(norm2, shift, clip, boot=False):
             b = {k: torch.empty(T, N, device="cuda") for k in ("rew", "done", "adv", "ret")}
             carry, sums = torch.zeros(N, dtype=torch.float64, device="cuda"), torch.zeros(3, dtype=torch.float64, device="cuda")
             scratch = torch.zeros(int(lib.rp_rollout_tail_scratch_doubles()), dtype=torch.float64, device="cuda")
 
             def run():
-                pn.check(lib.rp_rollout_tail_dev(ptr(rew_raw), ptr(done_i), ptr(val), ptr(last), SCALE, ptr(norm2), clip, ptr(shift), GAMMA,
-                                                 LAM, ptr(carry), ptr(b["rew"]), ptr(b["done"]), ptr(b["adv"]), ptr(b["ret"]), ptr(sums),
-                                                 ptr(scratch), T, N, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+                fn = lib.rp_rollout_tail_boot_dev if boot else lib.rp_rollout_tail_dev
+                pn.check(fn(ptr(rew_raw), ptr(code_i if boot else done_i), ptr(val), ptr(last), SCALE, ptr(norm2), clip, ptr(shift), GAMMA,
+                            LAM, ptr(carry), ptr(b["rew"]), ptr(b["done"]), ptr(b["adv"]), ptr(b["ret"]), ptr(sums),
+                            ptr(scratch), T, N, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
             return captured(run)
 
         norm2 = torch.tensor([[-0.4], [2.5]], device="cuda")
         shift = torch.tensor([-0.4], dtype=torch.float64, device="cuda")
-        names = ["parent_a", "parent_b", "one_launch_identity", "one_launch_statistics"]
-        fns = [parent(), parent(), fused(None, None, float("inf")), fused(norm2, shift, 0.05)]
+        names = ["parent_a", "parent_b", "one_launch_identity", "one_launch_statistics", "boot_identity", "boot_statistics"]
+        fns = [parent(), parent(), fused(None, None, float("inf")), fused(norm2, shift, 0.05), fused(None, None, float("inf"), True),
+               fused(norm2, shift, 0.05, True)]
         times = alternate(fns, args.reps, args.rounds)
         passes = {name: 9 * T * N * 4 for name in names}
         out = {"what": "rollout tail", "shape": "%d x %d" % (N, T), "blocks": int(lib.rp_rollout_tail_blocks(T, N))}
@@ -109,6 +114,8 @@ def tail_shapes(args):
         pa, pb = out["parent_a"]["median_us"], out["parent_b"]["median_us"]
         out["parent_spread_us"] = round(max(max(times[0]), max(times[1])) - min(min(times[0]), min(times[1])), 2)
         out["one_launch_over_parent"] = round(out["one_launch_statistics"]["median_us"] / (0.5 * (pa + pb)), 4)
+        out["boot_identity_over_parent"] = round(out["boot_identity"]["median_us"] / (0.5 * (pa + pb)), 4)
+        out["boot_over_one_launch"] = round(out["boot_statistics"]["median_us"] / out["one_launch_statistics"]["median_us"], 4)
         print(json.dumps(out), flush=True)
         del fns
 
