@@ -78,6 +78,7 @@ class EnvConfig(ctypes.Structure):
 
 
 RB_IO_MAX_DELAY = 7
+RB_ACTION_OBS_MAX = 8      # rb_env_action_obs_configure: at most this many action rows behind the observation
 RB_DONE_NONE, RB_DONE_TERMINATED, RB_DONE_TRUNCATED = 0, 1, 2      # the done words while rb_env_done_kind_configure holds
 
 
@@ -145,6 +146,9 @@ SIGNATURES = {
     "rb_env_io_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
                                      ctypes.POINTER(ctypes.c_int32)]),
     "rb_env_io_sample_delay_dev": (ctypes.c_int, [_sim, _vp]),
+    "rb_env_action_obs_configure": (ctypes.c_int, [_sim, ctypes.c_int32]),
+    "rb_env_action_obs_rows": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_int32)]),
+    "rb_env_action_obs_count": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32]),
     "rb_env_done_kind_configure": (ctypes.c_int, [_sim, ctypes.c_int]),
     "rb_env_done_kind_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp)]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),

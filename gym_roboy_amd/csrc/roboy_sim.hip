@@ -49,6 +49,7 @@
 #include "env_params.hpp"             // per-env physical parameters (rb_params_*)
 #include "env_obs.hpp"                // tendon channels in the fused env step's observation (rb_env_obs_*)
 #include "env_io.hpp"                 // per-env action latency and sensor noise in the fused env step (rb_env_io_*)
+#include "env_hist.hpp"               // the last K commanded actions as observation columns (rb_env_action_obs_*)
 
 namespace {
 
@@ -558,7 +559,7 @@ struct rb_sim {
     // the extended kernels - the nominal or the parameter form - instead of the dispatch table's row / the parameter kernel
     int obs_mask = 0;
     float obs_scale[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-    int obs_dim() const { return 3 * n_q + rbo::n_channels(obs_mask) * n_t; }
+    int obs_dim() const { return 3 * n_q + rbo::n_channels(obs_mask) * n_t + hist_rows * n_t; }
     // action latency and sensor noise of the env step (env_io.hpp; rb_env_io_*): while configured, the env-step entry launches the io
     // kernels - nominal or parameter form, with or without channels.  Planes [n] each; the ring [io_slots][n][n_t] only with delay_hi > 0
     bool io = false;
@@ -566,6 +567,9 @@ struct rb_sim {
     uint32_t *d_io_delay = nullptr, *d_io_draws = nullptr, *d_io_rows = nullptr;
     float *d_io_hist = nullptr;
     int io_slots = 0;
+    // the last K handed action rows as observation columns (env_hist.hpp; rb_env_action_obs_*): while K > 0 the env-step entry launches
+    // the history kernels, with or without any of the above, and the ring exists whatever delay_hi is (io_slots above max(delay_hi, K - 1))
+    int hist_rows = 0;
     // episode-end codes (rb_env_done_kind_*): while enabled, every env-step launch is followed by done_kind_kernel over its range.
     // Planes [n] each: the goal counter d_ep_cnt[2n + i] as of env i's last episode end, and the last step's codes
     bool done_kind = false;
@@ -820,8 +824,8 @@ rbo::ObsArgs<NT> obs_args(const rb_sim *s, bool staged = false) {
 rbio::IoArgs io_args(const rb_sim *s, long first) {
     rbio::IoArgs io;
     std::memset(&io, 0, sizeof(io));
-    const rb_env_io_config &cfg = s->io_cfg;
-    io.delay = s->d_io_delay + first; io.delay_draws = s->d_io_draws + first; io.rows = s->d_io_rows + first;
+    const rb_env_io_config cfg = s->io ? s->io_cfg : rb_env_io_config{};      // (no io configuration, K > 0: zeros and the ring)
+    if (s->io) { io.delay = s->d_io_delay + first; io.delay_draws = s->d_io_draws + first; io.rows = s->d_io_rows + first; }
     io.hist = s->d_io_hist ? s->d_io_hist + first * s->n_t : nullptr;
     io.slot_stride = long(s->n) * s->n_t;
     io.slot_mask = s->io_slots ? s->io_slots - 1 : 0;
@@ -841,6 +845,30 @@ void io_free(rb_sim *s) {
     (void)hipFree(s->d_io_delay); (void)hipFree(s->d_io_draws); (void)hipFree(s->d_io_rows); (void)hipFree(s->d_io_hist);
     s->d_io_delay = nullptr; s->d_io_draws = nullptr; s->d_io_rows = nullptr; s->d_io_hist = nullptr;
     s->io = false; s->io_slots = 0;
+}
+// the ring both options share: S slots, the smallest power of two above max(delay_hi, K - 1); none without a delay range and K = 0
+int ring_slots_wanted(int delay_hi, int hist_rows) {
+    if (delay_hi <= 0 && hist_rows <= 0) return 0;
+    const int reach = delay_hi > hist_rows - 1 ? delay_hi : hist_rows - 1;
+    int slots = 1;
+    while (slots <= reach) slots *= 2;
+    return slots;
+}
+// ... rebuilt (zeroed) for the handle as configured
+int ring_rebuild(rb_sim *s) {
+    (void)hipFree(s->d_io_hist);
+    s->d_io_hist = nullptr;
+    s->io_slots = ring_slots_wanted(s->io ? s->io_cfg.delay_hi : 0, s->hist_rows);
+    if (!s->io_slots) return RB_OK;
+    const size_t bytes = sizeof(float) * size_t(s->io_slots) * size_t(s->n) * size_t(s->n_t);
+    const hipError_t e = hipMalloc(&s->d_io_hist, bytes);
+    if (e != hipSuccess) {                   // no ring: neither a delay range nor action rows (their kernels index it unasked)
+        s->d_io_hist = nullptr; s->io_slots = 0; s->hist_rows = 0;
+        if (s->io) s->io_cfg.delay_lo = s->io_cfg.delay_hi = 0;
+        return fail(RB_EHIP, std::string("the action history ring: ") + hipGetErrorString(e));
+    }
+    RB_HIP(hipMemsetAsync(s->d_io_hist, 0, bytes, s->stream));
+    return RB_OK;
 }
 // rb_env_reset_dev's observation rows on such a handle: the state the reset kernel has just written, every set-point 0
 void obs_rows_launch(rb_sim *s, float *d_obs) {
@@ -886,7 +914,8 @@ template <int INTEG>
 int ext_env_launch(rb_sim *s, const Launch &L) {
     MsjEnvArgs a = msj_env_args(s, L);
     a.obs = L.obs + L.i0 * s->obs_dim();                 // the row stride is the handle's obs_dim (9 without channels)
-    const bool par = s->params, io = s->io, rows = io || s->obs_mask;       // rows: TendonObs writes them (env_obs.hpp)
+    const int K = s->hist_rows;                           // > 0: the history kernels (env_hist.hpp), an io argument of zeros without io
+    const bool par = s->params, io = s->io || K > 0, rows = io || s->obs_mask;       // rows: TendonObs writes them (env_obs.hpp)
     return with_consts(s, [&](const auto &c, auto bk) {
         using CONST = std::decay_t<decltype(c)>;
         constexpr bool BK = decltype(bk)::value;
@@ -909,6 +938,12 @@ int ext_env_launch(rb_sim *s, const Launch &L) {
         auto io_step = [&](auto block, auto unroll) {
             return go(rbio::msj_io_env_step<INTEG, decltype(block)::value, decltype(unroll)::value, CONST, BK>, oa, io_args(s, L.i0));
         };
+        if (K > 0) {
+            const rbh::HistIoArgs hio{io_args(s, L.i0), {K, s->obs_dim() - K * s->n_t}};
+            if (par) return go(rbh::msj_hist_params_env_step<INTEG, 256, CONST, BK>, param_args(s, L), oa, hio);
+            if constexpr (BK) if (small) return go(rbh::msj_hist_env_step<INTEG, 64, 8, CONST, BK>, oa, hio);
+            return go(rbh::msj_hist_env_step<INTEG, 256, U, CONST, BK>, oa, hio);
+        }
         if (par && io) return go(rbio::msj_io_params_env_step<INTEG, 256, CONST, BK>, param_args(s, L), oa, io_args(s, L.i0));
         if (io) {
             if constexpr (BK) if (small) return io_step(std::integral_constant<int, 64>{}, std::integral_constant<int, 8>{});
@@ -1577,9 +1612,9 @@ int rb_env_reset_dev(rb_sim *s, float *d_obs) {
     else
         hipLaunchKernelGGL(env_reset_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream,
                            s->box, s->d_q, s->d_qd, s->d_feas, s->d_goal, s->d_step_num, s->d_ep_ret,
-                           s->d_goal_count, s->obs_mask ? nullptr : d_obs, s->n, s->seed, uint64_t(s->env0));
+                           s->d_goal_count, s->obs_mask || s->hist_rows ? nullptr : d_obs, s->n, s->seed, uint64_t(s->env0));
     RB_HIP(hipGetLastError());
-    if (s->obs_mask && d_obs) {               // rows of obs_dim floats: the tendon columns at the zero pose, every set-point 0
+    if ((s->obs_mask || s->hist_rows) && d_obs) {      // rows of obs_dim floats: the tendon columns at the zero pose, every set-point 0
         obs_rows_launch(s, d_obs);
         RB_HIP(hipGetLastError());
     }
@@ -1590,9 +1625,19 @@ int rb_env_reset_dev(rb_sim *s, float *d_obs) {
     if (s->io && d_obs) {                     // sensor readings too: the rows' noise, in place (the episode restarts, the history needs nothing)
         const rbio::IoArgs io = io_args(s, 0);
         if (io.noise_blocks) {
-            hipLaunchKernelGGL(rbio::io_noise_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, s->obs_dim(), io, s->n, s->seed, uint64_t(s->env0));
+            const int od = s->obs_dim();
+            if (s->hist_rows)                 // (the noise stops in front of the action blocks: row stride and noised width apart)
+                hipLaunchKernelGGL(rbh::hist_noise_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, od, od - s->hist_rows * s->n_t, io,
+                                   long(s->n), s->seed, uint64_t(s->env0));
+            else
+                hipLaunchKernelGGL(rbio::io_noise_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, od, io, s->n, s->seed, uint64_t(s->env0));
             RB_HIP(hipGetLastError());
         }
+    }
+    if (s->hist_rows && d_obs) {              // nothing has been handed yet: K zero blocks
+        const int od = s->obs_dim();
+        hipLaunchKernelGGL(rbh::hist_zero_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, od, od - s->hist_rows * s->n_t, long(s->n));
+        RB_HIP(hipGetLastError());
     }
     return RB_OK;
 }
@@ -1640,28 +1685,63 @@ int rb_env_io_configure(rb_sim *s, const rb_env_io_config *cfg) {
     rc = drop_graphs(s);
     if (rc) return rc;
     io_free(s);
-    if (!cfg) return RB_OK;
+    if (!cfg) return ring_rebuild(s);        // (the ring stays for the action columns, rb_env_action_obs_configure)
     const size_t n = size_t(s->n);
-    RB_HIP(hipMalloc(&s->d_io_delay, sizeof(uint32_t) * n));
-    RB_HIP(hipMalloc(&s->d_io_draws, sizeof(uint32_t) * n));
-    RB_HIP(hipMalloc(&s->d_io_rows, sizeof(uint32_t) * n));
-    RB_HIP(hipMemsetAsync(s->d_io_draws, 0, sizeof(uint32_t) * n, s->stream));
-    RB_HIP(hipMemsetAsync(s->d_io_rows, 0, sizeof(uint32_t) * n, s->stream));
-    s->io_slots = 0;
-    if (cfg->delay_hi > 0) {
-        s->io_slots = 1;
-        while (s->io_slots <= cfg->delay_hi) s->io_slots *= 2;
-        const size_t bytes = sizeof(float) * size_t(s->io_slots) * n * size_t(s->n_t);
-        RB_HIP(hipMalloc(&s->d_io_hist, bytes));
-        RB_HIP(hipMemsetAsync(s->d_io_hist, 0, bytes, s->stream));
+    auto planes = [&]() -> int {
+        RB_HIP(hipMalloc(&s->d_io_delay, sizeof(uint32_t) * n));
+        RB_HIP(hipMalloc(&s->d_io_draws, sizeof(uint32_t) * n));
+        RB_HIP(hipMalloc(&s->d_io_rows, sizeof(uint32_t) * n));
+        RB_HIP(hipMemsetAsync(s->d_io_draws, 0, sizeof(uint32_t) * n, s->stream));
+        RB_HIP(hipMemsetAsync(s->d_io_rows, 0, sizeof(uint32_t) * n, s->stream));
+        return RB_OK;
+    };
+    rc = planes();
+    if (rc) {                                // no io configuration; action rows keep a ring of their own (or are switched off with it)
+        io_free(s);
+        (void)ring_rebuild(s);               // (clears the action rows itself where it fails too)
+        return rc;
     }
     s->io_cfg = *cfg;
     s->io = true;
+    rc = ring_rebuild(s);
+    if (rc) return rc;
     return rb_env_io_sample_delay_dev(s, nullptr);      // draw 0 of every env
+}
+// ---- the last K commanded actions as observation columns (env_hist.hpp) ----
+int32_t rb_env_action_obs_count(int32_t n_q, int32_t n_t, uint32_t channel_mask, int32_t rows) {
+    if (rows < 0 || rows > RB_ACTION_OBS_MAX) return -1;
+    const int32_t lead = rb_env_obs_count(n_q, n_t, channel_mask);
+    return lead < 0 ? -1 : lead + rows * n_t;
+}
+int rb_env_action_obs_configure(rb_sim *s, int32_t rows) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
+    if (rows < 0 || rows > RB_ACTION_OBS_MAX) return fail(RB_EINVAL, "action rows in the observation: 0 <= rows <= RB_ACTION_OBS_MAX");
+    if (s->tree && rows)
+        return fail(RB_EUNSUPPORTED, "action columns in the observation are built for ball-joint robots (1-16 tendons); joint trees have none");
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);                       // nothing in flight may still write rows of the old width or use the ring
+    if (rc) return rc;
+    rc = drop_graphs(s);
+    if (rc) return rc;
+    const int delay_hi = s->io ? s->io_cfg.delay_hi : 0;
+    const bool resize = ring_slots_wanted(delay_hi, rows) != s->io_slots;
+    s->hist_rows = rows;
+    if (!resize) return RB_OK;
+    if (s->io) {                             // another S: planes, counters and ring as a fresh io configuration leaves them
+        const rb_env_io_config cfg = s->io_cfg;
+        return rb_env_io_configure(s, &cfg);
+    }
+    return ring_rebuild(s);
+}
+int rb_env_action_obs_rows(rb_sim *s, int32_t *rows) {
+    if (check(s) || !rows) return fail(RB_EINVAL, "null argument");
+    *rows = s->hist_rows;
+    return RB_OK;
 }
 int rb_env_io_ptr(rb_sim *s, uint32_t **d_delay, uint32_t **d_delay_draws, uint32_t **d_rows, float **d_history, int32_t *slots) {
     if (check(s)) return RB_EINVAL;
-    if (!s->io) return fail(RB_EINVAL, "no io configuration (rb_env_io_configure)");
+    if (!s->io && !s->hist_rows) return fail(RB_EINVAL, "no io configuration (rb_env_io_configure)");
     if (d_delay) *d_delay = s->d_io_delay;
     if (d_delay_draws) *d_delay_draws = s->d_io_draws;
     if (d_rows) *d_rows = s->d_io_rows;
@@ -1937,7 +2017,9 @@ int rb_dispatch_current(rb_sim *s, int entry, rb_dispatch_row *out) {
     if (entry == ENTRY_FUSED && (s->tree || s->ntx)) return fail(RB_EUNSUPPORTED, "fused rollout is built for 8-tendon ball-joint robots");
     if (extension_serves(s, entry))
         return fail(RB_EUNSUPPORTED,
-                    s->params ? "per-env parameters are enabled: the parameter kernels (env_params.hpp) are not rows of the dispatch table"
+                    s->hist_rows && entry == ENTRY_ENV
+                        ? "action rows are set (rb_env_action_obs_configure): the history env-step kernels (env_hist.hpp) are not rows of the dispatch table"
+                    : s->params ? "per-env parameters are enabled: the parameter kernels (env_params.hpp) are not rows of the dispatch table"
                     : s->io   ? "an io configuration is set (rb_env_io_configure): the io env-step kernels (env_io.hpp) are not rows of the dispatch table"
                               : "tendon channels are set (rb_env_obs_configure): the extended env-step kernels (env_obs.hpp) are not rows of the dispatch table");
     RB_HIP(hipSetDevice(s->device));

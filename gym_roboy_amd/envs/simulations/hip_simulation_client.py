@@ -264,6 +264,17 @@ class HipBatchSimulation:
             nat.check(self._lib.rb_env_io_sample_delay_dev(self._h, ctypes.c_void_p(self._d_param_mask)))
         self.synchronize()
 
+    # -- the last K commanded actions as observation columns (rb_env_action_obs_*; ball-joint robots) -----
+    def configure_action_obs(self, rows: int):
+        """``rows`` = K action rows behind the env step's observation (0 switches them off).  Needs the env layer configured; a
+        change of the action history's slot count resets it (and an io configuration's planes and counters)."""
+        nat.check(self._lib.rb_env_action_obs_configure(self._h, int(rows)))
+
+    def action_obs_rows(self) -> int:
+        rows = ctypes.c_int32()
+        nat.check(self._lib.rb_env_action_obs_rows(self._h, ctypes.byref(rows)))
+        return int(rows.value)
+
     # -- device-pointer interface (no host copies) ------------------------
     def state_ptrs(self):
         q, qd, f = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()

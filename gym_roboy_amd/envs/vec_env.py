@@ -14,7 +14,7 @@ one returned).
 ``step`` takes actions ``[N, n_t]`` in ``[-1, 1]`` either as a numpy array
 (copied to the device) or as a CUDA ``torch.Tensor`` (used in place), and
 returns ``(obs [N, obs_dim], reward [N], done [N], infos)`` of the same kind;
-``obs_dim`` is ``3 n_q``, or ``3 n_q + C n_t`` with ``tendon_obs`` (C channels).
+``obs_dim`` is ``3 n_q``, or ``3 n_q + C n_t`` with ``tendon_obs`` (C channels), plus ``K n_t`` with ``action_obs=K``.
 """
 import ctypes
 
@@ -87,6 +87,23 @@ def action_delay_range(action_delay):
     return lo, hi, ranged
 
 
+def action_obs_rows(action_obs) -> int:
+    """None -> 0, K -> K: the number of action rows behind the observation, 0 <= K <= 8"""
+    if action_obs is None:
+        return 0
+    if isinstance(action_obs, bool) or not isinstance(action_obs, (int, np.integer)) or not 0 <= int(action_obs) <= nat.RB_ACTION_OBS_MAX:
+        raise ValueError("action_obs: an int, 0 <= K <= %d, got %r" % (nat.RB_ACTION_OBS_MAX, action_obs))
+    return int(action_obs)
+
+
+def action_obs_bounds(low, high, n_t: int, rows: int):
+    """The observation box with K = ``rows`` action rows behind it: ``rows * n_t`` more columns, each within [-1, 1] (the clamp
+    the env step applies to an action).  Returns ``(low, high)`` as float32 arrays."""
+    extra = int(rows) * int(n_t)
+    return (np.concatenate((np.asarray(low, np.float32), np.full(extra, -1.0, np.float32))),
+            np.concatenate((np.asarray(high, np.float32), np.full(extra, 1.0, np.float32))))
+
+
 class RoboyVecEnv:
 
     def __init__(self, robot: RoboyRobot, num_envs: int, seed: int = 0,
@@ -95,7 +112,7 @@ class RoboyVecEnv:
                  auto_reset: bool = True, integrator="euler", n_substeps: int = 1,
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
                  randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None,
-                 report_truncation: bool = False):
+                 report_truncation: bool = False, action_obs=None):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
@@ -108,6 +125,10 @@ class RoboyVecEnv:
         ``action_delay``: an int ``d`` - every step is driven by the action handed in ``d`` steps earlier in the same episode (the rest
         command, every set-point 0, before that) - or a pair ``(lo, hi)``: each env draws its own delay, again at every auto-reset.
         At most 7.  Both combine with ``randomization`` and ``tendon_obs``; ball-joint robots.
+        ``action_obs``: an int ``K`` (1..8) - the row grows by ``K n_t`` columns behind everything else: the last K actions the env was
+        handed in this episode, newest first, clamped to [-1, 1] as the step clamps them, zeros where the episode is younger (every
+        block behind a reset or an auto-reset).  What a memoryless policy needs under ``action_delay``: the commands still on
+        their way.  Never noised; ``observation_space`` grows by columns within [-1, 1]; ball-joint robots.
         ``report_truncation``: tell the episodes that ended at ``max_episode_length`` from those that reached their goal (DESIGN.md
         §17; every robot, every kernel form, every option above).  ``step()`` returns ``done`` as bools as before, and
         ``truncated()`` gives the last step's ``[N]`` bools: True where the time limit alone ended the episode (an env that
@@ -118,6 +139,7 @@ class RoboyVecEnv:
         obs_names = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
         sig = sensor_noise_sigmas(sensor_noise, obs_names)               # (bad options: before anything is allocated)
         d_lo, d_hi, ranged = action_delay_range(action_delay)
+        n_action_rows = action_obs_rows(action_obs)
         self.robot = robot
         self.num_envs = int(num_envs)
         self.sim = HipBatchSimulation(robot, num_envs, integrator=integrator, n_substeps=n_substeps,
@@ -154,7 +176,8 @@ class RoboyVecEnv:
         self.obs_dim = 3 * self.n_q
         if self.tendon_obs:
             # before anything is captured into a graph: the extended kernels replace the handle's env-step kernels from here on
-            nat.check(self.sim._lib.rb_env_obs_configure(self.sim.handle, tendon_obs_mask(self.tendon_obs), nat.fptr(self.tendon_obs_scale)))
+            self._or_close(lambda: nat.check(self.sim._lib.rb_env_obs_configure(self.sim.handle, tendon_obs_mask(self.tendon_obs),
+                                                                                nat.fptr(self.tendon_obs_scale))))
             dim = ctypes.c_int32()
             nat.check(self.sim._lib.rb_env_obs_dim(self.sim.handle, ctypes.byref(dim)))
             self.obs_dim = int(dim.value)
@@ -165,6 +188,16 @@ class RoboyVecEnv:
                 lo.append(np.full(self.n_t, b[0], np.float32))
                 hi.append(np.full(self.n_t, b[1], np.float32))
             self.observation_space = spaces.Box(low=np.concatenate(lo), high=np.concatenate(hi), dtype="float32")
+            assert self.observation_space.shape == (self.obs_dim,)
+        self.action_obs = n_action_rows
+        if self.action_obs:
+            # before anything is captured into a graph: the history kernels replace the env-step kernels from here on
+            self._or_close(lambda: self.sim.configure_action_obs(self.action_obs))
+            dim = ctypes.c_int32()
+            nat.check(self.sim._lib.rb_env_obs_dim(self.sim.handle, ctypes.byref(dim)))
+            self.obs_dim = int(dim.value)
+            lo, hi = action_obs_bounds(self.observation_space.low, self.observation_space.high, self.n_t, self.action_obs)
+            self.observation_space = spaces.Box(low=lo, high=hi, dtype="float32")
             assert self.observation_space.shape == (self.obs_dim,)
         n = self.num_envs
         self._d_act = self.sim.malloc(4 * n * self.n_t)
@@ -180,8 +213,8 @@ class RoboyVecEnv:
         self.randomization = randomization
         if randomization is not None:
             # before anything is captured into a graph: the parameter kernels replace the handle's step kernels from here on
-            self.sim.enable_params()
-            self.sim.set_param_ranges(randomization, resample_on_reset=True)
+            self._or_close(self.sim.enable_params)
+            self._or_close(lambda: self.sim.set_param_ranges(randomization, resample_on_reset=True))
         self.sensor_noise = dict(sensor_noise or {})
         self.action_delay = None if action_delay is None else ((d_lo, d_hi) if ranged else d_lo)
         self._io = bool(sig.any() or d_hi > 0)
@@ -192,12 +225,20 @@ class RoboyVecEnv:
             for c in range(4):
                 io.sigma_tendon[c] = float(sig[2 + c])
             io.delay_lo, io.delay_hi, io.resample_on_reset = d_lo, d_hi, int(ranged)
-            self.sim.configure_io(io)
+            self._or_close(lambda: self.sim.configure_io(io))
         self.report_truncation = bool(report_truncation)
         self._last_done_codes = None   # truncated(): the last torch step's int32 codes (None: the last step was not a torch step)
         if self.report_truncation:
             # before anything is captured into a graph: every env-step launch is followed by the small kernel that writes the codes
             nat.check(self.sim._lib.rb_env_done_kind_configure(self.sim.handle, 1))
+
+    def _or_close(self, configure):
+        """an option the library refuses (a joint tree asked for a ball-joint option) must not leave the simulation's handle behind"""
+        try:
+            configure()
+        except Exception:
+            self.sim.close()
+            raise
 
     # ------------------------------------------------------------------
     def reset(self):

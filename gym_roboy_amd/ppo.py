@@ -671,11 +671,14 @@ def _tendon_obs_of(env):
 
 
 def _env_io_of(env):
-    """What a checkpoint records about the conditions the policy was trained under (RoboyVecEnv's sensor_noise and action_delay):
-    not part of the observation's layout, so a checkpoint loads on any env - playback (visualize_agent) reads them back."""
+    """What a checkpoint records about the conditions the policy was trained under (RoboyVecEnv's sensor_noise, action_delay and
+    action_obs - the last of them IS part of the row's layout: K n_t more columns): playback (visualize_agent) reads them back."""
     delay = getattr(env, "action_delay", None)
-    return {"sensor_noise": {k: float(v) for k, v in dict(getattr(env, "sensor_noise", None) or {}).items()},
-            "action_delay": list(delay) if isinstance(delay, tuple) else delay}
+    out = {"sensor_noise": {k: float(v) for k, v in dict(getattr(env, "sensor_noise", None) or {}).items()},
+           "action_delay": list(delay) if isinstance(delay, tuple) else delay}
+    if getattr(env, "action_obs", 0):          # (an env without the option records what it always recorded)
+        out["action_obs"] = int(env.action_obs)
+    return out
 
 
 def _fused_kernels_apply(policy, obs_dim, act_dim):
@@ -698,7 +701,9 @@ class PPO:
                  normalize_reward=False, clip_reward=10.0, reward_norm_prime=True, bootstrap_timeouts=False):
         """fused_policy / fused_update: None = the fused MFMA kernels whenever they apply (a GPU, MlpPolicy's shape,
         dimensions the kernels support), True = insist, False = the torch path (the statement the kernels are
-        tested against).
+        tested against).  The gradient kernel takes up to 63 observation columns: an env with ``action_obs=K`` stays fused while
+        ``obs_dim`` fits (MsjRobot with length and force: 25 + 8 K columns, K <= 4) and falls back to the torch path above that
+        unless the fused kernels are insisted on.
         rollout_chains: graph mode with the fused policy step - 2 = the rollout as two independent chains of (policy step, env
         step) launches over the two halves of the batch on two streams, joined in front of GAE (the sub-range entry points of
         include/roboy_sim.h: one half's launch gaps and load / store phases lie under the other half's kernels; the results do

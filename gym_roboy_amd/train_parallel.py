@@ -44,6 +44,9 @@ def main(argv=None):
     ap.add_argument("--action-delay", default="", metavar="D | LO:HI",
                     help="steps by which every action acts late (at most 7): one number, or a range each env draws from at every "
                          "episode start, e.g. 0:3; stored in the checkpoint")
+    ap.add_argument("--action-obs", type=int, default=0, metavar="K",
+                    help="append the last K commanded actions (at most 8, newest first, zeros where the episode is younger) to the "
+                         "observation: what the policy needs to compensate --action-delay; stored in the checkpoint")
     ap.add_argument("--normalize-obs", action="store_true",
                     help="running mean / variance normalisation of the observation inside the policy kernels (what "
                          "stable-baselines calls VecNormalize); the statistics are stored in the checkpoint")
@@ -90,7 +93,7 @@ def main(argv=None):
     env = RoboyVecEnv(MsjRobot(), args.num_envs, seed=args.seed, device=local_rank,
                       env_id_offset=rank * args.num_envs, tendon_obs=tendon_obs or None, tendon_obs_scale=tendon_obs_scale or None,
                       sensor_noise=sensor_noise or None, action_delay=action_delay,
-                      report_truncation=args.bootstrap_timeouts)
+                      report_truncation=args.bootstrap_timeouts, action_obs=args.action_obs or None)
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,

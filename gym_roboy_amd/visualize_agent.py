@@ -43,16 +43,17 @@ def main(argv=None):
     tendon_obs = ck.get("tendon_obs", {}).get("channels", [])
     env_io = ck.get("env_io", {})
     sensor_noise, action_delay = env_io.get("sensor_noise") or None, env_io.get("action_delay")
+    action_obs = int(env_io.get("action_obs") or 0)
     if isinstance(action_delay, list):
         action_delay = tuple(action_delay)
-    if tendon_obs or sensor_noise or action_delay:
-        # trained with tendon channels in the observation (train_parallel --tendon-obs), sensor noise or an action delay
-        # (--sensor-noise, --action-delay): the same row, under the same conditions, comes from a RoboyVecEnv of one env, which resets
+    if tendon_obs or sensor_noise or action_delay or action_obs:
+        # trained with tendon channels in the observation (train_parallel --tendon-obs), sensor noise, an action delay or the last
+        # actions in the observation (--sensor-noise, --action-delay, --action-obs): the same row, under the same conditions, comes from a RoboyVecEnv of one env, which resets
         # itself on done and returns the reset observation.  RoboyEnv, one env stepped from the host, offers neither noise nor delay.
         from .envs.vec_env import TENDON_OBS_CHANNELS, RoboyVecEnv
         scale = dict(zip(TENDON_OBS_CHANNELS, ck["tendon_obs"]["scale"])) if tendon_obs else None
         vec = RoboyVecEnv(MsjRobot(), 1, tendon_obs=tendon_obs or None, tendon_obs_scale=scale, sensor_noise=sensor_noise,
-                          action_delay=action_delay)
+                          action_delay=action_delay, action_obs=action_obs or None)
         reset = lambda: vec.reset()[0]
 
         def step(a):

@@ -424,6 +424,47 @@ int rb_env_io_configure(rb_sim *sim, const rb_env_io_config *cfg);
 int rb_env_io_ptr(rb_sim *sim, uint32_t **d_delay, uint32_t **d_delay_draws, uint32_t **d_rows, float **d_history, int32_t *slots);
 int rb_env_io_sample_delay_dev(rb_sim *sim, const uint8_t *d_mask);
 
+/* ---- the last K commanded actions as observation columns of the fused env step (ABI 6, additive) ----
+ * Ball-joint robots (1..16 tendons) only; a joint tree is refused with RB_EUNSUPPORTED.  Opt-in per handle; composes with per-env
+ * parameters, tendon channels, sensor noise and action latency (any subset, none of them included).  What a memoryless policy
+ * needs to compensate a latency: the commands that are still on their way.
+ * Row.  With rows = K, 1 <= K <= RB_ACTION_OBS_MAX, the rows that the env-step, env-step-range and env-reset entries write are
+ *   [q, qd, goal | the tendon channels as above | K blocks of n_t action columns, the newest block first],
+ * obs_dim = 3 n_q + C n_t + K n_t floats, which is what the obs_dim query reports and the stride the range entry applies to
+ * first_env.  The first 3 n_q + C n_t columns and every other output of the step (reward, done, codes, state, statistics, goal,
+ * parameter and delay redraws, the noise counters) are bit for bit what the same handle gives without the option.
+ * Blocks.  With s the env's step counter as the step leaves it (the counter on entry + 1, or 1 behind an auto-reset), block j
+ * (0-based) holds, per component, the action row the caller HANDED IN at episode step s - 1 - j of the same episode, clamped to
+ * [-1, 1] as the step clamps it: the handed row, not the one a delay applied.  Where s - 1 - j < 1 the block is all 0.0f: the row of
+ * an env that was auto-reset carries K zero blocks, so do the env-reset rows, and the first step behind a reset reports the handed
+ * row in block 0 and zeros behind it.  Without auto_reset the counter and the history run on, as the delay's do.  The action columns
+ * are never noised and never scaled; the noise on the other columns keeps its generator blocks numbered by row position, so it
+ * gives the same noised leading columns with and without the option.
+ * Ring.  The rows come from the latency's device ring history[S][n_envs][n_t], with S the smallest power of two above
+ * max(delay_hi, K - 1) here: it exists whenever K > 0, also without an io configuration, and the io pointer query reports it
+ * (and S) then too, with NULL planes.  Every env reads only slots it wrote itself in the running episode; an auto-reset clears
+ * nothing.  The ring is indexed by the step counter: a caller that rewrites the counters (the step_num argument of the set-goal
+ * call) reads whatever those slots hold.
+ * While K > 0 the env-step entries run the history kernels (csrc/env_hist.hpp), one env per lane in the nominal or the parameter
+ * form, whatever rb_select_kernel chose, and rb_dispatch_current refuses RB_ENTRY_ENV_STEP with RB_EUNSUPPORTED.
+ * "Bit for bit" above therefore holds against a handle that runs the same step text: one with parameters, channels or an io
+ * configuration (their kernels are one env per lane too), or - without any of them - one whose env step is its env-per-lane row
+ * (RB_KERNEL_ENV_PER_LANE selected).  A bare handle under RB_KERNEL_AUTO may step with another form (octets, lane pairs), which
+ * rounds differently: against that the state agrees within the forms' parity tolerance, not to the bit - as for the two
+ * extensions above.
+ *   configure: needs rb_env_configure; 0 switches the option off (the handle's previous kernels and rows again); drains the
+ *              handle's streams and evicts the cached rollout graphs.  Callable before or after the io configure call: whichever
+ *              of the two changes S rebuilds the ring, zeroed, and leaves the io planes and counters as a fresh io configuration
+ *              does - reset the envs before stepping on.  RB_EINVAL outside 0..RB_ACTION_OBS_MAX, RB_EUNSUPPORTED for a joint tree.
+ *   rows:      K as configured (0: off).
+ *   count:     3 n_q + popcount(mask) n_t + rows n_t, without a handle or a device; -1 for unknown bits, negative counts or
+ *              rows outside 0..RB_ACTION_OBS_MAX.
+ * RB_ABI_VERSION is still 6, for the reason given above: look the configure function up before relying on these three. */
+#define RB_ACTION_OBS_MAX 8
+int rb_env_action_obs_configure(rb_sim *sim, int32_t rows);
+int rb_env_action_obs_rows(rb_sim *sim, int32_t *rows);
+int32_t rb_env_action_obs_count(int32_t n_q, int32_t n_t, uint32_t channel_mask, int32_t rows);
+
 /* ---- episode-end codes: which episodes ended at the time limit ----
  * The fused env step ends an episode when the goal is reached or when the episode is max_episode_length steps old, and reports
  * both as done = 1.  While enabled, every env-step entry (rb_env_step_dev, rb_env_step_range_dev; every kernel form, both robot
