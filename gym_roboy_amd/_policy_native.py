@@ -61,6 +61,12 @@ SIGNATURES = {
 }
 # the same tail with value bootstrapping where the done word is 2 (truncated): the same argument list
 SIGNATURES["rp_rollout_tail_boot_dev"] = SIGNATURES["rp_rollout_tail_dev"]
+# update diagnostics (approx_kl, clip_frac in the action net's spare slots): rp_ppo_grad_norm_dev's argument list; and clip + Adam
+# with the learning rate on the device, moved by the KL-adaptive rule (looked up by name: the ABI version stays 5)
+SIGNATURES["rp_ppo_grad_diag_dev"] = SIGNATURES["rp_ppo_grad_norm_dev"]
+SIGNATURES["rp_clip_adam_kl_dev"] = (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p] +
+                                     [ctypes.c_float] * 7 + [ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                             ctypes.c_void_p])
 
 
 
@@ -114,7 +120,8 @@ def pack(params, obs_dim, act_dim, train=False):
 
 
 def grad_layout(obs_dim, act_dim):
-    """{parameter name: (offset, shape)} inside the gradient vector of rp_ppo_grad_dev, plus "pi_loss" / "vf_loss"."""
+    """{parameter name: (offset, shape)} inside the gradient vector of rp_ppo_grad_dev, plus "pi_loss" / "vf_loss" and the action
+    net's "approx_kl" / "clip_frac" slots (defined after rp_ppo_grad_diag_dev only)."""
     gs = int(load().rp_grad_floats(obs_dim, act_dim)) // 2
     out = {}
     for net, n_out, base in (("pi", act_dim, 0), ("vf", 1, gs)):
@@ -126,6 +133,8 @@ def grad_layout(obs_dim, act_dim):
             out["log_std"] = (o, (act_dim,))
         o += n_out
         out["%s_loss" % net] = (o, ())
+        if net == "pi":
+            out["approx_kl"], out["clip_frac"] = (o + 1, ()), (o + 2, ())
     return out, 2 * gs
 
 

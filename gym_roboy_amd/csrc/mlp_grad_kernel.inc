@@ -5,17 +5,33 @@
 // obs_operand() (mlp_common.hpp) with the statistics norm = float[2][obs_dim]: the staged form normalises the rows once as they go to
 // LDS; the direct and the prefetched form where the raw value is read (scalar loads of the K step's pair in the forward pass, the
 // lane's column pair loaded per tile for dW1).  No LDS for the statistics: the budget of every form is what it was.
-#if RP_NORM
+// RP_DIAG 1 (the action net only; DESIGN.md §19): mlp_grad_diag_kernel / mlp_grad_norm_diag_kernel also leave the update's diagnostics
+// in the spare slots behind the loss term: x = logp - logp_old, approx_kl = sum 0.5 x^2 / B at loss + 1 - one more per-lane sum beside
+// loss_sum, under the same `live` guard, kept in the lane's pad word of the delta3 staging (row stride NJ + 1: word NJ is never staged)
+// instead of a register the tile loop has not got - and clip_frac = #{rc != ratio} / B at loss + 2, counted per tile over the wave (a
+// ballot of the live lanes the clamp acted on: the running count is wave-uniform and costs no vector register).  RP_DIAG 0 expands
+// to the text as it was.
+#if RP_NORM && RP_DIAG
+#define RP_KERNEL mlp_grad_norm_diag_kernel
+#elif RP_NORM
 #define RP_KERNEL mlp_grad_norm_kernel
-#define RP_NORM_PARAMS , const float *__restrict__ norm, float clip
+#elif RP_DIAG
+#define RP_KERNEL mlp_grad_diag_kernel
 #else
 #define RP_KERNEL mlp_grad_kernel
+#endif
+#if RP_NORM
+#define RP_NORM_PARAMS , const float *__restrict__ norm, float clip
+#else
 #define RP_NORM_PARAMS
 #endif
 template <int NET, int KX, int NJ, bool PF>
 __global__ void __launch_bounds__(256, 1)
 RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
     static_assert(!PF || KX == 1, "the prefetching form is the small instance's");
+#if RP_DIAG
+    static_assert(NET == 0, "the diagnostics are the action net's");
+#endif
     constexpr int OT = (NJ + 31) / 32;                     // 32-row tiles of the outputs
     extern __shared__ float4 lds4[];
     float *lds = reinterpret_cast<float *>(lds4);
@@ -68,6 +84,10 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc3[m][r] = 0.0f;
     float loss_sum = 0.0f;
+#if RP_DIAG
+    S3[lane * S3S + NJ] = 0.0f;                             // this lane's sum of 0.5 x^2 / B
+    int n_clipped = 0;                                      // wave-uniform: samples of this wave's tiles whose ratio the clamp changed
+#endif
 #pragma unroll
     for (int o = 0; o < HT; ++o) {
         db2[o] = 0.0f;
@@ -283,6 +303,13 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
             const float t1 = -A * ratio, t2 = -A * rc;
             const float g = live ? (t1 >= t2 ? -A : 0.0f) * ratio * a.inv_B : 0.0f;      // dL / dlogp
             if (live) loss_sum += fmaxf(t1, t2) * a.inv_B;
+#if RP_DIAG
+            {
+                const float x = lp - (PF ? PB[(obs_dim + act_dim + 1) * PFS + lane] : a.logp_old[ii]);
+                S3[lane * S3S + NJ] += live ? 0.5f * x * x * a.inv_B : 0.0f;
+                n_clipped += __builtin_popcountll(__ballot(live && rc != ratio));
+            }
+#endif
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
                 if (j < act_dim) {
@@ -486,6 +513,12 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ls += __shfl_xor(ls, off, 64);
     if (lane == 0) P[g.loss] = ls;
+#if RP_DIAG
+    float kl = S3[lane * S3S + NJ];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) kl += __shfl_xor(kl, off, 64);
+    if (lane == 0) { P[g.loss + 1] = kl; P[g.loss + 2] = float(n_clipped) * a.inv_B; }
+#endif
     // the workgroup's waves fold their partials into wave 0's (fixed order: bit-reproducible), so the reduction
     // kernel reads one partial per workgroup instead of one per wave
     __syncthreads();
@@ -499,3 +532,4 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
 #undef RP_KERNEL
 #undef RP_NORM_PARAMS
 #undef RP_NORM
+#undef RP_DIAG

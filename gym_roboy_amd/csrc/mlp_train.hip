@@ -78,10 +78,18 @@ struct TrainArgs {
 // LDS-DMA one tile ahead, double-buffered per wave; without it they are loaded when the tile starts (the indexed minibatch
 // of 8 388 608 samples: 4.4 ms against 3.5 contiguous, 29 % of the wave cycles waiting)
 // the instances of one kernel text (KX: 32-column tiles of [obs | 1]; NJ: bound of the outputs; PF: inputs by LDS-DMA - see the text):
-// without normalisation and with it
+// without normalisation and with it; and the action net's diagnostics instances of both (RP_DIAG 1: approx_kl and clip_frac)
 #define RP_NORM 0
+#define RP_DIAG 0
 #include "mlp_grad_kernel.inc"
 #define RP_NORM 1
+#define RP_DIAG 0
+#include "mlp_grad_kernel.inc"
+#define RP_NORM 0
+#define RP_DIAG 1
+#include "mlp_grad_kernel.inc"
+#define RP_NORM 1
+#define RP_DIAG 1
 #include "mlp_grad_kernel.inc"
 
 // out[k] = sum over the partials (one per workgroup, `gstride` apart)
@@ -144,11 +152,20 @@ bool grad_fits(int obs_dim, int act_dim) {
     return grad_lds_bytes(L, 0, small ? 8 : 64, small ? 1 : 2) <= 160 * 1024;
 }
 
-template <int NET, int KX, int NJ, bool PF = false>
+template <int NET, int KX, int NJ, bool PF = false, bool DIAG = false>
 int launch_grad(const TrainArgs &a, const float *norm, float clip, long blocks, size_t lds, int dev, hipStream_t stream) {
     // the opt-in above 64 KB of dynamic LDS is per kernel AND per device (mlp_common.hpp: grant_lds)
     constexpr int kernel_id = 1 + NET * 2 + (KX - 1) + (PF ? 4 : 0);
-    if (norm) {                                            // the normalising instance: a kernel of its own, a grant of its own
+    if constexpr (DIAG) {                                  // the diagnostics instances (the action net's): kernels and grants of their own
+        static_assert(NET == 0, "the diagnostics are the action net's");
+        if (norm) {
+            if (int rc = grant_lds(reinterpret_cast<const void *>(&mlp_grad_norm_diag_kernel<NET, KX, NJ, PF>), kernel_id + 27, dev, lds)) return rc;
+            hipLaunchKernelGGL((mlp_grad_norm_diag_kernel<NET, KX, NJ, PF>), dim3(unsigned(blocks)), dim3(64 * WAVES_PER_BLOCK), lds, stream, a, norm, clip);
+        } else {
+            if (int rc = grant_lds(reinterpret_cast<const void *>(&mlp_grad_diag_kernel<NET, KX, NJ, PF>), kernel_id + 18, dev, lds)) return rc;
+            hipLaunchKernelGGL((mlp_grad_diag_kernel<NET, KX, NJ, PF>), dim3(unsigned(blocks)), dim3(64 * WAVES_PER_BLOCK), lds, stream, a);
+        }
+    } else if (norm) {                                            // the normalising instance: a kernel of its own, a grant of its own
         if (int rc = grant_lds(reinterpret_cast<const void *>(&mlp_grad_norm_kernel<NET, KX, NJ, PF>), kernel_id + 9, dev, lds)) return rc;
         hipLaunchKernelGGL((mlp_grad_norm_kernel<NET, KX, NJ, PF>), dim3(unsigned(blocks)), dim3(64 * WAVES_PER_BLOCK), lds, stream, a, norm, clip);
     } else {
@@ -240,10 +257,14 @@ int rp_ppo_grad_dev(const float *d_packed_train, const float *d_obs, const float
                                 act_dim, cliprange, vf_coef, nullptr, 0.0f, d_grad, d_workspace, stream);
 }
 
-int rp_ppo_grad_norm_dev(const float *d_packed_train, const float *d_obs, const float *d_act, const float *d_adv,
-                         const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
-                         const int64_t *d_index, int64_t batch, int obs_dim, int act_dim, float cliprange, float vf_coef,
-                         const float *d_norm, float clip, float *d_grad, float *d_workspace, void *stream) {
+}  // extern "C"
+
+namespace {
+// the three entry points share their checks and their launches; diag: the action net's launch is its diagnostics instance
+int ppo_grad_launch(bool diag, const float *d_packed_train, const float *d_obs, const float *d_act, const float *d_adv,
+                    const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
+                    const int64_t *d_index, int64_t batch, int obs_dim, int act_dim, float cliprange, float vf_coef,
+                    const float *d_norm, float clip, float *d_grad, float *d_workspace, void *stream) {
     if (d_norm && !(clip > 0.0f)) return fail(RP_EINVAL, "clip must be > 0");
     if (!d_packed_train || !d_obs || !d_act || !d_adv || !d_logp_old || !d_val_old || !d_ret || !d_grad || !d_workspace)
         return fail(RP_EINVAL, "null argument");
@@ -266,7 +287,11 @@ int rp_ppo_grad_norm_dev(const float *d_packed_train, const float *d_obs, const 
     const int form = rp_grad_form(obs_dim, act_dim);                     // 2: small + prefetch, 1: small, 0: general
     const bool small = form >= 1, pf = form == 2;
     const int pf0 = obs_dim + act_dim + 4, pf1 = obs_dim + 4;           // rows of one input buffer (mlp_grad_kernel: pf_rows)
-    if (pf) rc = launch_grad<0, 1, 8, true>(a, d_norm, clip, blocks, lds_of(0, 8, 1, pf0), dev, st);
+    if (diag) {
+        if (pf) rc = launch_grad<0, 1, 8, true, true>(a, d_norm, clip, blocks, lds_of(0, 8, 1, pf0), dev, st);
+        else if (small) rc = launch_grad<0, 1, 8, false, true>(a, d_norm, clip, blocks, lds_of(0, 8, 1), dev, st);
+        else rc = launch_grad<0, 2, 64, false, true>(a, d_norm, clip, blocks, lds_of(0, 64, 2), dev, st);
+    } else if (pf) rc = launch_grad<0, 1, 8, true>(a, d_norm, clip, blocks, lds_of(0, 8, 1, pf0), dev, st);
     else if (small) rc = launch_grad<0, 1, 8>(a, d_norm, clip, blocks, lds_of(0, 8, 1), dev, st);
     else rc = launch_grad<0, 2, 64>(a, d_norm, clip, blocks, lds_of(0, 64, 2), dev, st);
     if (rc) return rc;
@@ -282,6 +307,25 @@ int rp_ppo_grad_norm_dev(const float *d_packed_train, const float *d_obs, const 
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RP_EHIP, std::string("reduce_partials_kernel: ") + hipGetErrorString(e));
     return RP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rp_ppo_grad_norm_dev(const float *d_packed_train, const float *d_obs, const float *d_act, const float *d_adv,
+                         const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
+                         const int64_t *d_index, int64_t batch, int obs_dim, int act_dim, float cliprange, float vf_coef,
+                         const float *d_norm, float clip, float *d_grad, float *d_workspace, void *stream) {
+    return ppo_grad_launch(false, d_packed_train, d_obs, d_act, d_adv, d_adv_stats, d_logp_old, d_val_old, d_ret, d_index, batch, obs_dim,
+                           act_dim, cliprange, vf_coef, d_norm, clip, d_grad, d_workspace, stream);
+}
+
+int rp_ppo_grad_diag_dev(const float *d_packed_train, const float *d_obs, const float *d_act, const float *d_adv,
+                         const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
+                         const int64_t *d_index, int64_t batch, int obs_dim, int act_dim, float cliprange, float vf_coef,
+                         const float *d_norm, float clip, float *d_grad, float *d_workspace, void *stream) {
+    return ppo_grad_launch(true, d_packed_train, d_obs, d_act, d_adv, d_adv_stats, d_logp_old, d_val_old, d_ret, d_index, batch, obs_dim,
+                           act_dim, cliprange, vf_coef, d_norm, clip, d_grad, d_workspace, stream);
 }
 
 }  // extern "C"

@@ -295,35 +295,24 @@ struct AdamArgs {
     int pi_end, vf_begin, vf_end; // the parameters' slots: [0, pi_end) and [vf_begin, vf_end); the rest of the vector (loss terms,
                                  // the value net's unused log-std slot, padding) is neither counted in the norm nor updated
 };
-__global__ void __launch_bounds__(1024)
-clip_adam_kernel(const AdamArgs a) {
-    __shared__ float sh[16];
-    auto grad = [&](int i) {
-        if (!(i < a.pi_end || (i >= a.vf_begin && i < a.vf_end))) return 0.0f;
-        float g = a.g[i] * a.gscale;
-        if (i >= a.ls_off && i < a.ls_off + a.ls_len) g -= a.ent_coef;
-        return g;
-    };
-    float ss = 0.0f;
-    for (int i = threadIdx.x; i < a.n; i += 1024) { const float g = grad(i); ss += g * g; }
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    float tot = 0.0f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) tot += sh[w];
-    // torch.nn.utils.clip_grad_norm_: coefficient max_norm / (norm + 1e-6), clamped to 1
-    const float coef = fminf(a.max_norm / (sqrtf(tot) + 1e-6f), 1.0f);
-    const float step = a.lr / a.bc1, isb2 = 1.0f / sqrtf(a.bc2);
-    for (int i = threadIdx.x; i < a.n; i += 1024) {
-        if (!(i < a.pi_end || (i >= a.vf_begin && i < a.vf_end))) continue;
-        const float g = grad(i) * coef;
-        const float m = a.beta1 * a.m[i] + (1.0f - a.beta1) * g;
-        const float v = a.beta2 * a.v[i] + (1.0f - a.beta2) * g * g;
-        a.m[i] = m; a.v[i] = v;
-        a.p[i] -= step * m / (sqrtf(v) * isb2 + a.eps);     // torch.optim.Adam: denom = sqrt(v) / sqrt(bc2) + eps
-    }
+// the learning-rate rule of clip_adam_kl_kernel (rsl_rl's "adaptive" schedule), in fp32: kl = the action net's
+// approx_kl slot of the gradient vector times gscale (the mean over the ranks after an all-reduce)
+struct KlArgs {
+    float *lr;                   // one float on the device: read by every thread, rewritten by one
+    int kl_slot;
+    float desired, factor, lr_min, lr_max;
+};
+__device__ __forceinline__ float adapt_lr(float lr, float kl, const KlArgs &k) {
+    if (kl > 2.0f * k.desired) return fmaxf(k.lr_min, lr / k.factor);
+    if (kl < 0.5f * k.desired && kl > 0.0f) return fminf(k.lr_max, lr * k.factor);
+    return lr;                                              // (every comparison is false on a NaN)
 }
+// the kernel's text, once per instance: clip_adam_kernel (the learning rate a host float: the instruction stream it has always had) and
+// clip_adam_kl_kernel, which takes the learning rate from the device and moves it by the rule in front of the step
+#define RP_KL 0
+#include "clip_adam_kernel.inc"
+#define RP_KL 1
+#include "clip_adam_kernel.inc"
 
 // the two instances of rollout_tail_kernel.inc share their argument list, their checks and their grid
 int rollout_tail_launch(decltype(&rollout_tail_kernel) kernel, const char *name, const float *d_rew_raw, const int32_t *d_done_i, const float *d_val, const float *d_last_val,
@@ -343,6 +332,36 @@ int rollout_tail_launch(decltype(&rollout_tail_kernel) kernel, const char *name,
                        d_ret, d_sums3, d_scratch, n_steps, (long long)n_envs);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RP_EHIP, std::string(name) + ": " + hipGetErrorString(e));
+    return RP_OK;
+}
+
+// rp_clip_adam_dev (d_lr == NULL: the learning rate is the host float) and rp_clip_adam_kl_dev share their checks and their arguments
+int clip_adam_launch(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int act_dim, float lr, float *d_lr,
+                     float desired_kl, float lr_factor, float lr_min, float lr_max, float beta1, float beta2, float eps, int64_t step,
+                     float max_grad_norm, float grad_scale, float ent_coef, void *stream) {
+    if (!d_params || !d_grad || !d_m || !d_v) return fail(RP_EINVAL, "null argument");
+    if (step < 1) return fail(RP_EINVAL, "step counts from 1");
+    const int64_t n = rp_grad_floats(obs_dim, act_dim);
+    if (n < 0) return RP_EUNSUPPORTED;
+    DeviceScope scope(d_params); if (scope.rc) return scope.rc;
+    AdamArgs a;
+    a.p = d_params; a.g = d_grad; a.m = d_m; a.v = d_v; a.n = int(n);
+    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+    a.bc1 = float(1.0 - pow(double(beta1), double(step))); a.bc2 = float(1.0 - pow(double(beta2), double(step)));
+    a.max_norm = max_grad_norm; a.gscale = grad_scale; a.ent_coef = ent_coef;
+    // layout of the gradient vector (mlp_common.hpp: goff_of): per net w1, b1, w2, b2, w3, b3, log_std, loss (4)
+    const GOff pi = goff_of(obs_dim, act_dim), vf = goff_of(obs_dim, 1);
+    const int gs = gstride_of(obs_dim, act_dim);
+    a.ls_off = pi.ls; a.ls_len = act_dim;
+    a.pi_end = pi.loss; a.vf_begin = gs; a.vf_end = gs + vf.ls;
+    if (d_lr) {
+        KlArgs k;
+        k.lr = d_lr; k.kl_slot = pi.loss + 1; k.desired = desired_kl; k.factor = lr_factor; k.lr_min = lr_min; k.lr_max = lr_max;
+        hipLaunchKernelGGL(clip_adam_kl_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a, k);
+    } else
+        hipLaunchKernelGGL(clip_adam_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RP_EHIP, std::string("clip_adam_kernel: ") + hipGetErrorString(e));
     return RP_OK;
 }
 
@@ -448,25 +467,19 @@ int rp_rollout_tail_boot_dev(const float *d_rew_raw, const int32_t *d_done_i, co
 int rp_clip_adam_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int act_dim, float lr,
                      float beta1, float beta2, float eps, int64_t step, float max_grad_norm, float grad_scale, float ent_coef,
                      void *stream) {
-    if (!d_params || !d_grad || !d_m || !d_v) return fail(RP_EINVAL, "null argument");
-    if (step < 1) return fail(RP_EINVAL, "step counts from 1");
-    const int64_t n = rp_grad_floats(obs_dim, act_dim);
-    if (n < 0) return RP_EUNSUPPORTED;
-    DeviceScope scope(d_params); if (scope.rc) return scope.rc;
-    AdamArgs a;
-    a.p = d_params; a.g = d_grad; a.m = d_m; a.v = d_v; a.n = int(n);
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-    a.bc1 = float(1.0 - pow(double(beta1), double(step))); a.bc2 = float(1.0 - pow(double(beta2), double(step)));
-    a.max_norm = max_grad_norm; a.gscale = grad_scale; a.ent_coef = ent_coef;
-    // layout of the gradient vector (mlp_common.hpp: goff_of): per net w1, b1, w2, b2, w3, b3, log_std, loss (4)
-    const GOff pi = goff_of(obs_dim, act_dim), vf = goff_of(obs_dim, 1);
-    const int gs = gstride_of(obs_dim, act_dim);
-    a.ls_off = pi.ls; a.ls_len = act_dim;
-    a.pi_end = pi.loss; a.vf_begin = gs; a.vf_end = gs + vf.ls;
-    hipLaunchKernelGGL(clip_adam_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(RP_EHIP, std::string("clip_adam_kernel: ") + hipGetErrorString(e));
-    return RP_OK;
+    return clip_adam_launch(d_params, d_grad, d_m, d_v, obs_dim, act_dim, lr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, beta1, beta2, eps, step,
+                            max_grad_norm, grad_scale, ent_coef, stream);
+}
+
+int rp_clip_adam_kl_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int act_dim, float *d_lr,
+                        float desired_kl, float lr_factor, float lr_min, float lr_max, float beta1, float beta2, float eps, int64_t step,
+                        float max_grad_norm, float grad_scale, float ent_coef, void *stream) {
+    if (!d_lr) return fail(RP_EINVAL, "null argument");
+    if (!(desired_kl > 0.0f)) return fail(RP_EINVAL, "desired_kl must be > 0");
+    if (!(lr_factor > 1.0f)) return fail(RP_EINVAL, "lr_factor must be > 1");
+    if (!(lr_min > 0.0f) || !(lr_min <= lr_max)) return fail(RP_EINVAL, "need 0 < lr_min <= lr_max");
+    return clip_adam_launch(d_params, d_grad, d_m, d_v, obs_dim, act_dim, 0.0f, d_lr, desired_kl, lr_factor, lr_min, lr_max, beta1, beta2,
+                            eps, step, max_grad_norm, grad_scale, ent_coef, stream);
 }
 
 }  // extern "C"

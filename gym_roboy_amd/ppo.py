@@ -26,6 +26,11 @@ is all-reduced once per minibatch.  At 262 144 envs a PPO iteration goes from 49
 11 ms + 0.11 s.  ``fused_policy=False, fused_update=False`` select the torch path, which is what
 the kernels are tested against.
 
+``diagnostics=True`` adds stable-baselines PPO2's ``approxkl`` and ``clipfrac`` of the last minibatch to what ``update()`` returns;
+``lr_schedule="adaptive"`` moves the learning rate by them, minibatch by minibatch (rsl_rl's schedule: cut above twice the desired KL,
+raised below half of it).  On the fused path the two sums come out of the action net's gradient kernel and the learning rate lives
+on the device, read and moved by the optimiser's own launch: no read-back between minibatches.
+
 ``normalize_obs=True`` keeps a running mean / variance of every observation column (``ObsNorm``: what stable-baselines calls
 ``VecNormalize``, for the observation) and feeds the networks ``clip((obs - mean) / sqrt(var + eps))``.  The fused kernels
 normalise as they fetch their operands (``rp_act_norm_dev``, ``rp_ppo_grad_norm_dev``): the rollout buffers keep the raw
@@ -34,8 +39,24 @@ with that rollout's moments after the update's last minibatch.
 """
 import math
 
+import numpy as np
 import torch
 from torch import nn
+
+LR_SCHEDULES = ("adaptive",)
+
+
+def adapt_lr(lr, kl, desired_kl, lr_factor, lr_min, lr_max):
+    """The KL-adaptive learning-rate rule in numpy float32, rounding as rp_clip_adam_kl_dev does: cut by ``lr_factor``
+    (one IEEE division) above twice the desired KL, raised by it below half of it - unless the KL is 0 or NaN - and kept inside
+    [lr_min, lr_max]."""
+    f32 = np.float32
+    lr, kl, d, f = f32(lr), f32(kl), f32(desired_kl), f32(lr_factor)
+    if kl > f32(2.0) * d:
+        return max(f32(lr_min), lr / f)
+    if kl < f32(0.5) * d and kl > f32(0.0):
+        return min(f32(lr_max), lr * f)
+    return lr
 
 
 class ObsNorm:
@@ -500,12 +521,14 @@ class FusedPolicyGrad:
 
     @torch.no_grad()
     def run(self, obs, act, adv, logp_old, val_old, ret, cliprange, vf_coef, ent_coef, index=None, adv_stats=None,
-            entropy_grad=True, norm=None):
+            entropy_grad=True, norm=None, diagnostics=False):
         """index (int64 [B], optional): minibatch sample i is row index[i] of obs / act / logp_old / val_old / ret
         (the whole rollout's tensors, no gathered copies).  adv: in minibatch order and normalised by the caller, or
         - with adv_stats (minibatch_adv_stats()) - the rollout's raw advantage, indexed like the rest and normalised
         in the kernel.  entropy_grad=False leaves the entropy bonus of the log-std to FusedAdam.step().  norm (an ``ObsNorm``,
-        optional): obs holds raw observations, normalised where the kernels fetch them (rp_ppo_grad_norm_dev)."""
+        optional): obs holds raw observations, normalised where the kernels fetch them (rp_ppo_grad_norm_dev).  diagnostics: the
+        action net's launch is its diagnostics instance (rp_ppo_grad_diag_dev), which also leaves the minibatch's approx_kl and
+        clip_frac in the vector (``diag()``)."""
         c = self._ct
         B = int(index.shape[0]) if (index is not None and adv_stats is not None) else int(adv.shape[0])
         flat = torch.cat([self._named[k].detach().reshape(-1) for k in self._pn.PARAM_ORDER] + [self._zero])
@@ -515,7 +538,14 @@ class FusedPolicyGrad:
             self._ws = torch.empty(need, device=obs.device)
         ptr = lambda t: c.c_void_p(t.data_ptr()) if t is not None else None
         stream = c.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-        if norm is None:
+        if diagnostics:
+            if norm is not None:
+                _check_norm(norm, self.obs_dim, obs.device)
+            self._pn.check(self._lib.rp_ppo_grad_diag_dev(
+                ptr(packed), ptr(obs), ptr(act), ptr(adv), ptr(adv_stats), ptr(logp_old), ptr(val_old), ptr(ret), ptr(index), B,
+                self.obs_dim, self.act_dim, float(cliprange), float(vf_coef), ptr(norm.norm) if norm is not None else None,
+                float(norm.clip) if norm is not None else 0.0, ptr(self._g), ptr(self._ws), stream))
+        elif norm is None:
             self._pn.check(self._lib.rp_ppo_grad_dev(
                 ptr(packed), ptr(obs), ptr(act), ptr(adv), ptr(adv_stats), ptr(logp_old), ptr(val_old), ptr(ret), ptr(index), B,
                 self.obs_dim, self.act_dim,
@@ -534,15 +564,24 @@ class FusedPolicyGrad:
         vf = self._g[self._layout["vf_loss"][0]]
         return pg, vf
 
+    def diag(self):
+        """(approx_kl, clip_frac) of the last ``run(diagnostics=True)``: views of the gradient vector's two slots."""
+        return self._g[self._layout["approx_kl"][0]], self._g[self._layout["clip_frac"][0]]
+
 
 class FusedAdam:
     """``clip_grad_norm_`` + ``torch.optim.Adam.step`` as ONE launch (include/roboy_policy.h: rp_clip_adam_dev) over the
     flat gradient vector of a ``FusedPolicyGrad``.  The policy's parameters become views of one flat buffer laid out
     like that vector, so the kernel updates them in place and the cross-rank average is one all-reduce of one
-    contiguous tensor.  State (first / second moments, step count) is checkpointed by ``state_dict()``."""
+    contiguous tensor.  State (first / second moments, step count) is checkpointed by ``state_dict()``.
+    schedule ({"desired_kl", "lr_factor", "lr_min", "lr_max"}, optional): the learning rate is a one-float device tensor
+    (``lr_dev``) that rp_clip_adam_kl_dev moves by the KL-adaptive rule in front of every step, from the approx_kl slot a
+    ``FusedPolicyGrad.run(diagnostics=True)`` left in the gradient vector - summed over the ranks with the rest of it."""
 
-    def __init__(self, fgrad, lr, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5):
+    def __init__(self, fgrad, lr, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5, schedule=None):
         self._f = fgrad
+        self.schedule = dict(schedule) if schedule is not None else None
+        self.lr_dev = torch.full((1,), float(np.float32(lr)), device=fgrad._g.device) if schedule is not None else None
         self.lr, self.betas, self.eps, self.max_grad_norm = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(max_grad_norm)
         g = fgrad._g
         self.params = torch.zeros_like(g)
@@ -569,9 +608,17 @@ class FusedAdam:
             scale = 1.0 / dist.get_world_size()
         self.t += 1
         ptr = lambda t: c.c_void_p(t.data_ptr())
+        stream = c.c_void_p(torch.cuda.current_stream(f._g.device).cuda_stream)
+        if self.schedule is not None:
+            k = self.schedule
+            f._pn.check(f._lib.rp_clip_adam_kl_dev(ptr(self.params), ptr(f._g), ptr(self.m), ptr(self.v), f.obs_dim, f.act_dim,
+                                                   ptr(self.lr_dev), k["desired_kl"], k["lr_factor"], k["lr_min"], k["lr_max"],
+                                                   self.betas[0], self.betas[1], self.eps, self.t, self.max_grad_norm, scale,
+                                                   float(ent_coef), stream))
+            return scale
         f._pn.check(f._lib.rp_clip_adam_dev(ptr(self.params), ptr(f._g), ptr(self.m), ptr(self.v), f.obs_dim, f.act_dim, self.lr,
                                             self.betas[0], self.betas[1], self.eps, self.t, self.max_grad_norm, scale, float(ent_coef),
-                                            c.c_void_p(torch.cuda.current_stream(f._g.device).cuda_stream)))
+                                            stream))
         return scale
 
     def state_dict(self):
@@ -698,7 +745,8 @@ class PPO:
                  learning_rate=2.5e-4, cliprange=0.2, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5,
                  device="cuda", dist=None, reward_scale=1.0, seed=0, use_graphs=False, fused_policy=None,
                  fused_update=None, rollout_chains=None, normalize_obs=False, clip_obs=10.0, obs_norm_prime=True,
-                 normalize_reward=False, clip_reward=10.0, reward_norm_prime=True, bootstrap_timeouts=False):
+                 normalize_reward=False, clip_reward=10.0, reward_norm_prime=True, bootstrap_timeouts=False,
+                 lr_schedule=None, desired_kl=0.01, lr_factor=1.5, lr_min=1e-5, lr_max=1e-2, diagnostics=False):
         """fused_policy / fused_update: None = the fused MFMA kernels whenever they apply (a GPU, MlpPolicy's shape,
         dimensions the kernels support), True = insist, False = the torch path (the statement the kernels are
         tested against).  The gradient kernel takes up to 63 observation columns: an env with ``action_obs=K`` stays fused while
@@ -719,7 +767,31 @@ class PPO:
         bootstrap_timeouts: an episode that ended at the env's time limit is not treated as if its return stopped there - GAE adds
         gamma * V(last observation before the limit) to that step's reward (``gae_boot``).  Needs an env built with
         ``report_truncation=True``.  With the fused policy step the rollout's tail is one launch (rp_rollout_tail_boot_dev), under
-        ``normalize_reward`` or not; the rollout dict gains ``"trunc"`` ([T, N] floats, 1 where the step was truncated)."""
+        ``normalize_reward`` or not; the rollout dict gains ``"trunc"`` ([T, N] floats, 1 where the step was truncated).
+        diagnostics: ``update()`` also returns ``"approx_kl"`` = mean 0.5 (logp - logp_old)^2 and ``"clip_frac"`` = the share of samples
+        whose ratio left [1 - cliprange, 1 + cliprange], of the last minibatch (stable-baselines PPO2's approxkl / clipfrac).
+        lr_schedule: None = ``learning_rate`` for the whole run; "adaptive" (implies diagnostics) = rsl_rl's schedule, applied in front
+        of every minibatch's optimiser step in float32 (``adapt_lr``): approx_kl above 2 desired_kl divides the learning rate by
+        lr_factor, approx_kl below desired_kl / 2 (and above 0) multiplies it, within [lr_min, lr_max]; with several ranks the KL is
+        their mean, so every rank takes the same decision.  ``update()`` then returns ``"lr"`` too and ``agent.learning_rate`` reads
+        the current value.  ``lr_history``: assign a list and every minibatch appends its (approx_kl, lr after the rule) - device
+        tensors on the fused path, which adds no synchronisation by it.  DESIGN.md §19."""
+        if lr_schedule is not None and lr_schedule not in LR_SCHEDULES:
+            raise ValueError("unknown lr_schedule %r: None or one of %r" % (lr_schedule, LR_SCHEDULES))
+        if not desired_kl > 0.0:
+            raise ValueError("desired_kl must be > 0")
+        if not lr_factor > 1.0:
+            raise ValueError("lr_factor must be > 1")
+        if not (lr_min > 0.0 and lr_min <= lr_max):
+            raise ValueError("need 0 < lr_min <= lr_max")
+        if lr_schedule is not None and not lr_min <= learning_rate <= lr_max:
+            raise ValueError("learning_rate %r outside [lr_min, lr_max] = [%r, %r]" % (learning_rate, lr_min, lr_max))
+        self.lr_schedule = lr_schedule
+        self.diagnostics = bool(diagnostics) or lr_schedule is not None
+        self.desired_kl, self.lr_factor, self.lr_min, self.lr_max = float(desired_kl), float(lr_factor), float(lr_min), float(lr_max)
+        self._lr0 = learning_rate
+        self._lr32 = np.float32(learning_rate)       # the scheduled learning rate of the torch path, float32 as the kernel's
+        self.lr_history = None
         self.env, self.dist, self.device = env, dist, torch.device(device)
         self._chains_arg = rollout_chains
         torch.manual_seed(seed)
@@ -744,7 +816,7 @@ class PPO:
             auto = self.device.type == "cuda" and _fused_kernels_apply(self.policy, obs_dim, act_dim)
             fused_policy = auto if fused_policy is None else fused_policy
             fused_update = auto if fused_update is None else fused_update
-        self.opt = torch.optim.Adam(self.policy.parameters(), lr=learning_rate, eps=1e-5)
+        self.opt = torch.optim.Adam(self.policy.parameters(), lr=float(self._lr32) if lr_schedule is not None else learning_rate, eps=1e-5)
         self._epoch = 0                       # update epochs so far: keys the fused path's sample order
         self._seed = int(seed) + (7919 * dist.get_rank() if multi_rank else 0)
         self._rollout_graph = None
@@ -763,7 +835,10 @@ class PPO:
             if self.device.type != "cuda":
                 raise ValueError("fused_update needs a GPU")
             self._fgrad = FusedPolicyGrad(self.policy)
-            self._fadam = FusedAdam(self._fgrad, learning_rate, eps=1e-5, max_grad_norm=max_grad_norm)
+            schedule = None
+            if lr_schedule is not None:
+                schedule = {"desired_kl": self.desired_kl, "lr_factor": self.lr_factor, "lr_min": self.lr_min, "lr_max": self.lr_max}
+            self._fadam = FusedAdam(self._fgrad, learning_rate, eps=1e-5, max_grad_norm=max_grad_norm, schedule=schedule)
         self.n_steps, self.nminibatches, self.noptepochs = n_steps, nminibatches, noptepochs
         self.gamma, self.lam, self.cliprange = gamma, lam, cliprange
         self.ent_coef, self.vf_coef, self.max_grad_norm = ent_coef, vf_coef, max_grad_norm
@@ -786,6 +861,19 @@ class PPO:
         self._rew_raw = None                  # the last rollout's raw reward (kept with normalize_reward: learn() reports it)
         self.num_timesteps = 0
         self._obs = None
+
+    @property
+    def learning_rate(self):
+        """The learning rate the next optimiser step starts from (with a schedule on the fused path: read back from the device)."""
+        if self._fgrad is not None:
+            return float(self._fadam.lr_dev.item()) if self.lr_schedule is not None else self._fadam.lr
+        return float(self.opt.param_groups[0]["lr"])
+
+    def _set_lr(self, lr):
+        self._lr32 = np.float32(lr)
+        self.opt.param_groups[0]["lr"] = float(self._lr32)
+        if self._fgrad is not None and self._fadam.lr_dev is not None:
+            self._fadam.lr_dev.fill_(float(self._lr32))
 
     def _to_tensor(self, x, dtype=torch.float32):
         return x.to(self.device, dtype) if torch.is_tensor(x) else torch.as_tensor(x, dtype=dtype, device=self.device)
@@ -1124,29 +1212,52 @@ class PPO:
         v_clip = flat["val"][idx] + (v - flat["val"][idx]).clamp(-self.cliprange, self.cliprange)
         vf = 0.5 * torch.max((v - flat["ret"][idx]) ** 2, (v_clip - flat["ret"][idx]) ** 2).mean()
         ent = d.entropy().sum(-1).mean()
-        return pg - self.ent_coef * ent + self.vf_coef * vf, pg, vf, ent
+        kl = cf = None
+        if self.diagnostics:
+            with torch.no_grad():
+                x = logp - flat["logp"][idx]
+                kl = (0.5 * x * x).mean()
+                cf = ((ratio < 1 - self.cliprange) | (ratio > 1 + self.cliprange)).to(x.dtype).mean()
+        return pg - self.ent_coef * ent + self.vf_coef * vf, pg, vf, ent, kl, cf
 
     def _minibatch_step_fused(self, flat, idx):
         """Four launches + two small reductions per minibatch: advantage statistics, the two gradient kernels (which
         gather the rollout's rows through idx and normalise the advantage per sample), clip + Adam."""
         stats = self._fgrad.minibatch_adv_stats(flat["adv"], idx)
         pg, vf = self._fgrad.run(flat["obs"], flat["act"], flat["adv"], flat["logp"], flat["val"], flat["ret"], self.cliprange,
-                                 self.vf_coef, self.ent_coef, index=idx, adv_stats=stats, entropy_grad=False, norm=self.obs_norm)
+                                 self.vf_coef, self.ent_coef, index=idx, adv_stats=stats, entropy_grad=False, norm=self.obs_norm,
+                                 diagnostics=self.diagnostics)
         scale = self._fadam.step(self.ent_coef, self.dist)          # all-reduces the gradient vector first when ranks > 1
         ent = (0.5 + 0.5 * math.log(2 * math.pi) + self.policy.log_std.detach()).sum()
         pg, vf = pg * scale, vf * scale                              # (the loss slots were summed over the ranks with the rest)
-        return pg - self.ent_coef * ent + self.vf_coef * vf, pg, vf, ent
+        kl = cf = None
+        if self.diagnostics:
+            kl, cf = (t * scale for t in self._fgrad.diag())         # (... and so were the diagnostics' slots)
+            if self.lr_history is not None and self.lr_schedule is not None:
+                self.lr_history.append((kl, self._fadam.lr_dev[0].clone()))
+        return pg - self.ent_coef * ent + self.vf_coef * vf, pg, vf, ent, kl, cf
 
     def _minibatch_step(self, flat, idx):
         if self._fgrad is not None:
             return self._minibatch_step_fused(flat, idx)
-        loss, pg, vf, ent = self._minibatch_loss(flat, idx)
+        loss, pg, vf, ent, kl, cf = self._minibatch_loss(flat, idx)
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         average_gradients(self.policy, self.dist)
         nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
+        if self.lr_schedule is not None:
+            # the rule, in front of the step of the same minibatch; with ranks on their mean KL: the same decision everywhere
+            dist = self.dist
+            if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                kl = kl.clone()
+                dist.all_reduce(kl)
+                kl = kl / dist.get_world_size()
+            self._lr32 = adapt_lr(self._lr32, kl.item(), self.desired_kl, self.lr_factor, self.lr_min, self.lr_max)
+            self.opt.param_groups[0]["lr"] = float(self._lr32)
+            if self.lr_history is not None:
+                self.lr_history.append((float(kl.item()), float(self._lr32)))
         self.opt.step()
-        return loss, pg, vf, ent
+        return loss, pg, vf, ent, kl, cf
 
     def _sample_order(self, n):
         """The epoch's sample order.  Torch path: torch.randperm (a sort of n random keys).  Fused path: a keyed bijection
@@ -1181,8 +1292,13 @@ class PPO:
             self.obs_norm.update(flat["obs"], self.dist)
         if out is None:
             return {}
-        loss, pg, vf, ent = out
-        return {"loss": loss.item(), "pg_loss": pg.item(), "vf_loss": vf.item(), "entropy": ent.item()}
+        loss, pg, vf, ent, kl, cf = out
+        stats = {"loss": loss.item(), "pg_loss": pg.item(), "vf_loss": vf.item(), "entropy": ent.item()}
+        if self.diagnostics:
+            stats["approx_kl"], stats["clip_frac"] = kl.item(), cf.item()
+        if self.lr_schedule is not None:
+            stats["lr"] = self.learning_rate
+        return stats
 
     def learn(self, total_timesteps, log=None):
         target = self.num_timesteps + total_timesteps
@@ -1200,11 +1316,15 @@ class PPO:
 
     def save(self, path):
         opt = self._fadam.state_dict() if self._fgrad is not None else self.opt.state_dict()
-        torch.save({"policy": self.policy.state_dict(), "optimizer": opt, "num_timesteps": self.num_timesteps,
-                    "epoch": self._epoch, "tendon_obs": _tendon_obs_of(self.env), "env_io": _env_io_of(self.env),
-                    "obs_norm": self.obs_norm.state_dict() if self.obs_norm is not None else None,
-                    "reward_norm": self.reward_norm.state_dict() if self.reward_norm is not None else None,
-                    "bootstrap_timeouts": self.bootstrap_timeouts}, path)
+        ck = {"policy": self.policy.state_dict(), "optimizer": opt, "num_timesteps": self.num_timesteps,
+              "epoch": self._epoch, "tendon_obs": _tendon_obs_of(self.env), "env_io": _env_io_of(self.env),
+              "obs_norm": self.obs_norm.state_dict() if self.obs_norm is not None else None,
+              "reward_norm": self.reward_norm.state_dict() if self.reward_norm is not None else None,
+              "bootstrap_timeouts": self.bootstrap_timeouts}
+        if self.lr_schedule is not None:             # (an agent without a schedule writes the checkpoint it always wrote)
+            ck["lr_schedule"] = {"kind": self.lr_schedule, "desired_kl": self.desired_kl, "lr_factor": self.lr_factor,
+                                 "lr_min": self.lr_min, "lr_max": self.lr_max, "lr": self.learning_rate}
+        torch.save(ck, path)
 
     def load(self, path):
         ck = torch.load(path, map_location=self.device)
@@ -1247,6 +1367,13 @@ class PPO:
                 raise ValueError("optimiser state of another policy layout: %d values, this policy's flat vector has %d"
                                  % (ck["optimizer"]["m"].numel(), n))
             self.opt.load_state_dict(adam_state_flat_to_torch(ck["optimizer"], self.policy, layout, self.opt.state_dict()))
+        # torch's optimiser state brings its learning rate along: a schedule continues from the checkpoint's scheduled rate where
+        # both sides have one; otherwise the agent keeps its own (also against a rate some schedule had moved)
+        sched = ck.get("lr_schedule")
+        if self.lr_schedule is not None:
+            self._set_lr(sched["lr"] if sched is not None else self._lr32)
+        elif sched is not None:
+            self.opt.param_groups[0]["lr"] = self._lr0
         self.num_timesteps = ck["num_timesteps"]
         self._epoch = int(ck.get("epoch", 0))
         if self._fused is not None:

@@ -18,6 +18,12 @@ import os
 TRAINING_STEPS_BETWEEN_BACKUPS = 100000
 
 
+def log_line(stats):
+    """An update's statistics as they are printed: four decimals, and three significant digits for the small ones (the approximate KL
+    and the learning rate of --lr-schedule, which four decimals would print as 0.0003 or 0)."""
+    return {k: float("%.3g" % v) if k in ("approx_kl", "lr") else round(v, 4) for k, v in stats.items()}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("num_envs", type=int, help="environments per GPU (the reference's num_cpu)")
@@ -58,6 +64,13 @@ def main(argv=None):
     ap.add_argument("--bootstrap-timeouts", action="store_true",
                     help="episodes that end at the time limit bootstrap the value of their last observation in GAE instead of "
                          "ending the return there (the env then reports truncation); recorded in the checkpoint")
+    ap.add_argument("--lr-schedule", default=None, choices=("adaptive",),
+                    help="adaptive = move the learning rate by the update's approximate KL, minibatch by minibatch (cut above twice "
+                         "--desired-kl, raised below half of it); the log line then shows approx_kl, clip_frac and lr; stored in the "
+                         "checkpoint")
+    ap.add_argument("--desired-kl", type=float, default=0.01, metavar="KL", help="the KL the adaptive schedule steers to (default 0.01)")
+    ap.add_argument("--lr-min", type=float, default=1e-5, metavar="LR", help="lower bound of the scheduled learning rate (default 1e-5)")
+    ap.add_argument("--lr-max", type=float, default=1e-2, metavar="LR", help="upper bound of the scheduled learning rate (default 1e-2)")
     args = ap.parse_args(argv)
     sensor_noise = {k: float(v) for k, v in (item.split("=", 1) for item in args.sensor_noise.split(",") if item)}
     action_delay = None
@@ -99,12 +112,13 @@ def main(argv=None):
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,
                 fused_update=not args.torch_policy, normalize_obs=args.normalize_obs, clip_obs=args.clip_obs,
                 normalize_reward=args.normalize_reward, clip_reward=args.clip_reward,
-                bootstrap_timeouts=args.bootstrap_timeouts)
+                bootstrap_timeouts=args.bootstrap_timeouts, lr_schedule=args.lr_schedule, desired_kl=args.desired_kl,
+                lr_min=args.lr_min, lr_max=args.lr_max)
     if os.path.exists(model_file):
         agent.load(model_file)                  # resume from the last backup
     for _ in range(args.rounds):
         agent.learn(total_timesteps=args.steps_per_round,
-                    log=(lambda s: print({k: round(v, 4) for k, v in s.items()})) if rank == 0 else None)
+                    log=(lambda s: print(log_line(s))) if rank == 0 else None)
         # episode statistics of ALL ranks' envs: the 8-double block of every rank, summed (RCCL; gloo: through the host)
         from .sharding import STAT_KEYS, allreduce_stats, summarize
         local = env.stats()

@@ -76,7 +76,8 @@ int rp_pack_train(const rp_mlp_params *host_params, int obs_dim, int act_dim, fl
 
 /* The gradient vector d_grad: two blocks of rp_grad_floats() / 2 floats, action net then value net, each in torch
  * layout  [w1 (64 x obs), b1 (64), w2 (64 x 64), b2 (64), w3 (out x 64), b3 (out), log_std (out; zero for the value
- * net), loss term, 3 spare]  padded to a multiple of 4 (out = act_dim / 1). */
+ * net), loss term, 3 spare]  padded to a multiple of 4 (out = act_dim / 1).  The action net's first two spare slots carry approx_kl
+ * and clip_frac after rp_ppo_grad_diag_dev (below), and only after it. */
 int64_t rp_grad_floats(int obs_dim, int act_dim);
 int64_t rp_ppo_workspace_floats(int obs_dim, int act_dim, int64_t batch);
 
@@ -181,6 +182,34 @@ int rp_rollout_tail_boot_dev(const float *d_rew_raw, const int32_t *d_done_i, co
                              const float *d_norm2, float clip, const double *d_shift, double gamma, double lam, double *d_ret_carry,
                              float *d_rew, float *d_done, float *d_adv, float *d_ret, double *d_sums3, double *d_scratch, int n_steps,
                              int64_t n_envs, void *stream);
+/* ---- update diagnostics and the KL-adaptive learning rate (PPO(diagnostics=True / lr_schedule="adaptive")) ----
+ * For a minibatch of B samples with x_i = logp(act_i | obs_i) - logp_old_i, ratio_i = exp(x_i) and cliprange c:
+ *     approx_kl = (1 / B) sum_i 0.5 x_i^2                     (stable-baselines PPO2's `approxkl`)
+ *     clip_frac = (1 / B) #{i: ratio_i < 1 - c or ratio_i > 1 + c}   (a sample counts when the kernel's own clamp changed its ratio)
+ * rp_ppo_grad_diag_dev is rp_ppo_grad_norm_dev - the same argument list, d_norm == NULL selecting the unnormalised kernels, the same
+ * four launches, workspace, limits and errors - whose action-net launch is a diagnostics instance of the same kernel text: it
+ * additionally leaves approx_kl at d_grad[L + 1] and clip_frac at d_grad[L + 2], L = the action net's loss slot (the first two of
+ * its three spare slots).  approx_kl is a per-lane fp32 sum under the same guard and 1 / B factor as the loss term; clip_frac is
+ * counted per wave (an integer) and scaled by 1 / B once per wave; both then take the loss term's road - one partial per wave, folded
+ * per workgroup in wave order, summed by the reduction launch - so they are bit-reproducible from call to call.  The gradient and
+ * the two loss terms are what rp_ppo_grad_norm_dev computes.  The value net's block is untouched.  The spare slots are DEFINED ONLY
+ * after this entry point: rp_ppo_grad_dev / rp_ppo_grad_norm_dev leave whatever their partial sums held there, and nothing reads it. */
+int rp_ppo_grad_diag_dev(const float *d_packed_train, const float *d_obs, const float *d_act, const float *d_adv,
+                         const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
+                         const int64_t *d_index, int64_t batch, int obs_dim, int act_dim, float cliprange, float vf_coef,
+                         const float *d_norm, float clip, float *d_grad, float *d_workspace, void *stream);
+/* rp_clip_adam_dev with the learning rate on the device (d_lr: one float, read and rewritten) and rsl_rl's "adaptive" schedule in front
+ * of the step of the same minibatch, in fp32, every thread computing it redundantly:
+ *     kl = d_grad[L + 1] * grad_scale                          (after an all-reduce: the mean over the ranks)
+ *     if      kl > 2 desired_kl               lr = max(lr_min, lr / lr_factor)      (IEEE division, one rounding)
+ *     else if kl < desired_kl / 2 and kl > 0  lr = min(lr_max, lr * lr_factor)
+ *     else                                    lr unchanged     (every comparison is false on a NaN)
+ * Adam then steps with the new lr, which one thread stores to d_lr[0] once every thread has read the old one; clip_grad_norm_ and
+ * the moments are exactly rp_clip_adam_dev's, and like it the kernel reads no other non-parameter slot and writes none.  One launch,
+ * no host read-back.  RP_EINVAL: null pointers, desired_kl not > 0, lr_factor not > 1, lr_min not > 0, lr_min > lr_max, step < 1. */
+int rp_clip_adam_kl_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int act_dim, float *d_lr,
+                        float desired_kl, float lr_factor, float lr_min, float lr_max, float beta1, float beta2, float eps, int64_t step,
+                        float max_grad_norm, float grad_scale, float ent_coef, void *stream);
 /* test hook: would a grant of lds_bytes of dynamic LDS be issued for (kernel id, device) now?  Records it. */
 int rp_debug_lds_grant_needed(int kernel_id, int dev, int64_t lds_bytes);
 /* which form of the gradient kernels rp_ppo_grad_dev launches for this policy: 2 = the small instance (obs_dim <= 31, up to 8
