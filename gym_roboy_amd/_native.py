@@ -81,6 +81,11 @@ RB_IO_MAX_DELAY = 7
 RB_ACTION_OBS_MAX = 8      # rb_env_action_obs_configure: at most this many action rows behind the observation
 RB_DONE_NONE, RB_DONE_TERMINATED, RB_DONE_TRUNCATED = 0, 1, 2      # the done words while rb_env_done_kind_configure holds
 
+# rb_env_critic_obs_configure: the blocks of a privileged critic row, in row order, with their bits; the widest row
+CRITIC_OBS_BLOCKS = ("state", "age", "params", "delay", "actions")
+RB_CRITIC_STATE, RB_CRITIC_AGE, RB_CRITIC_PARAMS, RB_CRITIC_DELAY, RB_CRITIC_ACTIONS = 1, 2, 4, 8, 16
+RB_CRITIC_OBS_MAX_DIM = 63
+
 
 class EnvIoConfig(ctypes.Structure):
     """rb_env_io_config: sensor-noise standard deviations and the action-delay range of the fused env step"""
@@ -151,6 +156,13 @@ SIGNATURES = {
     "rb_env_action_obs_count": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32]),
     "rb_env_done_kind_configure": (ctypes.c_int, [_sim, ctypes.c_int]),
     "rb_env_done_kind_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp)]),
+    "rb_env_critic_obs_configure": (ctypes.c_int, [_sim, ctypes.c_uint32]),
+    "rb_env_critic_obs_dim": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_int32)]),
+    "rb_env_critic_obs_count": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32]),
+    "rb_env_critic_obs_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp)]),
+    "rb_env_step_critic_dev": (ctypes.c_int, [_sim, _vp, _vp, _vp, _vp, _vp]),
+    "rb_env_step_range_critic_dev": (ctypes.c_int, [_sim, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

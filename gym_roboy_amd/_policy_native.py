@@ -67,7 +67,17 @@ SIGNATURES["rp_ppo_grad_diag_dev"] = SIGNATURES["rp_ppo_grad_norm_dev"]
 SIGNATURES["rp_clip_adam_kl_dev"] = (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p] +
                                      [ctypes.c_float] * 7 + [ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                              ctypes.c_void_p])
-
+# an asymmetric critic: the value net on rows, a blob and statistics of its own - two more instances of the policy-step
+# kernel, the existing gradient and optimiser kernels launched with per-net arguments (looked up by name: the ABI version stays 5)
+_vp, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+SIGNATURES["rp_act_asym_dev"] = (_i, [_vp] * 8 + [ctypes.c_int64, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, _vp, _i, _vp])
+SIGNATURES["rp_act_asym_norm_dev"] = (_i, [_vp] * 8 + [ctypes.c_int64, _i, _i, _i, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, _vp, _i,
+                                                       _vp, _vp, _f, _f, _vp])
+SIGNATURES["rp_grad_asym_floats"] = (ctypes.c_int64, [_i, _i, _i])
+SIGNATURES["rp_ppo_asym_workspace_floats"] = (ctypes.c_int64, [_i, _i, _i, ctypes.c_int64])
+SIGNATURES["rp_ppo_grad_asym_dev"] = (_i, [_vp] * 11 + [ctypes.c_int64, _i, _i, _i, _f, _f, _vp, _vp, _f, _f, _i, _vp, _vp, _vp])
+SIGNATURES["rp_clip_adam_asym_dev"] = (_i, [_vp] * 4 + [_i, _i, _i] + [_f] * 4 + [ctypes.c_int64, _f, _f, _f, _vp])
+SIGNATURES["rp_clip_adam_kl_asym_dev"] = (_i, [_vp] * 4 + [_i, _i, _i, _vp] + [_f] * 7 + [ctypes.c_int64, _f, _f, _f, _vp])
 
 
 def library_path():
@@ -98,9 +108,10 @@ def check(rc):
 PARAM_ORDER = ("pi_w1", "pi_b1", "pi_w2", "pi_b2", "pi_w3", "pi_b3", "vf_w1", "vf_b1", "vf_w2", "vf_b2", "vf_w3", "vf_b3", "log_std")
 
 
-def param_shapes(obs_dim, act_dim, hidden=64):
+def param_shapes(obs_dim, act_dim, hidden=64, critic_obs_dim=None):
+    """critic_obs_dim: the value net's input width where it is not the action net's (an asymmetric critic)"""
     return {"pi_w1": (hidden, obs_dim), "pi_b1": (hidden,), "pi_w2": (hidden, hidden), "pi_b2": (hidden,),
-            "pi_w3": (act_dim, hidden), "pi_b3": (act_dim,), "vf_w1": (hidden, obs_dim), "vf_b1": (hidden,),
+            "pi_w3": (act_dim, hidden), "pi_b3": (act_dim,), "vf_w1": (hidden, critic_obs_dim or obs_dim), "vf_b1": (hidden,),
             "vf_w2": (hidden, hidden), "vf_b2": (hidden,), "vf_w3": (1, hidden), "vf_b3": (1,), "log_std": (act_dim,)}
 
 
@@ -119,14 +130,21 @@ def pack(params, obs_dim, act_dim, train=False):
     return out
 
 
-def grad_layout(obs_dim, act_dim):
+def grad_layout(obs_dim, act_dim, critic_obs_dim=None):
     """{parameter name: (offset, shape)} inside the gradient vector of rp_ppo_grad_dev, plus "pi_loss" / "vf_loss" and the action
-    net's "approx_kl" / "clip_frac" slots (defined after rp_ppo_grad_diag_dev only)."""
+    net's "approx_kl" / "clip_frac" slots (defined after rp_ppo_grad_diag_dev only).  critic_obs_dim: the vector of
+    rp_ppo_grad_asym_dev - the value net's block behind the action net's, laid out for its own input width."""
     gs = int(load().rp_grad_floats(obs_dim, act_dim)) // 2
+    if critic_obs_dim is not None:
+        return _grad_layout(obs_dim, critic_obs_dim, act_dim, gs, int(load().rp_grad_asym_floats(obs_dim, critic_obs_dim, act_dim)))
+    return _grad_layout(obs_dim, obs_dim, act_dim, gs, 2 * gs)
+
+
+def _grad_layout(obs_dim, vf_dim, act_dim, gs, total):
     out = {}
-    for net, n_out, base in (("pi", act_dim, 0), ("vf", 1, gs)):
+    for net, n_out, base, width in (("pi", act_dim, 0, obs_dim), ("vf", 1, gs, vf_dim)):
         o = base
-        for name, shape in (("w1", (64, obs_dim)), ("b1", (64,)), ("w2", (64, 64)), ("b2", (64,)), ("w3", (n_out, 64)), ("b3", (n_out,))):
+        for name, shape in (("w1", (64, width)), ("b1", (64,)), ("w2", (64, 64)), ("b2", (64,)), ("w3", (n_out, 64)), ("b3", (n_out,))):
             out["%s_%s" % (net, name)] = (o, shape)
             o += int(np.prod(shape))
         if net == "pi":
@@ -135,7 +153,7 @@ def grad_layout(obs_dim, act_dim):
         out["%s_loss" % net] = (o, ())
         if net == "pi":
             out["approx_kl"], out["clip_frac"] = (o + 1, ()), (o + 2, ())
-    return out, 2 * gs
+    return out, total
 
 
 def gather_map(obs_dim, act_dim, train=False):
@@ -151,3 +169,23 @@ def gather_map(obs_dim, act_dim, train=False):
     m = pack(params, obs_dim, act_dim, train).astype(np.int64) - 1
     m[m < 0] = off                             # the appended zero
     return m, off
+
+
+def gather_map_asym(obs_dim, critic_obs_dim, act_dim, train=False):
+    """``gather_map`` for an asymmetric critic: two index maps (m_pi, m_vf) into concat(params in PARAM_ORDER, [0.0]) - vf_w1 there
+    is (64, critic_obs_dim) - for the blob packed for (obs_dim, act_dim), which the action net is read from, and the blob packed
+    for (critic_obs_dim, act_dim), which the value net is read from.  The first layer of the net a blob is NOT read for has another
+    width than the blob's: its operands are the appended zero."""
+    shapes = param_shapes(obs_dim, act_dim, critic_obs_dim=critic_obs_dim)
+    params, off = {}, 0
+    for k in PARAM_ORDER:
+        size = int(np.prod(shapes[k]))
+        params[k] = (np.arange(off, off + size, dtype=np.float32) + 1.0).reshape(shapes[k])
+        off += size
+    assert off < (1 << 24)                     # exact in float32
+    maps = []
+    for width, filler in ((obs_dim, "vf_w1"), (critic_obs_dim, "pi_w1")):
+        m = pack(dict(params, **{filler: np.zeros((64, width), np.float32)}), width, act_dim, train).astype(np.int64) - 1
+        m[m < 0] = off
+        maps.append(m)
+    return maps[0], maps[1], off

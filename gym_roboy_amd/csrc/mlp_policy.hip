@@ -175,10 +175,19 @@ __device__ __forceinline__ void net_forward(const float *lds, const Layout &L, i
     }
 }
 
-// the two instances of one kernel text: without normalisation and with it
+// the instances of one kernel text: without normalisation and with it; and the asymmetric critic's instances of both (RP_ASYM 1: the
+// value net on rows and a blob of its own, one net per workgroup - DESIGN.md §20)
 #define RP_NORM 0
+#define RP_ASYM 0
 #include "mlp_act_kernel.inc"
 #define RP_NORM 1
+#define RP_ASYM 0
+#include "mlp_act_kernel.inc"
+#define RP_NORM 0
+#define RP_ASYM 1
+#include "mlp_act_kernel.inc"
+#define RP_NORM 1
+#define RP_ASYM 1
 #include "mlp_act_kernel.inc"
 
 }  // namespace
@@ -273,6 +282,50 @@ int rp_act_norm_dev(const float *d_packed, const float *d_obs, float *d_act, flo
                            d_step_base, deterministic);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(RP_EHIP, std::string("mlp_act_kernel: ") + hipGetErrorString(e));
+    return RP_OK;
+}
+
+// ---- the policy step of an asymmetric critic ----
+int rp_act_asym_dev(const float *d_packed_pi, const float *d_packed_vf, const float *d_obs, const float *d_cobs, float *d_act, float *d_logp,
+                    float *d_value, float *d_mean, int64_t n, int obs_dim, int cobs_dim, int act_dim, uint64_t seed, uint64_t sample_offset,
+                    uint32_t step, const uint32_t *d_step_base, int deterministic, void *stream) {
+    return rp_act_asym_norm_dev(d_packed_pi, d_packed_vf, d_obs, d_cobs, d_act, d_logp, d_value, d_mean, n, obs_dim, cobs_dim, act_dim, seed,
+                                sample_offset, step, d_step_base, deterministic, nullptr, nullptr, 0.0f, 0.0f, stream);
+}
+
+int rp_act_asym_norm_dev(const float *d_packed_pi, const float *d_packed_vf, const float *d_obs, const float *d_cobs, float *d_act, float *d_logp,
+                         float *d_value, float *d_mean, int64_t n, int obs_dim, int cobs_dim, int act_dim, uint64_t seed,
+                         uint64_t sample_offset, uint32_t step, const uint32_t *d_step_base, int deterministic, const float *d_norm_pi,
+                         const float *d_norm_vf, float clip_pi, float clip_vf, void *stream) {
+    if ((d_norm_pi == nullptr) != (d_norm_vf == nullptr)) return fail(RP_EINVAL, "statistics for both nets, or for neither");
+    if (d_norm_pi && (!(clip_pi > 0.0f) || !(clip_vf > 0.0f))) return fail(RP_EINVAL, "clip must be > 0");
+    if (!d_packed_pi || !d_packed_vf || !d_obs || !d_cobs || !d_act || !d_logp || !d_value) return fail(RP_EINVAL, "null argument");
+    if (n < 1) return fail(RP_EINVAL, "n must be >= 1");
+    if (rp_packed_floats(obs_dim, act_dim) < 0 || rp_packed_floats(cobs_dim, act_dim) < 0) return RP_EUNSUPPORTED;
+    // dynamic LDS: the larger of the two nets' staged blocks (one net per workgroup; never above the default 64 KB: 58 KB at the limits)
+    const Layout Lp = layout_of(obs_dim, act_dim), Lv = layout_of(cobs_dim, act_dim);
+    const size_t pi_floats = size_t(HT) * Lp.k1s * 64 + HT * HT * 16 * 64 + HT * 64 + size_t(Lp.ot_pi) * (HT * 16 * 64 + 64) + 64;
+    const size_t vf_floats = size_t(HT) * Lv.k1s * 64 + HT * HT * 16 * 64 + HT * 64 + HT * 16 * 64 + 64;
+    const size_t lds = sizeof(float) * (pi_floats > vf_floats ? pi_floats : vf_floats);
+    if (lds > 64 * 1024) return fail(RP_EUNSUPPORTED, "policy too large for the LDS-resident form");
+    int dev = 0;
+    DeviceScope scope(d_packed_pi); if (scope.rc) return scope.rc; dev = scope.dev;       // the blob's device is the device of the call
+    const int n_cu = cu_count(dev);
+    const long n_tiles = (n + 63) / 64;
+    // per net: 4 waves per workgroup, persistent over the tiles; both nets together two workgroups per CU, as the symmetric step
+    long net_blocks = (n_tiles + 3) / 4;              // items of a net = its tiles
+    if (net_blocks > n_cu) net_blocks = n_cu;
+    const dim3 grid(unsigned(2 * net_blocks)), block(256);
+    if (d_norm_pi)
+        hipLaunchKernelGGL(mlp_act_asym_norm_kernel, grid, block, lds, static_cast<hipStream_t>(stream), d_packed_pi, d_obs, d_act, d_logp, d_value,
+                           d_mean, long(n), obs_dim, act_dim, seed, sample_offset, step, d_step_base, deterministic, d_packed_vf, d_cobs, cobs_dim,
+                           int(net_blocks), d_norm_pi, clip_pi, d_norm_vf, clip_vf);
+    else
+        hipLaunchKernelGGL(mlp_act_asym_kernel, grid, block, lds, static_cast<hipStream_t>(stream), d_packed_pi, d_obs, d_act, d_logp, d_value,
+                           d_mean, long(n), obs_dim, act_dim, seed, sample_offset, step, d_step_base, deterministic, d_packed_vf, d_cobs, cobs_dim,
+                           int(net_blocks));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RP_EHIP, std::string("mlp_act_asym_kernel: ") + hipGetErrorString(e));
     return RP_OK;
 }
 

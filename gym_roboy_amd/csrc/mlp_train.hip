@@ -260,50 +260,65 @@ int rp_ppo_grad_dev(const float *d_packed_train, const float *d_obs, const float
 }  // extern "C"
 
 namespace {
-// the three entry points share their checks and their launches; diag: the action net's launch is its diagnostics instance
-int ppo_grad_launch(bool diag, const float *d_packed_train, const float *d_obs, const float *d_act, const float *d_adv,
-                    const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
-                    const int64_t *d_index, int64_t batch, int obs_dim, int act_dim, float cliprange, float vf_coef,
-                    const float *d_norm, float clip, float *d_grad, float *d_workspace, void *stream) {
-    if (d_norm && !(clip > 0.0f)) return fail(RP_EINVAL, "clip must be > 0");
-    if (!d_packed_train || !d_obs || !d_act || !d_adv || !d_logp_old || !d_val_old || !d_ret || !d_grad || !d_workspace)
-        return fail(RP_EINVAL, "null argument");
-    if (batch < 1) return fail(RP_EINVAL, "batch must be >= 1");
-    if (rp_train_packed_floats(obs_dim, act_dim) < 0) return RP_EUNSUPPORTED;
-    int dev = 0;
-    DeviceScope scope(d_packed_train); if (scope.rc) return scope.rc; dev = scope.dev;      // the blob's device is the device of the call
+// One net's launch: the instance its OWN input width asks for (rp_grad_form: small + prefetch, small, general), with the arguments
+// `a` as they stand (a.packed, a.obs, a.obs_dim, a.gstride and a.partials are that net's).  diag: the action net's diagnostics instance.
+template <int NET>
+int grad_net_launch(bool diag, const TrainArgs &a, const float *d_norm, float clip, long blocks, int dev, hipStream_t st) {
+    const int obs_dim = a.obs_dim, act_dim = a.act_dim;
     const Layout L = layout_of(obs_dim, act_dim);
-    const int gs = gstride_of(obs_dim, act_dim);
-    const long blocks = grad_blocks(batch), waves = blocks * WAVES_PER_BLOCK;
-    auto lds_of = [&](int net, int nj, int kx_inst, int pf_rows = 0) { return grad_lds_bytes(L, net, nj, kx_inst, pf_rows); };
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    TrainArgs a;
-    a.packed = d_packed_train; a.obs = d_obs; a.act = d_act; a.adv = d_adv; a.adv_stats = d_adv_stats; a.logp_old = d_logp_old; a.val_old = d_val_old;
-    a.ret = d_ret; a.index = reinterpret_cast<const long long *>(d_index); a.B = batch; a.obs_dim = obs_dim; a.act_dim = act_dim; a.gstride = gs; a.cliprange = cliprange;
-    a.vf_coef = vf_coef; a.inv_B = 1.0f / float(batch);
-    const int kx = (obs_dim + 1 + 31) / 32;
-    int rc;
-    a.partials = d_workspace;
+    auto lds_of = [&](int nj, int kx_inst, int pf_rows = 0) { return grad_lds_bytes(L, NET, nj, kx_inst, pf_rows); };
     const int form = rp_grad_form(obs_dim, act_dim);                     // 2: small + prefetch, 1: small, 0: general
     const bool small = form >= 1, pf = form == 2;
-    const int pf0 = obs_dim + act_dim + 4, pf1 = obs_dim + 4;           // rows of one input buffer (mlp_grad_kernel: pf_rows)
-    if (diag) {
-        if (pf) rc = launch_grad<0, 1, 8, true, true>(a, d_norm, clip, blocks, lds_of(0, 8, 1, pf0), dev, st);
-        else if (small) rc = launch_grad<0, 1, 8, false, true>(a, d_norm, clip, blocks, lds_of(0, 8, 1), dev, st);
-        else rc = launch_grad<0, 2, 64, false, true>(a, d_norm, clip, blocks, lds_of(0, 64, 2), dev, st);
-    } else if (pf) rc = launch_grad<0, 1, 8, true>(a, d_norm, clip, blocks, lds_of(0, 8, 1, pf0), dev, st);
-    else if (small) rc = launch_grad<0, 1, 8>(a, d_norm, clip, blocks, lds_of(0, 8, 1), dev, st);
-    else rc = launch_grad<0, 2, 64>(a, d_norm, clip, blocks, lds_of(0, 64, 2), dev, st);
-    if (rc) return rc;
-    a.partials = d_workspace + waves * gs;
-    if (pf) rc = launch_grad<1, 1, 8, true>(a, d_norm, clip, blocks, lds_of(1, 8, 1, pf1), dev, st);
-    else if (small) rc = launch_grad<1, 1, 8>(a, d_norm, clip, blocks, lds_of(1, 8, 1), dev, st);
-    else rc = launch_grad<1, 2, 8>(a, d_norm, clip, blocks, lds_of(1, 8, 2), dev, st);
-    if (rc) return rc;
-    for (int net = 0; net < 2; ++net) {
-        hipLaunchKernelGGL(reduce_partials_kernel, dim3((gs + 255) / 256), dim3(256), 0, st, d_workspace + net * waves * gs,
-                           int(blocks), WAVES_PER_BLOCK * gs, gs, d_grad + net * gs);       // one folded partial per workgroup
+    const int pf_rows = obs_dim + (NET == 0 ? act_dim : 0) + 4;         // rows of one input buffer (mlp_grad_kernel: pf_rows)
+    if constexpr (NET == 0) {
+        if (diag) {
+            if (pf) return launch_grad<0, 1, 8, true, true>(a, d_norm, clip, blocks, lds_of(8, 1, pf_rows), dev, st);
+            if (small) return launch_grad<0, 1, 8, false, true>(a, d_norm, clip, blocks, lds_of(8, 1), dev, st);
+            return launch_grad<0, 2, 64, false, true>(a, d_norm, clip, blocks, lds_of(64, 2), dev, st);
+        }
+        if (pf) return launch_grad<0, 1, 8, true>(a, d_norm, clip, blocks, lds_of(8, 1, pf_rows), dev, st);
+        if (small) return launch_grad<0, 1, 8>(a, d_norm, clip, blocks, lds_of(8, 1), dev, st);
+        return launch_grad<0, 2, 64>(a, d_norm, clip, blocks, lds_of(64, 2), dev, st);
+    } else {
+        if (pf) return launch_grad<1, 1, 8, true>(a, d_norm, clip, blocks, lds_of(8, 1, pf_rows), dev, st);
+        if (small) return launch_grad<1, 1, 8>(a, d_norm, clip, blocks, lds_of(8, 1), dev, st);
+        return launch_grad<1, 2, 8>(a, d_norm, clip, blocks, lds_of(8, 2), dev, st);
     }
+}
+
+// Every gradient entry point: its checks and its launches.  The symmetric ones hand both nets the same blob, rows, width and
+// statistics; rp_ppo_grad_asym_dev gives the value net (NET 1) its own - the kernels are the same instances either way.  The gradient
+// vector: the action net's block at stride gstride_of(obs_dim, act_dim), then the value net's at gstride_of(cobs_dim, act_dim); the
+// workspace: the action net's partials, then the value net's.  diag: the action net's launch is its diagnostics instance.
+int ppo_grad_launch(bool diag, const float *d_packed_pi, const float *d_packed_vf, const float *d_obs, const float *d_cobs, const float *d_act,
+                    const float *d_adv, const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
+                    const int64_t *d_index, int64_t batch, int obs_dim, int cobs_dim, int act_dim, float cliprange, float vf_coef,
+                    const float *d_norm_pi, float clip_pi, const float *d_norm_vf, float clip_vf, float *d_grad, float *d_workspace, void *stream) {
+    if ((d_norm_pi && !(clip_pi > 0.0f)) || (d_norm_vf && !(clip_vf > 0.0f))) return fail(RP_EINVAL, "clip must be > 0");
+    if (!d_packed_pi || !d_packed_vf || !d_obs || !d_cobs || !d_act || !d_adv || !d_logp_old || !d_val_old || !d_ret || !d_grad || !d_workspace)
+        return fail(RP_EINVAL, "null argument");
+    if (batch < 1) return fail(RP_EINVAL, "batch must be >= 1");
+    if (rp_train_packed_floats(obs_dim, act_dim) < 0 || rp_train_packed_floats(cobs_dim, act_dim) < 0) return RP_EUNSUPPORTED;
+    int dev = 0;
+    DeviceScope scope(d_packed_pi); if (scope.rc) return scope.rc; dev = scope.dev;         // the blob's device is the device of the call
+    const int gs_pi = gstride_of(obs_dim, act_dim), gs_vf = gstride_of(cobs_dim, act_dim);
+    const long blocks = grad_blocks(batch), waves = blocks * WAVES_PER_BLOCK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    TrainArgs a;
+    a.packed = d_packed_pi; a.obs = d_obs; a.act = d_act; a.adv = d_adv; a.adv_stats = d_adv_stats; a.logp_old = d_logp_old; a.val_old = d_val_old;
+    a.ret = d_ret; a.index = reinterpret_cast<const long long *>(d_index); a.B = batch; a.obs_dim = obs_dim; a.act_dim = act_dim; a.gstride = gs_pi; a.cliprange = cliprange;
+    a.vf_coef = vf_coef; a.inv_B = 1.0f / float(batch);
+    a.partials = d_workspace;
+    int rc = grad_net_launch<0>(diag, a, d_norm_pi, clip_pi, blocks, dev, st);
+    if (rc) return rc;
+    a.packed = d_packed_vf; a.obs = d_cobs; a.obs_dim = cobs_dim; a.gstride = gs_vf;
+    a.partials = d_workspace + waves * gs_pi;
+    rc = grad_net_launch<1>(false, a, d_norm_vf, clip_vf, blocks, dev, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((gs_pi + 255) / 256), dim3(256), 0, st, d_workspace, int(blocks), WAVES_PER_BLOCK * gs_pi, gs_pi,
+                       d_grad);                                                             // one folded partial per workgroup
+    hipLaunchKernelGGL(reduce_partials_kernel, dim3((gs_vf + 255) / 256), dim3(256), 0, st, d_workspace + waves * gs_pi, int(blocks),
+                       WAVES_PER_BLOCK * gs_vf, gs_vf, d_grad + gs_pi);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RP_EHIP, std::string("reduce_partials_kernel: ") + hipGetErrorString(e));
     return RP_OK;
@@ -316,16 +331,38 @@ int rp_ppo_grad_norm_dev(const float *d_packed_train, const float *d_obs, const 
                          const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
                          const int64_t *d_index, int64_t batch, int obs_dim, int act_dim, float cliprange, float vf_coef,
                          const float *d_norm, float clip, float *d_grad, float *d_workspace, void *stream) {
-    return ppo_grad_launch(false, d_packed_train, d_obs, d_act, d_adv, d_adv_stats, d_logp_old, d_val_old, d_ret, d_index, batch, obs_dim,
-                           act_dim, cliprange, vf_coef, d_norm, clip, d_grad, d_workspace, stream);
+    return ppo_grad_launch(false, d_packed_train, d_packed_train, d_obs, d_obs, d_act, d_adv, d_adv_stats, d_logp_old, d_val_old, d_ret, d_index, batch,
+                           obs_dim, obs_dim, act_dim, cliprange, vf_coef, d_norm, clip, d_norm, clip, d_grad, d_workspace, stream);
 }
 
 int rp_ppo_grad_diag_dev(const float *d_packed_train, const float *d_obs, const float *d_act, const float *d_adv,
                          const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
                          const int64_t *d_index, int64_t batch, int obs_dim, int act_dim, float cliprange, float vf_coef,
                          const float *d_norm, float clip, float *d_grad, float *d_workspace, void *stream) {
-    return ppo_grad_launch(true, d_packed_train, d_obs, d_act, d_adv, d_adv_stats, d_logp_old, d_val_old, d_ret, d_index, batch, obs_dim,
-                           act_dim, cliprange, vf_coef, d_norm, clip, d_grad, d_workspace, stream);
+    return ppo_grad_launch(true, d_packed_train, d_packed_train, d_obs, d_obs, d_act, d_adv, d_adv_stats, d_logp_old, d_val_old, d_ret, d_index, batch,
+                           obs_dim, obs_dim, act_dim, cliprange, vf_coef, d_norm, clip, d_norm, clip, d_grad, d_workspace, stream);
+}
+
+// ---- the asymmetric critic: the value net on rows and a blob of its own, the same kernel instances ----
+int64_t rp_grad_asym_floats(int obs_dim, int cobs_dim, int act_dim) {
+    if (rp_train_packed_floats(obs_dim, act_dim) < 0 || rp_train_packed_floats(cobs_dim, act_dim) < 0) return RP_EUNSUPPORTED;
+    return int64_t(gstride_of(obs_dim, act_dim)) + int64_t(gstride_of(cobs_dim, act_dim));
+}
+
+int64_t rp_ppo_asym_workspace_floats(int obs_dim, int cobs_dim, int act_dim, int64_t batch) {
+    const int64_t n = rp_grad_asym_floats(obs_dim, cobs_dim, act_dim);
+    if (n < 0 || batch < 1) return RP_EUNSUPPORTED;
+    return grad_blocks(batch) * WAVES_PER_BLOCK * n;
+}
+
+int rp_ppo_grad_asym_dev(const float *d_packed_pi, const float *d_packed_vf, const float *d_obs, const float *d_cobs, const float *d_act,
+                         const float *d_adv, const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
+                         const int64_t *d_index, int64_t batch, int obs_dim, int cobs_dim, int act_dim, float cliprange, float vf_coef,
+                         const float *d_norm_pi, const float *d_norm_vf, float clip_pi, float clip_vf, int diag, float *d_grad,
+                         float *d_workspace, void *stream) {
+    if ((d_norm_pi == nullptr) != (d_norm_vf == nullptr)) return fail(RP_EINVAL, "statistics for both nets, or for neither");
+    return ppo_grad_launch(diag != 0, d_packed_pi, d_packed_vf, d_obs, d_cobs, d_act, d_adv, d_adv_stats, d_logp_old, d_val_old, d_ret, d_index,
+                           batch, obs_dim, cobs_dim, act_dim, cliprange, vf_coef, d_norm_pi, clip_pi, d_norm_vf, clip_vf, d_grad, d_workspace, stream);
 }
 
 }  // extern "C"

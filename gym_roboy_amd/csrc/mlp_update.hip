@@ -335,13 +335,14 @@ int rollout_tail_launch(decltype(&rollout_tail_kernel) kernel, const char *name,
     return RP_OK;
 }
 
-// rp_clip_adam_dev (d_lr == NULL: the learning rate is the host float) and rp_clip_adam_kl_dev share their checks and their arguments
-int clip_adam_launch(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int act_dim, float lr, float *d_lr,
+// rp_clip_adam_dev (d_lr == NULL: the learning rate is the host float) and rp_clip_adam_kl_dev share their checks and their arguments;
+// so do their asymmetric forms, whose value net's block is laid out for cobs_dim input columns (the symmetric ones: cobs_dim = obs_dim)
+int clip_adam_launch(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int cobs_dim, int act_dim, float lr, float *d_lr,
                      float desired_kl, float lr_factor, float lr_min, float lr_max, float beta1, float beta2, float eps, int64_t step,
                      float max_grad_norm, float grad_scale, float ent_coef, void *stream) {
     if (!d_params || !d_grad || !d_m || !d_v) return fail(RP_EINVAL, "null argument");
     if (step < 1) return fail(RP_EINVAL, "step counts from 1");
-    const int64_t n = rp_grad_floats(obs_dim, act_dim);
+    const int64_t n = rp_grad_asym_floats(obs_dim, cobs_dim, act_dim);
     if (n < 0) return RP_EUNSUPPORTED;
     DeviceScope scope(d_params); if (scope.rc) return scope.rc;
     AdamArgs a;
@@ -350,7 +351,7 @@ int clip_adam_launch(float *d_params, const float *d_grad, float *d_m, float *d_
     a.bc1 = float(1.0 - pow(double(beta1), double(step))); a.bc2 = float(1.0 - pow(double(beta2), double(step)));
     a.max_norm = max_grad_norm; a.gscale = grad_scale; a.ent_coef = ent_coef;
     // layout of the gradient vector (mlp_common.hpp: goff_of): per net w1, b1, w2, b2, w3, b3, log_std, loss (4)
-    const GOff pi = goff_of(obs_dim, act_dim), vf = goff_of(obs_dim, 1);
+    const GOff pi = goff_of(obs_dim, act_dim), vf = goff_of(cobs_dim, 1);
     const int gs = gstride_of(obs_dim, act_dim);
     a.ls_off = pi.ls; a.ls_len = act_dim;
     a.pi_end = pi.loss; a.vf_begin = gs; a.vf_end = gs + vf.ls;
@@ -467,18 +468,32 @@ int rp_rollout_tail_boot_dev(const float *d_rew_raw, const int32_t *d_done_i, co
 int rp_clip_adam_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int act_dim, float lr,
                      float beta1, float beta2, float eps, int64_t step, float max_grad_norm, float grad_scale, float ent_coef,
                      void *stream) {
-    return clip_adam_launch(d_params, d_grad, d_m, d_v, obs_dim, act_dim, lr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, beta1, beta2, eps, step,
+    return clip_adam_launch(d_params, d_grad, d_m, d_v, obs_dim, obs_dim, act_dim, lr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, beta1, beta2, eps, step,
+                            max_grad_norm, grad_scale, ent_coef, stream);
+}
+
+int rp_clip_adam_asym_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int cobs_dim, int act_dim, float lr,
+                          float beta1, float beta2, float eps, int64_t step, float max_grad_norm, float grad_scale, float ent_coef,
+                          void *stream) {
+    return clip_adam_launch(d_params, d_grad, d_m, d_v, obs_dim, cobs_dim, act_dim, lr, nullptr, 0.0f, 0.0f, 0.0f, 0.0f, beta1, beta2, eps, step,
                             max_grad_norm, grad_scale, ent_coef, stream);
 }
 
 int rp_clip_adam_kl_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int act_dim, float *d_lr,
                         float desired_kl, float lr_factor, float lr_min, float lr_max, float beta1, float beta2, float eps, int64_t step,
                         float max_grad_norm, float grad_scale, float ent_coef, void *stream) {
+    return rp_clip_adam_kl_asym_dev(d_params, d_grad, d_m, d_v, obs_dim, obs_dim, act_dim, d_lr, desired_kl, lr_factor, lr_min, lr_max, beta1,
+                                    beta2, eps, step, max_grad_norm, grad_scale, ent_coef, stream);
+}
+
+int rp_clip_adam_kl_asym_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int cobs_dim, int act_dim, float *d_lr,
+                             float desired_kl, float lr_factor, float lr_min, float lr_max, float beta1, float beta2, float eps, int64_t step,
+                             float max_grad_norm, float grad_scale, float ent_coef, void *stream) {
     if (!d_lr) return fail(RP_EINVAL, "null argument");
     if (!(desired_kl > 0.0f)) return fail(RP_EINVAL, "desired_kl must be > 0");
     if (!(lr_factor > 1.0f)) return fail(RP_EINVAL, "lr_factor must be > 1");
     if (!(lr_min > 0.0f) || !(lr_min <= lr_max)) return fail(RP_EINVAL, "need 0 < lr_min <= lr_max");
-    return clip_adam_launch(d_params, d_grad, d_m, d_v, obs_dim, act_dim, 0.0f, d_lr, desired_kl, lr_factor, lr_min, lr_max, beta1, beta2,
+    return clip_adam_launch(d_params, d_grad, d_m, d_v, obs_dim, cobs_dim, act_dim, 0.0f, d_lr, desired_kl, lr_factor, lr_min, lr_max, beta1, beta2,
                             eps, step, max_grad_norm, grad_scale, ent_coef, stream);
 }
 

@@ -50,6 +50,7 @@
 #include "env_obs.hpp"                // tendon channels in the fused env step's observation (rb_env_obs_*)
 #include "env_io.hpp"                 // per-env action latency and sensor noise in the fused env step (rb_env_io_*)
 #include "env_hist.hpp"               // the last K commanded actions as observation columns (rb_env_action_obs_*)
+#include "env_critic.hpp"             // privileged critic rows behind the fused env step (rb_env_critic_obs_*)
 
 namespace {
 
@@ -574,6 +575,13 @@ struct rb_sim {
     // Planes [n] each: the goal counter d_ep_cnt[2n + i] as of env i's last episode end, and the last step's codes
     bool done_kind = false;
     uint32_t *d_done_seen = nullptr, *d_done_kind = nullptr;
+    // privileged critic rows (env_critic.hpp; rb_env_critic_obs_*): while the mask is set, every env-step launch and every reset is
+    // followed by critic_rows_kernel over its range.  critic_dim: the row width the mask had when it was configured; the plane [n][Dc]
+    int critic_mask = 0, critic_dim = 0;
+    float *d_critic = nullptr;
+    int critic_width() const {
+        return rbc::row_dim(critic_mask, n_q, params ? n_params : 0, hist_rows * n_t);
+    }
 };
 
 namespace {
@@ -961,6 +969,31 @@ int extension_launch(rb_sim *s, int entry, const Launch &L) {
     if (entry == ENTRY_ENV) return euler ? ext_env_launch<0>(s, L) : ext_env_launch<1>(s, L);
     return fail(RB_EUNSUPPORTED, "per-env parameters have no fused-rollout kernel (rb_params_disable first)");
 }
+// ---- privileged critic rows (env_critic.hpp): one launch behind an env step or a reset, over the envs [i0, i0 + cnt) ----
+// the options the mask was configured against are still there, and the row is as wide as the plane's
+int critic_check(rb_sim *s) {
+    const int m = s->critic_mask;
+    if ((m & rbc::PARAMS && !s->params) || (m & rbc::DELAY && !s->io) || (m & rbc::ACTIONS && !s->hist_rows) || s->critic_width() != s->critic_dim)
+        return fail(RB_EINVAL, "an option the critic rows depend on changed after rb_env_critic_obs_configure: configure the rows again");
+    return RB_OK;
+}
+// d_obs: the observation rows the step has just written (null: no rows, zero action blocks); out: rows [n][Dc] of the whole batch
+int critic_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float *d_obs, float *out) {
+    if (cnt <= 0) return RB_OK;
+    rbc::CriticArgs a;
+    a.q = s->d_q; a.qd = s->d_qd; a.goal = s->d_goal; a.step_num = s->d_step_num;
+    a.par = s->params ? s->d_params : nullptr;
+    a.delay = s->io ? s->d_io_delay : nullptr;
+    a.obs = d_obs; a.out = out;
+    a.n = s->n; a.i0 = i0; a.i1 = i0 + cnt;
+    a.max_len = float(s->env.max_len);
+    a.nq = s->n_q; a.np = s->params ? s->n_params : 0; a.mask = s->critic_mask; a.dc = s->critic_dim;
+    a.od = s->obs_dim(); a.act_cols = s->hist_rows * s->n_t; a.lead = a.od - a.act_cols;
+    a.flat = reinterpret_cast<uintptr_t>(out) % 16 == 0 ? 1 : 0;
+    hipLaunchKernelGGL(rbc::critic_rows_kernel, dim3(blocks_for(cnt, 256)), dim3(256), sizeof(float) * 256 * size_t(a.dc), stream, a);
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
 void params_free(rb_sim *s) {
     (void)hipFree(s->d_params); (void)hipFree(s->d_param_draws); (void)hipFree(s->d_param_ranges);
     s->d_params = nullptr; s->d_param_draws = nullptr; s->d_param_ranges = nullptr;
@@ -1154,6 +1187,7 @@ void rb_destroy(rb_sim *s) {
     params_free(s);
     io_free(s);
     (void)hipFree(s->d_done_seen); (void)hipFree(s->d_done_kind);
+    (void)hipFree(s->d_critic);
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1639,6 +1673,11 @@ int rb_env_reset_dev(rb_sim *s, float *d_obs) {
         hipLaunchKernelGGL(rbh::hist_zero_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, od, od - s->hist_rows * s->n_t, long(s->n));
         RB_HIP(hipGetLastError());
     }
+    if (s->critic_mask) {                     // the privileged rows of the reset state, behind every kernel that wrote the rows above
+        int rc = critic_check(s);
+        if (rc == RB_OK) rc = critic_launch(s, 0, s->n, s->stream, d_obs, s->d_critic);
+        if (rc) return rc;
+    }
     return RB_OK;
 }
 
@@ -1787,6 +1826,52 @@ int rb_env_done_kind_ptr(rb_sim *s, uint32_t **d_kind) {
     return RB_OK;
 }
 
+// ---- privileged critic rows behind the fused env step (env_critic.hpp) ----
+int32_t rb_env_critic_obs_count(int32_t n_q, int32_t n_t, uint32_t mask, int32_t n_params, int32_t action_rows) {
+    if (n_q < 0 || n_t < 0 || n_params < 0 || action_rows < 0 || (mask & ~uint32_t(RB_CRITIC_ALL))) return -1;
+    return mask ? rbc::row_dim(int(mask | RB_CRITIC_STATE), n_q, n_params, action_rows * n_t) : 0;
+}
+int rb_env_critic_obs_configure(rb_sim *s, uint32_t mask) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
+    if (mask & ~uint32_t(RB_CRITIC_ALL))
+        return fail(RB_EINVAL, "unknown bits in the critic-row mask (RB_CRITIC_STATE | _AGE | _PARAMS | _DELAY | _ACTIONS)");
+    if (s->tree && mask)
+        return fail(RB_EUNSUPPORTED, "critic rows are built for ball-joint robots (1-16 tendons); joint trees have none");
+    if (mask) mask |= RB_CRITIC_STATE;       // (always selected)
+    if (mask & RB_CRITIC_PARAMS && !s->params) return fail(RB_EINVAL, "critic rows: RB_CRITIC_PARAMS needs per-env parameters (rb_params_enable first)");
+    if (mask & RB_CRITIC_DELAY && !s->io) return fail(RB_EINVAL, "critic rows: RB_CRITIC_DELAY needs an io configuration (rb_env_io_configure first)");
+    if (mask & RB_CRITIC_ACTIONS && !s->hist_rows)
+        return fail(RB_EINVAL, "critic rows: RB_CRITIC_ACTIONS needs action rows in the observation (rb_env_action_obs_configure first)");
+    const int dim = rbc::row_dim(int(mask), s->n_q, s->params ? s->n_params : 0, s->hist_rows * s->n_t);
+    if (dim > RB_CRITIC_OBS_MAX_DIM)
+        return fail(RB_EINVAL, "critic rows: " + std::to_string(dim) + " columns, at most RB_CRITIC_OBS_MAX_DIM = 63 (the PPO gradient kernels' input limit)");
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);                       // nothing in flight may still write rows of the old width
+    if (rc) return rc;
+    rc = drop_graphs(s);
+    if (rc) return rc;
+    (void)hipFree(s->d_critic);
+    s->d_critic = nullptr; s->critic_mask = 0; s->critic_dim = 0;
+    if (!mask) return RB_OK;
+    const size_t bytes = sizeof(float) * size_t(s->n) * size_t(dim);
+    RB_HIP(hipMalloc(&s->d_critic, bytes));
+    s->critic_mask = int(mask); s->critic_dim = dim;
+    // the rows of the envs as they stand (no observation rows at hand: zero action blocks, as behind a reset)
+    return critic_launch(s, 0, s->n, s->stream, nullptr, s->d_critic);
+}
+int rb_env_critic_obs_dim(rb_sim *s, int32_t *dim) {
+    if (check(s) || !dim) return fail(RB_EINVAL, "null argument");
+    *dim = s->critic_dim;
+    return RB_OK;
+}
+int rb_env_critic_obs_ptr(rb_sim *s, float **d_rows) {
+    if (check(s) || !d_rows) return fail(RB_EINVAL, "null argument");
+    if (!s->critic_mask) return fail(RB_EINVAL, "critic rows are not enabled (rb_env_critic_obs_configure)");
+    *d_rows = s->d_critic;
+    return RB_OK;
+}
+
 int rb_env_obs_dim(rb_sim *s, int32_t *obs_dim) {
     if (check(s) || !obs_dim) return fail(RB_EINVAL, "null argument");
     *obs_dim = s->obs_dim();
@@ -1809,11 +1894,19 @@ int rb_env_set_goal(rb_sim *s, const float *goal_q, const uint32_t *step_num) {
 
 // RoboyEnv.step for envs [i0, i0 + cnt) on `stream`; the array arguments are those of the whole batch (the launchers apply the
 // offsets).  Sub-ranges: every ball-joint form and the joint trees' one-wave-per-64-envs form (Row::ranges).
-static int env_step_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done) {
+// d_cobs: where the range's critic rows go while rb_env_critic_obs_configure holds (null: the handle's plane)
+static int env_step_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done,
+                           float *d_cobs = nullptr) {
+    if (s->critic_mask) { const int rc = critic_check(s); if (rc) return rc; }       // (before anything is enqueued)
     Launch L;
     L.i0 = i0; L.cnt = cnt; L.stream = stream; L.act = d_act; L.obs = d_obs; L.reward = d_reward; L.done = d_done;
     const int rc = dispatch(s, ENTRY_ENV, L);
-    if (rc != RB_OK || !s->done_kind) return rc;
+    if (rc != RB_OK) return rc;
+    if (s->critic_mask) {                     // the privileged rows of the range, from the planes as the step left them (same stream)
+        const int rc2 = critic_launch(s, i0, cnt, stream, d_obs, d_cobs ? d_cobs : s->d_critic);
+        if (rc2) return rc2;
+    }
+    if (!s->done_kind) return RB_OK;
     // the episode-end codes of the range, behind whichever kernel stepped it (same stream)
     hipLaunchKernelGGL(done_kind_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, d_done, s->d_ep_cnt + 2 * size_t(s->n),
                        s->d_done_seen, s->d_done_kind, i0, i0 + cnt);
@@ -1827,6 +1920,17 @@ int rb_env_step_dev(rb_sim *s, const float *d_act, float *d_obs, float *d_reward
     if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
     if (!s->tree && reinterpret_cast<uintptr_t>(d_act) % 16) return fail(RB_EINVAL, "action slab must be 16-byte aligned");
     int rc = env_step_launch(s, 0, s->n, s->stream, d_act, d_obs, d_reward, d_done);
+    if (rc == RB_OK) s->env_steps += double(s->n);
+    return rc;
+}
+
+int rb_env_step_critic_dev(rb_sim *s, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done, float *d_cobs) {
+    if (check(s) || !d_act || !d_obs || !d_reward || !d_done || !d_cobs) return fail(RB_EINVAL, "null argument");
+    RB_HIP(hipSetDevice(s->device));
+    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
+    if (!s->critic_mask) return fail(RB_EINVAL, "critic rows are not enabled (rb_env_critic_obs_configure)");
+    if (reinterpret_cast<uintptr_t>(d_act) % 16) return fail(RB_EINVAL, "action slab must be 16-byte aligned");
+    int rc = env_step_launch(s, 0, s->n, s->stream, d_act, d_obs, d_reward, d_done, d_cobs);
     if (rc == RB_OK) s->env_steps += double(s->n);
     return rc;
 }
@@ -1846,6 +1950,20 @@ int rb_env_step_range_dev(rb_sim *s, int64_t first_env, int64_t n_envs, void *hi
     hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
     CallStreamScope scope(s, st);          // a first call captured on the caller's stream defers the run-time builds (capturing())
     int rc = env_step_launch(s, long(first_env), long(n_envs), st, d_act, d_obs, d_reward, d_done);
+    if (rc == RB_OK) { s->env_steps += double(n_envs); rc = note_caller_stream(s, st); }
+    return rc;
+}
+int rb_env_step_range_critic_dev(rb_sim *s, int64_t first_env, int64_t n_envs, void *hip_stream, const float *d_act, float *d_obs, float *d_reward,
+                                 uint32_t *d_done, float *d_cobs) {
+    if (check(s) || !d_act || !d_obs || !d_reward || !d_done || !d_cobs) return fail(RB_EINVAL, "null argument");
+    RB_HIP(hipSetDevice(s->device));
+    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
+    if (!s->critic_mask) return fail(RB_EINVAL, "critic rows are not enabled (rb_env_critic_obs_configure)");
+    if (reinterpret_cast<uintptr_t>(d_act) % 16) return fail(RB_EINVAL, "action slab must be 16-byte aligned");
+    if (range_ok(s, first_env, n_envs)) return RB_EINVAL;
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+    CallStreamScope scope(s, st);          // a first call captured on the caller's stream defers the run-time builds (capturing())
+    int rc = env_step_launch(s, long(first_env), long(n_envs), st, d_act, d_obs, d_reward, d_done, d_cobs);
     if (rc == RB_OK) { s->env_steps += double(n_envs); rc = note_caller_stream(s, st); }
     return rc;
 }

@@ -104,6 +104,35 @@ def action_obs_bounds(low, high, n_t: int, rows: int):
             np.concatenate((np.asarray(high, np.float32), np.full(extra, 1.0, np.float32))))
 
 
+def critic_obs_spec(critic_obs, n_q: int, n_t: int, randomization: bool = False, action_delay=None, action_obs=None):
+    """Block names of a privileged critic row (``RoboyVecEnv(critic_obs=...)``; any order, no repeats; ``"state"`` is always part of the
+    row, named or not) -> ``(names in row order, the mask of rb_env_critic_obs_configure, Dc)`` for a ball-joint robot with ``n_q``
+    joints and ``n_t`` tendons.  None or an empty list: ``((), 0, 0)``.  ``ValueError`` for an unknown name, for a block whose option
+    the env does not have (``params``: ``randomization``; ``delay``: an ``action_delay`` above 0; ``actions``: ``action_obs=K``) and
+    for a row wider than 63 columns, the PPO gradient kernels' input limit."""
+    if critic_obs is None:
+        return (), 0, 0
+    names = [critic_obs] if isinstance(critic_obs, str) else list(critic_obs)
+    unknown = [c for c in names if c not in nat.CRITIC_OBS_BLOCKS]
+    if unknown or len(set(names)) != len(names):
+        raise ValueError("critic_obs takes distinct names out of %s, got %r" % (nat.CRITIC_OBS_BLOCKS, critic_obs))
+    if not names:
+        return (), 0, 0
+    rows = action_obs_rows(action_obs)
+    needs = {"params": (bool(randomization), "randomization"), "delay": (action_delay_range(action_delay)[1] > 0, "an action_delay above 0"),
+             "actions": (rows > 0, "action_obs=K")}
+    for c in names:
+        if c in needs and not needs[c][0]:
+            raise ValueError("critic_obs: %r needs %s" % (c, needs[c][1]))
+    names = tuple(c for c in nat.CRITIC_OBS_BLOCKS if c == "state" or c in names)
+    width = {"state": 3 * n_q, "age": 1, "params": 2 * n_t + 4, "delay": 1, "actions": rows * n_t}
+    dim = sum(width[c] for c in names)
+    if dim > nat.RB_CRITIC_OBS_MAX_DIM:
+        raise ValueError("critic_obs: %s is %d columns wide, at most %d (the PPO gradient kernels' input limit)"
+                         % (names, dim, nat.RB_CRITIC_OBS_MAX_DIM))
+    return names, sum(1 << nat.CRITIC_OBS_BLOCKS.index(c) for c in names), dim
+
+
 class RoboyVecEnv:
 
     def __init__(self, robot: RoboyRobot, num_envs: int, seed: int = 0,
@@ -112,7 +141,7 @@ class RoboyVecEnv:
                  auto_reset: bool = True, integrator="euler", n_substeps: int = 1,
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
                  randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None,
-                 report_truncation: bool = False, action_obs=None):
+                 report_truncation: bool = False, action_obs=None, critic_obs=None):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
@@ -135,7 +164,15 @@ class RoboyVecEnv:
         reaches its goal on its last permitted step is not truncated).  ``step_dev`` and ``step_range_dev`` then leave episode-end
         CODES in ``d_done`` - 0 not done, 1 terminated, 2 truncated (``_native.RB_DONE_*``) - so ``done != 0`` is the done of an env
         without the option.  The ``info`` dicts stay empty: a dict per env does not scale to 262 144 envs, so there is no
-        ``TimeLimit.truncated`` key."""
+        ``TimeLimit.truncated`` key.
+        ``critic_obs``: block names out of ``("state", "age", "params", "delay", "actions")`` - every step and reset also writes a
+        PRIVILEGED row per env for an asymmetric critic (ball-joint robots): ``[q, qd, goal`` exactly as the planes hold
+        them, without noise ``| episode age / max_episode_length | the env's parameters (needs randomization) | its action delay (needs
+        action_delay) | the K action blocks of the observation (needs action_obs)]``, ``critic_obs_dim`` columns, ``"state"``
+        always.  The row belongs to the observation row returned with it (an auto-reset env shows its reset state, new goal and redrawn
+        parameters).  ``critic_obs()`` returns the last rows; observations, rewards, dones and statistics are unchanged."""
+        desc = robot.get_description()
+        crit_names, crit_mask, crit_dim = critic_obs_spec(critic_obs, desc.n_q, desc.n_t, randomization is not None, action_delay, action_obs)
         obs_names = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
         sig = sensor_noise_sigmas(sensor_noise, obs_names)               # (bad options: before anything is allocated)
         d_lo, d_hi, ranged = action_delay_range(action_delay)
@@ -231,6 +268,16 @@ class RoboyVecEnv:
         if self.report_truncation:
             # before anything is captured into a graph: every env-step launch is followed by the small kernel that writes the codes
             nat.check(self.sim._lib.rb_env_done_kind_configure(self.sim.handle, 1))
+        self.critic_obs_names, self.critic_obs_dim = crit_names, 0
+        self._last_cobs = None         # critic_obs(): the last torch step's rows (None: the handle's plane holds the last rows)
+        if crit_mask:
+            # after the options the row reads, before anything is captured into a graph: every env-step launch and reset is followed
+            # by the small kernel that writes the rows
+            self._or_close(lambda: nat.check(self.sim._lib.rb_env_critic_obs_configure(self.sim.handle, crit_mask)))
+            dim = ctypes.c_int32()
+            nat.check(self.sim._lib.rb_env_critic_obs_dim(self.sim.handle, ctypes.byref(dim)))
+            self.critic_obs_dim = int(dim.value)
+            assert self.critic_obs_dim == crit_dim
 
     def _or_close(self, configure):
         """an option the library refuses (a joint tree asked for a ball-joint option) must not leave the simulation's handle behind"""
@@ -245,6 +292,7 @@ class RoboyVecEnv:
         if self.randomization is not None:
             self.sim.sample_params()
         nat.check(self.sim._lib.rb_env_reset_dev(self.sim.handle, ctypes.c_void_p(self._d_obs)))
+        self._last_cobs = None
         self.sim.synchronize()
         return self.sim.download(self._d_obs, (self.num_envs, self.obs_dim))
 
@@ -269,28 +317,42 @@ class RoboyVecEnv:
         self.step_dev(self._d_act, self._d_obs, self._d_rew, self._d_done)
         self._last_actions = _IN_SLAB
         self._last_done_codes = None
+        self._last_cobs = None
         self.sim.synchronize()
         n = self.num_envs
         return (self.sim.download(self._d_obs, (n, self.obs_dim)),
                 self.sim.download(self._d_rew, (n,)),
                 self.sim.download(self._d_done, (n,), np.uint32).astype(bool), [{}] * n)
 
-    def step_dev(self, d_act, d_obs, d_rew, d_done):
+    def step_dev(self, d_act, d_obs, d_rew, d_done, d_cobs=None):
         """Raw device-pointer form: asynchronous on the simulation's stream.  ``d_obs`` holds ``num_envs * obs_dim`` floats.
-        ``d_done``: ``num_envs`` uint32, 0 / 1 - with ``report_truncation`` the codes 0 / 1 (terminated) / 2 (truncated)."""
-        nat.check(self.sim._lib.rb_env_step_dev(
-            self.sim.handle, ctypes.c_void_p(d_act), ctypes.c_void_p(d_obs),
-            ctypes.c_void_p(d_rew), ctypes.c_void_p(d_done)))
+        ``d_done``: ``num_envs`` uint32, 0 / 1 - with ``report_truncation`` the codes 0 / 1 (terminated) / 2 (truncated).
+        ``d_cobs`` (needs ``critic_obs``): ``num_envs * critic_obs_dim`` floats that take the step's critic rows; None leaves them
+        in the handle's own plane (``critic_obs()``)."""
+        if d_cobs is None:
+            nat.check(self.sim._lib.rb_env_step_dev(
+                self.sim.handle, ctypes.c_void_p(d_act), ctypes.c_void_p(d_obs),
+                ctypes.c_void_p(d_rew), ctypes.c_void_p(d_done)))
+        else:
+            nat.check(self.sim._lib.rb_env_step_critic_dev(
+                self.sim.handle, ctypes.c_void_p(d_act), ctypes.c_void_p(d_obs),
+                ctypes.c_void_p(d_rew), ctypes.c_void_p(d_done), ctypes.c_void_p(d_cobs)))
 
-    def step_range_dev(self, first_env, n_envs, stream_ptr, d_act, d_obs, d_rew, d_done):
+    def step_range_dev(self, first_env, n_envs, stream_ptr, d_act, d_obs, d_rew, d_done, d_cobs=None):
         """``step_dev`` for envs [first_env, first_env + n_envs) on the stream ``stream_ptr`` (None: the simulation's); the
         pointers are those of the WHOLE batch's arrays.  Disjoint ranges may be stepped concurrently on different streams
         (``rb_env_step_range_dev``): how a closed-loop caller overlaps one half's launch gaps and memory phases with the
         other half's arithmetic (``gym_roboy_amd/ppo.py``).  With ``report_truncation`` the range's ``d_done`` words are the codes
-        0 / 1 / 2 as ``step_dev`` leaves them, written on the same stream."""
-        nat.check(self.sim._lib.rb_env_step_range_dev(
-            self.sim.handle, int(first_env), int(n_envs), ctypes.c_void_p(int(stream_ptr or 0)), ctypes.c_void_p(d_act),
-            ctypes.c_void_p(d_obs), ctypes.c_void_p(d_rew), ctypes.c_void_p(d_done)))
+        0 / 1 / 2 as ``step_dev`` leaves them, written on the same stream.  ``d_cobs`` (needs ``critic_obs``): the WHOLE batch's
+        ``[num_envs, critic_obs_dim]`` array, whose rows of the range are written on the same stream; None: the handle's plane."""
+        if d_cobs is None:
+            nat.check(self.sim._lib.rb_env_step_range_dev(
+                self.sim.handle, int(first_env), int(n_envs), ctypes.c_void_p(int(stream_ptr or 0)), ctypes.c_void_p(d_act),
+                ctypes.c_void_p(d_obs), ctypes.c_void_p(d_rew), ctypes.c_void_p(d_done)))
+        else:
+            nat.check(self.sim._lib.rb_env_step_range_critic_dev(
+                self.sim.handle, int(first_env), int(n_envs), ctypes.c_void_p(int(stream_ptr or 0)), ctypes.c_void_p(d_act),
+                ctypes.c_void_p(d_obs), ctypes.c_void_p(d_rew), ctypes.c_void_p(d_done), ctypes.c_void_p(d_cobs)))
 
     def range_capable(self) -> bool:
         return self.sim.range_capable(env_layer=True)
@@ -306,7 +368,9 @@ class RoboyVecEnv:
         obs = torch.empty((n, self.obs_dim), dtype=torch.float32, device=actions.device)
         rew = torch.empty((n,), dtype=torch.float32, device=actions.device)
         done = torch.empty((n,), dtype=torch.int32, device=actions.device)
-        self.step_dev(actions.data_ptr(), obs.data_ptr(), rew.data_ptr(), done.data_ptr())
+        cobs = torch.empty((n, self.critic_obs_dim), dtype=torch.float32, device=actions.device) if self.critic_obs_dim else None
+        self.step_dev(actions.data_ptr(), obs.data_ptr(), rew.data_ptr(), done.data_ptr(), None if cobs is None else cobs.data_ptr())
+        self._last_cobs = cobs
         self._last_actions = actions
         self._last_done_codes = done if self.report_truncation else None
         return obs, rew, done.bool(), [{}] * n
@@ -323,6 +387,19 @@ class RoboyVecEnv:
         nat.check(self.sim._lib.rb_env_done_kind_ptr(self.sim.handle, ctypes.byref(kind)))
         self.sim.synchronize()
         return self.sim.download(kind.value, (self.num_envs,), np.uint32) == nat.RB_DONE_TRUNCATED
+
+    def critic_obs(self):
+        """``[N, critic_obs_dim]``: the privileged rows that belong to the observation rows last returned.  A CUDA tensor after a torch
+        step; otherwise numpy, read from the handle's plane after a synchronisation (a reset, a numpy step, ``step_dev`` /
+        ``step_range_dev`` without ``d_cobs``).  Needs ``critic_obs``."""
+        if not self.critic_obs_dim:
+            raise RuntimeError("this RoboyVecEnv writes no critic rows (critic_obs=None)")
+        if self._last_cobs is not None:
+            return self._last_cobs
+        rows = ctypes.c_void_p()
+        nat.check(self.sim._lib.rb_env_critic_obs_ptr(self.sim.handle, ctypes.byref(rows)))
+        self.sim.synchronize()
+        return self.sim.download(rows.value, (self.num_envs, self.critic_obs_dim))
 
     def tendon_state(self, actions=None):
         """Per-tendon state of every env at its current state (``HipBatchSimulation.tendon_state``), the set-points formed

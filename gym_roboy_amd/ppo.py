@@ -325,13 +325,18 @@ class MlpPolicy(nn.Module):
     diagonal Gaussian with a state-independent log-std (stable_baselines' MlpPolicy)."""
 
     obs_norm = None        # an ObsNorm once set_obs_norm() was called: a plain attribute, not a parameter or buffer
+    critic_obs_norm = None  # ... and the critic rows' own, where the critic is asymmetric
 
-    def __init__(self, obs_dim: int, act_dim: int, hidden: int = 64):
+    def __init__(self, obs_dim: int, act_dim: int, hidden: int = 64, critic_obs_dim=None):
+        """critic_obs_dim: an asymmetric critic - the value net's first layer takes that many columns and ``value()``
+        reads the env's privileged critic rows, not the observation; only the action net is ever deployed.  None: both nets read the
+        observation.  The ``state_dict`` keys are the same either way."""
         super().__init__()
-        def mlp(out):
-            return nn.Sequential(nn.Linear(obs_dim, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh(),
+        self.critic_obs_dim = None if critic_obs_dim is None else int(critic_obs_dim)
+        def mlp(out, width=obs_dim):
+            return nn.Sequential(nn.Linear(width, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh(),
                                  nn.Linear(hidden, out))
-        self.pi, self.vf = mlp(act_dim), mlp(1)
+        self.pi, self.vf = mlp(act_dim), mlp(1, obs_dim if critic_obs_dim is None else self.critic_obs_dim)
         self.log_std = nn.Parameter(torch.zeros(act_dim))
         for m in self.modules():
             if isinstance(m, nn.Linear):
@@ -340,10 +345,12 @@ class MlpPolicy(nn.Module):
         nn.init.orthogonal_(self.pi[-1].weight, 0.01)
         nn.init.orthogonal_(self.vf[-1].weight, 1.0)
 
-    def set_obs_norm(self, obs_norm):
+    def set_obs_norm(self, obs_norm, critic_obs_norm=None):
         """An ``ObsNorm`` (or None): ``dist()`` and ``value()`` then see the normalised observation.  The statistics are neither
-        parameters nor buffers of the module (``state_dict()`` keeps its keys) and carry no gradient."""
+        parameters nor buffers of the module (``state_dict()`` keeps its keys) and carry no gradient.  critic_obs_norm: a second
+        ``ObsNorm`` over the critic rows, which is what ``value()`` of an asymmetric critic applies."""
         self.obs_norm = obs_norm
+        self.critic_obs_norm = critic_obs_norm
         return self
 
     def dist(self, obs):
@@ -353,15 +360,20 @@ class MlpPolicy(nn.Module):
         return torch.distributions.Normal(self.pi(obs), self.log_std.exp(), validate_args=False)
 
     def value(self, obs):
-        if self.obs_norm is not None:
-            obs = self.obs_norm.apply(obs)
+        """The value of observation rows - of CRITIC rows [.., critic_obs_dim] where the critic is asymmetric."""
+        norm = self.obs_norm if self.critic_obs_dim is None else self.critic_obs_norm
+        if norm is not None:
+            obs = norm.apply(obs)
         return self.vf(obs).squeeze(-1)
 
     @torch.no_grad()
-    def act(self, obs, deterministic=False):
+    def act(self, obs, deterministic=False, cobs=None):
+        """cobs: the critic rows that belong to ``obs`` (an asymmetric critic needs them for the value; None there: no value)"""
         d = self.dist(obs)
         # mean + std * eps rather than d.sample(): torch.normal(mean, std) checks std >= 0 on the host
         a = d.mean if deterministic else d.mean + d.stddev * torch.randn_like(d.mean)
+        if self.critic_obs_dim is not None:
+            return a, d.log_prob(a).sum(-1), (self.value(cobs) if cobs is not None else None)
         return a, d.log_prob(a).sum(-1), self.value(obs)
 
 
@@ -435,8 +447,15 @@ class FusedPolicyStep:
         if policy.pi[0].out_features != 64 or len(policy.pi) != 5:
             raise ValueError("the fused policy step is built for MlpPolicy's two hidden layers of 64 units")
         dev = policy.log_std.device
-        m, total = pn.gather_map(self.obs_dim, self.act_dim)
-        self._map = torch.from_numpy(m).to(dev)
+        # an asymmetric critic: the value net reads rows of its own width through a blob of its own
+        self.cobs_dim = getattr(policy, "critic_obs_dim", None)
+        if self.cobs_dim is None:
+            m, total = pn.gather_map(self.obs_dim, self.act_dim)
+            self._map = torch.from_numpy(m).to(dev)
+        else:
+            m_pi, m_vf, total = pn.gather_map_asym(self.obs_dim, self.cobs_dim, self.act_dim)
+            self._map = torch.from_numpy(np.concatenate((m_pi, m_vf))).to(dev)
+            self._split = int(m_pi.shape[0])
         self._zero = torch.zeros(1, device=dev)
         self.seed = int(seed)
 
@@ -447,18 +466,36 @@ class FusedPolicyStep:
 
     @torch.no_grad()
     def pack(self):
+        """The operand blob - with an asymmetric critic both blobs, one behind the other (one gather)"""
         flat = torch.cat([p.detach().reshape(-1) for p in self._params()] + [self._zero])
         return flat[self._map]
 
     @torch.no_grad()
     def act_into(self, obs, act, logp, val, step=0, packed=None, mean=None, sample_offset=0, deterministic=False,
-                 step_base=None, norm=None):
+                 step_base=None, norm=None, cobs=None, cnorm=None):
         """obs [n, obs_dim] (contiguous, fp32, cuda) -> act [n, act_dim], logp [n], val [n] (preallocated).
-        norm (an ``ObsNorm``, optional): the observation is normalised as the kernel fetches it (rp_act_norm_dev)."""
+        norm (an ``ObsNorm``, optional): the observation is normalised as the kernel fetches it (rp_act_norm_dev).
+        cobs [n, critic_obs_dim] and cnorm: the critic rows and their statistics, for a policy with an asymmetric critic
+        (rp_act_asym_dev / rp_act_asym_norm_dev)."""
         c = self._ct
         packed = self.pack() if packed is None else packed
         ptr = lambda t: c.c_void_p(t.data_ptr()) if t is not None else None
         stream = c.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        if self.cobs_dim is not None:
+            if cobs is None or tuple(cobs.shape) != (obs.shape[0], self.cobs_dim) or not cobs.is_contiguous() or cobs.dtype != torch.float32:
+                raise ValueError("an asymmetric critic needs contiguous float32 critic rows [%d, %d]" % (obs.shape[0], self.cobs_dim))
+            if (norm is None) != (cnorm is None):
+                raise ValueError("statistics for both nets, or for neither")
+            blobs = (ptr(packed[:self._split]), ptr(packed[self._split:]))
+            head = blobs + (ptr(obs), ptr(cobs), ptr(act), ptr(logp), ptr(val), ptr(mean), int(obs.shape[0]), self.obs_dim, self.cobs_dim,
+                            self.act_dim, self.seed, int(sample_offset), int(step), ptr(step_base), int(bool(deterministic)))
+            if norm is None:
+                self._pn.check(self._lib.rp_act_asym_dev(*head, stream))
+            else:
+                _check_norm(norm, self.obs_dim, obs.device)
+                _check_norm(cnorm, self.cobs_dim, obs.device)
+                self._pn.check(self._lib.rp_act_asym_norm_dev(*head, ptr(norm.norm), ptr(cnorm.norm), float(norm.clip), float(cnorm.clip), stream))
+            return packed
         if norm is None:
             self._pn.check(self._lib.rp_act_dev(
                 ptr(packed), ptr(obs), ptr(act), ptr(logp), ptr(val), ptr(mean), int(obs.shape[0]), self.obs_dim, self.act_dim,
@@ -490,10 +527,16 @@ class FusedPolicyGrad:
                 or policy.vf[0].out_features != 64 or policy.vf[2].out_features != 64):
             raise ValueError("the fused PPO gradient is built for MlpPolicy's two hidden layers of 64 units")
         dev = policy.log_std.device
-        m, _ = pn.gather_map(self.obs_dim, self.act_dim, train=True)
-        self._map = torch.from_numpy(m).to(dev)
+        self.cobs_dim = getattr(policy, "critic_obs_dim", None)      # an asymmetric critic: the value net's own width, blob and rows
+        if self.cobs_dim is None:
+            m, _ = pn.gather_map(self.obs_dim, self.act_dim, train=True)
+            self._map = torch.from_numpy(m).to(dev)
+        else:
+            m_pi, m_vf, _ = pn.gather_map_asym(self.obs_dim, self.cobs_dim, self.act_dim, train=True)
+            self._map = torch.from_numpy(np.concatenate((m_pi, m_vf))).to(dev)
+            self._split = int(m_pi.shape[0])
         self._zero = torch.zeros(1, device=dev)
-        layout, n = pn.grad_layout(self.obs_dim, self.act_dim)
+        layout, n = pn.grad_layout(self.obs_dim, self.act_dim, self.cobs_dim)
         self._g = torch.zeros(n, device=dev)
         self._layout = layout
         pi, vf = policy.pi, policy.vf
@@ -521,24 +564,42 @@ class FusedPolicyGrad:
 
     @torch.no_grad()
     def run(self, obs, act, adv, logp_old, val_old, ret, cliprange, vf_coef, ent_coef, index=None, adv_stats=None,
-            entropy_grad=True, norm=None, diagnostics=False):
+            entropy_grad=True, norm=None, diagnostics=False, cobs=None, cnorm=None):
         """index (int64 [B], optional): minibatch sample i is row index[i] of obs / act / logp_old / val_old / ret
         (the whole rollout's tensors, no gathered copies).  adv: in minibatch order and normalised by the caller, or
         - with adv_stats (minibatch_adv_stats()) - the rollout's raw advantage, indexed like the rest and normalised
         in the kernel.  entropy_grad=False leaves the entropy bonus of the log-std to FusedAdam.step().  norm (an ``ObsNorm``,
         optional): obs holds raw observations, normalised where the kernels fetch them (rp_ppo_grad_norm_dev).  diagnostics: the
         action net's launch is its diagnostics instance (rp_ppo_grad_diag_dev), which also leaves the minibatch's approx_kl and
-        clip_frac in the vector (``diag()``)."""
+        clip_frac in the vector (``diag()``).  cobs, cnorm: the critic rows (indexed like obs) and their statistics, for a policy
+        with an asymmetric critic (rp_ppo_grad_asym_dev: the same kernels, the value net's launch on its own arguments)."""
         c = self._ct
         B = int(index.shape[0]) if (index is not None and adv_stats is not None) else int(adv.shape[0])
         flat = torch.cat([self._named[k].detach().reshape(-1) for k in self._pn.PARAM_ORDER] + [self._zero])
         packed = flat[self._map]
-        need = int(self._lib.rp_ppo_workspace_floats(self.obs_dim, self.act_dim, B))
+        if self.cobs_dim is None:
+            need = int(self._lib.rp_ppo_workspace_floats(self.obs_dim, self.act_dim, B))
+        else:
+            need = int(self._lib.rp_ppo_asym_workspace_floats(self.obs_dim, self.cobs_dim, self.act_dim, B))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, device=obs.device)
         ptr = lambda t: c.c_void_p(t.data_ptr()) if t is not None else None
         stream = c.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-        if diagnostics:
+        if self.cobs_dim is not None:
+            if cobs is None or cobs.shape[-1] != self.cobs_dim or not cobs.is_contiguous() or cobs.dtype != torch.float32:
+                raise ValueError("an asymmetric critic needs contiguous float32 critic rows of %d columns" % self.cobs_dim)
+            if (norm is None) != (cnorm is None):
+                raise ValueError("statistics for both nets, or for neither")
+            if norm is not None:
+                _check_norm(norm, self.obs_dim, obs.device)
+                _check_norm(cnorm, self.cobs_dim, obs.device)
+            self._pn.check(self._lib.rp_ppo_grad_asym_dev(
+                ptr(packed[:self._split]), ptr(packed[self._split:]), ptr(obs), ptr(cobs), ptr(act), ptr(adv), ptr(adv_stats), ptr(logp_old),
+                ptr(val_old), ptr(ret), ptr(index), B, self.obs_dim, self.cobs_dim, self.act_dim, float(cliprange), float(vf_coef),
+                ptr(norm.norm) if norm is not None else None, ptr(cnorm.norm) if cnorm is not None else None,
+                float(norm.clip) if norm is not None else 0.0, float(cnorm.clip) if cnorm is not None else 0.0, int(bool(diagnostics)),
+                ptr(self._g), ptr(self._ws), stream))
+        elif diagnostics:
             if norm is not None:
                 _check_norm(norm, self.obs_dim, obs.device)
             self._pn.check(self._lib.rp_ppo_grad_diag_dev(
@@ -609,6 +670,18 @@ class FusedAdam:
         self.t += 1
         ptr = lambda t: c.c_void_p(t.data_ptr())
         stream = c.c_void_p(torch.cuda.current_stream(f._g.device).cuda_stream)
+        if f.cobs_dim is not None:              # an asymmetric critic: the same kernels over its longer vector
+            if self.schedule is not None:
+                k = self.schedule
+                f._pn.check(f._lib.rp_clip_adam_kl_asym_dev(ptr(self.params), ptr(f._g), ptr(self.m), ptr(self.v), f.obs_dim, f.cobs_dim,
+                                                            f.act_dim, ptr(self.lr_dev), k["desired_kl"], k["lr_factor"], k["lr_min"],
+                                                            k["lr_max"], self.betas[0], self.betas[1], self.eps, self.t,
+                                                            self.max_grad_norm, scale, float(ent_coef), stream))
+            else:
+                f._pn.check(f._lib.rp_clip_adam_asym_dev(ptr(self.params), ptr(f._g), ptr(self.m), ptr(self.v), f.obs_dim, f.cobs_dim,
+                                                         f.act_dim, self.lr, self.betas[0], self.betas[1], self.eps, self.t,
+                                                         self.max_grad_norm, scale, float(ent_coef), stream))
+            return scale
         if self.schedule is not None:
             k = self.schedule
             f._pn.check(f._lib.rp_clip_adam_kl_dev(ptr(self.params), ptr(f._g), ptr(self.m), ptr(self.v), f.obs_dim, f.act_dim,
@@ -728,6 +801,12 @@ def _env_io_of(env):
     return out
 
 
+def _critic_obs_of(env):
+    """What a checkpoint records about the critic's rows (RoboyVecEnv's critic_obs): the value net only makes sense on the row it
+    was trained on.  An env without the option has no names."""
+    return list(getattr(env, "critic_obs_names", ()) or ())
+
+
 def _fused_kernels_apply(policy, obs_dim, act_dim):
     """MlpPolicy's shape (two hidden layers of 64 units per net) in dimensions the kernels of include/roboy_policy.h
     support, and the library is there."""
@@ -735,7 +814,9 @@ def _fused_kernels_apply(policy, obs_dim, act_dim):
         from . import _policy_native as pn
         ok_shape = (isinstance(policy, MlpPolicy) and len(policy.pi) == 5 and len(policy.vf) == 5
                     and all(l.out_features == 64 for l in (policy.pi[0], policy.pi[2], policy.vf[0], policy.vf[2])))
-        return bool(ok_shape and pn.load().rp_train_packed_floats(obs_dim, act_dim) > 0)
+        cd = getattr(policy, "critic_obs_dim", None)
+        return bool(ok_shape and pn.load().rp_train_packed_floats(obs_dim, act_dim) > 0
+                    and (cd is None or pn.load().rp_train_packed_floats(cd, act_dim) > 0))
     except Exception:
         return False
 
@@ -746,7 +827,8 @@ class PPO:
                  device="cuda", dist=None, reward_scale=1.0, seed=0, use_graphs=False, fused_policy=None,
                  fused_update=None, rollout_chains=None, normalize_obs=False, clip_obs=10.0, obs_norm_prime=True,
                  normalize_reward=False, clip_reward=10.0, reward_norm_prime=True, bootstrap_timeouts=False,
-                 lr_schedule=None, desired_kl=0.01, lr_factor=1.5, lr_min=1e-5, lr_max=1e-2, diagnostics=False):
+                 lr_schedule=None, desired_kl=0.01, lr_factor=1.5, lr_min=1e-5, lr_max=1e-2, diagnostics=False,
+                 asymmetric_critic=False):
         """fused_policy / fused_update: None = the fused MFMA kernels whenever they apply (a GPU, MlpPolicy's shape,
         dimensions the kernels support), True = insist, False = the torch path (the statement the kernels are
         tested against).  The gradient kernel takes up to 63 observation columns: an env with ``action_obs=K`` stays fused while
@@ -775,7 +857,12 @@ class PPO:
         lr_factor, approx_kl below desired_kl / 2 (and above 0) multiplies it, within [lr_min, lr_max]; with several ranks the KL is
         their mean, so every rank takes the same decision.  ``update()`` then returns ``"lr"`` too and ``agent.learning_rate`` reads
         the current value.  ``lr_history``: assign a list and every minibatch appends its (approx_kl, lr after the rule) - device
-        tensors on the fused path, which adds no synchronisation by it.  DESIGN.md §19."""
+        tensors on the fused path, which adds no synchronisation by it.  DESIGN.md §19.
+        asymmetric_critic: the value net is trained on the env's privileged critic rows (``RoboyVecEnv(critic_obs=...)``: the exact
+        state, the env's own parameters and delay) instead of the noisy, late observation the actor gets - in simulation they are
+        free, and only the actor is deployed.  The rollout keeps ``cobs`` beside ``obs`` and every value - the rollout's, the last
+        one, the minibatch loss - reads it; ``normalize_obs`` keeps a second set of statistics for it.  Eager and graph modes, torch
+        and fused paths.  DESIGN.md §20."""
         if lr_schedule is not None and lr_schedule not in LR_SCHEDULES:
             raise ValueError("unknown lr_schedule %r: None or one of %r" % (lr_schedule, LR_SCHEDULES))
         if not desired_kl > 0.0:
@@ -797,11 +884,26 @@ class PPO:
         torch.manual_seed(seed)
         obs_dim = env.observation_space.shape[0]
         act_dim = env.action_space.shape[0]
-        self.policy = (policy or MlpPolicy(obs_dim, act_dim)).to(self.device)
+        self.asymmetric_critic = bool(asymmetric_critic)
+        self.cobs_dim = None
+        if self.asymmetric_critic:
+            self.cobs_dim = int(getattr(env, "critic_obs_dim", 0) or 0)
+            if self.cobs_dim < 1:
+                raise ValueError("asymmetric_critic needs an env that writes critic rows: RoboyVecEnv(critic_obs=(\"state\", ...))")
+            if policy is not None and getattr(policy, "critic_obs_dim", None) != self.cobs_dim:
+                raise ValueError("asymmetric_critic: the env's critic rows have %d columns, the policy's value net reads %r"
+                                 % (self.cobs_dim, getattr(policy, "critic_obs_dim", None)))
+        elif policy is not None and getattr(policy, "critic_obs_dim", None) is not None:
+            raise ValueError("a policy with an asymmetric critic needs PPO(asymmetric_critic=True)")
+        self.policy = (policy or MlpPolicy(obs_dim, act_dim, critic_obs_dim=self.cobs_dim)).to(self.device)
         self.obs_norm = ObsNorm(obs_dim, self.device, clip=clip_obs) if normalize_obs else None
+        self.cobs_norm = ObsNorm(self.cobs_dim, self.device, clip=clip_obs) if normalize_obs and self.asymmetric_critic else None
         self._obs_norm_prime = bool(obs_norm_prime)
         if self.obs_norm is not None or getattr(self.policy, "obs_norm", None) is not None:
-            self.policy.set_obs_norm(self.obs_norm)
+            if self.asymmetric_critic:
+                self.policy.set_obs_norm(self.obs_norm, self.cobs_norm)
+            else:
+                self.policy.set_obs_norm(self.obs_norm)
         if dist is not None and dist.is_available() and dist.is_initialized():
             for p in self.policy.parameters():          # same initial weights on every rank
                 dist.broadcast(p.data, 0)
@@ -861,6 +963,25 @@ class PPO:
         self._rew_raw = None                  # the last rollout's raw reward (kept with normalize_reward: learn() reports it)
         self.num_timesteps = 0
         self._obs = None
+        self._cobs = None                     # the critic rows that belong to _obs (asymmetric_critic)
+
+    def _critic_rows(self):
+        """the env's critic rows of the observation last returned, on the agent's device"""
+        return self._to_tensor(self.env.critic_obs())
+
+    def _update_obs_norms(self, obs_rows, cobs_rows):
+        """Merge a rollout's moments into the observation statistics - and the critic rows' into theirs, the two sets of sums
+        all-reduced over the ranks as ONE tensor."""
+        if self.cobs_norm is None:
+            return self.obs_norm.update(obs_rows, self.dist)
+        a, c = self.obs_norm, self.cobs_norm
+        sa, sc = a.moments(obs_rows.to(a.device)), c.moments(cobs_rows.to(c.device))
+        dist = self.dist
+        if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            both = torch.cat([sa, sc])
+            _all_reduce_sums(both, dist)
+            sa.copy_(both[:sa.numel()]); sc.copy_(both[sa.numel():])
+        a.merge(sa); c.merge(sc)
 
     @property
     def learning_rate(self):
@@ -891,26 +1012,32 @@ class PPO:
         chain's half on its own stream."""
         env, T = self.env, self.n_steps
         whole = stream_ptr is None
+        asym = self.asymmetric_critic
         b["obs"][0][lo:hi].copy_(b["carry"][lo:hi])
+        if asym:
+            b["cobs"][0][lo:hi].copy_(b["ccarry"][lo:hi])
         packed = self._fused.pack() if self._fused is not None else None     # (inside the graph: re-gathered on every replay)
         for t in range(T):
+            # (asymmetric critic: the env step writes the critic rows of its range straight into the rollout's next slice)
+            d_cobs = b["cobs"][t + 1].data_ptr() if asym else None
             if self._fused is not None:
                 # straight into the rollout buffers; the env kernel clamps the action to its box itself.  The noise is keyed by
                 # the GLOBAL sample index (sample_offset): the same draw however the batch is cut
                 self._fused.act_into(b["obs"][t][lo:hi], b["act"][t][lo:hi], b["logp"][t][lo:hi], b["val"][t][lo:hi], step=t,
-                                     packed=packed, step_base=self._step_base, sample_offset=lo, norm=self.obs_norm)
+                                     packed=packed, step_base=self._step_base, sample_offset=lo, norm=self.obs_norm,
+                                     cobs=b["cobs"][t][lo:hi] if asym else None, cnorm=self.cobs_norm)
                 if whole:
                     env.step_dev(b["act"][t].data_ptr(), b["obs"][t + 1].data_ptr(), b["rew_raw"][t].data_ptr(),
-                                 b["done_i"][t].data_ptr())
+                                 b["done_i"][t].data_ptr(), *((d_cobs,) if asym else ()))
                 else:
                     env.step_range_dev(lo, hi - lo, stream_ptr, b["act"][t].data_ptr(), b["obs"][t + 1].data_ptr(),
-                                       b["rew_raw"][t].data_ptr(), b["done_i"][t].data_ptr())
+                                       b["rew_raw"][t].data_ptr(), b["done_i"][t].data_ptr(), *((d_cobs,) if asym else ()))
                 continue
-            a, logp, v = self.policy.act(b["obs"][t])
+            a, logp, v = self.policy.act(b["obs"][t], cobs=b["cobs"][t]) if asym else self.policy.act(b["obs"][t])
             b["act"][t].copy_(a); b["logp"][t].copy_(logp); b["val"][t].copy_(v)
             clipped = a.clamp(-1.0, 1.0).contiguous()
             env.step_dev(clipped.data_ptr(), b["obs"][t + 1].data_ptr(), b["rew_raw"][t].data_ptr(),
-                         b["done_i"][t].data_ptr())
+                         b["done_i"][t].data_ptr(), *((d_cobs,) if asym else ()))
 
     def _rollout_tail_norm(self, b):
         """``_rollout_tail`` under return normalisation of the reward: with the fused policy step everything behind the value of the
@@ -919,7 +1046,7 @@ class PPO:
         if self._fused is not None:
             self._step_base += T
         with torch.no_grad():
-            last_value = self.policy.value(b["obs"][T])
+            last_value = self.policy.value(self._value_rows(b, T))
         if self._fused is not None:
             rn.tail(b["rew_raw"], b["done_i"], b["val"], last_value.contiguous(), self.reward_scale, self.lam, b["rew"], b["done"],
                     b["adv"], b["ret"], boot=self.bootstrap_timeouts)
@@ -935,7 +1062,7 @@ class PPO:
             b["adv"].copy_(adv); b["ret"].copy_(ret)
         if self.bootstrap_timeouts:
             b["trunc"].copy_((b["done_i"] == 2).to(torch.float32))
-        b["carry"].copy_(b["obs"][T])
+        self._carry_over(b, T)
 
     def _rollout_tail_boot(self, b):
         """``_rollout_tail`` with ``bootstrap_timeouts`` and without reward normalisation: with the fused policy step one launch
@@ -945,7 +1072,7 @@ class PPO:
         if self._fused is not None:
             self._step_base += T
         with torch.no_grad():
-            last_value = self.policy.value(b["obs"][T])
+            last_value = self.policy.value(self._value_rows(b, T))
         if self._fused is not None:
             self._boot_tail.tail(b["rew_raw"], b["done_i"], b["val"], last_value.contiguous(), self.reward_scale, self.lam, b["rew"],
                                  b["done"], b["adv"], b["ret"], boot=True, identity=True)
@@ -955,7 +1082,7 @@ class PPO:
             adv, ret = gae_boot(b["rew"], b["val"], b["done_i"], last_value, self.gamma, self.lam)
             b["adv"].copy_(adv); b["ret"].copy_(ret)
         b["trunc"].copy_((b["done_i"] == 2).to(torch.float32))
-        b["carry"].copy_(b["obs"][T])
+        self._carry_over(b, T)
 
     def _rollout_tail(self, b):
         if self.reward_norm is not None:
@@ -968,13 +1095,22 @@ class PPO:
         b["rew"].copy_(b["rew_raw"] * self.reward_scale)
         b["done"].copy_(b["done_i"].to(torch.float32))
         with torch.no_grad():
-            last_value = self.policy.value(b["obs"][T])
+            last_value = self.policy.value(self._value_rows(b, T))
         if self._fused is not None:
             gae_fused(b["rew"], b["val"], b["done"], last_value.contiguous(), self.gamma, self.lam, b["adv"], b["ret"])
         else:
             adv, ret = gae(b["rew"], b["val"], b["done"], last_value, self.gamma, self.lam)
             b["adv"].copy_(adv); b["ret"].copy_(ret)
+        self._carry_over(b, T)
+
+    def _value_rows(self, b, t):
+        """the rows the value net reads at step t of the graph's buffers"""
+        return b["cobs"][t] if self.asymmetric_critic else b["obs"][t]
+
+    def _carry_over(self, b, T):
         b["carry"].copy_(b["obs"][T])
+        if self.asymmetric_critic:
+            b["ccarry"].copy_(b["cobs"][T])
 
     def _rollout_body(self, b):
         self._rollout_steps(b, 0, b["carry"].shape[0])
@@ -1007,11 +1143,17 @@ class PPO:
              "carry": z(N, od)}
         if self.bootstrap_timeouts:
             b["trunc"] = z(T, N)
+        asym = self.asymmetric_critic
+        if asym:
+            b["cobs"], b["ccarry"] = z(T + 1, N, self.cobs_dim), z(N, self.cobs_dim)
         if self._obs is None and self.reward_norm is not None:
             self.reward_norm.reset_returns(N)
         if self._boot_tail is not None:
             self._boot_tail.reset_returns(N)
-        b["carry"].copy_(self._to_tensor(env.reset()) if self._obs is None else self._obs)
+        fresh = self._obs is None
+        b["carry"].copy_(self._to_tensor(env.reset()) if fresh else self._obs)
+        if asym:
+            b["ccarry"].copy_(self._critic_rows() if fresh else self._cobs)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         # the env kernel is launched on the simulation's stream: make that the capture stream
@@ -1022,9 +1164,11 @@ class PPO:
             env.sim.specialization()
         with torch.cuda.stream(side), torch.no_grad():
             # first use of the GEMM library for these shapes (handle, workspace) must not fall into the capture
-            self.policy.act(b["carry"]); self.policy.value(b["carry"])
+            self.policy.act(b["carry"], cobs=b["ccarry"]) if asym else self.policy.act(b["carry"])
+            self.policy.value(b["ccarry"] if asym else b["carry"])
             if self._fused is not None:       # its one-time launch configuration must not fall into the capture either
-                self._fused.act_into(b["carry"], b["act"][0], b["logp"][0], b["val"][0], deterministic=True, norm=self.obs_norm)
+                self._fused.act_into(b["carry"], b["act"][0], b["logp"][0], b["val"][0], deterministic=True, norm=self.obs_norm,
+                                     cobs=b["ccarry"] if asym else None, cnorm=self.cobs_norm)
                 if self.reward_norm is not None:  # nor the tail kernel's (on a copy of the returns: they must not move)
                     self.reward_norm.tail(b["rew_raw"], b["done_i"], b["val"], b["val"][0], self.reward_scale, self.lam, b["rew"],
                                           b["done"], b["adv"], b["ret"], ret_carry=self.reward_norm.ret_carry.clone(),
@@ -1083,6 +1227,8 @@ class PPO:
         if hasattr(self.env, "note_replayed_steps"):
             self.env.note_replayed_steps(T)
         self._obs = b["carry"]
+        if self.asymmetric_critic:
+            self._cobs = b["ccarry"]
         self.num_timesteps += T * b["carry"].shape[0]
         if self.reward_norm is not None:
             # behind the replay and outside the graph: the all-reduce and the merge of the rollout's return moments
@@ -1092,6 +1238,8 @@ class PPO:
                 "done": b["done"], "adv": b["adv"], "ret": b["ret"]}
         if self.bootstrap_timeouts:
             roll["trunc"] = b["trunc"]
+        if self.asymmetric_critic:
+            roll["cobs"] = b["cobs"][:T]
         return roll
 
     def collect(self):
@@ -1107,19 +1255,23 @@ class PPO:
                 roll = self._collect_rollout()
                 self.num_timesteps = before
                 if prime_obs:
-                    self.obs_norm.update(roll["obs"].reshape(-1, roll["obs"].shape[-1]), self.dist)
+                    self._update_obs_norms(roll["obs"].reshape(-1, roll["obs"].shape[-1]),
+                                           roll["cobs"].reshape(-1, roll["cobs"].shape[-1]) if self.asymmetric_critic else None)
         return self._collect_rollout()
 
     def _collect_rollout(self):
         if self.use_graphs:
             return self._collect_graph()
         env, T = self.env, self.n_steps
+        asym = self.asymmetric_critic
         if self._obs is None:
             self._obs = self._to_tensor(env.reset())
+            if asym:
+                self._cobs = self._critic_rows()
             if self.reward_norm is not None:
                 self.reward_norm.reset_returns(self._obs.shape[0])
         N = self._obs.shape[0]
-        buf = {k: [] for k in ("obs", "act", "logp", "val", "rew", "done")}
+        buf = {k: [] for k in ("obs", "act", "logp", "val", "rew", "done") + (("cobs",) if asym else ())}
         raw, codes = [], []
         boot = self.bootstrap_timeouts
         if boot and self._fused is not None:
@@ -1130,12 +1282,16 @@ class PPO:
                 o = self._obs.contiguous()
                 a = torch.empty(N, self._fused.act_dim, device=self.device)
                 logp, v = torch.empty(N, device=self.device), torch.empty(N, device=self.device)
-                self._fused.act_into(o, a, logp, v, step=t, packed=packed, step_base=self._step_base, norm=self.obs_norm)
+                self._fused.act_into(o, a, logp, v, step=t, packed=packed, step_base=self._step_base, norm=self.obs_norm,
+                                     cobs=self._cobs.contiguous() if asym else None, cnorm=self.cobs_norm)
             else:
-                a, logp, v = self.policy.act(self._obs)
+                a, logp, v = self.policy.act(self._obs, cobs=self._cobs) if asym else self.policy.act(self._obs)
             clipped = a.clamp(-1.0, 1.0).contiguous()        # the env's action box (roboy_env.py:31)
             obs, rew, done, _ = env.step(clipped if self.device.type == "cuda" else clipped.cpu().numpy())
             buf["obs"].append(self._obs); buf["act"].append(a); buf["logp"].append(logp); buf["val"].append(v)
+            if asym:
+                buf["cobs"].append(self._cobs)
+                self._cobs = self._critic_rows()
             rew = self._to_tensor(rew)
             if self.reward_norm is not None:
                 raw.append(rew)
@@ -1154,11 +1310,16 @@ class PPO:
             roll["rew"] = self.reward_norm.apply(roll["rew"])
             self.reward_norm.update(self.dist)
         with torch.no_grad():
-            last_value = self.policy.value(self._obs)
+            last_value = self.policy.value(self._cobs if asym else self._obs)
         if boot:
             codes = torch.stack(codes)
             roll["trunc"] = (codes == 2).to(torch.float32)
             roll["adv"], roll["ret"] = gae_boot(roll["rew"], roll["val"], codes, last_value, self.gamma, self.lam)
+        elif asym and self._fused is not None and self.reward_norm is None:
+            # the tail as the graph modes run it (rp_gae_dev, not the torch loop, whose roundings differ): with an asymmetric critic
+            # eager and captured rollouts agree bit for bit, as they do under bootstrap_timeouts
+            roll["adv"], roll["ret"] = gae_fused(roll["rew"].contiguous(), roll["val"].contiguous(), roll["done"].contiguous(),
+                                                 last_value.contiguous(), self.gamma, self.lam)
         else:
             roll["adv"], roll["ret"] = gae(roll["rew"], roll["val"], roll["done"], last_value, self.gamma, self.lam)
         self.num_timesteps += T * N
@@ -1176,18 +1337,26 @@ class PPO:
         roll = {"obs": z(T, N, self._obs.shape[1]), "act": z(T, N, self._fused.act_dim), "logp": z(T, N), "val": z(T, N),
                 "rew": z(T, N), "done": z(T, N), "adv": z(T, N), "ret": z(T, N)}
         rew_raw, codes = z(T, N), z(T, N, dtype=torch.int32)
+        asym = self.asymmetric_critic
+        if asym:
+            roll["cobs"] = z(T, N, self.cobs_dim)
         packed = self._fused.pack()
         for t in range(T):
             roll["obs"][t].copy_(self._obs)
+            if asym:
+                roll["cobs"][t].copy_(self._cobs)
             self._fused.act_into(roll["obs"][t], roll["act"][t], roll["logp"][t], roll["val"][t], step=t, packed=packed,
-                                 step_base=self._step_base, norm=self.obs_norm)
+                                 step_base=self._step_base, norm=self.obs_norm, cobs=roll["cobs"][t] if asym else None,
+                                 cnorm=self.cobs_norm)
             obs, rew, done, _ = env.step(roll["act"][t].clamp(-1.0, 1.0).contiguous())
             rew_raw[t].copy_(rew)
             codes[t].copy_(done.to(torch.int32) + env.truncated().to(torch.int32))
             self._obs = obs
+            if asym:
+                self._cobs = self._critic_rows()
         self._step_base += T
         with torch.no_grad():
-            last_value = self.policy.value(self._obs).contiguous()
+            last_value = self.policy.value(self._cobs if asym else self._obs).contiguous()
         if self.reward_norm is not None:
             self._rew_raw = rew_raw
             self.reward_norm.tail(rew_raw, codes, roll["val"], last_value, self.reward_scale, self.lam, roll["rew"], roll["done"],
@@ -1208,7 +1377,7 @@ class PPO:
         logp = d.log_prob(act).sum(-1)
         ratio = (logp - flat["logp"][idx]).exp()
         pg = torch.max(-adv * ratio, -adv * ratio.clamp(1 - self.cliprange, 1 + self.cliprange)).mean()
-        v = self.policy.value(obs)
+        v = self.policy.value(flat["cobs"][idx] if self.asymmetric_critic else obs)
         v_clip = flat["val"][idx] + (v - flat["val"][idx]).clamp(-self.cliprange, self.cliprange)
         vf = 0.5 * torch.max((v - flat["ret"][idx]) ** 2, (v_clip - flat["ret"][idx]) ** 2).mean()
         ent = d.entropy().sum(-1).mean()
@@ -1226,7 +1395,8 @@ class PPO:
         stats = self._fgrad.minibatch_adv_stats(flat["adv"], idx)
         pg, vf = self._fgrad.run(flat["obs"], flat["act"], flat["adv"], flat["logp"], flat["val"], flat["ret"], self.cliprange,
                                  self.vf_coef, self.ent_coef, index=idx, adv_stats=stats, entropy_grad=False, norm=self.obs_norm,
-                                 diagnostics=self.diagnostics)
+                                 diagnostics=self.diagnostics, cobs=flat["cobs"] if self.asymmetric_critic else None,
+                                 cnorm=self.cobs_norm)
         scale = self._fadam.step(self.ent_coef, self.dist)          # all-reduces the gradient vector first when ranks > 1
         ent = (0.5 + 0.5 * math.log(2 * math.pi) + self.policy.log_std.detach()).sum()
         pg, vf = pg * scale, vf * scale                              # (the loss slots were summed over the ranks with the rest)
@@ -1289,7 +1459,7 @@ class PPO:
                 out = self._minibatch_step(flat, perm[s:s + mb])
         if self.obs_norm is not None:
             # the statistics move only now: rollout and update saw the same ones (old and new log-probabilities of the same inputs)
-            self.obs_norm.update(flat["obs"], self.dist)
+            self._update_obs_norms(flat["obs"], flat["cobs"] if self.asymmetric_critic else None)
         if out is None:
             return {}
         loss, pg, vf, ent, kl, cf = out
@@ -1321,6 +1491,10 @@ class PPO:
               "obs_norm": self.obs_norm.state_dict() if self.obs_norm is not None else None,
               "reward_norm": self.reward_norm.state_dict() if self.reward_norm is not None else None,
               "bootstrap_timeouts": self.bootstrap_timeouts}
+        if self.asymmetric_critic:                   # (an agent without the option writes the checkpoint it always wrote)
+            ck["critic_obs"] = _critic_obs_of(self.env)
+            ck["critic_obs_dim"] = self.cobs_dim
+            ck["critic_obs_norm"] = self.cobs_norm.state_dict() if self.cobs_norm is not None else None
         if self.lr_schedule is not None:             # (an agent without a schedule writes the checkpoint it always wrote)
             ck["lr_schedule"] = {"kind": self.lr_schedule, "desired_kl": self.desired_kl, "lr_factor": self.lr_factor,
                                  "lr_min": self.lr_min, "lr_max": self.lr_max, "lr": self.learning_rate}
@@ -1331,6 +1505,12 @@ class PPO:
         if ck.get("tendon_obs", _tendon_obs_of(None)) != _tendon_obs_of(self.env):
             raise ValueError("the checkpoint was trained on the observation %r, this env gives %r (RoboyVecEnv's tendon_obs / "
                              "tendon_obs_scale)" % (ck.get("tendon_obs", _tendon_obs_of(None)), _tendon_obs_of(self.env)))
+        if ("critic_obs" in ck) != self.asymmetric_critic:
+            raise ValueError("the checkpoint was trained %s an asymmetric critic, this agent runs %s one (PPO's asymmetric_critic)"
+                             % (("with", "without") if not self.asymmetric_critic else ("without", "with")))
+        if self.asymmetric_critic and (ck["critic_obs"] != _critic_obs_of(self.env) or int(ck["critic_obs_dim"]) != self.cobs_dim):
+            raise ValueError("the checkpoint's critic was trained on the rows %r (%d columns), this env writes %r (%d; RoboyVecEnv's "
+                             "critic_obs)" % (ck["critic_obs"], int(ck["critic_obs_dim"]), _critic_obs_of(self.env), self.cobs_dim))
         if (ck.get("obs_norm") is not None) != (self.obs_norm is not None):      # (a checkpoint without the key: written without it)
             raise ValueError("the checkpoint was trained %s observation normalisation, this agent runs %s it (PPO's normalize_obs)"
                              % (("with", "without") if self.obs_norm is None else ("without", "with")))
@@ -1340,6 +1520,8 @@ class PPO:
         if self.obs_norm is not None:
             self.obs_norm.load_state_dict(ck["obs_norm"])
             self._obs_norm_prime = self._obs_norm_prime and float(ck["obs_norm"]["count"]) == 0.0
+            if self.cobs_norm is not None:
+                self.cobs_norm.load_state_dict(ck["critic_obs_norm"])
         if self.reward_norm is not None:
             self.reward_norm.load_state_dict(ck["reward_norm"])
             self.reward_norm.reset_returns()                 # the running returns are not stored: they start afresh
@@ -1362,7 +1544,7 @@ class PPO:
         else:
             # a checkpoint of the fused path resumed on the torch path: torch's per-parameter state from the flat moments
             from . import _policy_native as pn
-            layout, n = pn.grad_layout(self.policy.pi[0].in_features, self.policy.pi[-1].out_features)
+            layout, n = pn.grad_layout(self.policy.pi[0].in_features, self.policy.pi[-1].out_features, self.cobs_dim)
             if int(ck["optimizer"]["m"].numel()) != int(n):
                 raise ValueError("optimiser state of another policy layout: %d values, this policy's flat vector has %d"
                                  % (ck["optimizer"]["m"].numel(), n))

@@ -53,6 +53,10 @@ def main(argv=None):
     ap.add_argument("--action-obs", type=int, default=0, metavar="K",
                     help="append the last K commanded actions (at most 8, newest first, zeros where the episode is younger) to the "
                          "observation: what the policy needs to compensate --action-delay; stored in the checkpoint")
+    ap.add_argument("--critic-obs", default="", metavar="BLOCK,...",
+                    help="an asymmetric critic: the value net is trained on privileged rows the env writes beside the observation - state "
+                         "(exact q, qd, goal; always part of the row), age, params, delay (needs --action-delay), actions (needs "
+                         "--action-obs), e.g. state,age,delay,actions; only the actor is deployed; recorded in the checkpoint")
     ap.add_argument("--normalize-obs", action="store_true",
                     help="running mean / variance normalisation of the observation inside the policy kernels (what "
                          "stable-baselines calls VecNormalize); the statistics are stored in the checkpoint")
@@ -78,6 +82,7 @@ def main(argv=None):
         parts = [int(x) for x in args.action_delay.split(":")]
         action_delay = parts[0] if len(parts) == 1 else (parts[0], parts[1])
     tendon_obs = tuple(c for c in args.tendon_obs.split(",") if c)
+    critic_obs = tuple(c for c in args.critic_obs.split(",") if c)
     tendon_obs_scale = {k: float(v) for k, v in (item.split("=", 1) for item in args.tendon_obs_scale.split(",") if item)}
 
     import torch
@@ -106,14 +111,15 @@ def main(argv=None):
     env = RoboyVecEnv(MsjRobot(), args.num_envs, seed=args.seed, device=local_rank,
                       env_id_offset=rank * args.num_envs, tendon_obs=tendon_obs or None, tendon_obs_scale=tendon_obs_scale or None,
                       sensor_noise=sensor_noise or None, action_delay=action_delay,
-                      report_truncation=args.bootstrap_timeouts, action_obs=args.action_obs or None)
+                      report_truncation=args.bootstrap_timeouts, action_obs=args.action_obs or None,
+                      critic_obs=critic_obs or None)
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,
                 fused_update=not args.torch_policy, normalize_obs=args.normalize_obs, clip_obs=args.clip_obs,
                 normalize_reward=args.normalize_reward, clip_reward=args.clip_reward,
                 bootstrap_timeouts=args.bootstrap_timeouts, lr_schedule=args.lr_schedule, desired_kl=args.desired_kl,
-                lr_min=args.lr_min, lr_max=args.lr_max)
+                lr_min=args.lr_min, lr_max=args.lr_max, asymmetric_critic=bool(critic_obs))
     if os.path.exists(model_file):
         agent.load(model_file)                  # resume from the last backup
     for _ in range(args.rounds):

@@ -68,7 +68,9 @@ def main(argv=None):
             o, r, d, _ = env.step(a)
             return o, r, d
         n_obs, n_act = env.observation_space.shape[0], env.action_space.shape[0]
-    policy = MlpPolicy(n_obs, n_act)
+    # (a checkpoint of PPO's asymmetric_critic: the value net has its own input width and is not evaluated - the actor alone is played
+    # back, and no critic row is needed)
+    policy = MlpPolicy(n_obs, n_act, critic_obs_dim=ck.get("critic_obs_dim"))
     if ck["policy"]["pi.0.weight"].shape[1] != n_obs:
         raise SystemExit("%s holds a policy over %d observation columns, this env gives %d: it was not written by this "
                          "train_parallel" % (args.model, ck["policy"]["pi.0.weight"].shape[1], n_obs))

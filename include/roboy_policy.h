@@ -210,6 +210,48 @@ int rp_ppo_grad_diag_dev(const float *d_packed_train, const float *d_obs, const 
 int rp_clip_adam_kl_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int act_dim, float *d_lr,
                         float desired_kl, float lr_factor, float lr_min, float lr_max, float beta1, float beta2, float eps, int64_t step,
                         float max_grad_norm, float grad_scale, float ent_coef, void *stream);
+/* ---- an asymmetric critic: the value net on privileged rows of its own (PPO(asymmetric_critic=True)) ----
+ * The action net reads obs [n][obs_dim] through a blob packed for (obs_dim, act_dim); the value net reads cobs [n][cobs_dim] (the
+ * env's critic rows: roboy_sim.h, rb_env_critic_obs_*) through a blob packed for (cobs_dim, act_dim).  A blob holds both nets'
+ * operands; each net is read from its own blob only, so the value weights of the first blob and the action weights of the second are
+ * never used (a caller may pack the same rp_mlp_params twice with the first-layer matrix of the net that does not apply left at any
+ * width-correct filler).  RP_ABI_VERSION is still 5: nothing that existed changed.
+ *
+ * rp_act_asym_dev / rp_act_asym_norm_dev: the policy step.  Two further instances of the policy-step kernel's text with ONE NET PER
+ * WORKGROUP - a workgroup stages only its net's operands in LDS, half of the symmetric step's - otherwise rp_act_dev's work items,
+ * network arithmetic and epilogue: actions, log-probabilities, means and the Philox keys are those of rp_act_dev(obs) for the same
+ * (seed, sample_offset, step), and the values those of rp_act_dev(cobs) on a policy of input width cobs_dim with the same value
+ * weights.  The norm form takes statistics and a clip per net (both or neither: both NULL launches the plain instance). */
+int rp_act_asym_dev(const float *d_packed_pi, const float *d_packed_vf, const float *d_obs, const float *d_cobs, float *d_act, float *d_logp,
+                    float *d_value, float *d_mean, int64_t n, int obs_dim, int cobs_dim, int act_dim, uint64_t seed, uint64_t sample_offset,
+                    uint32_t step, const uint32_t *d_step_base, int deterministic, void *stream);
+int rp_act_asym_norm_dev(const float *d_packed_pi, const float *d_packed_vf, const float *d_obs, const float *d_cobs, float *d_act, float *d_logp,
+                         float *d_value, float *d_mean, int64_t n, int obs_dim, int cobs_dim, int act_dim, uint64_t seed,
+                         uint64_t sample_offset, uint32_t step, const uint32_t *d_step_base, int deterministic, const float *d_norm_pi,
+                         const float *d_norm_vf, float clip_pi, float clip_vf, void *stream);
+/* The gradient: NO new kernel.  The existing instances are launched with per-net arguments - the action net with (d_packed_pi, d_obs,
+ * obs_dim, d_norm_pi, clip_pi), the value net with (d_packed_vf, d_cobs, cobs_dim, d_norm_vf, clip_vf) - and each net's form
+ * (rp_grad_form) is chosen from its own width.  d_packed_*: rp_pack_train blobs.  The gradient vector: the action net's block of
+ * rp_grad_floats(obs_dim, act_dim) / 2 floats, then the value net's of rp_grad_floats(cobs_dim, act_dim) / 2, each in the layout
+ * above (w1 is 64 x obs_dim / 64 x cobs_dim): rp_grad_asym_floats() in all.  Each block is bit-equal to the same block of
+ * rp_ppo_grad_norm_dev / rp_ppo_grad_diag_dev on a symmetric policy of that width and those weights.  Statistics for both nets or for
+ * neither; diag != 0: the action net's launch is its diagnostics instance (rp_ppo_grad_diag_dev).  d_workspace:
+ * rp_ppo_asym_workspace_floats() floats.  Every other argument, limit and error is rp_ppo_grad_dev's. */
+int64_t rp_grad_asym_floats(int obs_dim, int cobs_dim, int act_dim);
+int64_t rp_ppo_asym_workspace_floats(int obs_dim, int cobs_dim, int act_dim, int64_t batch);
+int rp_ppo_grad_asym_dev(const float *d_packed_pi, const float *d_packed_vf, const float *d_obs, const float *d_cobs, const float *d_act,
+                         const float *d_adv, const float *d_adv_stats, const float *d_logp_old, const float *d_val_old, const float *d_ret,
+                         const int64_t *d_index, int64_t batch, int obs_dim, int cobs_dim, int act_dim, float cliprange, float vf_coef,
+                         const float *d_norm_pi, const float *d_norm_vf, float clip_pi, float clip_vf, int diag, float *d_grad,
+                         float *d_workspace, void *stream);
+/* The optimiser: NO new kernel.  rp_clip_adam_dev / rp_clip_adam_kl_dev over a vector of rp_grad_asym_floats() floats in the layout
+ * of rp_ppo_grad_asym_dev's gradient; every other argument, rule and error is theirs. */
+int rp_clip_adam_asym_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int cobs_dim, int act_dim, float lr,
+                          float beta1, float beta2, float eps, int64_t step, float max_grad_norm, float grad_scale, float ent_coef,
+                          void *stream);
+int rp_clip_adam_kl_asym_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int cobs_dim, int act_dim, float *d_lr,
+                             float desired_kl, float lr_factor, float lr_min, float lr_max, float beta1, float beta2, float eps, int64_t step,
+                             float max_grad_norm, float grad_scale, float ent_coef, void *stream);
 /* test hook: would a grant of lds_bytes of dynamic LDS be issued for (kernel id, device) now?  Records it. */
 int rp_debug_lds_grant_needed(int kernel_id, int dev, int64_t lds_bytes);
 /* which form of the gradient kernels rp_ppo_grad_dev launches for this policy: 2 = the small instance (obs_dim <= 31, up to 8

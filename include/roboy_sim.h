@@ -488,6 +488,50 @@ int32_t rb_env_action_obs_count(int32_t n_q, int32_t n_t, uint32_t channel_mask,
 int rb_env_done_kind_configure(rb_sim *sim, int enable);
 int rb_env_done_kind_ptr(rb_sim *sim, uint32_t **d_kind);
 
+/* ---- privileged critic rows: the exact state and the env's hidden parameters, for an asymmetric critic ----
+ * §12-§18 make the observation row noisy, late and blind to the env's own parameters on purpose.  A value net that is only trained
+ * and never deployed may see what the simulator knows.  While a mask is set, every env-step entry (rb_env_step_dev,
+ * rb_env_step_range_dev and the two entries below; every ball-joint kernel form and extension) is followed on the same stream, over
+ * the same envs, by one small kernel that writes a second row per env; rb_env_reset_dev is followed by it too.  It reads the planes as
+ * the step left them - after any auto-reset and redraw - so the row describes the state, goal, parameters and delay that the returned
+ * observation row belongs to.  Blocks, in this order, each present only if its bit is set:
+ *   RB_CRITIC_STATE    3 n_q   q, qd, goal from the planes: the observation's first 3 n_q columns without noise.  Always selected:
+ *                              a non-zero mask implies it
+ *   RB_CRITIC_AGE      1       float(step_num) / float(max_episode_length), one fp32 division (1 / max_len behind a reset)
+ *   RB_CRITIC_PARAMS   np      the parameter planes in plane order (rb_params_ptr), unscaled; needs rb_params_enable
+ *   RB_CRITIC_DELAY    1       float(delay) (rb_env_io_ptr); needs rb_env_io_configure
+ *   RB_CRITIC_ACTIONS  K n_t   a bitwise copy of the observation row's K action blocks (never noised, zeros behind a reset); needs
+ *                              rb_env_action_obs_configure(K > 0)
+ * Tendon channels are not offered: their exact values are in no plane, and the observation row's copies may be noised.
+ * Observations, rewards, done words, state and statistics are those of a handle without the option.  Ball-joint robots; a joint
+ * tree is refused with RB_EUNSUPPORTED.
+ *   configure: after rb_env_configure and after the options the mask depends on (RB_EINVAL otherwise, and RB_EINVAL for a row wider
+ *              than RB_CRITIC_OBS_MAX_DIM, the PPO gradient kernels' input limit).  Drains the handle's streams and evicts the cached
+ *              rollout graphs: call it before a caller captures env steps.  mask = 0 frees the plane: the handle launches exactly
+ *              what it launched before.  Changing an option the mask depends on afterwards makes the env-step entries fail with
+ *              RB_EINVAL until the rows are configured again.
+ *   dim:       Dc, the row width (0 while off).  count: the same from the numbers alone, -1 for an unknown bit.
+ *   ptr:       the handle's own plane [n_envs][Dc], written by rb_env_step_dev, rb_env_step_range_dev and rb_env_reset_dev;
+ *              RB_EINVAL while off.  rb_env_set_goal does not rewrite it.
+ *   rb_env_step_critic_dev / rb_env_step_range_critic_dev: the same steps with the rows written to d_cobs ([n_envs][Dc] of the
+ *              WHOLE batch; a range writes its own rows) instead of the handle's plane - a captured rollout writes its [t + 1] slice
+ *              directly.  Full waves store float4 runs where d_cobs is 16-byte aligned, one row per lane where it is not.
+ * RB_ABI_VERSION is still 6 (nothing that existed changed): look rb_env_critic_obs_configure up before relying on it. */
+#define RB_CRITIC_STATE 1u
+#define RB_CRITIC_AGE 2u
+#define RB_CRITIC_PARAMS 4u
+#define RB_CRITIC_DELAY 8u
+#define RB_CRITIC_ACTIONS 16u
+#define RB_CRITIC_ALL 31u
+#define RB_CRITIC_OBS_MAX_DIM 63
+int rb_env_critic_obs_configure(rb_sim *sim, uint32_t mask);
+int rb_env_critic_obs_dim(rb_sim *sim, int32_t *dim);
+int32_t rb_env_critic_obs_count(int32_t n_q, int32_t n_t, uint32_t mask, int32_t n_params, int32_t action_rows);
+int rb_env_critic_obs_ptr(rb_sim *sim, float **d_rows);
+int rb_env_step_critic_dev(rb_sim *sim, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done, float *d_cobs);
+int rb_env_step_range_critic_dev(rb_sim *sim, int64_t first_env, int64_t n_envs, void *hip_stream,
+                                 const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done, float *d_cobs);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
