@@ -851,7 +851,8 @@ class PPO:
         ``report_truncation=True``.  With the fused policy step the rollout's tail is one launch (rp_rollout_tail_boot_dev), under
         ``normalize_reward`` or not; the rollout dict gains ``"trunc"`` ([T, N] floats, 1 where the step was truncated).
         diagnostics: ``update()`` also returns ``"approx_kl"`` = mean 0.5 (logp - logp_old)^2 and ``"clip_frac"`` = the share of samples
-        whose ratio left [1 - cliprange, 1 + cliprange], of the last minibatch (stable-baselines PPO2's approxkl / clipfrac).
+        whose ratio left [1 - cliprange, 1 + cliprange], of the last minibatch (stable-baselines PPO2's approxkl / clipfrac).  With several
+        ranks the loss terms and these two are the ranks' means, on both optimiser paths.
         lr_schedule: None = ``learning_rate`` for the whole run; "adaptive" (implies diagnostics) = rsl_rl's schedule, applied in front
         of every minibatch's optimiser step in float32 (``adapt_lr``): approx_kl above 2 desired_kl divides the learning rate by
         lr_factor, approx_kl below desired_kl / 2 (and above 0) multiplies it, within [lr_min, lr_max]; with several ranks the KL is
@@ -1415,13 +1416,18 @@ class PPO:
         loss.backward()
         average_gradients(self.policy, self.dist)
         nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
+        dist = self.dist
+        if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            # what update() reports is the mean over the ranks, as the fused path's slots are (one small all-reduce); the KL with it
+            terms = torch.stack([pg.detach(), vf.detach()] + ([kl, cf] if self.diagnostics else []))
+            dist.all_reduce(terms)
+            terms = terms / dist.get_world_size()
+            pg, vf = terms[0], terms[1]
+            if self.diagnostics:
+                kl, cf = terms[2], terms[3]
+            loss = pg - self.ent_coef * ent.detach() + self.vf_coef * vf
         if self.lr_schedule is not None:
             # the rule, in front of the step of the same minibatch; with ranks on their mean KL: the same decision everywhere
-            dist = self.dist
-            if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                kl = kl.clone()
-                dist.all_reduce(kl)
-                kl = kl / dist.get_world_size()
             self._lr32 = adapt_lr(self._lr32, kl.item(), self.desired_kl, self.lr_factor, self.lr_min, self.lr_max)
             self.opt.param_groups[0]["lr"] = float(self._lr32)
             if self.lr_history is not None:
