@@ -216,8 +216,11 @@ struct Carry1 { V3 Rrow; float p, w, vo; };
 // by the eight lanes of its octet inside the level loop (a sincos and ~25 vector instructions per level there)
 struct Rot { V3 c0, c1, c2; };
 __device__ __forceinline__ Rot rodrigues(V3 ax, float q) {
+    // sinf / cosf to the last place, not the hardware's v_sin_f32 / v_cos_f32: a deep chain multiplies an error in a joint's
+    // rotation by every link behind it (the 32-link chain of the tests: an absolute 2e-7 in sine and cosine moves an acceleration by
+    // up to 7.5e-6 of the largest one), and this runs once per joint and evaluation, outside the level loops
     float sn, cs;
-    __sincosf(q, &sn, &cs);
+    sincosf(q, &sn, &cs);
     const float oc = 1.0f - cs;        // I + sin K + (1 - cos) K^2
     Rot r;
     r.c0 = {1.0f - oc * (ax.y * ax.y + ax.z * ax.z), sn * ax.z + oc * ax.x * ax.y, -sn * ax.y + oc * ax.x * ax.z};

@@ -189,3 +189,5 @@ def test_first_step_with_raw_actions_matches_fp64_at_the_clipped_set_points(c, m
     assert eq < tol and eqd < tol
     near = np.minimum(np.abs(qo - desc.q_lo), np.abs(qo - desc.q_hi)).min(axis=1) < 1e-5
     assert not np.any((f1 != fo) & ~near & live)
+    from limit_edge_util import decided_envs                   # ... and wherever the oracle's angle before the clamp is clear of every limit
+    assert not np.any((f1 != fo) & live & decided_envs(desc, q, qd, clipped_rescale64(robot, act[0]), c["integ"], 1, tol))

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import random_states
+from limit_edge_util import decided_envs
 
 pytestmark = pytest.mark.gpu
 
@@ -49,6 +50,9 @@ def _check_step(robot, oracle, n, integrator, nsub, seed, kernel=0):
     near = (np.minimum(np.abs(qo - desc.q_lo), np.abs(qo - desc.q_hi)).min(axis=1) < 1e-5)
     mismatch = f1 != fo
     assert not np.any(mismatch & ~near)
+    # (that rule excuses every env the oracle clamps; this one holds the flag wherever the oracle's angle BEFORE the clamp is clear
+    # of every limit in every substep: tests/limit_edge_util.py)
+    assert not np.any(mismatch & decided_envs(desc, q, qd, sp, integrator, nsub, TOL))
     sim.close()
     return np.abs(q1 - qo).max(), np.abs(qd1 - qdo).max()
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import random_states
+from limit_edge_util import decided_envs
 from random_robots import random_tree_robot
 
 pytestmark = pytest.mark.gpu
@@ -49,6 +50,7 @@ def test_random_tree_robot_matches_oracle(seed):
     assert np.all(np.abs(qd1 - qdo) < tol), (desc.n_q, desc.n_t, np.abs(qd1 - qdo).max())
     near = np.minimum(np.abs(qo - desc.q_lo), np.abs(qo - desc.q_hi)).min(axis=1) < 1e-5
     assert not np.any((f1 != fo) & ~near)
+    assert not np.any((f1 != fo) & decided_envs(desc, q, qd, sp, integrator, nsub, tol))      # tests/limit_edge_util.py
     # a second step from the kernel's own state: the working set of the first launch leaves nothing behind
     q2, qd2, _ = sim.forward_step_command(sp)
     qo2, qdo2, _ = COracle(desc, "f64").step(q1, qd1, sp, integrator=0 if integrator == "euler" else 1, n_substeps=nsub)
@@ -86,6 +88,7 @@ def test_random_tree_robot_env_per_lane_kernel_matches_oracle(seed):
     assert np.all(np.abs(q1 - qa) < 2 * tol) and np.all(np.abs(qd1 - qda) < 2 * tol)
     near = np.minimum(np.abs(qo - desc.q_lo), np.abs(qo - desc.q_hi)).min(axis=1) < 1e-5
     assert not np.any((f1 != fo) & ~near)
+    assert not np.any((f1 != fo) & decided_envs(desc, q, qd, sp, integrator, 1, tol))         # tests/limit_edge_util.py
     sim.close()
 
 
@@ -135,6 +138,7 @@ def test_random_tree_robot_split_form_matches_oracle(seed, kernel):
     assert np.all(np.abs(qd1 - qdo) < tol), (desc.n_q, desc.n_t, np.abs(qd1 - qdo).max())
     near = np.minimum(np.abs(qo - desc.q_lo), np.abs(qo - desc.q_hi)).min(axis=1) < 1e-5
     assert not np.any((f1 != fo) & ~near)
+    assert not np.any((f1 != fo) & decided_envs(desc, q, qd, sp, integrator, 2 if seed == 5 else 1, tol))     # tests/limit_edge_util.py
     sim.close()
 
 
@@ -261,6 +265,7 @@ def _ball_check(robot, desc, n, integrator, nsub, seed, kernel=0, sample=1):
     assert np.abs(qd1[idx] - qdo).max() < TOL, np.abs(qd1[idx] - qdo).max()
     near = np.minimum(np.abs(qo - desc.q_lo), np.abs(qo - desc.q_hi)).min(axis=1) < 1e-5
     assert not np.any((f1[idx] != fo) & ~near)
+    assert not np.any((f1[idx] != fo) & decided_envs(desc, q[idx], qd[idx], sp[idx], integrator, nsub, TOL))  # tests/limit_edge_util.py
     spec = sim.specialization()
     sim.close()
     return spec

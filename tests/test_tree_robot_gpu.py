@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import random_states
+from limit_edge_util import decided_envs
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5
@@ -45,6 +46,7 @@ def _check(robot, oracle, n, integrator, nsub, seed, kernel=None, expect=OCTET):
     assert np.abs(qd1 - qdo).max() < TOL, np.abs(qd1 - qdo).max()
     near = np.minimum(np.abs(qo - desc.q_lo), np.abs(qo - desc.q_hi)).min(axis=1) < 1e-5
     assert not np.any((f1 != fo) & ~near)
+    assert not np.any((f1 != fo) & decided_envs(desc, q, qd, sp, integrator, nsub, TOL))      # tests/limit_edge_util.py
     sim.close()
 
 
