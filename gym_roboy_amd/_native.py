@@ -163,6 +163,8 @@ SIGNATURES = {
     "rb_env_step_critic_dev": (ctypes.c_int, [_sim, _vp, _vp, _vp, _vp, _vp]),
     "rb_env_step_range_critic_dev": (ctypes.c_int, [_sim, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "rb_env_goal_pool_set": (ctypes.c_int, [_sim, _fp, ctypes.c_int64]),
+    "rb_env_goal_pool_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64)]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

@@ -20,8 +20,9 @@
 
 namespace rb {
 
-// (stream 2 is the policy's sampling noise, mlp_common.hpp; 3 the per-env physical parameters, env_params.hpp)
-enum { STREAM_ACTIONS = 0, STREAM_GOALS = 1, STREAM_PARAMS = 3 };
+// (stream 2 is the policy's sampling noise, mlp_common.hpp; 3 the per-env physical parameters, env_params.hpp; 4 the row of a goal
+// pool, env_goal.hpp)
+enum { STREAM_ACTIONS = 0, STREAM_GOALS = 1, STREAM_PARAMS = 3, STREAM_GOAL_POOL = 4 };
 
 struct Philox4 { uint32_t v[4]; };
 

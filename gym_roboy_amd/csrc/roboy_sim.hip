@@ -51,6 +51,7 @@
 #include "env_io.hpp"                 // per-env action latency and sensor noise in the fused env step (rb_env_io_*)
 #include "env_hist.hpp"               // the last K commanded actions as observation columns (rb_env_action_obs_*)
 #include "env_critic.hpp"             // privileged critic rows behind the fused env step (rb_env_critic_obs_*)
+#include "env_goal.hpp"               // goals drawn from a pool of poses (rb_env_goal_pool_*)
 
 namespace {
 
@@ -582,6 +583,10 @@ struct rb_sim {
     int critic_width() const {
         return rbc::row_dim(critic_mask, n_q, params ? n_params : 0, hist_rows * n_t);
     }
+    // goal pool (env_goal.hpp; rb_env_goal_pool_*): while set, every env-step launch and every reset is followed by goal_pool_kernel
+    // over its range, and rb_sample_goals(_dev) return pool rows.  Rows [m][n_q]; m is fixed by the first call, the pointer never moves
+    float *d_goal_pool = nullptr;
+    int64_t goal_pool_m = 0;
 };
 
 namespace {
@@ -994,6 +999,18 @@ int critic_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float 
     RB_HIP(hipGetLastError());
     return RB_OK;
 }
+// ---- goal pool (env_goal.hpp): one launch behind an env step (d_done: its done words) or a reset (null: every env), over [i0, i0 + cnt) ----
+int goal_pool_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const uint32_t *d_done, float *d_obs) {
+    rbg::GoalPoolArgs a;
+    a.pool = s->d_goal_pool; a.done = d_done; a.goal_count = s->d_goal_count; a.goal = s->d_goal; a.obs = d_obs;
+    a.n = s->n; a.i0 = i0; a.i1 = i0 + cnt;
+    a.seed = s->seed; a.env0 = uint64_t(s->env0);
+    a.m = uint32_t(s->goal_pool_m);
+    a.nq = s->n_q; a.od = s->obs_dim(); a.rows = s->tree ? 1 : 0;
+    hipLaunchKernelGGL(rbg::goal_pool_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, a);
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
 void params_free(rb_sim *s) {
     (void)hipFree(s->d_params); (void)hipFree(s->d_param_draws); (void)hipFree(s->d_param_ranges);
     s->d_params = nullptr; s->d_param_draws = nullptr; s->d_param_ranges = nullptr;
@@ -1188,6 +1205,7 @@ void rb_destroy(rb_sim *s) {
     io_free(s);
     (void)hipFree(s->d_done_seen); (void)hipFree(s->d_done_kind);
     (void)hipFree(s->d_critic);
+    (void)hipFree(s->d_goal_pool);
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1406,8 +1424,12 @@ int rb_sample_goals(rb_sim *s, const uint8_t *mask, float *goal_q) {
         d_mask = s->d_u8;
     }
     if (mask) RB_HIP(hipMemsetAsync(s->d_rows, 0, sizeof(float) * s->n * s->n_q, s->stream));
-    hipLaunchKernelGGL(sample_goals_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream,
-                       s->d_rows, s->d_goal_count, d_mask, s->box, s->n_q, s->n, s->seed, uint64_t(s->env0), 1);
+    if (s->d_goal_pool)
+        hipLaunchKernelGGL(rbg::goal_pool_sample_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->d_goal_pool,
+                           uint32_t(s->goal_pool_m), s->d_rows, s->d_goal_count, d_mask, s->n_q, s->n, s->seed, uint64_t(s->env0), 1);
+    else
+        hipLaunchKernelGGL(sample_goals_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream,
+                           s->d_rows, s->d_goal_count, d_mask, s->box, s->n_q, s->n, s->seed, uint64_t(s->env0), 1);
     RB_HIP(hipGetLastError());
     RB_HIP(hipMemcpyAsync(goal_q, s->d_rows, sizeof(float) * s->n * s->n_q, hipMemcpyDeviceToHost, s->stream));
     RB_HIP(hipStreamSynchronize(s->stream));
@@ -1570,6 +1592,8 @@ int rb_rollout_fused_dev(rb_sim *s, const float *d_ring, int ring, int n_steps, 
     if (reinterpret_cast<uintptr_t>(d_ring) % 16) return fail(RB_EINVAL, "action ring must be 16-byte aligned");
     if (s->tree || s->ntx) return fail(RB_EUNSUPPORTED, "fused rollout is built for 8-tendon ball-joint robots");
     if (s->params) return params_refuse(s, "the fused rollout (rb_rollout_fused_dev)");
+    if (s->d_goal_pool)
+        return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) redraws goals inside one kernel and cannot draw them from a goal pool");
     if (n_steps == 0) return RB_OK;
     const long n = s->n;
     maybe_jit(s);
@@ -1592,8 +1616,12 @@ int rb_fill_actions_dev(rb_sim *s, float *d_act, uint32_t step) {
 int rb_sample_goals_dev(rb_sim *s, const uint8_t *d_mask, float *d_goal_q) {
     if (check(s) || !d_goal_q) return fail(RB_EINVAL, "null argument");
     RB_HIP(hipSetDevice(s->device));
-    hipLaunchKernelGGL(sample_goals_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream,
-                       d_goal_q, s->d_goal_count, d_mask, s->box, s->n_q, s->n, s->seed, uint64_t(s->env0), 0);
+    if (s->d_goal_pool)
+        hipLaunchKernelGGL(rbg::goal_pool_sample_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->d_goal_pool,
+                           uint32_t(s->goal_pool_m), d_goal_q, s->d_goal_count, d_mask, s->n_q, s->n, s->seed, uint64_t(s->env0), 0);
+    else
+        hipLaunchKernelGGL(sample_goals_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream,
+                           d_goal_q, s->d_goal_count, d_mask, s->box, s->n_q, s->n, s->seed, uint64_t(s->env0), 0);
     RB_HIP(hipGetLastError());
     return RB_OK;
 }
@@ -1672,6 +1700,10 @@ int rb_env_reset_dev(rb_sim *s, float *d_obs) {
         const int od = s->obs_dim();
         hipLaunchKernelGGL(rbh::hist_zero_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, od, od - s->hist_rows * s->n_t, long(s->n));
         RB_HIP(hipGetLastError());
+    }
+    if (s->d_goal_pool) {                     // every env's goal becomes the pool row of the draw the reset kernel made
+        const int rc = goal_pool_launch(s, 0, s->n, s->stream, nullptr, d_obs);
+        if (rc) return rc;
     }
     if (s->critic_mask) {                     // the privileged rows of the reset state, behind every kernel that wrote the rows above
         int rc = critic_check(s);
@@ -1872,6 +1904,45 @@ int rb_env_critic_obs_ptr(rb_sim *s, float **d_rows) {
     return RB_OK;
 }
 
+// ---- goal pool: env goals drawn from a set of poses instead of the box (env_goal.hpp) ----
+int rb_env_goal_pool_set(rb_sim *s, const float *goal_q, int64_t m) {
+    if (check(s) || !goal_q) return fail(RB_EINVAL, "null argument");
+    if (m < 1 || m > int64_t(UINT32_MAX)) return fail(RB_EINVAL, "goal pool: m must be >= 1 (and below 2^32)");
+    if (s->d_goal_pool && m != s->goal_pool_m)
+        return fail(RB_EINVAL, "goal pool: the handle's pool has " + std::to_string(s->goal_pool_m) + " rows, fixed by the first call; got " + std::to_string(m));
+    // the angle box of rb_env_configure, or the robot's own box (what rb_sample_goals draws from) without an env layer
+    for (int64_t r = 0; r < m; ++r)
+        for (int j = 0; j < s->n_q; ++j) {
+            const float v = goal_q[r * s->n_q + j];
+            const float lo = s->env_ready ? s->env.a_lo : s->box.lo[j], hi = s->env_ready ? s->env.a_hi : s->box.hi[j];
+            if (!std::isfinite(v) || v < lo || v > hi)
+                return fail(RB_EINVAL, "goal pool: row " + std::to_string(r) + ", joint " + std::to_string(j) + " is not finite or outside the angle box");
+        }
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);                       // nothing in flight may still read the rows
+    if (rc) return rc;
+    const size_t bytes = sizeof(float) * size_t(m) * size_t(s->n_q);
+    if (!s->d_goal_pool) {
+        float *d = nullptr;
+        hipError_t e = hipMalloc(&d, bytes);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RB_ENOMEM : RB_EHIP, std::string("hipMalloc (goal pool): ") + hipGetErrorString(e));
+        e = hipMemcpy(d, goal_q, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { (void)hipFree(d); return fail(RB_EHIP, std::string("hipMemcpy (goal pool): ") + hipGetErrorString(e)); }
+        s->d_goal_pool = d; s->goal_pool_m = m;      // (from here on the env step and the reset launch goal_pool_kernel)
+        // an env layer already drew every env's goal from the box (rb_env_configure resets): that draw's pool row takes its place,
+        // counters untouched, so from here on every goal of the handle is a row of the pool
+        return s->env_ready ? goal_pool_launch(s, 0, s->n, s->stream, nullptr, nullptr) : RB_OK;
+    }
+    RB_HIP(hipMemcpy(s->d_goal_pool, goal_q, bytes, hipMemcpyHostToDevice));      // in place: a captured graph reads the new rows on its next replay
+    return RB_OK;
+}
+int rb_env_goal_pool_ptr(rb_sim *s, float **d_pool, int64_t *m) {
+    if (check(s) || !d_pool || !m) return fail(RB_EINVAL, "null argument");
+    if (!s->d_goal_pool) return fail(RB_EINVAL, "no goal pool is set (rb_env_goal_pool_set)");
+    *d_pool = s->d_goal_pool; *m = s->goal_pool_m;
+    return RB_OK;
+}
+
 int rb_env_obs_dim(rb_sim *s, int32_t *obs_dim) {
     if (check(s) || !obs_dim) return fail(RB_EINVAL, "null argument");
     *obs_dim = s->obs_dim();
@@ -1902,6 +1973,10 @@ static int env_step_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, con
     L.i0 = i0; L.cnt = cnt; L.stream = stream; L.act = d_act; L.obs = d_obs; L.reward = d_reward; L.done = d_done;
     const int rc = dispatch(s, ENTRY_ENV, L);
     if (rc != RB_OK) return rc;
+    if (s->d_goal_pool) {                     // the done envs' new goal becomes a pool row, in front of everything that reads the goal (same stream)
+        const int rc1 = goal_pool_launch(s, i0, cnt, stream, d_done, d_obs);
+        if (rc1) return rc1;
+    }
     if (s->critic_mask) {                     // the privileged rows of the range, from the planes as the step left them (same stream)
         const int rc2 = critic_launch(s, i0, cnt, stream, d_obs, d_cobs ? d_cobs : s->d_critic);
         if (rc2) return rc2;

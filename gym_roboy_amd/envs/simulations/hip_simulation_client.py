@@ -44,6 +44,7 @@ class HipBatchSimulation:
         self._stream = None            # what set_stream last handed to the library (None: the handle's own stream)
         self.n_params = 0              # P while per-env parameters are enabled
         self._d_param_mask = None      # sample_params(mask): device copy of the mask (first use)
+        self._goal_pool_m = 0          # rows of the goal pool set through set_goal_pool (0: none)
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -344,16 +345,35 @@ class HipBatchSimulation:
         nat.check(self._lib.rb_sample_goals_dev(self._h, ctypes.c_void_p(d_mask or 0),
                                                 ctypes.c_void_p(d_goal)))
 
+    # -- goal pool (rb_env_goal_pool_*) --------------------
+    def set_goal_pool(self, goals):
+        """Draw goals from the rows of ``goals`` (an ``envs.goals.GoalPool`` or an array ``[m, n_q]`` inside the robot's joint limits)
+        instead of the box: ``get_new_goal_joint_angles`` / ``sample_goals_dev`` then return pool rows.  The first call fixes m; a
+        later one replaces the rows in place."""
+        from ..goals import goal_rows
+        rows = goal_rows(goals, self.n_q, self._desc.q_lo, self._desc.q_hi, m=self._goal_pool_m or None)
+        nat.check(self._lib.rb_env_goal_pool_set(self._h, nat.fptr(rows), rows.shape[0]))
+        self._goal_pool_m = int(rows.shape[0])
+
+    def goal_pool(self) -> np.ndarray:
+        """The pool's rows ``[m, n_q]`` as the device holds them."""
+        d_pool, m = ctypes.c_void_p(), ctypes.c_int64()
+        nat.check(self._lib.rb_env_goal_pool_ptr(self._h, ctypes.byref(d_pool), ctypes.byref(m)))
+        self.synchronize()
+        return self.download(d_pool.value, (int(m.value), self.n_q))
+
 
 class HipSimulationClient(SimulationClient):
     """Single-env ``SimulationClient`` backed by a batch of one on the GPU."""
 
     def __init__(self, robot: RoboyRobot, process_idx: int = 1, timeout_secs: int = 2,
-                 integrator="euler", n_substeps: int = 1, device: int = 0, seed: int = 0):
+                 integrator="euler", n_substeps: int = 1, device: int = 0, seed: int = 0, goals=None):
         # process_idx plays the role it has in the reference (which simulator
         # instance, ros_simulation_client.py:27-30): here, the global env id
         # that keys this env's random streams.  timeout_secs is accepted for
         # signature compatibility; an in-process call cannot time out.
+        # goals: an envs.goals.GoalPool or rows [m, n_q] - get_new_goal_joint_angles returns rows of that pool (the reference's
+        # simulator hands out FEASIBLE poses, ros_simulation_client.py:73-81), by the rule the vectorised env uses.
         self.robot = robot
         self._timeout_secs = timeout_secs
         self._step_size = 0.1   # ros_simulation_client.py:22
@@ -361,6 +381,12 @@ class HipSimulationClient(SimulationClient):
                                        n_substeps=n_substeps, device=device, seed=seed,
                                        env_id_offset=int(process_idx))
         self._n_t = robot.get_action_space().shape[0]
+        if goals is not None:
+            try:
+                self._sim.set_goal_pool(goals)
+            except Exception:
+                self._sim.close()
+                raise
 
     def _state(self, q, qd, feasible) -> RobotState:
         # float64 arrays like the reference's (ROS float lists -> np.array)

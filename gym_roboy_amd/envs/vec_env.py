@@ -22,6 +22,7 @@ import numpy as np
 
 from .. import _native as nat
 from .._gymcompat import spaces
+from . import goals as envgoals
 from . import reward as rw
 from .robots import RoboyRobot
 from .simulations.hip_simulation_client import HipBatchSimulation
@@ -141,7 +142,7 @@ class RoboyVecEnv:
                  auto_reset: bool = True, integrator="euler", n_substeps: int = 1,
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
                  randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None,
-                 report_truncation: bool = False, action_obs=None, critic_obs=None):
+                 report_truncation: bool = False, action_obs=None, critic_obs=None, goals=None):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
@@ -170,7 +171,12 @@ class RoboyVecEnv:
         them, without noise ``| episode age / max_episode_length | the env's parameters (needs randomization) | its action delay (needs
         action_delay) | the K action blocks of the observation (needs action_obs)]``, ``critic_obs_dim`` columns, ``"state"``
         always.  The row belongs to the observation row returned with it (an auto-reset env shows its reset state, new goal and redrawn
-        parameters).  ``critic_obs()`` returns the last rows; observations, rewards, dones and statistics are unchanged."""
+        parameters).  ``critic_obs()`` returns the last rows; observations, rewards, dones and statistics are unchanged.
+        ``goals``: an ``envs.goals.GoalPool`` (``reachable_goals(robot, m)``) or an array ``[m, n_q]`` inside the angle box - every goal
+        the env draws, at a reset and at every episode end, is a row of this pool instead of a point uniform in the goal box: row
+        ``k(seed, global env id, draw number)`` (every robot, every kernel form, every option above).  Reward and done of
+        the step that ends an episode use the old goal as before; ``set_goal`` still overrides.  ``goal_pool()`` returns the rows,
+        ``set_goal_pool(rows)`` replaces them in place by as many others.  None: the env launches exactly what it launched before."""
         desc = robot.get_description()
         crit_names, crit_mask, crit_dim = critic_obs_spec(critic_obs, desc.n_q, desc.n_t, randomization is not None, action_delay, action_obs)
         obs_names = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
@@ -207,7 +213,16 @@ class RoboyVecEnv:
             if not (np.all(box.low == box.low[0]) and np.all(box.high == box.high[0])):
                 raise NotImplementedError("fused env layer expects uniform per-joint boxes")
         self._cfg = cfg
+        # (bad rows: before anything is configured)
+        pool_rows = None if goals is None else self._or_close(lambda: envgoals.goal_rows(goals, self.n_q, angles.low, angles.high))
+        self.goal_recipe = dict(goals.recipe) if isinstance(goals, envgoals.GoalPool) else {}
         nat.check(self.sim._lib.rb_env_configure(self.sim.handle, ctypes.byref(cfg)))
+        self._goal_pool_m = 0
+        if pool_rows is not None:
+            # before anything is captured into a graph: every env-step launch and reset is followed by the small kernel that puts the
+            # pool's rows in place of the box goals (the first call also turns the goal rb_env_configure's reset drew, draw 0, into its
+            # pool row: the draw counters stay those of an env without a pool)
+            self._or_close(lambda: self._set_goal_pool_rows(pool_rows))
         self.tendon_obs = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
         self.tendon_obs_scale = tendon_obs_scales(tendon_obs_scale)
         self.obs_dim = 3 * self.n_q
@@ -282,10 +297,35 @@ class RoboyVecEnv:
     def _or_close(self, configure):
         """an option the library refuses (a joint tree asked for a ball-joint option) must not leave the simulation's handle behind"""
         try:
-            configure()
+            return configure()
         except Exception:
             self.sim.close()
             raise
+
+    # -- goal pool (rb_env_goal_pool_*; DESIGN.md §22) -------------------
+    def _set_goal_pool_rows(self, rows):
+        nat.check(self.sim._lib.rb_env_goal_pool_set(self.sim.handle, nat.fptr(rows), rows.shape[0]))
+        self._goal_pool_m = int(rows.shape[0])
+
+    def goal_pool(self) -> np.ndarray:
+        """The pool's rows ``[m, n_q]`` as the device holds them; needs ``goals``."""
+        if not self._goal_pool_m:
+            raise RuntimeError("this RoboyVecEnv draws its goals from the box (goals=None)")
+        d_pool, m = ctypes.c_void_p(), ctypes.c_int64()
+        nat.check(self.sim._lib.rb_env_goal_pool_ptr(self.sim.handle, ctypes.byref(d_pool), ctypes.byref(m)))
+        self.sim.synchronize()
+        return self.sim.download(d_pool.value, (int(m.value), self.n_q))
+
+    def set_goal_pool(self, goals):
+        """Replace the pool's rows in place by as many others (a ``GoalPool`` or an array ``[m, n_q]``), between steps: goals drawn from
+        now on - also by a captured graph's next replay, the device rows do not move - are rows of the new pool; goals already drawn
+        stay until their env draws again.  Needs ``goals``; ``ValueError`` for another size."""
+        if not self._goal_pool_m:
+            raise RuntimeError("this RoboyVecEnv draws its goals from the box (goals=None): a pool is given at construction")
+        angles = self.robot.get_joint_angles_space()
+        rows = envgoals.goal_rows(goals, self.n_q, angles.low, angles.high, m=self._goal_pool_m)
+        self._set_goal_pool_rows(rows)
+        self.goal_recipe = dict(goals.recipe) if isinstance(goals, envgoals.GoalPool) else {}
 
     # ------------------------------------------------------------------
     def reset(self):

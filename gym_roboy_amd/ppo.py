@@ -1501,6 +1501,8 @@ class PPO:
             ck["critic_obs"] = _critic_obs_of(self.env)
             ck["critic_obs_dim"] = self.cobs_dim
             ck["critic_obs_norm"] = self.cobs_norm.state_dict() if self.cobs_norm is not None else None
+        if getattr(self.env, "_goal_pool_m", 0):     # (an env that draws its goals from the box writes the checkpoint it always wrote)
+            ck["goals"] = {"q": torch.from_numpy(self.env.goal_pool()), "recipe": dict(getattr(self.env, "goal_recipe", {}) or {})}
         if self.lr_schedule is not None:             # (an agent without a schedule writes the checkpoint it always wrote)
             ck["lr_schedule"] = {"kind": self.lr_schedule, "desired_kl": self.desired_kl, "lr_factor": self.lr_factor,
                                  "lr_min": self.lr_min, "lr_max": self.lr_max, "lr": self.learning_rate}
@@ -1517,6 +1519,9 @@ class PPO:
         if self.asymmetric_critic and (ck["critic_obs"] != _critic_obs_of(self.env) or int(ck["critic_obs_dim"]) != self.cobs_dim):
             raise ValueError("the checkpoint's critic was trained on the rows %r (%d columns), this env writes %r (%d; RoboyVecEnv's "
                              "critic_obs)" % (ck["critic_obs"], int(ck["critic_obs_dim"]), _critic_obs_of(self.env), self.cobs_dim))
+        # the goal pool the checkpoint was trained on (rows and recipe; None: box goals), for a caller that wants the same goals again:
+        # visualize_agent replays with them.  The env keeps its own pool - the policy reads a goal as columns, whichever way it was drawn
+        self.checkpoint_goals = ck.get("goals")
         if (ck.get("obs_norm") is not None) != (self.obs_norm is not None):      # (a checkpoint without the key: written without it)
             raise ValueError("the checkpoint was trained %s observation normalisation, this agent runs %s it (PPO's normalize_obs)"
                              % (("with", "without") if self.obs_norm is None else ("without", "with")))

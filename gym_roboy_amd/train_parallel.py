@@ -24,6 +24,20 @@ def log_line(stats):
     return {k: float("%.3g" % v) if k in ("approx_kl", "lr") else round(v, 4) for k, v in stats.items()}
 
 
+DEFAULT_GOAL_POOL = 16384
+ENV_INTEGRATOR = "euler"                         # RoboyVecEnv's default: the pool is settled with the integrator the env steps with
+
+
+def parse_goals(text):
+    """``--goals``: "" -> 0 (box goals), "reachable" -> 16384, "reachable:M" -> M"""
+    if not text:
+        return 0
+    kind, _, m = text.partition(":")
+    if kind != "reachable" or (m and (not m.isdigit() or int(m) < 1)):
+        raise SystemExit("--goals takes reachable or reachable:M with M >= 1, got %r" % text)
+    return int(m) if m else DEFAULT_GOAL_POOL
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("num_envs", type=int, help="environments per GPU (the reference's num_cpu)")
@@ -57,6 +71,10 @@ def main(argv=None):
                     help="an asymmetric critic: the value net is trained on privileged rows the env writes beside the observation - state "
                          "(exact q, qd, goal; always part of the row), age, params, delay (needs --action-delay), actions (needs "
                          "--action-obs), e.g. state,age,delay,actions; only the actor is deployed; recorded in the checkpoint")
+    ap.add_argument("--goals", default="", metavar="reachable[:M]",
+                    help="draw every goal from a pool of M poses (default 16384) the robot holds under constant set-points, made once "
+                         "at start with the run's seed and integrator (envs.goals.reachable_goals; every rank makes the same pool) "
+                         "instead of uniformly in the goal box; rows and recipe are stored in the checkpoint")
     ap.add_argument("--normalize-obs", action="store_true",
                     help="running mean / variance normalisation of the observation inside the policy kernels (what "
                          "stable-baselines calls VecNormalize); the statistics are stored in the checkpoint")
@@ -84,6 +102,7 @@ def main(argv=None):
     tendon_obs = tuple(c for c in args.tendon_obs.split(",") if c)
     critic_obs = tuple(c for c in args.critic_obs.split(",") if c)
     tendon_obs_scale = {k: float(v) for k, v in (item.split("=", 1) for item in args.tendon_obs_scale.split(",") if item)}
+    goals_m = parse_goals(args.goals)
 
     import torch
     from .envs.robots import MsjRobot
@@ -108,7 +127,13 @@ def main(argv=None):
     if rank == 0:
         os.makedirs(results, exist_ok=True)
 
-    env = RoboyVecEnv(MsjRobot(), args.num_envs, seed=args.seed, device=local_rank,
+    goals = None
+    if goals_m:
+        from .envs.goals import reachable_goals
+        goals = reachable_goals(MsjRobot(), goals_m, seed=args.seed, integrator=ENV_INTEGRATOR, device=local_rank)
+        if rank == 0:
+            print("goal pool:", goals.recipe)
+    env = RoboyVecEnv(MsjRobot(), args.num_envs, seed=args.seed, device=local_rank, integrator=ENV_INTEGRATOR, goals=goals,
                       env_id_offset=rank * args.num_envs, tendon_obs=tendon_obs or None, tendon_obs_scale=tendon_obs_scale or None,
                       sensor_noise=sensor_noise or None, action_delay=action_delay,
                       report_truncation=args.bootstrap_timeouts, action_obs=args.action_obs or None,

@@ -46,6 +46,8 @@ def main(argv=None):
     action_obs = int(env_io.get("action_obs") or 0)
     if isinstance(action_delay, list):
         action_delay = tuple(action_delay)
+    goals = ck.get("goals")                       # trained on a goal pool (train_parallel --goals): replay draws from the stored rows
+    goal_rows = None if goals is None else np.asarray(goals["q"], dtype=np.float32)
     if tendon_obs or sensor_noise or action_delay or action_obs:
         # trained with tendon channels in the observation (train_parallel --tendon-obs), sensor noise, an action delay or the last
         # actions in the observation (--sensor-noise, --action-delay, --action-obs): the same row, under the same conditions, comes from a RoboyVecEnv of one env, which resets
@@ -53,7 +55,7 @@ def main(argv=None):
         from .envs.vec_env import TENDON_OBS_CHANNELS, RoboyVecEnv
         scale = dict(zip(TENDON_OBS_CHANNELS, ck["tendon_obs"]["scale"])) if tendon_obs else None
         vec = RoboyVecEnv(MsjRobot(), 1, tendon_obs=tendon_obs or None, tendon_obs_scale=scale, sensor_noise=sensor_noise,
-                          action_delay=action_delay, action_obs=action_obs or None)
+                          action_delay=action_delay, action_obs=action_obs or None, goals=goal_rows)
         reset = lambda: vec.reset()[0]
 
         def step(a):
@@ -61,7 +63,7 @@ def main(argv=None):
             return o[0], float(r[0]), False
         n_obs, n_act = vec.observation_space.shape[0], vec.action_space.shape[0]
     else:
-        env = RoboyEnv(simulation_client=HipSimulationClient(robot=MsjRobot()))
+        env = RoboyEnv(simulation_client=HipSimulationClient(robot=MsjRobot(), goals=goal_rows))
         reset = env.reset
 
         def step(a):

@@ -532,6 +532,35 @@ int rb_env_step_critic_dev(rb_sim *sim, const float *d_act, float *d_obs, float 
 int rb_env_step_range_critic_dev(rb_sim *sim, int64_t first_env, int64_t n_envs, void *hip_stream,
                                  const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done, float *d_cobs);
 
+/* ---- goal pool: env goals drawn from a set of poses the robot can hold instead of the goal box ----
+ * The reference asks its simulator for a FEASIBLE goal pose (ros_..py:73-81); a goal uniform in a box need not be one the tendons can
+ * hold.  While a handle holds a pool of m rows [m][n_q], goal number `draw` of the env with global id gid = env_id_offset + i is row
+ *     k = (uint64(w) * uint64(m)) >> 32,   w = word 0 of Philox4x32-10(key = seed, counter = (gid, draw, stream 4 << 8 | 0))
+ * of the pool, bit for bit: one multiply-shift and no rejection loop, so a row's probability is off 1 / m by at most 2^-32 (a relative
+ * bias of at most m / 2^32).  Keyed by the global env id: goals do not depend on sharding.  `draw` is the env's goal counter, which
+ * advances as without a pool (+1 at a reset; at an episode end +1, or +2 with auto_reset, where the row is the one of the second draw).
+ * Where it applies:
+ *   - every env-step entry, every kernel form, every robot class: one small kernel directly behind the step kernel (same stream, same
+ *     envs, in front of the critic rows and the episode-end codes) gives each env that is done its row, in the goal plane and in
+ *     columns [2 n_q, 3 n_q) of its observation row - with and without auto_reset.  Envs that are not done are untouched.  Reward,
+ *     done and statistics of the step that ended the episode used the old goal, as without a pool;
+ *   - rb_env_reset_dev: every env's goal, in the plane and (d_obs != NULL) in the observation row;
+ *   - rb_sample_goals and rb_sample_goals_dev: rows of the pool by the same rule, so a single-env client draws what the batched env does.
+ * rb_rollout_fused_dev redraws goals inside one kernel and returns RB_EUNSUPPORTED while a pool is set.  rb_env_set_goal still
+ * overrides everything.  A handle without a pool launches exactly what it launched before.
+ *   set: goal_q is a host array [m][n_q], m >= 1; every value finite and inside the angle box of rb_env_configure (without an env layer:
+ *        inside the robot's own box, which rb_sample_goals draws from), else RB_EINVAL before anything is enqueued or changed.  The
+ *        first call fixes m for the handle's lifetime and allocates the device copy; a later call with the same m overwrites the rows
+ *        IN PLACE - the pointer never moves, so a graph captured earlier reads the new rows on its next replay - and one with another
+ *        m is refused with RB_EINVAL.  Drains the handle's streams and copies synchronously: call the first one before a caller
+ *        captures env steps, later ones between steps.  The first call on a handle with an env layer also replaces every env's
+ *        current goal, drawn from the box, by the pool row of that same draw (counters untouched): from then on every goal of the
+ *        handle is a row of the pool.  After a later call, goals already drawn stay until their env draws again.
+ *   ptr: the device rows and m; RB_EINVAL while no pool is set.
+ * RB_ABI_VERSION is still 6 (nothing that existed changed): look rb_env_goal_pool_set up before relying on it. */
+int rb_env_goal_pool_set(rb_sim *sim, const float *goal_q /* host, [m][n_q] */, int64_t m);
+int rb_env_goal_pool_ptr(rb_sim *sim, float **d_pool, int64_t *m);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
