@@ -85,6 +85,9 @@ RB_DONE_NONE, RB_DONE_TERMINATED, RB_DONE_TRUNCATED = 0, 1, 2      # the done wo
 CRITIC_OBS_BLOCKS = ("state", "age", "params", "delay", "actions")
 RB_CRITIC_STATE, RB_CRITIC_AGE, RB_CRITIC_PARAMS, RB_CRITIC_DELAY, RB_CRITIC_ACTIONS = 1, 2, 4, 8, 16
 RB_CRITIC_OBS_MAX_DIM = 63
+# rb_env_goal_curriculum_configure: the most levels; what the index plane reads behind rb_env_set_goal
+RB_GOAL_LEVELS_MAX = 256
+RB_GOAL_INDEX_NONE = 0xFFFFFFFF
 
 
 class EnvIoConfig(ctypes.Structure):
@@ -165,6 +168,12 @@ SIGNATURES = {
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "rb_env_goal_pool_set": (ctypes.c_int, [_sim, _fp, ctypes.c_int64]),
     "rb_env_goal_pool_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64)]),
+    "rb_env_goal_curriculum_configure": (ctypes.c_int, [_sim, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "rb_env_goal_level_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp)]),
+    "rb_env_goal_index_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp)]),
+    "rb_env_goal_levels_set": (ctypes.c_int, [_sim, _u32p]),
+    "rb_env_goal_level_hist_dev": (ctypes.c_int, [_sim, _vp, _vp]),
+    "rb_env_goal_level_hist": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_uint64)]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

@@ -587,6 +587,12 @@ struct rb_sim {
     // over its range, and rb_sample_goals(_dev) return pool rows.  Rows [m][n_q]; m is fixed by the first call, the pointer never moves
     float *d_goal_pool = nullptr;
     int64_t goal_pool_m = 0;
+    // goal curriculum over the pool's row order (env_goal.hpp; rb_env_goal_curriculum_*): while curr_L > 0, goal_pool_launch enqueues
+    // goal_curriculum_kernel in place of goal_pool_kernel.  Planes [n] each: the env's level, the row it holds, and the goals-reached
+    // counter d_ep_cnt[2n + i] as of its last episode end (a copy of its own: episode-end codes may be off)
+    uint32_t curr_L = 0, curr_up = 0, curr_down = 0;
+    uint32_t *d_goal_level = nullptr, *d_goal_index = nullptr, *d_goal_seen = nullptr;      // one allocation, d_goal_level its start
+    uint64_t *d_goal_hist = nullptr;          // [L] counts behind the planes: rb_env_goal_level_hist's device buffer
 };
 
 namespace {
@@ -1007,7 +1013,15 @@ int goal_pool_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const uin
     a.seed = s->seed; a.env0 = uint64_t(s->env0);
     a.m = uint32_t(s->goal_pool_m);
     a.nq = s->n_q; a.od = s->obs_dim(); a.rows = s->tree ? 1 : 0;
-    hipLaunchKernelGGL(rbg::goal_pool_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, a);
+    if (s->curr_L) {                          // a curriculum: the same launch, the row drawn inside the env's window
+        rbg::GoalCurriculumArgs c;
+        c.p = a;
+        c.level = s->d_goal_level; c.index = s->d_goal_index; c.seen = s->d_goal_seen;
+        c.reached = s->d_ep_cnt + 2 * size_t(s->n);
+        c.L = s->curr_L; c.up = s->curr_up; c.down = s->curr_down;
+        hipLaunchKernelGGL(rbg::goal_curriculum_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, c);
+    } else
+        hipLaunchKernelGGL(rbg::goal_pool_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, a);
     RB_HIP(hipGetLastError());
     return RB_OK;
 }
@@ -1019,6 +1033,10 @@ void params_free(rb_sim *s) {
 // refusal of the entry points that have no parameter form
 int params_refuse(rb_sim *s, const char *what) {
     return fail(RB_EUNSUPPORTED, std::string(what) + " has no per-env-parameter form: the handle has parameters enabled (rb_params_disable first)");
+}
+// rb_sample_goals(_dev) on a handle with a goal curriculum: without an env step there is no episode outcome to move a level
+int curriculum_refuse_sample(rb_sim *) {
+    return fail(RB_EUNSUPPORTED, "rb_sample_goals: the handle has a goal curriculum, whose levels move with the env layer's episode ends");
 }
 
 }  // namespace
@@ -1206,6 +1224,7 @@ void rb_destroy(rb_sim *s) {
     (void)hipFree(s->d_done_seen); (void)hipFree(s->d_done_kind);
     (void)hipFree(s->d_critic);
     (void)hipFree(s->d_goal_pool);
+    (void)hipFree(s->d_goal_level);          // (with it the index plane, the seen plane and the histogram counts)
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1417,6 +1436,7 @@ int rb_step(rb_sim *s, const float *act, float act_scale, float *q, float *qd, u
 
 int rb_sample_goals(rb_sim *s, const uint8_t *mask, float *goal_q) {
     if (check(s) || !goal_q) return fail(RB_EINVAL, "null argument");
+    if (s->curr_L) return curriculum_refuse_sample(s);
     RB_HIP(hipSetDevice(s->device));
     const uint8_t *d_mask = nullptr;
     if (mask) {
@@ -1615,6 +1635,7 @@ int rb_fill_actions_dev(rb_sim *s, float *d_act, uint32_t step) {
 
 int rb_sample_goals_dev(rb_sim *s, const uint8_t *d_mask, float *d_goal_q) {
     if (check(s) || !d_goal_q) return fail(RB_EINVAL, "null argument");
+    if (s->curr_L) return curriculum_refuse_sample(s);
     RB_HIP(hipSetDevice(s->device));
     if (s->d_goal_pool)
         hipLaunchKernelGGL(rbg::goal_pool_sample_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->d_goal_pool,
@@ -1654,6 +1675,7 @@ int rb_env_configure(rb_sim *s, const rb_env_config *cfg) {
     RB_HIP(hipMemsetAsync(s->d_ep_sum, 0, sizeof(double) * size_t(s->n) * 2, s->stream));
     RB_HIP(hipMemsetAsync(s->d_ep_cnt, 0, sizeof(uint32_t) * size_t(s->n) * 3, s->stream));
     if (s->done_kind) RB_HIP(hipMemsetAsync(s->d_done_seen, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
+    if (s->curr_L) RB_HIP(hipMemsetAsync(s->d_goal_seen, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
     RB_HIP(hipMemsetAsync(s->d_infeas_n, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
     s->env_steps = 0.0;
     s->env_ready = true;
@@ -1701,7 +1723,8 @@ int rb_env_reset_dev(rb_sim *s, float *d_obs) {
         hipLaunchKernelGGL(rbh::hist_zero_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, od, od - s->hist_rows * s->n_t, long(s->n));
         RB_HIP(hipGetLastError());
     }
-    if (s->d_goal_pool) {                     // every env's goal becomes the pool row of the draw the reset kernel made
+    if (s->d_goal_pool) {                     // every env's goal becomes the pool row of the draw the reset kernel made (a curriculum:
+        // inside the env's window, levels as they stand, and its `seen` plane re-based to the counters like d_done_seen above)
         const int rc = goal_pool_launch(s, 0, s->n, s->stream, nullptr, d_obs);
         if (rc) return rc;
     }
@@ -1943,6 +1966,95 @@ int rb_env_goal_pool_ptr(rb_sim *s, float **d_pool, int64_t *m) {
     return RB_OK;
 }
 
+// ---- goal curriculum: a level per env over the pool's row order (env_goal.hpp) ----
+int rb_env_goal_curriculum_configure(rb_sim *s, int32_t levels, int32_t up, int32_t down, int32_t level0) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
+    if (!s->d_goal_pool) return fail(RB_EINVAL, "goal curriculum: no goal pool is set (rb_env_goal_pool_set first)");
+    if (s->curr_L) return fail(RB_EINVAL, "goal curriculum: already configured (once per handle: a captured graph holds the arguments by value)");
+    const int64_t most = s->goal_pool_m < RB_GOAL_LEVELS_MAX ? s->goal_pool_m : int64_t(RB_GOAL_LEVELS_MAX);
+    if (levels < 1 || levels > most)
+        return fail(RB_EINVAL, "goal curriculum: levels must be in 1.." + std::to_string(most) + " (at most the pool's rows and RB_GOAL_LEVELS_MAX = 256), got " +
+                                   std::to_string(levels));
+    if (up < 0 || down < 0) return fail(RB_EINVAL, "goal curriculum: up and down must be >= 0");
+    if (level0 < 0 || level0 >= levels) return fail(RB_EINVAL, "goal curriculum: level0 must be in 0..levels - 1");
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);                       // nothing in flight may still launch the pool's own kernel
+    if (rc) return rc;
+    rc = drop_graphs(s);
+    if (rc) return rc;
+    const size_t plane = sizeof(uint32_t) * size_t(s->n);
+    if (!s->d_goal_level) {                  // (one block: the three planes, then the host histogram's L counts)
+        uint32_t *d = nullptr;
+        const hipError_t e = hipMalloc(&d, 3 * plane + sizeof(uint64_t) * RB_GOAL_LEVELS_MAX + 8);
+        if (e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? RB_ENOMEM : RB_EHIP, std::string("hipMalloc (goal curriculum): ") + hipGetErrorString(e));
+        s->d_goal_level = d; s->d_goal_index = d + s->n; s->d_goal_seen = d + 2 * s->n;
+        s->d_goal_hist = reinterpret_cast<uint64_t *>((reinterpret_cast<uintptr_t>(d + 3 * s->n) + 7) & ~uintptr_t(7));
+    }
+    {
+        std::vector<uint32_t> l0(size_t(s->n), uint32_t(level0));
+        RB_HIP(hipMemcpy(s->d_goal_level, l0.data(), plane, hipMemcpyHostToDevice));
+    }
+    s->curr_L = uint32_t(levels); s->curr_up = uint32_t(up); s->curr_down = uint32_t(down);      // (from here on goal_pool_launch enqueues goal_curriculum_kernel)
+    // every env's current goal, a row of the whole pool, becomes the row of that same draw inside its window (counters untouched);
+    // the launch also sets `seen` to the counters as they stand and fills the index plane
+    return goal_pool_launch(s, 0, s->n, s->stream, nullptr, nullptr);
+}
+static int curriculum_check(rb_sim *s) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->curr_L) return fail(RB_EINVAL, "no goal curriculum is configured (rb_env_goal_curriculum_configure)");
+    return RB_OK;
+}
+int rb_env_goal_level_ptr(rb_sim *s, uint32_t **d_level) {
+    if (curriculum_check(s)) return RB_EINVAL;
+    if (!d_level) return fail(RB_EINVAL, "null argument");
+    *d_level = s->d_goal_level;
+    return RB_OK;
+}
+int rb_env_goal_index_ptr(rb_sim *s, uint32_t **d_index) {
+    if (curriculum_check(s)) return RB_EINVAL;
+    if (!d_index) return fail(RB_EINVAL, "null argument");
+    *d_index = s->d_goal_index;
+    return RB_OK;
+}
+int rb_env_goal_levels_set(rb_sim *s, const uint32_t *levels) {
+    if (curriculum_check(s)) return RB_EINVAL;
+    if (!levels) return fail(RB_EINVAL, "null argument");
+    for (long i = 0; i < s->n; ++i)
+        if (levels[i] >= s->curr_L)
+            return fail(RB_EINVAL, "goal levels: env " + std::to_string(i) + " has level " + std::to_string(levels[i]) + ", the curriculum has " +
+                                       std::to_string(s->curr_L) + " levels");
+    RB_HIP(hipSetDevice(s->device));
+    const int rc = drain(s);                 // nothing in flight may still move a level
+    if (rc) return rc;
+    RB_HIP(hipMemcpy(s->d_goal_level, levels, sizeof(uint32_t) * size_t(s->n), hipMemcpyHostToDevice));
+    return RB_OK;
+}
+int rb_env_goal_level_hist_dev(rb_sim *s, uint64_t *d_out, void *hip_stream) {
+    if (curriculum_check(s)) return RB_EINVAL;
+    if (!d_out) return fail(RB_EINVAL, "null argument");
+    RB_HIP(hipSetDevice(s->device));
+    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
+    RB_HIP(hipMemsetAsync(d_out, 0, sizeof(uint64_t) * s->curr_L, st));
+    unsigned g = blocks_for(s->n, 256);
+    if (g > 1024u) g = 1024u;                // (grid-stride beyond: at most 1024 x L atomics into the output)
+    hipLaunchKernelGGL(rbg::goal_level_hist_kernel, dim3(g), dim3(256), 0, st, s->d_goal_level, long(s->n), s->curr_L,
+                       reinterpret_cast<unsigned long long *>(d_out));
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
+int rb_env_goal_level_hist(rb_sim *s, uint64_t *out) {
+    if (curriculum_check(s)) return RB_EINVAL;
+    if (!out) return fail(RB_EINVAL, "null argument");
+    RB_HIP(hipSetDevice(s->device));
+    const int rc = rb_env_goal_level_hist_dev(s, s->d_goal_hist, nullptr);
+    if (rc) return rc;
+    RB_HIP(hipMemcpyAsync(out, s->d_goal_hist, sizeof(uint64_t) * s->curr_L, hipMemcpyDeviceToHost, s->stream));
+    RB_HIP(hipStreamSynchronize(s->stream));
+    return RB_OK;
+}
+
 int rb_env_obs_dim(rb_sim *s, int32_t *obs_dim) {
     if (check(s) || !obs_dim) return fail(RB_EINVAL, "null argument");
     *obs_dim = s->obs_dim();
@@ -1959,6 +2071,8 @@ int rb_env_set_goal(rb_sim *s, const float *goal_q, const uint32_t *step_num) {
     RB_HIP(hipGetLastError());
     if (step_num)
         RB_HIP(hipMemcpyAsync(s->d_step_num, step_num, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s->stream));
+    if (s->curr_L)                            // these goals are no row of the pool: RB_GOAL_INDEX_NONE, every byte 0xFF
+        RB_HIP(hipMemsetAsync(s->d_goal_index, 0xFF, sizeof(uint32_t) * n, s->stream));
     RB_HIP(hipStreamSynchronize(s->stream));
     return RB_OK;
 }
@@ -2087,6 +2201,7 @@ static int stats_reset(rb_sim *s) {
         RB_HIP(hipMemsetAsync(s->d_ep_sum, 0, sizeof(double) * size_t(s->n) * 2, s->stream));
         RB_HIP(hipMemsetAsync(s->d_ep_cnt, 0, sizeof(uint32_t) * size_t(s->n) * 3, s->stream));
         if (s->done_kind) RB_HIP(hipMemsetAsync(s->d_done_seen, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
+        if (s->curr_L) RB_HIP(hipMemsetAsync(s->d_goal_seen, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
     }
     RB_HIP(hipMemsetAsync(s->d_infeas_n, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
     s->env_steps = 0.0;

@@ -11,6 +11,7 @@ import numpy as np
 from . import reward as rw
 
 MAX_BATCHES = 4
+MAX_LEVELS = 256      # RB_GOAL_LEVELS_MAX: the most levels of a goal curriculum
 
 
 class GoalPool:
@@ -27,6 +28,49 @@ class GoalPool:
 
     def __len__(self):
         return self.q.shape[0]
+
+    def ordered(self, key="rest_distance"):
+        """A new ``GoalPool`` with the rows sorted from easiest to hardest, which is what a goal curriculum (``RoboyVecEnv(...,
+        goal_curriculum=...)``) takes row order for.  ``"rest_distance"``: by ``|q|_2`` from the zero pose every episode
+        starts from, formed in float64; a stable sort, so ties keep pool order.  ``source`` is permuted with the rows and the recipe
+        gains ``"ordered": key``."""
+        if key != "rest_distance":
+            raise ValueError("a goal pool is ordered by 'rest_distance', got %r" % (key,))
+        order = np.argsort(np.sqrt(np.sum(np.square(self.q.astype(np.float64)), axis=1)), kind="stable")
+        recipe = dict(self.recipe)
+        recipe["ordered"] = key
+        return GoalPool(self.q[order], recipe, None if self.source is None else self.source[order])
+
+
+def goal_curriculum_spec(goal_curriculum, m=None):
+    """``goal_curriculum``: None, an int ``L`` or ``dict(levels=, up=1, down=1, start=0)`` -> None or the dict with all four keys as
+    ints, checked as ``rb_env_goal_curriculum_configure`` checks them: ``1 <= levels <= min(m, 256)`` (``m``: the pool's rows, where
+    known), ``up, down >= 0``, ``0 <= start < levels``.  ``ValueError`` otherwise."""
+    if goal_curriculum is None:
+        return None
+    spec = {"levels": None, "up": 1, "down": 1, "start": 0}
+    if isinstance(goal_curriculum, dict):
+        unknown = sorted(set(goal_curriculum) - set(spec))
+        if unknown:
+            raise ValueError("goal_curriculum: unknown keys %s (levels, up, down, start)" % unknown)
+        spec.update(goal_curriculum)
+    elif isinstance(goal_curriculum, (int, np.integer)) and not isinstance(goal_curriculum, bool):
+        spec["levels"] = goal_curriculum
+    else:
+        raise ValueError("goal_curriculum is None, an int (the number of levels) or a dict(levels=, up=1, down=1, start=0), got %r"
+                         % (goal_curriculum,))
+    for k, v in spec.items():
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("goal_curriculum: %s must be an int, got %r" % (k, v))
+        spec[k] = int(v)
+    most = MAX_LEVELS if m is None else min(int(m), MAX_LEVELS)
+    if not 1 <= spec["levels"] <= most:
+        raise ValueError("goal_curriculum: levels must be in 1..%d (at most the pool's rows and %d), got %d" % (most, MAX_LEVELS, spec["levels"]))
+    if spec["up"] < 0 or spec["down"] < 0:
+        raise ValueError("goal_curriculum: up and down must be >= 0")
+    if not 0 <= spec["start"] < spec["levels"]:
+        raise ValueError("goal_curriculum: start must be in 0..levels - 1, got %d" % spec["start"])
+    return spec
 
 
 def goal_rows(goals, n_q: int, low, high, m=None) -> np.ndarray:

@@ -26,7 +26,10 @@ class RoboyEnv(BaseGoalEnv):
 
     def __init__(self, simulation_client: SimulationClient = None, seed: int = None,
                  joint_vel_penalty: bool = False,
-                 is_agent_getting_bonus_for_reaching_goal: bool = True, goals=None):
+                 is_agent_getting_bonus_for_reaching_goal: bool = True, goals=None, goal_curriculum=None):
+        if goal_curriculum is not None:
+            raise ValueError("goal_curriculum is an option of the vectorised env (RoboyVecEnv): a single-env client draws goals without "
+                             "an episode outcome that could move a level")
         if goals is not None and simulation_client is not None:
             raise ValueError("goals= belongs to the client that draws them: HipSimulationClient(robot, goals=...)")
         if simulation_client is None:

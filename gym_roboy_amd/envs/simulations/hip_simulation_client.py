@@ -367,13 +367,16 @@ class HipSimulationClient(SimulationClient):
     """Single-env ``SimulationClient`` backed by a batch of one on the GPU."""
 
     def __init__(self, robot: RoboyRobot, process_idx: int = 1, timeout_secs: int = 2,
-                 integrator="euler", n_substeps: int = 1, device: int = 0, seed: int = 0, goals=None):
+                 integrator="euler", n_substeps: int = 1, device: int = 0, seed: int = 0, goals=None, goal_curriculum=None):
         # process_idx plays the role it has in the reference (which simulator
         # instance, ros_simulation_client.py:27-30): here, the global env id
         # that keys this env's random streams.  timeout_secs is accepted for
         # signature compatibility; an in-process call cannot time out.
         # goals: an envs.goals.GoalPool or rows [m, n_q] - get_new_goal_joint_angles returns rows of that pool (the reference's
         # simulator hands out FEASIBLE poses, ros_simulation_client.py:73-81), by the rule the vectorised env uses.
+        if goal_curriculum is not None:
+            raise ValueError("goal_curriculum is an option of the vectorised env (RoboyVecEnv): a single-env client draws goals without "
+                             "an episode outcome that could move a level")
         self.robot = robot
         self._timeout_secs = timeout_secs
         self._step_size = 0.1   # ros_simulation_client.py:22

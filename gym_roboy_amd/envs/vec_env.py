@@ -17,6 +17,7 @@ returns ``(obs [N, obs_dim], reward [N], done [N], infos)`` of the same kind;
 ``obs_dim`` is ``3 n_q``, or ``3 n_q + C n_t`` with ``tendon_obs`` (C channels), plus ``K n_t`` with ``action_obs=K``.
 """
 import ctypes
+import warnings
 
 import numpy as np
 
@@ -142,7 +143,7 @@ class RoboyVecEnv:
                  auto_reset: bool = True, integrator="euler", n_substeps: int = 1,
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
                  randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None,
-                 report_truncation: bool = False, action_obs=None, critic_obs=None, goals=None):
+                 report_truncation: bool = False, action_obs=None, critic_obs=None, goals=None, goal_curriculum=None):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
@@ -176,13 +177,27 @@ class RoboyVecEnv:
         the env draws, at a reset and at every episode end, is a row of this pool instead of a point uniform in the goal box: row
         ``k(seed, global env id, draw number)`` (every robot, every kernel form, every option above).  Reward and done of
         the step that ends an episode use the old goal as before; ``set_goal`` still overrides.  ``goal_pool()`` returns the rows,
-        ``set_goal_pool(rows)`` replaces them in place by as many others.  None: the env launches exactly what it launched before."""
+        ``set_goal_pool(rows)`` replaces them in place by as many others.  None: the env launches exactly what it launched before.
+        ``goal_curriculum``: an int ``L`` or ``dict(levels=L, up=1, down=1, start=0)`` - a difficulty level per env over the pool's
+        rows taken from easiest to hardest (needs ``goals``): an env at level ``l`` draws from the first
+        ``(l + 1) m / L`` rows, moves ``up`` levels when an episode ends at its goal and ``down`` when it ends otherwise, and draws its
+        next goal at the new level.  A ``GoalPool`` whose recipe is not marked ordered is ordered by ``GoalPool.ordered()`` (distance
+        from the rest pose) with a warning; bare row arrays are taken as ordered.  ``goal_levels()``, ``goal_index()`` and
+        ``goal_level_histogram()`` read the levels, the rows held and the envs per level; ``set_goal_levels(levels)`` writes the levels.
+        At the top level an env draws exactly what it draws without the option."""
         desc = robot.get_description()
         crit_names, crit_mask, crit_dim = critic_obs_spec(critic_obs, desc.n_q, desc.n_t, randomization is not None, action_delay, action_obs)
         obs_names = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
         sig = sensor_noise_sigmas(sensor_noise, obs_names)               # (bad options: before anything is allocated)
         d_lo, d_hi, ranged = action_delay_range(action_delay)
         n_action_rows = action_obs_rows(action_obs)
+        curriculum = envgoals.goal_curriculum_spec(goal_curriculum)
+        if curriculum is not None:
+            if goals is None:
+                raise ValueError("goal_curriculum needs goals= (a pool whose row order it takes for difficulty order)")
+            if isinstance(goals, envgoals.GoalPool) and not goals.recipe.get("ordered"):
+                warnings.warn("goal_curriculum: the goal pool's recipe is not marked ordered; ordering it by rest_distance (GoalPool.ordered())")
+                goals = goals.ordered()
         self.robot = robot
         self.num_envs = int(num_envs)
         self.sim = HipBatchSimulation(robot, num_envs, integrator=integrator, n_substeps=n_substeps,
@@ -223,6 +238,14 @@ class RoboyVecEnv:
             # pool's rows in place of the box goals (the first call also turns the goal rb_env_configure's reset drew, draw 0, into its
             # pool row: the draw counters stay those of an env without a pool)
             self._or_close(lambda: self._set_goal_pool_rows(pool_rows))
+        self.goal_curriculum = None
+        if curriculum is not None:
+            # directly behind the pool, before anything is captured into a graph: from here on the curriculum's kernel stands in the
+            # pool kernel's place (the call also redraws every env's goal inside its window; the draw counters stay as they are)
+            self._or_close(lambda: envgoals.goal_curriculum_spec(curriculum, m=self._goal_pool_m))
+            self._or_close(lambda: nat.check(self.sim._lib.rb_env_goal_curriculum_configure(
+                self.sim.handle, curriculum["levels"], curriculum["up"], curriculum["down"], curriculum["start"])))
+            self.goal_curriculum = dict(curriculum)
         self.tendon_obs = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
         self.tendon_obs_scale = tendon_obs_scales(tendon_obs_scale)
         self.obs_dim = 3 * self.n_q
@@ -326,6 +349,59 @@ class RoboyVecEnv:
         rows = envgoals.goal_rows(goals, self.n_q, angles.low, angles.high, m=self._goal_pool_m)
         self._set_goal_pool_rows(rows)
         self.goal_recipe = dict(goals.recipe) if isinstance(goals, envgoals.GoalPool) else {}
+
+    # -- goal curriculum (rb_env_goal_curriculum_*) --------
+    def _curriculum_plane(self, getter):
+        """a uint32 plane [N] of the curriculum: numpy, or a CUDA int64 tensor when the last step was a torch step"""
+        if self.goal_curriculum is None:
+            raise RuntimeError("this RoboyVecEnv has no goal curriculum (goal_curriculum=None)")
+        ptr = ctypes.c_void_p()
+        nat.check(getter(self.sim.handle, ctypes.byref(ptr)))
+        self.sim.synchronize()
+        plane = self.sim.download(ptr.value, (self.num_envs,), np.uint32)
+        if _is_cuda_tensor(self._last_actions):
+            import torch
+            return torch.from_numpy(plane.astype(np.int64)).to(self._last_actions.device)
+        return plane
+
+    def goal_levels(self):
+        """``[N]``: every env's level, 0 (the easiest rows only) to ``levels - 1`` (the whole pool).  Needs ``goal_curriculum``."""
+        return self._curriculum_plane(self.sim._lib.rb_env_goal_level_ptr)
+
+    def goal_index(self):
+        """``[N]``: the pool row every env's goal is; ``_native.RB_GOAL_INDEX_NONE`` behind ``set_goal``.  Needs ``goal_curriculum``."""
+        return self._curriculum_plane(self.sim._lib.rb_env_goal_index_ptr)
+
+    def set_goal_levels(self, levels):
+        """Write every env's level ``[N]`` (ints below ``levels``), between steps: goals already drawn stay until their env draws
+        again.  ``ValueError`` for a level out of range, and nothing has changed then."""
+        if self.goal_curriculum is None:
+            raise RuntimeError("this RoboyVecEnv has no goal curriculum (goal_curriculum=None)")
+        if _is_cuda_tensor(levels):
+            levels = levels.cpu().numpy()
+        lv = np.asarray(levels)
+        if lv.shape != (self.num_envs,) or lv.dtype.kind not in "iu":
+            raise ValueError("levels must be %d ints" % self.num_envs)
+        if np.any(lv < 0) or np.any(lv >= self.goal_curriculum["levels"]):
+            raise ValueError("levels must lie in 0..%d" % (self.goal_curriculum["levels"] - 1))
+        lv = np.ascontiguousarray(lv, dtype=np.uint32)
+        nat.check(self.sim._lib.rb_env_goal_levels_set(self.sim.handle, lv.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+
+    def goal_level_histogram(self):
+        """``[levels]`` counts: how many envs sit at each level (one small kernel; numpy int64, or a CUDA tensor after a torch step)."""
+        if self.goal_curriculum is None:
+            raise RuntimeError("this RoboyVecEnv has no goal curriculum (goal_curriculum=None)")
+        n_levels = self.goal_curriculum["levels"]
+        if _is_cuda_tensor(self._last_actions):
+            import torch
+            device = self._last_actions.device
+            out = torch.empty((n_levels,), dtype=torch.int64, device=device)
+            nat.check(self.sim._lib.rb_env_goal_level_hist_dev(self.sim.handle, ctypes.c_void_p(out.data_ptr()),
+                                                               ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+            return out
+        out = np.empty(n_levels, np.uint64)
+        nat.check(self.sim._lib.rb_env_goal_level_hist(self.sim.handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return out.astype(np.int64)
 
     # ------------------------------------------------------------------
     def reset(self):

@@ -1503,6 +1503,11 @@ class PPO:
             ck["critic_obs_norm"] = self.cobs_norm.state_dict() if self.cobs_norm is not None else None
         if getattr(self.env, "_goal_pool_m", 0):     # (an env that draws its goals from the box writes the checkpoint it always wrote)
             ck["goals"] = {"q": torch.from_numpy(self.env.goal_pool()), "recipe": dict(getattr(self.env, "goal_recipe", {}) or {})}
+        curriculum = getattr(self.env, "goal_curriculum", None)
+        if curriculum is not None:                   # (an env without a goal curriculum writes the checkpoint it always wrote)
+            level = self.env.goal_levels()
+            ck["goal_curriculum"] = {"levels": curriculum["levels"], "up": curriculum["up"], "down": curriculum["down"],
+                                     "level": (level if torch.is_tensor(level) else torch.from_numpy(level.astype("int64"))).cpu()}
         if self.lr_schedule is not None:             # (an agent without a schedule writes the checkpoint it always wrote)
             ck["lr_schedule"] = {"kind": self.lr_schedule, "desired_kl": self.desired_kl, "lr_factor": self.lr_factor,
                                  "lr_min": self.lr_min, "lr_max": self.lr_max, "lr": self.learning_rate}
@@ -1522,6 +1527,16 @@ class PPO:
         # the goal pool the checkpoint was trained on (rows and recipe; None: box goals), for a caller that wants the same goals again:
         # visualize_agent replays with them.  The env keeps its own pool - the policy reads a goal as columns, whichever way it was drawn
         self.checkpoint_goals = ck.get("goals")
+        # the goal curriculum's levels go back into an env with as many levels and envs; otherwise the env keeps its own and the
+        # checkpoint's are kept here, as the goals above
+        self.checkpoint_goal_curriculum = None
+        saved = ck.get("goal_curriculum")
+        if saved is not None:
+            own = getattr(self.env, "goal_curriculum", None)
+            if own is not None and own["levels"] == int(saved["levels"]) and int(saved["level"].numel()) == self.env.num_envs:
+                self.env.set_goal_levels(saved["level"].cpu().numpy())
+            else:
+                self.checkpoint_goal_curriculum = saved
         if (ck.get("obs_norm") is not None) != (self.obs_norm is not None):      # (a checkpoint without the key: written without it)
             raise ValueError("the checkpoint was trained %s observation normalisation, this agent runs %s it (PPO's normalize_obs)"
                              % (("with", "without") if self.obs_norm is None else ("without", "with")))

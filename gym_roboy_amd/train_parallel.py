@@ -38,6 +38,29 @@ def parse_goals(text):
     return int(m) if m else DEFAULT_GOAL_POOL
 
 
+def parse_goal_curriculum(levels, up, down, goals_m):
+    """``--goal-levels L --goal-up U --goal-down D``: None without ``--goal-levels``, else RoboyVecEnv's ``goal_curriculum`` dict;
+    needs ``--goals`` (``goals_m``: its pool size, 0 without) and ``1 <= L <= min(M, 256)``, ``U, D >= 0``"""
+    if not levels:
+        if up is not None or down is not None:
+            raise SystemExit("--goal-up and --goal-down need --goal-levels")
+        return None
+    if not goals_m:
+        raise SystemExit("--goal-levels needs --goals (a curriculum runs over a goal pool)")
+    up, down = 1 if up is None else up, 1 if down is None else down
+    if not 1 <= levels <= min(goals_m, 256) or up < 0 or down < 0:
+        raise SystemExit("--goal-levels takes 1..min(M, 256), --goal-up and --goal-down take >= 0; got %d, %d, %d with a pool of %d"
+                         % (levels, up, down, goals_m))
+    return {"levels": levels, "up": up, "down": down, "start": 0}
+
+
+def level_summary(hist):
+    """the level histogram (summed over the ranks) as it is logged: the mean level and the share of envs at the top level"""
+    h = [float(x) for x in hist]
+    n = max(sum(h), 1.0)
+    return {"mean_level": sum(l * c for l, c in enumerate(h)) / n, "top_level_share": h[-1] / n}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("num_envs", type=int, help="environments per GPU (the reference's num_cpu)")
@@ -75,6 +98,12 @@ def main(argv=None):
                     help="draw every goal from a pool of M poses (default 16384) the robot holds under constant set-points, made once "
                          "at start with the run's seed and integrator (envs.goals.reachable_goals; every rank makes the same pool) "
                          "instead of uniformly in the goal box; rows and recipe are stored in the checkpoint")
+    ap.add_argument("--goal-levels", type=int, default=0, metavar="L",
+                    help="a goal curriculum over the pool ordered by distance from the rest pose (needs --goals): every env starts at "
+                         "level 0 of L, draws its goals from the nearest (level + 1) / L of the pool, and moves with its episodes' "
+                         "outcomes; levels are stored in the checkpoint")
+    ap.add_argument("--goal-up", type=int, default=None, metavar="U", help="levels up after an episode that reached its goal (default 1)")
+    ap.add_argument("--goal-down", type=int, default=None, metavar="D", help="levels down after an episode that did not (default 1)")
     ap.add_argument("--normalize-obs", action="store_true",
                     help="running mean / variance normalisation of the observation inside the policy kernels (what "
                          "stable-baselines calls VecNormalize); the statistics are stored in the checkpoint")
@@ -103,6 +132,7 @@ def main(argv=None):
     critic_obs = tuple(c for c in args.critic_obs.split(",") if c)
     tendon_obs_scale = {k: float(v) for k, v in (item.split("=", 1) for item in args.tendon_obs_scale.split(",") if item)}
     goals_m = parse_goals(args.goals)
+    goal_curriculum = parse_goal_curriculum(args.goal_levels, args.goal_up, args.goal_down, goals_m)
 
     import torch
     from .envs.robots import MsjRobot
@@ -131,13 +161,15 @@ def main(argv=None):
     if goals_m:
         from .envs.goals import reachable_goals
         goals = reachable_goals(MsjRobot(), goals_m, seed=args.seed, integrator=ENV_INTEGRATOR, device=local_rank)
+        if goal_curriculum is not None:
+            goals = goals.ordered()
         if rank == 0:
             print("goal pool:", goals.recipe)
     env = RoboyVecEnv(MsjRobot(), args.num_envs, seed=args.seed, device=local_rank, integrator=ENV_INTEGRATOR, goals=goals,
                       env_id_offset=rank * args.num_envs, tendon_obs=tendon_obs or None, tendon_obs_scale=tendon_obs_scale or None,
                       sensor_noise=sensor_noise or None, action_delay=action_delay,
                       report_truncation=args.bootstrap_timeouts, action_obs=args.action_obs or None,
-                      critic_obs=critic_obs or None)
+                      critic_obs=critic_obs or None, goal_curriculum=goal_curriculum)
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,
@@ -155,10 +187,17 @@ def main(argv=None):
         local = env.stats()
         block = torch.tensor([local[k] for k in STAT_KEYS], dtype=torch.float64,
                              device="cuda" if (dist is not None and args.backend == "nccl") else "cpu")
+        if goal_curriculum is not None:         # the envs per level ride along: [8 statistics | L counts]
+            hist = env.goal_level_histogram()
+            hist = hist if torch.is_tensor(hist) else torch.from_numpy(hist)
+            block = torch.cat((block, hist.to(block)))
         allreduce_stats(block, dist)
         if rank == 0:
             agent.save(model_file)
-            print("episode statistics (all ranks):", summarize(block.cpu()))
+            summary = summarize(block[:len(STAT_KEYS)].cpu())
+            if goal_curriculum is not None:
+                summary.update(level_summary(block[len(STAT_KEYS):].cpu()))
+            print("episode statistics (all ranks):", summary)
     if world > 1:
         dist.destroy_process_group()
     return agent

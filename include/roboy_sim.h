@@ -561,6 +561,45 @@ int rb_env_step_range_critic_dev(rb_sim *sim, int64_t first_env, int64_t n_envs,
 int rb_env_goal_pool_set(rb_sim *sim, const float *goal_q /* host, [m][n_q] */, int64_t m);
 int rb_env_goal_pool_ptr(rb_sim *sim, float **d_pool, int64_t *m);
 
+/* ---- goal curriculum: a difficulty level per env over an ORDERED goal pool ----
+ * A one-up / one-down staircase per env on top of a goal pool whose rows the caller has ordered from easiest to hardest (the library
+ * never sorts: row order is difficulty order).  Every env carries a level l in [0, L).  An env at level l draws from the rows
+ *     [0, hi(l)),   hi(l) = uint32((uint64(l + 1) * m) / L)
+ * so hi(L - 1) = m, hi(0) >= 1, and the windows are cumulative: easy goals keep occurring.  The draw is the pool's, scaled by the window:
+ *     k = (uint64(w) * uint64(hi(l))) >> 32,   w = word 0 of Philox4x32-10(key = seed, counter = (gid, draw, stream 4 << 8 | 0))
+ * with draw = goal counter - 1 after the step, as above.  An env at level L - 1 draws exactly the row a handle with the plain pool
+ * draws, and L = 1 is the plain pool plus the index plane.
+ * An episode end in a step (done word non-zero) decides the outcome first: "reached" iff the env's goals-reached counter (the
+ * statistics' n_goal_reached, per env) differs from the value the curriculum saw at the env's last episode end - the rule of the
+ * episode-end codes, on a plane of the curriculum's own, so the codes may be off.  Reached: l <- min(l + up, L - 1); not reached:
+ * l <- l - min(l, down).  Then the value seen becomes the counter, the row is drawn at the NEW level, its number goes into the index
+ * plane and its values into the goal plane and the observation row's goal columns, as the pool writes them.  Envs that are not done
+ * are untouched.  One kernel, launched IN PLACE of the pool's behind every env-step launch: the launches per step are a pool handle's.
+ *   - rb_env_reset_dev: levels do not move; the value seen becomes every env's counter; every env draws within its window.
+ *   - rb_env_configure again and rb_env_stats(_dev) with reset clear the value seen with the counters they clear.
+ *   - rb_env_set_goal: the index plane reads RB_GOAL_INDEX_NONE for every env until it draws again.
+ *   - rb_env_goal_pool_set in place (same m): levels and indices stay; the new rows must be ordered again, which is the caller's business.
+ *   - rb_rollout_fused_dev refuses while a pool is set; rb_sample_goals and rb_sample_goals_dev return RB_EUNSUPPORTED on a handle
+ *     with a curriculum (without an env layer there is no outcome to move a level).
+ *   configure: needs rb_env_configure and rb_env_goal_pool_set.  1 <= levels <= min(m, RB_GOAL_LEVELS_MAX), up >= 0, down >= 0,
+ *        0 <= level0 < levels, else RB_EINVAL before anything is enqueued or changed.  ONCE per handle - the arguments travel by value
+ *        in the kernel's argument block and a captured graph freezes them - a second call is RB_EINVAL.  Drains the handle's streams,
+ *        allocates the planes (level = level0 everywhere), then redraws every env's goal once by the rule above (draw counters
+ *        untouched: they stay those of a handle without a curriculum).  Call it before a caller captures env steps.
+ *   level_ptr, index_ptr: the device planes uint32 [n]; RB_EINVAL without a curriculum.
+ *   levels_set: host uint32 [n], every value < levels or RB_EINVAL before anything changes; drains the streams, copies, does not redraw.
+ *   level_hist_dev: d_out[levels] uint64 = how many envs sit at each level, on `hip_stream` (NULL: the handle's): a memset of d_out
+ *        and one kernel, capturable.  level_hist: the same into host memory, synchronous.
+ * RB_ABI_VERSION is still 6 (nothing that existed changed): look rb_env_goal_curriculum_configure up before relying on it. */
+#define RB_GOAL_LEVELS_MAX 256
+#define RB_GOAL_INDEX_NONE 0xFFFFFFFFu
+int rb_env_goal_curriculum_configure(rb_sim *sim, int32_t levels, int32_t up, int32_t down, int32_t level0);
+int rb_env_goal_level_ptr(rb_sim *sim, uint32_t **d_level);
+int rb_env_goal_index_ptr(rb_sim *sim, uint32_t **d_index);
+int rb_env_goal_levels_set(rb_sim *sim, const uint32_t *host_levels /* [n] */);
+int rb_env_goal_level_hist_dev(rb_sim *sim, uint64_t *d_out /* [levels] */, void *hip_stream);
+int rb_env_goal_level_hist(rb_sim *sim, uint64_t *out /* host, [levels] */);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
