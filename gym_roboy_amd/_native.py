@@ -174,6 +174,11 @@ SIGNATURES = {
     "rb_env_goal_levels_set": (ctypes.c_int, [_sim, _u32p]),
     "rb_env_goal_level_hist_dev": (ctypes.c_int, [_sim, _vp, _vp]),
     "rb_env_goal_level_hist": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_uint64)]),
+    "rb_env_goal_row_stats_enable": (ctypes.c_int, [_sim]),
+    "rb_env_goal_row_stats_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64)]),
+    "rb_env_goal_row_stats_read": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "rb_env_goal_row_stats_set": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_uint64)]),
+    "rb_env_goal_pool_permute": (ctypes.c_int, [_sim, _u32p]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

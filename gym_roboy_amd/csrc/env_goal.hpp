@@ -25,6 +25,11 @@
 // curriculum is configured goal_curriculum_kernel is launched IN PLACE of goal_pool_kernel: the launches per step are a pool handle's.
 // The window, the row and the level rule are plain functions a host compiler takes too (tests/hostmath/goal_curriculum_host.cpp):
 // without hipcc this header declares them and no kernel.
+//
+// Outcome counts per pool row (rb_env_goal_row_stats_*): while a handle has them enabled, goal_curriculum_stats_kernel
+// is launched IN PLACE of goal_curriculum_kernel - the same lane text plus, for a lane whose episode ended in an env step, one add
+// into attempts[row it was aimed at] and, if it reached it, one into reached[row].  rb_env_goal_pool_permute re-orders a live pool:
+// rows and counts on the host, the index plane by goal_index_permute_kernel.
 #pragma once
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -106,28 +111,109 @@ struct GoalCurriculumArgs {
     uint32_t L, up, down;
 };
 
+// One lane of the curriculum, as TEXT: goal_curriculum_kernel is this body and nothing else, and goal_curriculum_stats_kernel holds
+// it between its own loads and its adds, so neither calls through a function that could change the other's instruction stream.
+// `c`: the GoalCurriculumArgs; BLOCK: the lanes per workgroup of the kernel it stands in; EXIT: how a lane with nothing to do leaves
+// the text (`return`, or `break` where the text stands in a do { } while (0) and the kernel goes on behind it).
+#define RBG_CURRICULUM_LANE(c, BLOCK, EXIT)                                                                                             \
+    const GoalPoolArgs &a = c.p;                                                                                                        \
+    const long i = a.i0 + long(blockIdx.x) * BLOCK + threadIdx.x;                                                                       \
+    if (i >= a.i1) EXIT;                                                                                                                \
+    if (a.done && !a.done[i]) EXIT;                                                                                                     \
+    uint32_t l = c.level[i];                                                                                                            \
+    if (l >= c.L) l = c.L - 1u; /* (the plane is the caller's to write through rb_env_goal_level_ptr: never index past the pool) */    \
+    const uint32_t r = c.reached[i];                                                                                                    \
+    if (a.done) { /* an episode end moves the level; a reset (done = null) does not */                                                  \
+        l = curriculum_next_level(l, r != c.seen[i], c.up, c.down, c.L);                                                               \
+        c.level[i] = l;                                                                                                                 \
+    }                                                                                                                                   \
+    c.seen[i] = r;                                                                                                                      \
+    const uint32_t k = curriculum_row(a.seed, a.env0 + uint64_t(i), a.goal_count[i] - 1u, l, a.m, c.L);                                 \
+    c.index[i] = k;                                                                                                                     \
+    const float *row = a.pool + size_t(k) * a.nq;                                                                                       \
+    const int nq = a.nq;                                                                                                                \
+    for (int j = 0; j < nq; ++j) {                                                                                                      \
+        const float g = row[j];                                                                                                         \
+        a.goal[state_index(i, j, nq, a.n, a.rows)] = g;                                                                                 \
+        if (a.obs) a.obs[i * a.od + 2 * nq + j] = g;                                                                                    \
+    }
+
 __global__ void __launch_bounds__(256)
 goal_curriculum_kernel(const GoalCurriculumArgs c) {
-    const GoalPoolArgs &a = c.p;
-    const long i = a.i0 + long(blockIdx.x) * 256 + threadIdx.x;
-    if (i >= a.i1) return;
-    if (a.done && !a.done[i]) return;
-    uint32_t l = c.level[i];
-    if (l >= c.L) l = c.L - 1u;               // (the plane is the caller's to write through rb_env_goal_level_ptr: never index past the pool)
-    const uint32_t r = c.reached[i];
-    if (a.done) {                             // an episode end moves the level; a reset (done = null) does not
-        l = curriculum_next_level(l, r != c.seen[i], c.up, c.down, c.L);
-        c.level[i] = l;
+    RBG_CURRICULUM_LANE(c, 256, return)
+}
+
+// ---- outcome counts per pool row (rb_env_goal_row_stats_*): the curriculum's lane between the counting's loads and its adds ----
+// counts: uint64 [2][m], attempts[m] then reached[m].  A lane whose episode ended in an env step, aimed at row k0 = index[i] < m
+// (RB_GOAL_INDEX_NONE, behind rb_env_set_goal, is no row), adds 1 to attempts[k0] and, if its reached counter moved since its last
+// episode end - the outcome the level rule is about to use - 1 to reached[k0].  A reset launch (done = null) counts nothing.
+// Integer adds through global atomics whose result is unused: exact in any order, so ranges of one handle stepped on two streams
+// add into the same planes safely.
+//
+// One env per lane, 1024 lanes per workgroup.  Every lane reads its row and its outcome BEFORE the lane text writes the level, the
+// `seen` word or the index, and adds BEHIND it: the loads travel with the lane text's own, and the workgroup's barrier delays no
+// goal.  How the adds are made depends on how many of the workgroup's episodes ended (DESIGN.md §24 has the timings):
+//   - fewer than RBG_STATS_DENSE (training's ordinary step: a few per cent): each such lane adds into its row directly.  Lanes that
+//     share no row cost one memory-side request each, which is cheap while they are few;
+//   - otherwise (the envs time out together, or every step ends an episode): a histogram in LDS over the rows [0, RBG_STATS_BINS) -
+//     the first levels' windows, where the envs crowd - one word per row with attempts in the low half and reached in the high half
+//     (a workgroup adds at most 1024 to either).  It is flushed with one add per non-empty half, lane t taking the bins t, t + 1024,
+//     ...: neighbouring lanes add into neighbouring words, which the memory side takes as a few wide requests where the direct form
+//     sends one per lane.  A row beyond the bins is added to directly.
+struct GoalCurriculumStatsArgs {
+    GoalCurriculumArgs c;
+    unsigned long long *counts;               // [2][m]
+};
+
+#define RBG_STATS_BLOCK 1024
+#define RBG_STATS_BINS 4096u
+#define RBG_STATS_DENSE 512
+
+__global__ void __launch_bounds__(RBG_STATS_BLOCK)
+goal_curriculum_stats_kernel(const GoalCurriculumStatsArgs s) {
+    __shared__ uint32_t bins[RBG_STATS_BINS];
+    const GoalPoolArgs &p = s.c.p;
+    const long e = p.i0 + long(blockIdx.x) * RBG_STATS_BLOCK + threadIdx.x;
+    const bool ended = p.done && e < p.i1 && p.done[e];
+    uint32_t k0 = 0xFFFFFFFFu, hit = 0u;       // (no row)
+    if (ended) {                              // read here, in front of the lane text that overwrites them; used behind it
+        k0 = s.c.index[e];
+        hit = s.c.reached[e] != s.c.seen[e] ? 1u : 0u;
     }
-    c.seen[i] = r;
-    const uint32_t k = curriculum_row(a.seed, a.env0 + uint64_t(i), a.goal_count[i] - 1u, l, a.m, c.L);
-    c.index[i] = k;
-    const float *row = a.pool + size_t(k) * a.nq;
-    const int nq = a.nq;
-    for (int j = 0; j < nq; ++j) {
-        const float g = row[j];
-        a.goal[state_index(i, j, nq, a.n, a.rows)] = g;
-        if (a.obs) a.obs[i * a.od + 2 * nq + j] = g;
+    do {
+        RBG_CURRICULUM_LANE(s.c, RBG_STATS_BLOCK, break)
+    } while (0);
+    if (p.done) {                             // (uniform: a reset launch counts nothing)
+        if (__syncthreads_count(ended) >= RBG_STATS_DENSE) {
+            const uint32_t top = p.m < RBG_STATS_BINS ? p.m : RBG_STATS_BINS;
+            for (uint32_t b = threadIdx.x; b < top; b += RBG_STATS_BLOCK) bins[b] = 0u;
+            __syncthreads();
+            if (k0 < top) atomicAdd(&bins[k0], 1u | (hit << 16));
+            else if (k0 < p.m) {
+                atomicAdd(s.counts + k0, 1ull);
+                if (hit) atomicAdd(s.counts + p.m + k0, 1ull);
+            }
+            __syncthreads();
+            for (uint32_t b = threadIdx.x; b < top; b += RBG_STATS_BLOCK) {
+                const uint32_t w = bins[b];
+                if (w & 0xFFFFu) atomicAdd(s.counts + b, (unsigned long long)(w & 0xFFFFu));
+                if (w >> 16) atomicAdd(s.counts + p.m + b, (unsigned long long)(w >> 16));
+            }
+        } else if (k0 < p.m) {
+            atomicAdd(s.counts + k0, 1ull);
+            if (hit) atomicAdd(s.counts + p.m + k0, 1ull);
+        }
+    }
+}
+
+
+// rb_env_goal_pool_permute on a handle with a curriculum: index[i] <- inv[index[i]] (inv[old row] = new row), one env per lane,
+// grid-stride.  RB_GOAL_INDEX_NONE is no row (>= m) and stays as it is
+__global__ void __launch_bounds__(256)
+goal_index_permute_kernel(uint32_t *__restrict__ index, const uint32_t *__restrict__ inv, long n, uint32_t m) {
+    for (long i = long(blockIdx.x) * 256 + threadIdx.x; i < n; i += long(gridDim.x) * 256) {
+        const uint32_t k = index[i];
+        if (k < m) index[i] = inv[k];
     }
 }
 

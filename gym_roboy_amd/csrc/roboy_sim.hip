@@ -593,6 +593,9 @@ struct rb_sim {
     uint32_t curr_L = 0, curr_up = 0, curr_down = 0;
     uint32_t *d_goal_level = nullptr, *d_goal_index = nullptr, *d_goal_seen = nullptr;      // one allocation, d_goal_level its start
     uint64_t *d_goal_hist = nullptr;          // [L] counts behind the planes: rb_env_goal_level_hist's device buffer
+    // outcome counts per pool row (env_goal.hpp; rb_env_goal_row_stats_*): while non-null, goal_pool_launch enqueues
+    // goal_curriculum_stats_kernel in place of goal_curriculum_kernel.  [2][m]: attempts, then reached
+    uint64_t *d_goal_row_stats = nullptr;
 };
 
 namespace {
@@ -1019,7 +1022,12 @@ int goal_pool_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const uin
         c.level = s->d_goal_level; c.index = s->d_goal_index; c.seen = s->d_goal_seen;
         c.reached = s->d_ep_cnt + 2 * size_t(s->n);
         c.L = s->curr_L; c.up = s->curr_up; c.down = s->curr_down;
-        hipLaunchKernelGGL(rbg::goal_curriculum_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, c);
+        if (s->d_goal_row_stats) {            // outcome counts per row: the same launch again, two adds per episode end more
+            rbg::GoalCurriculumStatsArgs t;
+            t.c = c; t.counts = reinterpret_cast<unsigned long long *>(s->d_goal_row_stats);
+            hipLaunchKernelGGL(rbg::goal_curriculum_stats_kernel, dim3(blocks_for(cnt, RBG_STATS_BLOCK)), dim3(RBG_STATS_BLOCK), 0, stream, t);
+        } else
+            hipLaunchKernelGGL(rbg::goal_curriculum_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, c);
     } else
         hipLaunchKernelGGL(rbg::goal_pool_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, a);
     RB_HIP(hipGetLastError());
@@ -1225,6 +1233,7 @@ void rb_destroy(rb_sim *s) {
     (void)hipFree(s->d_critic);
     (void)hipFree(s->d_goal_pool);
     (void)hipFree(s->d_goal_level);          // (with it the index plane, the seen plane and the histogram counts)
+    (void)hipFree(s->d_goal_row_stats);
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -2053,6 +2062,114 @@ int rb_env_goal_level_hist(rb_sim *s, uint64_t *out) {
     RB_HIP(hipMemcpyAsync(out, s->d_goal_hist, sizeof(uint64_t) * s->curr_L, hipMemcpyDeviceToHost, s->stream));
     RB_HIP(hipStreamSynchronize(s->stream));
     return RB_OK;
+}
+
+// ---- outcome counts per pool row, and re-ordering a live pool (env_goal.hpp) ----
+int rb_env_goal_row_stats_enable(rb_sim *s) {
+    if (curriculum_check(s)) return RB_EINVAL;
+    if (s->d_goal_row_stats) return fail(RB_EINVAL, "goal row stats: already enabled (once per handle: a captured graph holds the kernel it was captured with)");
+    RB_HIP(hipSetDevice(s->device));
+    int rc = drain(s);                       // nothing in flight may still launch the curriculum's own kernel
+    if (rc) return rc;
+    rc = drop_graphs(s);
+    if (rc) return rc;
+    const size_t bytes = sizeof(uint64_t) * 2 * size_t(s->goal_pool_m);
+    uint64_t *d = nullptr;
+    hipError_t e = hipMalloc(&d, bytes);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RB_ENOMEM : RB_EHIP, std::string("hipMalloc (goal row stats): ") + hipGetErrorString(e));
+    e = hipMemset(d, 0, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { (void)hipFree(d); return fail(RB_EHIP, std::string("hipMemset (goal row stats): ") + hipGetErrorString(e)); }
+    s->d_goal_row_stats = d;                 // (from here on goal_pool_launch enqueues goal_curriculum_stats_kernel)
+    return RB_OK;
+}
+static int row_stats_check(rb_sim *s) {
+    if (check(s)) return RB_EINVAL;
+    if (!s->d_goal_row_stats) return fail(RB_EINVAL, "goal row stats are not enabled (rb_env_goal_row_stats_enable)");
+    return RB_OK;
+}
+int rb_env_goal_row_stats_ptr(rb_sim *s, uint64_t **d_counts, int64_t *m) {
+    if (row_stats_check(s)) return RB_EINVAL;
+    if (!d_counts || !m) return fail(RB_EINVAL, "null argument");
+    *d_counts = s->d_goal_row_stats; *m = s->goal_pool_m;
+    return RB_OK;
+}
+int rb_env_goal_row_stats_read(rb_sim *s, uint64_t *host, int clear) {
+    if (row_stats_check(s)) return RB_EINVAL;
+    if (!host) return fail(RB_EINVAL, "null argument");
+    RB_HIP(hipSetDevice(s->device));
+    const int rc = drain(s);                 // every count enqueued so far is in
+    if (rc) return rc;
+    const size_t bytes = sizeof(uint64_t) * 2 * size_t(s->goal_pool_m);
+    RB_HIP(hipMemcpy(host, s->d_goal_row_stats, bytes, hipMemcpyDeviceToHost));
+    if (clear) {
+        RB_HIP(hipMemset(s->d_goal_row_stats, 0, bytes));
+        RB_HIP(hipDeviceSynchronize());
+    }
+    return RB_OK;
+}
+int rb_env_goal_row_stats_set(rb_sim *s, const uint64_t *host) {
+    if (row_stats_check(s)) return RB_EINVAL;
+    if (!host) return fail(RB_EINVAL, "null argument");
+    const int64_t m = s->goal_pool_m;
+    for (int64_t k = 0; k < m; ++k)
+        if (host[m + k] > host[k])
+            return fail(RB_EINVAL, "goal row stats: row " + std::to_string(k) + " has reached " + std::to_string(host[m + k]) + " > attempts " +
+                                       std::to_string(host[k]));
+    RB_HIP(hipSetDevice(s->device));
+    const int rc = drain(s);                 // nothing in flight may still add to the planes
+    if (rc) return rc;
+    RB_HIP(hipMemcpy(s->d_goal_row_stats, host, sizeof(uint64_t) * 2 * size_t(m), hipMemcpyHostToDevice));
+    return RB_OK;
+}
+int rb_env_goal_pool_permute(rb_sim *s, const uint32_t *order) {
+    if (check(s) || !order) return fail(RB_EINVAL, "null argument");
+    if (!s->d_goal_pool) return fail(RB_EINVAL, "no goal pool is set (rb_env_goal_pool_set)");
+    const size_t m = size_t(s->goal_pool_m), nq = size_t(s->n_q);
+    std::vector<uint32_t> inv(m, UINT32_MAX);        // inv[old row] = new row
+    for (size_t j = 0; j < m; ++j) {
+        if (order[j] >= m) return fail(RB_EINVAL, "goal pool permute: entry " + std::to_string(j) + " is " + std::to_string(order[j]) + ", the pool has " + std::to_string(m) + " rows");
+        if (inv[order[j]] != UINT32_MAX) return fail(RB_EINVAL, "goal pool permute: row " + std::to_string(order[j]) + " occurs twice (not a permutation)");
+        inv[order[j]] = uint32_t(j);
+    }
+    RB_HIP(hipSetDevice(s->device));
+    const int rc = drain(s);                 // nothing in flight may still read the rows, the indices or the counts
+    if (rc) return rc;
+    uint32_t *d_inv = nullptr;
+    if (s->curr_L) {                         // (everything that can fail for want of memory: before anything changes)
+        const hipError_t e = hipMalloc(&d_inv, sizeof(uint32_t) * m);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RB_ENOMEM : RB_EHIP, std::string("hipMalloc (goal pool permute): ") + hipGetErrorString(e));
+    }
+    auto done = [&](hipError_t e, const char *what) {
+        (void)hipFree(d_inv);
+        return e == hipSuccess ? RB_OK : fail(RB_EHIP, std::string(what) + " (goal pool permute): " + hipGetErrorString(e));
+    };
+    // the rows through the host, back IN PLACE: the pointer never moves, so a graph captured earlier reads the new order
+    std::vector<float> rows(m * nq), out(m * nq);
+    hipError_t e = hipMemcpy(rows.data(), s->d_goal_pool, sizeof(float) * m * nq, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return done(e, "hipMemcpy");
+    for (size_t j = 0; j < m; ++j) std::memcpy(&out[j * nq], &rows[size_t(order[j]) * nq], sizeof(float) * nq);
+    e = hipMemcpy(s->d_goal_pool, out.data(), sizeof(float) * m * nq, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return done(e, "hipMemcpy");
+    if (s->d_goal_row_stats) {               // both count planes travel with their rows
+        std::vector<uint64_t> cnt(2 * m), cout2(2 * m);
+        e = hipMemcpy(cnt.data(), s->d_goal_row_stats, sizeof(uint64_t) * 2 * m, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return done(e, "hipMemcpy");
+        for (size_t j = 0; j < m; ++j) { cout2[j] = cnt[order[j]]; cout2[m + j] = cnt[m + order[j]]; }
+        e = hipMemcpy(s->d_goal_row_stats, cout2.data(), sizeof(uint64_t) * 2 * m, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return done(e, "hipMemcpy");
+    }
+    if (s->curr_L) {                         // every env keeps the pose it holds: its index becomes that row's new number
+        e = hipMemcpy(d_inv, inv.data(), sizeof(uint32_t) * m, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return done(e, "hipMemcpy");
+        unsigned g = blocks_for(s->n, 256);
+        if (g > 1024u) g = 1024u;            // (grid-stride beyond)
+        hipLaunchKernelGGL(rbg::goal_index_permute_kernel, dim3(g), dim3(256), 0, s->stream, s->d_goal_index, d_inv, long(s->n), uint32_t(m));
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        if (e != hipSuccess) return done(e, "index kernel");
+    }
+    return done(hipSuccess, "");
 }
 
 int rb_env_obs_dim(rb_sim *s, int32_t *obs_dim) {

@@ -14,9 +14,47 @@ MAX_BATCHES = 4
 MAX_LEVELS = 256      # RB_GOAL_LEVELS_MAX: the most levels of a goal curriculum
 
 
+def _count_array(x, name):
+    """counts as Python-int-exact numpy: a 1-d array of non-negative integers -> object array of Python ints"""
+    a = np.asarray(x)
+    if a.ndim != 1:
+        raise ValueError("%s must be a 1-d array of counts, got shape %s" % (name, a.shape))
+    if a.dtype.kind not in "iu" and not (a.dtype.kind == "O" and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in a)):
+        raise ValueError("%s must be integers, got dtype %s" % (name, a.dtype))
+    vals = [int(v) for v in a]
+    if any(v < 0 for v in vals):
+        raise ValueError("%s must be >= 0" % name)
+    return vals
+
+
+def reach_rate_order(attempts, reached, prior=(1, 2)):
+    """The permutation ``[m]`` (int64) that sorts pool rows from the most often reached to the least: by descending
+    ``(reached + a) / (attempts + b)`` with ``prior = (a, b)``, ``0 <= a <= b``, ``b > 0`` - the counts of
+    ``RoboyVecEnv.goal_row_stats()`` smoothed by ``b`` imagined attempts of which ``a`` reached.  Rates are compared as
+    exact rationals (``fractions.Fraction`` over Python ints, never floats: counts near 2^40 hold rates a float64 merges).  Ties keep
+    their current order; rows nobody has tried all tie at ``a / b``.  ``ValueError`` for mismatched shapes, negative counts,
+    ``reached > attempts`` or a prior outside the above."""
+    from fractions import Fraction
+    att, rch = _count_array(attempts, "attempts"), _count_array(reached, "reached")
+    if len(att) != len(rch):
+        raise ValueError("attempts and reached must have the same length, got %d and %d" % (len(att), len(rch)))
+    if any(r > t for r, t in zip(rch, att)):
+        raise ValueError("reached must not exceed attempts")
+    try:
+        a, b = prior
+        a, b = Fraction(a), Fraction(b)
+    except (TypeError, ValueError):
+        raise ValueError("prior is a pair (a, b) of numbers, got %r" % (prior,))
+    if a < 0 or b <= 0 or a > b:
+        raise ValueError("prior (a, b) needs 0 <= a <= b and b > 0, got %r" % (prior,))
+    rate = [(r + a) / (t + b) for r, t in zip(rch, att)]
+    return np.asarray(sorted(range(len(att)), key=lambda j: -rate[j]), dtype=np.int64)       # (sorted is stable)
+
+
 class GoalPool:
     """``q``: the poses ``[m, n_q]`` float32; ``recipe``: how they were made (``reachable_goals``' arguments plus the yield), or ``{}``;
-    ``source``: ``[m, 2]`` ints, the (batch, env) whose set-points (``settle_setpoints``) hold row j, or None."""
+    ``source``: ``[m, 2]`` ints, the (batch, env) whose set-points (``settle_setpoints``) hold row j, or None; ``order``: on a pool
+    made by ``ordered``, the permutation it applied (row j is row ``order[j]`` of the pool it was called on), else None."""
 
     def __init__(self, q, recipe=None, source=None):
         q = np.ascontiguousarray(q, dtype=np.float32)
@@ -25,21 +63,35 @@ class GoalPool:
         self.q = q
         self.recipe = dict(recipe or {})
         self.source = None if source is None else np.asarray(source, dtype=np.int64).reshape(q.shape[0], 2)
+        self.order = None
 
     def __len__(self):
         return self.q.shape[0]
 
-    def ordered(self, key="rest_distance"):
+    def ordered(self, key="rest_distance", attempts=None, reached=None, prior=(1, 2)):
         """A new ``GoalPool`` with the rows sorted from easiest to hardest, which is what a goal curriculum (``RoboyVecEnv(...,
         goal_curriculum=...)``) takes row order for.  ``"rest_distance"``: by ``|q|_2`` from the zero pose every episode
-        starts from, formed in float64; a stable sort, so ties keep pool order.  ``source`` is permuted with the rows and the recipe
-        gains ``"ordered": key``."""
-        if key != "rest_distance":
-            raise ValueError("a goal pool is ordered by 'rest_distance', got %r" % (key,))
-        order = np.argsort(np.sqrt(np.sum(np.square(self.q.astype(np.float64)), axis=1)), kind="stable")
+        starts from, formed in float64; a stable sort, so ties keep pool order.  ``"reach_rate"``: by how often a policy reached each
+        row, ``reach_rate_order(attempts, reached, prior)`` over counts ``[m]`` as ``RoboyVecEnv.goal_row_stats()`` gives them
+        (DESIGN.md §24).  ``source`` is permuted with the rows, the recipe gains ``"ordered": key`` and ``order`` holds the
+        permutation."""
+        if key == "rest_distance":
+            if attempts is not None or reached is not None:
+                raise ValueError("attempts and reached belong to key='reach_rate'")
+            order = np.argsort(np.sqrt(np.sum(np.square(self.q.astype(np.float64)), axis=1)), kind="stable")
+        elif key == "reach_rate":
+            if attempts is None or reached is None:
+                raise ValueError("key='reach_rate' needs attempts= and reached= (counts per row)")
+            order = reach_rate_order(attempts, reached, prior)
+            if len(order) != len(self):
+                raise ValueError("the pool has %d rows, the counts have %d" % (len(self), len(order)))
+        else:
+            raise ValueError("a goal pool is ordered by 'rest_distance' or 'reach_rate', got %r" % (key,))
         recipe = dict(self.recipe)
         recipe["ordered"] = key
-        return GoalPool(self.q[order], recipe, None if self.source is None else self.source[order])
+        pool = GoalPool(self.q[order], recipe, None if self.source is None else self.source[order])
+        pool.order = np.asarray(order, dtype=np.int64)
+        return pool
 
 
 def goal_curriculum_spec(goal_curriculum, m=None):

@@ -143,7 +143,8 @@ class RoboyVecEnv:
                  auto_reset: bool = True, integrator="euler", n_substeps: int = 1,
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
                  randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None,
-                 report_truncation: bool = False, action_obs=None, critic_obs=None, goals=None, goal_curriculum=None):
+                 report_truncation: bool = False, action_obs=None, critic_obs=None, goals=None, goal_curriculum=None,
+                 goal_row_stats: bool = False):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
@@ -184,7 +185,12 @@ class RoboyVecEnv:
         next goal at the new level.  A ``GoalPool`` whose recipe is not marked ordered is ordered by ``GoalPool.ordered()`` (distance
         from the rest pose) with a warning; bare row arrays are taken as ordered.  ``goal_levels()``, ``goal_index()`` and
         ``goal_level_histogram()`` read the levels, the rows held and the envs per level; ``set_goal_levels(levels)`` writes the levels.
-        At the top level an env draws exactly what it draws without the option."""
+        At the top level an env draws exactly what it draws without the option.
+        ``goal_row_stats``: count per pool row how many episodes were aimed at it and how many of them reached it (DESIGN.md §24;
+        needs ``goal_curriculum`` - ``goal_curriculum=1`` counts without a staircase).  ``goal_row_stats()`` reads the counts,
+        ``set_goal_row_stats`` writes them, ``permute_goal_pool(order)`` re-orders the live pool (any env with ``goals``) and
+        ``reorder_goals_by_reach_rate()`` re-orders it by the measured reach rate.  False: the env launches exactly what it launched
+        before."""
         desc = robot.get_description()
         crit_names, crit_mask, crit_dim = critic_obs_spec(critic_obs, desc.n_q, desc.n_t, randomization is not None, action_delay, action_obs)
         obs_names = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
@@ -198,6 +204,9 @@ class RoboyVecEnv:
             if isinstance(goals, envgoals.GoalPool) and not goals.recipe.get("ordered"):
                 warnings.warn("goal_curriculum: the goal pool's recipe is not marked ordered; ordering it by rest_distance (GoalPool.ordered())")
                 goals = goals.ordered()
+        if goal_row_stats and curriculum is None:
+            raise ValueError("goal_row_stats needs goal_curriculum= (the counts are kept by the row each env holds, the curriculum's index "
+                             "plane; goal_curriculum=1 is the plain pool plus that plane)")
         self.robot = robot
         self.num_envs = int(num_envs)
         self.sim = HipBatchSimulation(robot, num_envs, integrator=integrator, n_substeps=n_substeps,
@@ -246,6 +255,11 @@ class RoboyVecEnv:
             self._or_close(lambda: nat.check(self.sim._lib.rb_env_goal_curriculum_configure(
                 self.sim.handle, curriculum["levels"], curriculum["up"], curriculum["down"], curriculum["start"])))
             self.goal_curriculum = dict(curriculum)
+        self.goal_row_stats_enabled = False
+        if goal_row_stats:
+            # directly behind the curriculum, before anything is captured into a graph: the counting kernel stands in its kernel's place
+            self._or_close(lambda: nat.check(self.sim._lib.rb_env_goal_row_stats_enable(self.sim.handle)))
+            self.goal_row_stats_enabled = True
         self.tendon_obs = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
         self.tendon_obs_scale = tendon_obs_scales(tendon_obs_scale)
         self.obs_dim = 3 * self.n_q
@@ -402,6 +416,76 @@ class RoboyVecEnv:
         out = np.empty(n_levels, np.uint64)
         nat.check(self.sim._lib.rb_env_goal_level_hist(self.sim.handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return out.astype(np.int64)
+
+    # -- outcome counts per pool row (rb_env_goal_row_stats_*, rb_env_goal_pool_permute) --------
+    def _need_row_stats(self):
+        if not self.goal_row_stats_enabled:
+            raise RuntimeError("this RoboyVecEnv keeps no goal row stats (goal_row_stats=False)")
+
+    def goal_row_stats(self, reset: bool = False):
+        """``{"attempts": uint64 [m], "reached": uint64 [m]}``: per pool row, the episodes that ended while aimed at it and those of
+        them that reached it, since the counts were last cleared (``reset=True`` clears them behind the read).  Needs
+        ``goal_row_stats``."""
+        self._need_row_stats()
+        out = np.empty((2, self._goal_pool_m), np.uint64)
+        nat.check(self.sim._lib.rb_env_goal_row_stats_read(self.sim.handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(bool(reset))))
+        return {"attempts": out[0].copy(), "reached": out[1].copy()}
+
+    def set_goal_row_stats(self, attempts, reached):
+        """Write the counts ``[m]`` each (non-negative ints, ``reached <= attempts``), between steps.  ``ValueError`` otherwise, and
+        nothing has changed then."""
+        self._need_row_stats()
+        planes = []
+        for name, x in (("attempts", attempts), ("reached", reached)):
+            a = np.asarray(x.cpu().numpy() if _is_cuda_tensor(x) else x)
+            if a.shape != (self._goal_pool_m,) or a.dtype.kind not in "iu":
+                raise ValueError("%s must be %d ints" % (name, self._goal_pool_m))
+            if a.dtype.kind == "i" and np.any(a < 0):
+                raise ValueError("%s must be >= 0" % name)
+            planes.append(a.astype(np.uint64))
+        if np.any(planes[1] > planes[0]):
+            raise ValueError("reached must not exceed attempts")
+        both = np.ascontiguousarray(np.stack(planes))
+        nat.check(self.sim._lib.rb_env_goal_row_stats_set(self.sim.handle, both.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+
+    def permute_goal_pool(self, order):
+        """Re-order the live pool, between steps: new row ``j`` is old row ``order[j]`` (a permutation of ``0..m-1``, ``ValueError``
+        otherwise and nothing has changed).  The device rows are permuted in place, so a captured graph's next replay reads the new
+        order; every env keeps the goal it holds, ``goal_index()`` follows the rows, and the row counts travel with them.  Levels
+        stay.  Needs ``goals``; the recipe's ``"ordered"`` mark becomes ``"custom"``."""
+        if not self._goal_pool_m:
+            raise RuntimeError("this RoboyVecEnv draws its goals from the box (goals=None)")
+        a = np.asarray(order.cpu().numpy() if _is_cuda_tensor(order) else order)
+        m = self._goal_pool_m
+        if a.shape != (m,) or a.dtype.kind not in "iu":
+            raise ValueError("order must be %d ints, a permutation of 0..%d" % (m, m - 1))
+        if np.any(a < 0) or np.any(a >= m) or np.unique(a).size != m:
+            raise ValueError("order must be a permutation of 0..%d" % (m - 1))
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        nat.check(self.sim._lib.rb_env_goal_pool_permute(self.sim.handle, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        if self.goal_recipe.get("ordered"):
+            self.goal_recipe["ordered"] = "custom"
+
+    def reorder_goals_by_reach_rate(self, attempts=None, reached=None, prior=(1, 2), halve: bool = True):
+        """Re-order the live pool from the most often reached row to the least (``envs.goals.reach_rate_order``) and return the order
+        applied.  The rates come from this env's counts, or from ``attempts`` / ``reached`` where given (a multi-rank run passes the
+        sums over its ranks, so that every rank applies the same order).  ``halve``: afterwards every count of this env is shifted
+        right by one, so an older policy's outcomes fade by a fixed rule.  Needs ``goal_row_stats``."""
+        self._need_row_stats()
+        if (attempts is None) != (reached is None):
+            raise ValueError("give both attempts and reached, or neither")
+        if attempts is None:
+            own = self.goal_row_stats()
+            attempts, reached = own["attempts"], own["reached"]
+        order = envgoals.reach_rate_order(attempts, reached, prior)
+        if order.shape != (self._goal_pool_m,):
+            raise ValueError("the pool has %d rows, the counts have %d" % (self._goal_pool_m, order.shape[0]))
+        self.permute_goal_pool(order)
+        self.goal_recipe["ordered"] = "reach_rate"
+        if halve:
+            own = self.goal_row_stats()
+            self.set_goal_row_stats(own["attempts"] >> np.uint64(1), own["reached"] >> np.uint64(1))
+        return order
 
     # ------------------------------------------------------------------
     def reset(self):

@@ -1508,6 +1508,9 @@ class PPO:
             level = self.env.goal_levels()
             ck["goal_curriculum"] = {"levels": curriculum["levels"], "up": curriculum["up"], "down": curriculum["down"],
                                      "level": (level if torch.is_tensor(level) else torch.from_numpy(level.astype("int64"))).cpu()}
+        if getattr(self.env, "goal_row_stats_enabled", False):      # (an env without the counts writes the checkpoint it always wrote)
+            counts = self.env.goal_row_stats()       # per row of ck["goals"]["q"], which is the pool in its current order
+            ck["goal_row_stats"] = {k: torch.from_numpy(counts[k].astype("int64")) for k in ("attempts", "reached")}
         if self.lr_schedule is not None:             # (an agent without a schedule writes the checkpoint it always wrote)
             ck["lr_schedule"] = {"kind": self.lr_schedule, "desired_kl": self.desired_kl, "lr_factor": self.lr_factor,
                                  "lr_min": self.lr_min, "lr_max": self.lr_max, "lr": self.learning_rate}
@@ -1527,6 +1530,8 @@ class PPO:
         # the goal pool the checkpoint was trained on (rows and recipe; None: box goals), for a caller that wants the same goals again:
         # visualize_agent replays with them.  The env keeps its own pool - the policy reads a goal as columns, whichever way it was drawn
         self.checkpoint_goals = ck.get("goals")
+        # the outcome counts per row of that pool (None: the checkpoint's env kept none), kept here like the goals: the env keeps its own
+        self.checkpoint_goal_row_stats = ck.get("goal_row_stats")
         # the goal curriculum's levels go back into an env with as many levels and envs; otherwise the env keeps its own and the
         # checkpoint's are kept here, as the goals above
         self.checkpoint_goal_curriculum = None

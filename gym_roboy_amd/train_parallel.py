@@ -54,6 +54,31 @@ def parse_goal_curriculum(levels, up, down, goals_m):
     return {"levels": levels, "up": up, "down": down, "start": 0}
 
 
+GOAL_ORDERS = ("rest_distance", "reach_rate")
+
+
+def parse_goal_order(order, reorder_every, goal_curriculum):
+    """``--goal-order KEY --goal-reorder-every R``: ``reach_rate`` re-orders the pool by the measured reach rate per row after every
+    R-th round and needs ``--goal-levels`` (the counts are kept by the curriculum's index plane); R >= 1"""
+    if order not in GOAL_ORDERS:
+        raise SystemExit("--goal-order takes %s, got %r" % (" or ".join(GOAL_ORDERS), order))
+    if reorder_every < 1:
+        raise SystemExit("--goal-reorder-every takes R >= 1, got %d" % reorder_every)
+    if order == "reach_rate" and goal_curriculum is None:
+        raise SystemExit("--goal-order reach_rate needs --goal-levels (the counts per row are kept by the curriculum)")
+    if order != "reach_rate" and reorder_every != 1:
+        raise SystemExit("--goal-reorder-every needs --goal-order reach_rate")
+    return order == "reach_rate"
+
+
+def reach_rate_summary(attempts, reached, first_level_rows):
+    """the summed row counts as they are logged: the share of the episodes that reached their goal among those aimed at the first
+    level's rows, and at any row (0 where nothing was attempted)"""
+    a, r = [int(x) for x in attempts], [int(x) for x in reached]
+    k = int(first_level_rows)
+    return {"reach_rate_first_level": sum(r[:k]) / max(sum(a[:k]), 1), "reach_rate_whole_pool": sum(r) / max(sum(a), 1)}
+
+
 def level_summary(hist):
     """the level histogram (summed over the ranks) as it is logged: the mean level and the share of envs at the top level"""
     h = [float(x) for x in hist]
@@ -104,6 +129,12 @@ def main(argv=None):
                          "outcomes; levels are stored in the checkpoint")
     ap.add_argument("--goal-up", type=int, default=None, metavar="U", help="levels up after an episode that reached its goal (default 1)")
     ap.add_argument("--goal-down", type=int, default=None, metavar="D", help="levels down after an episode that did not (default 1)")
+    ap.add_argument("--goal-order", default="rest_distance", metavar="KEY",
+                    help="what the curriculum takes for difficulty: rest_distance (default: the pool stays ordered by distance from "
+                         "the rest pose) or reach_rate (needs --goal-levels: the run starts from that order, counts per pool row how "
+                         "many episodes aimed at it and how many reached it, and re-orders the live pool by the measured rate, summed "
+                         "over the ranks, after every R-th round; the counts are stored in the checkpoint)")
+    ap.add_argument("--goal-reorder-every", type=int, default=1, metavar="R", help="rounds between re-orderings (default 1)")
     ap.add_argument("--normalize-obs", action="store_true",
                     help="running mean / variance normalisation of the observation inside the policy kernels (what "
                          "stable-baselines calls VecNormalize); the statistics are stored in the checkpoint")
@@ -133,7 +164,9 @@ def main(argv=None):
     tendon_obs_scale = {k: float(v) for k, v in (item.split("=", 1) for item in args.tendon_obs_scale.split(",") if item)}
     goals_m = parse_goals(args.goals)
     goal_curriculum = parse_goal_curriculum(args.goal_levels, args.goal_up, args.goal_down, goals_m)
+    by_reach_rate = parse_goal_order(args.goal_order, args.goal_reorder_every, goal_curriculum)
 
+    import numpy as np
     import torch
     from .envs.robots import MsjRobot
     from .envs.vec_env import RoboyVecEnv
@@ -169,7 +202,7 @@ def main(argv=None):
                       env_id_offset=rank * args.num_envs, tendon_obs=tendon_obs or None, tendon_obs_scale=tendon_obs_scale or None,
                       sensor_noise=sensor_noise or None, action_delay=action_delay,
                       report_truncation=args.bootstrap_timeouts, action_obs=args.action_obs or None,
-                      critic_obs=critic_obs or None, goal_curriculum=goal_curriculum)
+                      critic_obs=critic_obs or None, goal_curriculum=goal_curriculum, **({"goal_row_stats": True} if by_reach_rate else {}))
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,
@@ -179,7 +212,7 @@ def main(argv=None):
                 lr_min=args.lr_min, lr_max=args.lr_max, asymmetric_critic=bool(critic_obs))
     if os.path.exists(model_file):
         agent.load(model_file)                  # resume from the last backup
-    for _ in range(args.rounds):
+    for round_no in range(args.rounds):
         agent.learn(total_timesteps=args.steps_per_round,
                     log=(lambda s: print(log_line(s))) if rank == 0 else None)
         # episode statistics of ALL ranks' envs: the 8-double block of every rank, summed (RCCL; gloo: through the host)
@@ -191,12 +224,24 @@ def main(argv=None):
             hist = env.goal_level_histogram()
             hist = hist if torch.is_tensor(hist) else torch.from_numpy(hist)
             block = torch.cat((block, hist.to(block)))
+        n_head = block.numel()
+        if by_reach_rate:                       # the counts per row ride along as well: [... | m attempts | m reached], exact below 2^53
+            counts = env.goal_row_stats()
+            rows = torch.from_numpy(np.concatenate((counts["attempts"], counts["reached"])).astype(np.float64))
+            block = torch.cat((block, rows.to(block)))
         allreduce_stats(block, dist)
+        row_counts = None
+        if by_reach_rate:
+            row_counts = block[n_head:].cpu().numpy().astype(np.uint64).reshape(2, goals_m)
+            if (round_no + 1) % args.goal_reorder_every == 0:      # every rank orders by the same sums: all ranks keep the same pool
+                env.reorder_goals_by_reach_rate(attempts=row_counts[0], reached=row_counts[1])
         if rank == 0:
             agent.save(model_file)
             summary = summarize(block[:len(STAT_KEYS)].cpu())
             if goal_curriculum is not None:
-                summary.update(level_summary(block[len(STAT_KEYS):].cpu()))
+                summary.update(level_summary(block[len(STAT_KEYS):n_head].cpu()))
+            if row_counts is not None:          # (by the order the round ran with: the first level's rows as they were)
+                summary.update(reach_rate_summary(row_counts[0], row_counts[1], goals_m // goal_curriculum["levels"]))
             print("episode statistics (all ranks):", summary)
     if world > 1:
         dist.destroy_process_group()

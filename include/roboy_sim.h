@@ -600,6 +600,42 @@ int rb_env_goal_levels_set(rb_sim *sim, const uint32_t *host_levels /* [n] */);
 int rb_env_goal_level_hist_dev(rb_sim *sim, uint64_t *d_out /* [levels] */, void *hip_stream);
 int rb_env_goal_level_hist(rb_sim *sim, uint64_t *out /* host, [levels] */);
 
+/* ---- outcome counts per pool row, and re-ordering a live pool by them ----
+ * The curriculum takes row order for difficulty order; these counts measure it.  Two planes uint64 [2][m] behind one pointer:
+ * attempts[m], then reached[m], zero when enabled.  The rule, in an env-step launch (every env-step entry, every kernel form), for an
+ * env whose done word is non-zero, BEFORE its level, the value seen and its index are written:
+ *     k0  = index[i]                                 (the row the ended episode was aimed at)
+ *     hit = goals-reached counter[i] != value seen[i] (the outcome the level rule uses)
+ *     k0 < m:  attempts[k0] += 1;  hit: reached[k0] += 1
+ * Everything else the env does is the curriculum's contract above, bit for bit.  Nothing is counted for an env whose index reads
+ * RB_GOAL_INDEX_NONE (behind rb_env_set_goal), nor by rb_env_reset_dev: the episodes a reset abandons are not attempts.  While
+ * enabled, one kernel (the curriculum's lane text plus the adds) is launched IN PLACE of the curriculum's: the launches per step stay
+ * a pool handle's.  The adds are global integer atomics whose result is unused: exact in any order, so ranges of one handle stepped
+ * on two streams (rb_env_step_range_dev) add into the same planes safely.
+ *   - rb_env_configure again, rb_env_stats(_dev) with reset, rb_env_reset_dev, rb_env_goal_levels_set and rb_env_goal_pool_set in
+ *     place do nothing to the counts: they are the caller's to clear (read with clear, or set).
+ *   - L = 1 ("the plain pool plus the index plane") is the way to count without a staircase; a handle without a curriculum has no
+ *     index plane and cannot count.  A handle that does not enable the counts launches exactly what it launched before.
+ *   enable: needs rb_env_goal_curriculum_configure, else RB_EINVAL.  ONCE per handle - it switches the kernel a captured graph would
+ *        have frozen - a second call is RB_EINVAL.  Drains the handle's streams, then allocates and zeroes the planes.  Call it before
+ *        a caller captures env steps.
+ *   ptr: the device planes and m.  read: the planes into host memory [2][m], synchronous, behind a drain of the handle's streams;
+ *        clear != 0 zeroes them after the copy.  set: host [2][m] into the planes, synchronous, behind a drain; a row with
+ *        reached > attempts is RB_EINVAL before anything changes.  All three: RB_EINVAL while the counts are not enabled.
+ *   rb_env_goal_pool_permute: new row j of the pool is old row order[j].  Any handle with a pool.  `order` is a host array [m] and must
+ *        be a permutation of 0..m-1, else RB_EINVAL before anything is enqueued or changed.  Drains the handle's streams and permutes
+ *        the device rows IN PLACE - the pointer never moves, so a graph captured earlier reads the new order on its next replay.  With a
+ *        curriculum the index plane is remapped (index <- new number of the row it held; RB_GOAL_INDEX_NONE stays), with counts both
+ *        planes are permuted the same way.  Levels, the values seen, the goal planes, the observation rows and every draw counter are
+ *        left alone.  Invariant before and after: for every env with an index, pool row index[i] equals the env's goal plane bit for
+ *        bit.  Synchronous; call it between steps.
+ * RB_ABI_VERSION is still 6 (nothing that existed changed): look rb_env_goal_row_stats_enable up before relying on it. */
+int rb_env_goal_row_stats_enable(rb_sim *sim);
+int rb_env_goal_row_stats_ptr(rb_sim *sim, uint64_t **d_counts /* [2][m] */, int64_t *m);
+int rb_env_goal_row_stats_read(rb_sim *sim, uint64_t *host /* [2][m] */, int clear);
+int rb_env_goal_row_stats_set(rb_sim *sim, const uint64_t *host /* [2][m] */);
+int rb_env_goal_pool_permute(rb_sim *sim, const uint32_t *order /* host, [m] */);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
