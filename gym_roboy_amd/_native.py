@@ -113,6 +113,7 @@ SIGNATURES = {
     "rb_destroy": (None, [_sim]),
     "rb_info": (ctypes.c_int, [_sim, ctypes.POINTER(SimInfo)]),
     "rb_select_kernel": (ctypes.c_int, [_sim, ctypes.c_int]),
+    "rb_mirror_info": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "rb_specialization": (ctypes.c_int, [_sim]),
     "rb_jit_cache_stats": (None, [ctypes.POINTER(ctypes.c_int64)] * 3),
     "rb_set_stream": (ctypes.c_int, [_sim, _vp]),

@@ -78,6 +78,9 @@ SIGNATURES["rp_ppo_asym_workspace_floats"] = (ctypes.c_int64, [_i, _i, _i, ctype
 SIGNATURES["rp_ppo_grad_asym_dev"] = (_i, [_vp] * 11 + [ctypes.c_int64, _i, _i, _i, _f, _f, _vp, _vp, _f, _f, _i, _vp, _vp, _vp])
 SIGNATURES["rp_clip_adam_asym_dev"] = (_i, [_vp] * 4 + [_i, _i, _i] + [_f] * 4 + [ctypes.c_int64, _f, _f, _f, _vp])
 SIGNATURES["rp_clip_adam_kl_asym_dev"] = (_i, [_vp] * 4 + [_i, _i, _i, _vp] + [_f] * 7 + [ctypes.c_int64, _f, _f, _f, _vp])
+# mirror-symmetry augmentation: the streaming pass that writes the mirrored half of the update's rows
+# (looked up by name: the ABI version stays 5)
+SIGNATURES["rp_mirror_rows_dev"] = (_i, [_vp, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp])
 
 
 def library_path():

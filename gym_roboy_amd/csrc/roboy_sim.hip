@@ -1376,6 +1376,22 @@ int rb_select_kernel(rb_sim *s, int kernel) {
     return RB_OK;
 }
 
+int rb_mirror_info(const rb_sim *s, int32_t *plane, int32_t *joint_sign, int32_t *tendon_image) {
+    if (check(s) || !plane || !joint_sign || !tendon_image) return fail(RB_EINVAL, "null argument");
+    // what rb_create found in the robot's constants (find_mirror_pairs), whatever kernel form steps the handle
+    if (s->tree || s->ntx || !s->pair_ok)
+        return fail(RB_EUNSUPPORTED, "this robot has no mirror plane (an 8-tendon ball-joint robot with its tendons in mirror-image pairs, "
+                                     "principal-axis inertia and symmetric joint limits has one)");
+    *plane = s->pair_mirror;
+    // the two joints whose axes lie in the mirror plane change sign (find_mirror_pairs' f0, f1): x-z (-1, +1, -1), y-z (+1, -1, -1)
+    for (int j = 0; j < 3; ++j) joint_sign[j] = (j == 2 || j == s->pair_mirror) ? -1 : 1;
+    for (int k = 0; k < 4; ++k) {
+        tendon_image[s->pair_half[k]] = s->pair_image[k];
+        tendon_image[s->pair_image[k]] = s->pair_half[k];
+    }
+    return RB_OK;
+}
+
 int rb_set_stream(rb_sim *s, void *hip_stream) {
     if (check(s)) return RB_EINVAL;
     { int rc = drain(s); if (rc) return rc; }                            // the previous stream and the chain streams

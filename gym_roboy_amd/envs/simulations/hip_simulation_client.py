@@ -84,6 +84,15 @@ class HipBatchSimulation:
     def select_kernel(self, kernel: int):
         nat.check(self._lib.rb_select_kernel(self._h, int(kernel)))
 
+    def mirror_info(self) -> dict:
+        """The robot's mirror symmetry (``rb_mirror_info``): ``{'plane': 0 (x-z) or 1 (y-z), 'joint_sign': int32 [n_q], 'tendon_image':
+        int32 [n_t]}``.  ``NativeError`` for a robot without a mirror plane."""
+        plane = ctypes.c_int32(-1)
+        sign, image = np.zeros(self.n_q, np.int32), np.zeros(self.n_t, np.int32)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        nat.check(self._lib.rb_mirror_info(self._h, ctypes.byref(plane), sign.ctypes.data_as(i32p), image.ctypes.data_as(i32p)))
+        return {"plane": int(plane.value), "joint_sign": sign, "tendon_image": image}
+
     def set_stream(self, stream_ptr):
         """``None``: the handle's own stream; ``0``: the device's default (null) stream, which is
         what ``torch.cuda.current_stream().cuda_stream`` is unless another stream was made

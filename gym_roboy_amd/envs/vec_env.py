@@ -588,6 +588,15 @@ class RoboyVecEnv:
         self.sim.synchronize()
         return self.sim.download(kind.value, (self.num_envs,), np.uint32) == nat.RB_DONE_TRUNCATED
 
+    def mirror_map(self):
+        """``(obs_src int32[obs_dim], obs_sign float32[obs_dim], act_src int32[n_t])``: the mirror image of this env's observation and
+        action rows as configured (``envs.symmetry.row_mirror_map`` on the library's ``rb_mirror_info``) - the twin
+        ``(obs[:, obs_src] * obs_sign, act[:, act_src])`` of a transition is a transition of the mirrored env.  Raises the library's
+        error for a robot without a mirror plane."""
+        from .symmetry import row_mirror_map
+        info = self.sim.mirror_info()
+        return row_mirror_map(self.n_q, self.n_t, info["joint_sign"], info["tendon_image"], self.tendon_obs, self.action_obs)
+
     def critic_obs(self):
         """``[N, critic_obs_dim]``: the privileged rows that belong to the observation rows last returned.  A CUDA tensor after a torch
         step; otherwise numpy, read from the handle's plane after a synchronisation (a reset, a numpy step, ``step_dev`` /

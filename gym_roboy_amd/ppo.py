@@ -36,6 +36,10 @@ on the device, read and moved by the optimiser's own launch: no read-back betwee
 normalise as they fetch their operands (``rp_act_norm_dev``, ``rp_ppo_grad_norm_dev``): the rollout buffers keep the raw
 observation and no normalised copy is ever written.  The statistics are frozen through a rollout and the update on it and merged
 with that rollout's moments after the update's last minibatch.
+
+``symmetry="augment"`` (an env with ``mirror_map()``: a robot with a mirror plane) runs every update on the rollout's samples and
+their mirror images: one streaming kernel (``rp_mirror_rows_dev``) writes the mirrored half of the [2 n, ...] sample set, and the
+gradient, statistics, sample-order and optimiser kernels run unchanged on twice the rows.
 """
 import math
 
@@ -44,6 +48,7 @@ import torch
 from torch import nn
 
 LR_SCHEDULES = ("adaptive",)
+SYMMETRY_MODES = ("augment",)
 
 
 def adapt_lr(lr, kl, desired_kl, lr_factor, lr_min, lr_max):
@@ -821,6 +826,56 @@ def _fused_kernels_apply(policy, obs_dim, act_dim):
         return False
 
 
+class _MirrorMaps:
+    """An env's ``mirror_map()`` on the agent's device: the column sources as int64 (torch indexing) and int32 (the
+    kernel's), the signs as float32 - and for the per-sample scalars the identity map of width 1.  ``rows(x, kind)`` is the torch
+    statement; ``rows_into(src, out, kind)`` fills a [2 n, width] buffer, first half = ``src``, second half = its image, with one
+    launch of rp_mirror_rows_dev."""
+
+    def __init__(self, maps, obs_dim, act_dim, device):
+        obs_src, obs_sign, act_src = (np.asarray(m) for m in maps)
+        for name, src, width in (("obs_src", obs_src, obs_dim), ("act_src", act_src, act_dim)):
+            if src.shape != (width,) or sorted(int(i) for i in src) != list(range(width)):
+                raise ValueError("mirror_map(): %s must be a permutation of the row's %d columns" % (name, width))
+        if obs_sign.shape != (obs_dim,) or not np.all(np.abs(obs_sign) == 1.0):
+            raise ValueError("mirror_map(): obs_sign must hold %d entries of +-1" % obs_dim)
+        dev = torch.device(device)
+        t = lambda a, dtype: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(dev)
+        self.device = dev
+        self.src = {"obs": t(obs_src, torch.int64), "act": t(act_src, torch.int64)}
+        self.sign = {"obs": t(obs_sign, torch.float32), "act": None}
+        self._src32 = {"obs": t(obs_src, torch.int32), "act": t(act_src, torch.int32), "one": torch.zeros(1, dtype=torch.int32, device=dev)}
+        self._sign32 = {"obs": self.sign["obs"], "act": torch.ones(act_dim, device=dev), "one": torch.ones(1, device=dev)}
+        self._native = None
+
+    def rows(self, x, kind):
+        """the image of rows of kind "obs" or "act" (``envs.symmetry.mirror_rows``: ``x[..., src] * sign``)"""
+        out = x[..., self.src[kind]]
+        return out if self.sign[kind] is None else out * self.sign[kind]
+
+    def kernel_applies(self):
+        """on a GPU the second halves come from rp_mirror_rows_dev (a missing library is an error there, as it is for the statistics'
+        kernels: no quiet torch path); on the CPU from ``rows``"""
+        if self.device.type != "cuda":
+            return False
+        if self._native is None:
+            import ctypes
+            from . import _policy_native as pn
+            self._native = (pn, ctypes, pn.load())           # (raises without the library, at every call)
+        return True
+
+    @torch.no_grad()
+    def rows_into(self, src, out, kind):
+        """out [2 n, width] (or [2 n]) <- [src; image of src], src [n, width] (or [n]) contiguous float32 on the GPU; kind: "obs",
+        "act", or "one" - the per-sample scalars, which are copied"""
+        pn, c, lib = self._native
+        n = int(src.shape[0])
+        width = int(src.shape[1]) if src.dim() == 2 else 1
+        ptr = lambda t: c.c_void_p(t.data_ptr())
+        pn.check(lib.rp_mirror_rows_dev(ptr(src), ptr(out), ptr(out[n:]), n, width, ptr(self._src32[kind]), ptr(self._sign32[kind]),
+                                        c.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)))
+
+
 class PPO:
     def __init__(self, env, policy=None, n_steps=128, nminibatches=4, noptepochs=4, gamma=0.99, lam=0.95,
                  learning_rate=2.5e-4, cliprange=0.2, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5,
@@ -828,7 +883,7 @@ class PPO:
                  fused_update=None, rollout_chains=None, normalize_obs=False, clip_obs=10.0, obs_norm_prime=True,
                  normalize_reward=False, clip_reward=10.0, reward_norm_prime=True, bootstrap_timeouts=False,
                  lr_schedule=None, desired_kl=0.01, lr_factor=1.5, lr_min=1e-5, lr_max=1e-2, diagnostics=False,
-                 asymmetric_critic=False):
+                 asymmetric_critic=False, symmetry=None):
         """fused_policy / fused_update: None = the fused MFMA kernels whenever they apply (a GPU, MlpPolicy's shape,
         dimensions the kernels support), True = insist, False = the torch path (the statement the kernels are
         tested against).  The gradient kernel takes up to 63 observation columns: an env with ``action_obs=K`` stays fused while
@@ -863,7 +918,22 @@ class PPO:
         state, the env's own parameters and delay) instead of the noisy, late observation the actor gets - in simulation they are
         free, and only the actor is deployed.  The rollout keeps ``cobs`` beside ``obs`` and every value - the rollout's, the last
         one, the minibatch loss - reads it; ``normalize_obs`` keeps a second set of statistics for it.  Eager and graph modes, torch
-        and fused paths.  DESIGN.md §20."""
+        and fused paths.  DESIGN.md §20.
+        symmetry: None, or "augment" - every update runs on the rollout's samples AND their mirror images (``augment``): for a robot
+        with a mirror plane the twin ``(M s, P a, r, M s')`` of a transition is as valid as the original and costs no simulation.
+        The same number of optimiser steps on minibatches twice the size; ``sample_orders`` index ``[0, 2 T N)``; the observation
+        statistics of ``normalize_obs`` are merged over the rows and their images.  Needs an env with ``mirror_map()`` (RoboyVecEnv on
+        a robot with a mirror plane); not with ``asymmetric_critic``, whose critic rows have no map yet.  ``symmetry_gap(roll)``
+        measures how far the policy is from the symmetry.  Eager and graph modes, torch and fused paths; the augmentation is
+        rank-local and sits in front of the collectives.  DESIGN.md §25."""
+        if symmetry not in (None,) + SYMMETRY_MODES:
+            raise ValueError("unknown symmetry %r: None or one of %r" % (symmetry, SYMMETRY_MODES))
+        if symmetry is not None and asymmetric_critic:
+            raise ValueError("symmetry=%r does not combine with asymmetric_critic: the critic rows (parameters, delay, age) have no "
+                             "mirror map yet" % (symmetry,))
+        if symmetry is not None and not callable(getattr(env, "mirror_map", None)):
+            raise ValueError("symmetry=%r needs an env that knows its mirror image: env.mirror_map() (RoboyVecEnv on a robot with a "
+                             "mirror plane)" % (symmetry,))
         if lr_schedule is not None and lr_schedule not in LR_SCHEDULES:
             raise ValueError("unknown lr_schedule %r: None or one of %r" % (lr_schedule, LR_SCHEDULES))
         if not desired_kl > 0.0:
@@ -962,6 +1032,11 @@ class PPO:
             raise ValueError("an env built with report_truncation=True leaves episode-end codes (0 / 1 / 2) in the done words of "
                              "step_dev, which the captured rollout reads as 0 / 1: pass bootstrap_timeouts=True or build the env without it")
         self._rew_raw = None                  # the last rollout's raw reward (kept with normalize_reward: learn() reports it)
+        self.symmetry = symmetry
+        self._mirror = None                   # symmetry: the env's row maps on the agent's device (_MirrorMaps)
+        if symmetry is not None:
+            self._mirror = _MirrorMaps(env.mirror_map(), obs_dim, act_dim, self.device)
+        self.last_rollout = None              # learn(): the rollout of its last update (graph mode: views of the graph's buffers)
         self.num_timesteps = 0
         self._obs = None
         self._cobs = None                     # the critic rows that belong to _obs (asymmetric_critic)
@@ -1255,7 +1330,9 @@ class PPO:
                 before = self.num_timesteps
                 roll = self._collect_rollout()
                 self.num_timesteps = before
-                if prime_obs:
+                if prime_obs and self.symmetry is not None:      # every merge is over the rows and their images: this one too
+                    self._update_obs_norms(self._with_images(roll["obs"].reshape(-1, roll["obs"].shape[-1])), None)
+                elif prime_obs:
                     self._update_obs_norms(roll["obs"].reshape(-1, roll["obs"].shape[-1]),
                                            roll["cobs"].reshape(-1, roll["cobs"].shape[-1]) if self.asymmetric_critic else None)
         return self._collect_rollout()
@@ -1450,12 +1527,73 @@ class PPO:
                                        c.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
         return self._perm_buf
 
+    AUGMENTED_KEYS = (("obs", "obs"), ("act", "act"), ("adv", "one"), ("logp", "one"), ("val", "one"), ("ret", "one"))
+
+    @torch.no_grad()
+    def augment(self, roll):
+        """The rollout and its mirror image as the update's sample set (``symmetry="augment"``): with n = T N,
+        ``{"obs", "act", "adv", "logp", "val", "ret"}`` as [2 n, ...] tensors - rows [0, n) the rollout's, rows [n, 2 n) ``obs = M obs``,
+        ``act = P act`` (the raw samples, as stored) and ``adv, logp, val, ret`` copied.  The old log-probability is the original's on
+        purpose: the mirrored sample was generated by the mirrored behaviour policy, whose density at (M s, P a) is pi_old(a | s) - the
+        permutation's Jacobian is 1.  On a GPU the halves are written by rp_mirror_rows_dev into buffers kept between updates (the
+        next ``augment`` overwrites them); on the CPU by the torch statement, the same numbers bit for bit."""
+        mm = self._mirror
+        if mm is None:
+            raise RuntimeError("this agent was built without symmetry=\"augment\"")
+        flat = {k: roll[k].reshape(-1, *roll[k].shape[2:]) for k, _ in self.AUGMENTED_KEYS}
+        if not mm.kernel_applies():
+            return {k: torch.cat([flat[k], flat[k] if kind == "one" else mm.rows(flat[k], kind)]).contiguous()
+                    for k, kind in self.AUGMENTED_KEYS}
+        n = int(flat["obs"].shape[0])
+        bufs = getattr(self, "_aug_bufs", None)
+        if bufs is None or bufs["obs"].shape[0] != 2 * n:
+            bufs = self._aug_bufs = {k: torch.empty((2 * n,) + tuple(flat[k].shape[1:]), dtype=torch.float32, device=self.device)
+                                     for k, _ in self.AUGMENTED_KEYS}
+        for k, kind in self.AUGMENTED_KEYS:
+            mm.rows_into(flat[k].to(torch.float32).contiguous(), bufs[k], kind)
+        return dict(bufs)
+
+    @torch.no_grad()
+    def _with_images(self, obs_rows):
+        """observation rows [rows, obs_dim] followed by their mirror images (the priming rollout's moments, as ``augment``'s are)"""
+        return torch.cat([obs_rows, self._mirror.rows(obs_rows, "obs")])
+
+    @torch.no_grad()
+    def _means_values(self, obs):
+        """(action mean [rows, act_dim], value [rows]) of observation rows by the agent's own policy step: the fused one
+        (deterministic, with its ``mean`` output) where the agent is fused, torch otherwise"""
+        if self._fused is None:
+            return self.policy.dist(obs).mean, self.policy.value(obs)
+        rows = int(obs.shape[0])
+        z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+        act, mean, logp, val = z(rows, self._fused.act_dim), z(rows, self._fused.act_dim), z(rows), z(rows)
+        self._fused.act_into(obs.contiguous(), act, logp, val, deterministic=True, mean=mean, norm=self.obs_norm)
+        return mean, val
+
+    @torch.no_grad()
+    def symmetry_gap(self, roll, max_rows=65536):
+        """How far the policy is from the robot's mirror symmetry on the first ``max_rows`` observation rows s of a rollout:
+        ``{"action": mean |mu(M s) - P mu(s)|^2 / act_dim, "value": mean |V(M s) - V(s)|}`` (0, 0 for an equivariant actor and an
+        invariant critic).  Needs ``symmetry="augment"``, which is where the maps come from."""
+        mm = self._mirror
+        if mm is None:
+            raise RuntimeError("this agent was built without symmetry=\"augment\"")
+        obs = roll["obs"].reshape(-1, roll["obs"].shape[-1])[:int(max_rows)].to(self.device, torch.float32).contiguous()
+        mu, v = self._means_values(obs)
+        mu_m, v_m = self._means_values(mm.rows(obs, "obs").contiguous())
+        d = mu_m - mm.rows(mu, "act")
+        return {"action": ((d * d).sum(-1).mean() / d.shape[-1]).item(), "value": (v_m - v).abs().mean().item()}
+
     def update(self, roll, sample_orders=None):
         """sample_orders (optional): one int64 index tensor per epoch instead of the generated order (tests feed the
         same orders to both optimiser paths)."""
-        flat = {k: v.reshape(-1, *v.shape[2:]) for k, v in roll.items()}
-        if self._fgrad is not None:          # the gradient kernels index the rollout tensors directly
-            flat = {k: v.contiguous() for k, v in flat.items()}
+        if self.symmetry is not None:
+            # everything below is the update it always was, on 2 n samples: the rollout's and their mirror images
+            flat = self.augment(roll)
+        else:
+            flat = {k: v.reshape(-1, *v.shape[2:]) for k, v in roll.items()}
+            if self._fgrad is not None:          # the gradient kernels index the rollout tensors directly
+                flat = {k: v.contiguous() for k, v in flat.items()}
         n = flat["obs"].shape[0]
         mb = max(n // self.nminibatches, 1)
         out = None
@@ -1480,6 +1618,8 @@ class PPO:
         target = self.num_timesteps + total_timesteps
         while self.num_timesteps < target:
             roll = self.collect()
+            if self.symmetry is not None:        # kept for symmetry_gap()
+                self.last_rollout = roll
             stats = self.update(roll)
             if self.reward_norm is not None:     # the env's raw reward, not the normalised one the agent learns from
                 stats["mean_reward"] = self._rew_raw.mean().item()
@@ -1511,6 +1651,8 @@ class PPO:
         if getattr(self.env, "goal_row_stats_enabled", False):      # (an env without the counts writes the checkpoint it always wrote)
             counts = self.env.goal_row_stats()       # per row of ck["goals"]["q"], which is the pool in its current order
             ck["goal_row_stats"] = {k: torch.from_numpy(counts[k].astype("int64")) for k in ("attempts", "reached")}
+        if self.symmetry is not None:                # (an agent without the option writes the checkpoint it always wrote)
+            ck["symmetry"] = self.symmetry
         if self.lr_schedule is not None:             # (an agent without a schedule writes the checkpoint it always wrote)
             ck["lr_schedule"] = {"kind": self.lr_schedule, "desired_kl": self.desired_kl, "lr_factor": self.lr_factor,
                                  "lr_min": self.lr_min, "lr_max": self.lr_max, "lr": self.learning_rate}
@@ -1524,6 +1666,9 @@ class PPO:
         if ("critic_obs" in ck) != self.asymmetric_critic:
             raise ValueError("the checkpoint was trained %s an asymmetric critic, this agent runs %s one (PPO's asymmetric_critic)"
                              % (("with", "without") if not self.asymmetric_critic else ("without", "with")))
+        if ck.get("symmetry") != self.symmetry:
+            raise ValueError("the checkpoint was trained with symmetry=%r, this agent runs symmetry=%r (PPO's symmetry)"
+                             % (ck.get("symmetry"), self.symmetry))
         if self.asymmetric_critic and (ck["critic_obs"] != _critic_obs_of(self.env) or int(ck["critic_obs_dim"]) != self.cobs_dim):
             raise ValueError("the checkpoint's critic was trained on the rows %r (%d columns), this env writes %r (%d; RoboyVecEnv's "
                              "critic_obs)" % (ck["critic_obs"], int(ck["critic_obs_dim"]), _critic_obs_of(self.env), self.cobs_dim))

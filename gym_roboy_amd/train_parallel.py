@@ -153,6 +153,10 @@ def main(argv=None):
     ap.add_argument("--desired-kl", type=float, default=0.01, metavar="KL", help="the KL the adaptive schedule steers to (default 0.01)")
     ap.add_argument("--lr-min", type=float, default=1e-5, metavar="LR", help="lower bound of the scheduled learning rate (default 1e-5)")
     ap.add_argument("--lr-max", type=float, default=1e-2, metavar="LR", help="upper bound of the scheduled learning rate (default 1e-2)")
+    ap.add_argument("--symmetry", default=None, choices=("augment",),
+                    help="augment = every update runs on the rollout's samples and their images in the robot's mirror plane (twice the "
+                         "samples per env step, no more simulation; not with --critic-obs); the round's statistics then show "
+                         "symmetry_gap_action, the policy's distance from the symmetry; recorded in the checkpoint")
     args = ap.parse_args(argv)
     sensor_noise = {k: float(v) for k, v in (item.split("=", 1) for item in args.sensor_noise.split(",") if item)}
     action_delay = None
@@ -209,7 +213,8 @@ def main(argv=None):
                 fused_update=not args.torch_policy, normalize_obs=args.normalize_obs, clip_obs=args.clip_obs,
                 normalize_reward=args.normalize_reward, clip_reward=args.clip_reward,
                 bootstrap_timeouts=args.bootstrap_timeouts, lr_schedule=args.lr_schedule, desired_kl=args.desired_kl,
-                lr_min=args.lr_min, lr_max=args.lr_max, asymmetric_critic=bool(critic_obs))
+                lr_min=args.lr_min, lr_max=args.lr_max, asymmetric_critic=bool(critic_obs),
+                symmetry=args.symmetry)
     if os.path.exists(model_file):
         agent.load(model_file)                  # resume from the last backup
     for round_no in range(args.rounds):
@@ -242,6 +247,8 @@ def main(argv=None):
                 summary.update(level_summary(block[len(STAT_KEYS):n_head].cpu()))
             if row_counts is not None:          # (by the order the round ran with: the first level's rows as they were)
                 summary.update(reach_rate_summary(row_counts[0], row_counts[1], goals_m // goal_curriculum["levels"]))
+            if args.symmetry and agent.last_rollout is not None:      # (rank 0's policy on rank 0's last rollout: the policy is shared)
+                summary["symmetry_gap_action"] = float("%.3g" % agent.symmetry_gap(agent.last_rollout)["action"])
             print("episode statistics (all ranks):", summary)
     if world > 1:
         dist.destroy_process_group()

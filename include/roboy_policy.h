@@ -252,6 +252,23 @@ int rp_clip_adam_asym_dev(float *d_params, const float *d_grad, float *d_m, floa
 int rp_clip_adam_kl_asym_dev(float *d_params, const float *d_grad, float *d_m, float *d_v, int obs_dim, int cobs_dim, int act_dim, float *d_lr,
                              float desired_kl, float lr_factor, float lr_min, float lr_max, float beta1, float beta2, float eps, int64_t step,
                              float max_grad_norm, float grad_scale, float ent_coef, void *stream);
+/* ---- mirror-symmetry augmentation (gym_roboy_amd/ppo.py: PPO(symmetry="augment")) ----
+ * A robot with a mirror plane gives every transition (s, a, r, s') a twin (M s, P a, r, M s') that costs no simulation: M flips the
+ * sign of some observation columns and swaps others with their partner's, P permutes the action's tendons.  The update then runs on
+ * the rollout's n samples AND their images, 2 n rows, through the unchanged gradient, statistics, sample-order and optimiser entry
+ * points above.  This is the one new launch: it materialises the second half.
+ *     d_mirror[r][c] = d_col_sign[c] * d_src[r][d_col_src[c]]      one IEEE multiply: a flipped 0 is -0
+ *     d_plain [r][c] = d_src[r][c]                                 where d_plain is given
+ * for rows x width floats; d_col_src (int32, entries in [0, width)) and d_col_sign are device arrays of `width` entries.  d_plain:
+ * NULL - not written; == d_src - allowed, and then skipped; otherwise a copy.  1 <= width <= 128.  The arrays of rows x width floats
+ * must not overlap - d_mirror with d_src, d_plain with d_mirror, d_plain with d_src unless it IS d_src: any overlap, partial ones
+ * included, is refused with RP_EINVAL (the address ranges are compared).
+ * No output needs more than the 4-byte alignment of a float: the halves of one [2 n, width] allocation are served as they lie
+ * (n = 321, width = 9: the second half starts 4-byte aligned), with 16-byte accesses wherever the run in question allows them.
+ * One entry point serves the observation rows (the env's map), the action rows (the tendon permutation) and - width 1, the identity
+ * map, sign +1 - the per-sample scalars.  rows == 0: nothing is launched.  Added by name: the ABI version stays 5. */
+int rp_mirror_rows_dev(const float *d_src, float *d_plain /* NULL: not written */, float *d_mirror, int64_t rows, int width,
+                       const int32_t *d_col_src, const float *d_col_sign, void *stream);
 /* test hook: would a grant of lds_bytes of dynamic LDS be issued for (kernel id, device) now?  Records it. */
 int rp_debug_lds_grant_needed(int kernel_id, int dev, int64_t lds_bytes);
 /* which form of the gradient kernels rp_ppo_grad_dev launches for this policy: 2 = the small instance (obs_dim <= 31, up to 8

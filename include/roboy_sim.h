@@ -164,6 +164,15 @@ int rb_info(const rb_sim *sim, rb_sim_info *info);
  *     tendon loop written out) and above (256-thread workgroups; RK4: the stages as a rolled loop over running sums) - equal to
  *     ~1 ulp, bit-identical only among handles on the same side of 65 536 envs. */
 int rb_select_kernel(rb_sim *sim, int kernel);
+/* The robot's mirror symmetry, as rb_create found it in the robot's constants (the two-lanes-per-env kernels step "the env's mirror
+ * image" by it; a learner can use it to double its data: DESIGN.md §25).  Seen in the mirror the robot is the same robot in the state
+ * (joint_sign * q, joint_sign * qd) with the set-points of tendon k and tendon tendon_image[k] exchanged.
+ *   plane         0: the x-z plane, 1: the y-z plane (as rb_dispatch_row.variant numbers them)
+ *   joint_sign    [n_q = 3]: (-1, +1, -1) for plane 0, (+1, -1, -1) for plane 1 - the joints whose axes lie in the plane change sign
+ *   tendon_image  [n_t = 8]: the partner of every tendon, an involution without fixed points
+ * Whatever kernel form is selected.  RB_EUNSUPPORTED for a robot without a mirror plane: every joint tree, every other tendon count,
+ * asymmetric ball-joint robots.  Added by name: the ABI version stays 6. */
+int rb_mirror_info(const rb_sim *sim, int32_t *plane, int32_t *joint_sign /* [n_q] */, int32_t *tendon_image /* [n_t] */);
 /* How the env-per-lane kernels of this handle get the robot's constants: RB_SPEC_NONE = through the kernarg
  * (scalar loads); RB_SPEC_TABLE = instances compiled ahead of time on the reference's MsjRobot (the handle's
  * constants equal that table bit for bit); RB_SPEC_JIT = instances compiled with hiprtc on this robot's own
