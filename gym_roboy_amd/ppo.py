@@ -47,6 +47,8 @@ import numpy as np
 import torch
 from torch import nn
 
+from .sharding import dist_ranks
+
 LR_SCHEDULES = ("adaptive",)
 SYMMETRY_MODES = ("augment",)
 
@@ -154,13 +156,7 @@ class ObsNorm:
         mean on every rank, so they add - are all-reduced once (the device tensor under nccl, through the host under gloo, as
         ``FusedAdam.step``): every rank then merges the same numbers and holds bit-identical statistics."""
         sums = self.moments(obs_rows.to(self.device))
-        if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            if sums.device.type != "cuda" or dist.get_backend() == "nccl":
-                dist.all_reduce(sums)
-            else:
-                host = sums.cpu()
-                dist.all_reduce(host)
-                sums.copy_(host)
+        _all_reduce_sums(sums, dist)
         self.merge(sums)
 
     def state_dict(self):
@@ -184,7 +180,7 @@ class ObsNorm:
 
 def _all_reduce_sums(sums, dist):
     """Sum a small float64 tensor over the ranks: the device tensor under nccl, through the host under gloo."""
-    if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    if dist_ranks(dist) > 1:
         if sums.device.type != "cuda" or dist.get_backend() == "nccl":
             dist.all_reduce(sums)
         else:
@@ -430,6 +426,23 @@ def gae_fused(rewards, values, dones, last_value, gamma, lam, adv_out=None, ret_
     return adv, ret
 
 
+def rollout_tail_form(fused, eager, reward_norm, boot, asym):
+    """Which statement turns a rollout's (rew_raw, done codes, val, last value) into (rew, done, adv, ret) - DESIGN.md §16's table:
+    "torch" (the scale, ``RewardNorm.scan`` / ``apply``, ``gae`` / ``gae_boot``), "gae_kernel" (the torch scale and ``gae_fused``) or
+    "tail_kernel" (one launch of ``RewardNorm.tail``: the agent's own statistics under ``reward_norm``, identity statistics on a
+    private carry under ``boot`` alone).  fused: the fused policy step; eager: through ``env.step``, not a captured graph; reward_norm,
+    boot, asym: PPO's ``normalize_reward``, ``bootstrap_timeouts``, ``asymmetric_critic``.  A captured fused rollout always runs a
+    kernel; an eager fused one runs the same kernel only under ``boot``, or under ``asym`` without ``reward_norm`` - the historical
+    exception (NEXT.md), which is why eager and captured advantages differ in the last bits everywhere else."""
+    if not fused:
+        return "torch"
+    if boot or (reward_norm and not eager):
+        return "tail_kernel"
+    if not eager or (asym and not reward_norm):
+        return "gae_kernel"
+    return "torch"
+
+
 def _check_norm(norm, obs_dim, device):
     if norm.obs_dim != obs_dim or norm.norm.device != device or norm.norm.dtype != torch.float32 or not norm.norm.is_contiguous():
         raise ValueError("observation statistics of %d columns on %s, the kernel reads %d on %s"
@@ -664,7 +677,7 @@ class FusedAdam:
     def step(self, ent_coef, dist=None):
         f, c = self._f, self._f._ct
         scale = 1.0
-        if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if dist_ranks(dist) > 1:
             if dist.get_backend() == "nccl":
                 dist.all_reduce(f._g)                      # one bucket: the whole gradient vector, contiguous
             else:                                          # rehearsal over gloo: through the host
@@ -773,9 +786,9 @@ def adam_state_flat_to_torch(fsd, policy, layout, template_sd):
 
 
 def average_gradients(module, dist=None):
-    if dist is None or not dist.is_available() or not dist.is_initialized() or dist.get_world_size() == 1:
+    world = dist_ranks(dist)
+    if world <= 1:
         return
-    world = dist.get_world_size()
     flat = torch.cat([p.grad.reshape(-1) for p in module.parameters() if p.grad is not None])
     dist.all_reduce(flat)          # one bucket: the policy is ~10^4 parameters
     flat /= world
@@ -975,13 +988,13 @@ class PPO:
                 self.policy.set_obs_norm(self.obs_norm, self.cobs_norm)
             else:
                 self.policy.set_obs_norm(self.obs_norm)
-        if dist is not None and dist.is_available() and dist.is_initialized():
+        if dist_ranks(dist) > 0:                        # an initialised group, be it of one rank
             for p in self.policy.parameters():          # same initial weights on every rank
                 dist.broadcast(p.data, 0)
             # ... but each rank's own exploration noise and minibatch order: the reference seeds worker
             # `rank` with seed + rank (/root/reference/gym_roboy/train_parallel.py:24)
             torch.manual_seed(seed + dist.get_rank())
-        multi_rank = dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        multi_rank = dist_ranks(dist) > 1
         # the rollout (policy step, env step, GAE) is rank-local, so it is captured on every rank; the collectives
         # (gradient average, statistics) stay outside the graph
         self.use_graphs = bool(use_graphs) and self.device.type == "cuda" and hasattr(env, "step_dev")
@@ -1052,10 +1065,9 @@ class PPO:
             return self.obs_norm.update(obs_rows, self.dist)
         a, c = self.obs_norm, self.cobs_norm
         sa, sc = a.moments(obs_rows.to(a.device)), c.moments(cobs_rows.to(c.device))
-        dist = self.dist
-        if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if dist_ranks(self.dist) > 1:
             both = torch.cat([sa, sc])
-            _all_reduce_sums(both, dist)
+            _all_reduce_sums(both, self.dist)
             sa.copy_(both[:sa.numel()]); sc.copy_(both[sa.numel():])
         a.merge(sa); c.merge(sc)
 
@@ -1087,106 +1099,78 @@ class PPO:
         """The T (policy step, env step) pairs of envs [lo, hi): the whole batch on the env's stream (stream_ptr None), or one
         chain's half on its own stream."""
         env, T = self.env, self.n_steps
-        whole = stream_ptr is None
         asym = self.asymmetric_critic
         b["obs"][0][lo:hi].copy_(b["carry"][lo:hi])
         if asym:
             b["cobs"][0][lo:hi].copy_(b["ccarry"][lo:hi])
         packed = self._fused.pack() if self._fused is not None else None     # (inside the graph: re-gathered on every replay)
         for t in range(T):
+            self._policy_step(b["obs"][t][lo:hi], b["cobs"][t][lo:hi] if asym else None, b["act"][t][lo:hi], b["logp"][t][lo:hi],
+                              b["val"][t][lo:hi], t, packed, lo)
+            # the fused step's action goes to the env kernel as it is: the kernel clamps it to its box itself
+            act = b["act"][t] if self._fused is not None else b["act"][t].clamp(-1.0, 1.0).contiguous()
             # (asymmetric critic: the env step writes the critic rows of its range straight into the rollout's next slice)
-            d_cobs = b["cobs"][t + 1].data_ptr() if asym else None
-            if self._fused is not None:
-                # straight into the rollout buffers; the env kernel clamps the action to its box itself.  The noise is keyed by
-                # the GLOBAL sample index (sample_offset): the same draw however the batch is cut
-                self._fused.act_into(b["obs"][t][lo:hi], b["act"][t][lo:hi], b["logp"][t][lo:hi], b["val"][t][lo:hi], step=t,
-                                     packed=packed, step_base=self._step_base, sample_offset=lo, norm=self.obs_norm,
-                                     cobs=b["cobs"][t][lo:hi] if asym else None, cnorm=self.cobs_norm)
-                if whole:
-                    env.step_dev(b["act"][t].data_ptr(), b["obs"][t + 1].data_ptr(), b["rew_raw"][t].data_ptr(),
-                                 b["done_i"][t].data_ptr(), *((d_cobs,) if asym else ()))
-                else:
-                    env.step_range_dev(lo, hi - lo, stream_ptr, b["act"][t].data_ptr(), b["obs"][t + 1].data_ptr(),
-                                       b["rew_raw"][t].data_ptr(), b["done_i"][t].data_ptr(), *((d_cobs,) if asym else ()))
-                continue
-            a, logp, v = self.policy.act(b["obs"][t], cobs=b["cobs"][t]) if asym else self.policy.act(b["obs"][t])
-            b["act"][t].copy_(a); b["logp"][t].copy_(logp); b["val"][t].copy_(v)
-            clipped = a.clamp(-1.0, 1.0).contiguous()
-            env.step_dev(clipped.data_ptr(), b["obs"][t + 1].data_ptr(), b["rew_raw"][t].data_ptr(),
-                         b["done_i"][t].data_ptr(), *((d_cobs,) if asym else ()))
+            ptrs = (act.data_ptr(), b["obs"][t + 1].data_ptr(), b["rew_raw"][t].data_ptr(), b["done_i"][t].data_ptr(),
+                    b["cobs"][t + 1].data_ptr() if asym else None)
+            if stream_ptr is None:
+                env.step_dev(*ptrs)
+            else:
+                env.step_range_dev(lo, hi - lo, stream_ptr, *ptrs)
 
-    def _rollout_tail_norm(self, b):
-        """``_rollout_tail`` under return normalisation of the reward: with the fused policy step everything behind the value of the
-        last observation is one launch (rp_rollout_tail_dev); otherwise the torch statement and ``gae``."""
-        T, rn = self.n_steps, self.reward_norm
+    def _policy_step(self, obs_t, cobs_t, act_t, logp_t, val_t, t, packed, sample_offset=0):
+        """Step t's policy step on rows of the rollout's tensors (cobs_t: their critic rows, None with a symmetric critic): one launch
+        of the fused kernel straight into ``act_t``, ``logp_t``, ``val_t``, or ``policy.act`` and three copies.  The kernel's noise is
+        keyed by the GLOBAL sample index (``sample_offset`` + row): the same draw however the batch is cut."""
         if self._fused is not None:
-            self._step_base += T
+            self._fused.act_into(obs_t, act_t, logp_t, val_t, step=t, packed=packed, step_base=self._step_base,
+                                 sample_offset=sample_offset, norm=self.obs_norm, cobs=cobs_t, cnorm=self.cobs_norm)
+            return
+        # (a caller's own policy whose act() takes no ``cobs`` keyword keeps working where the critic is symmetric)
+        a, logp, v = self.policy.act(obs_t) if cobs_t is None else self.policy.act(obs_t, cobs=cobs_t)
+        act_t.copy_(a); logp_t.copy_(logp); val_t.copy_(v)
+
+    def _tail_kernel(self, b, last_value, ret_carry=None):
+        """The tail as one launch (rp_rollout_tail_dev / rp_rollout_tail_boot_dev): on the agent's own return statistics under
+        ``normalize_reward``, under identity statistics on ``_boot_tail``'s private carry (its sums are discarded) otherwise."""
+        rn = self.reward_norm if self.reward_norm is not None else self._boot_tail
+        rn.tail(b["rew_raw"], b["done_i"], b["val"], last_value, self.reward_scale, self.lam, b["rew"], b["done"], b["adv"], b["ret"],
+                ret_carry=ret_carry, boot=self.bootstrap_timeouts, identity=self.reward_norm is None)
+
+    def _rollout_tail(self, b, value_rows=None, eager=False):
+        """Everything behind a rollout's last env step, for the captured graph (one chain and two) and the eager rollout alike: the
+        [T, N] tensors ``rew_raw``, ``done_i`` (int32: 0 / 1, episode-end codes under ``bootstrap_timeouts``) and ``val`` of ``b`` and
+        the value of ``value_rows`` - the rows the value net reads for the last observation; None: the graph's buffers' own, which are
+        then carried over as the next replay's first - become ``rew``, ``done``, ``adv``, ``ret`` (and ``trunc``), by the form
+        ``rollout_tail_form`` names.  The all-reduce and merge of the return statistics are the caller's: they stay outside a graph."""
+        T, rn, boot = self.n_steps, self.reward_norm, self.bootstrap_timeouts
+        if value_rows is None:
+            value_rows = b["cobs"][T] if self.asymmetric_critic else b["obs"][T]
+        form = rollout_tail_form(self._fused is not None, eager, rn is not None, boot, self.asymmetric_critic)
+        if self._fused is not None:
+            self._step_base += T                                             # fresh noise on the next rollout
         with torch.no_grad():
-            last_value = self.policy.value(self._value_rows(b, T))
-        if self._fused is not None:
-            rn.tail(b["rew_raw"], b["done_i"], b["val"], last_value.contiguous(), self.reward_scale, self.lam, b["rew"], b["done"],
-                    b["adv"], b["ret"], boot=self.bootstrap_timeouts)
+            last_value = self.policy.value(value_rows)
+        if form == "tail_kernel":
+            self._tail_kernel(b, last_value.contiguous())
         else:
             r_s = b["rew_raw"] * self.reward_scale
-            b["done"].copy_(((b["done_i"] != 0) if self.bootstrap_timeouts else b["done_i"]).to(torch.float32))
-            rn.scan(r_s, b["done_i"])
-            b["rew"].copy_(rn.apply(r_s))
-            if self.bootstrap_timeouts:
-                adv, ret = gae_boot(b["rew"], b["val"], b["done_i"], last_value, self.gamma, self.lam)
+            if rn is not None:                   # the returns' scan on the scaled reward, the statistics frozen through it
+                rn.scan(r_s, b["done_i"])
+                r_s = rn.apply(r_s)
+            b["rew"].copy_(r_s)
+            b["done"].copy_(((b["done_i"] != 0) if boot else b["done_i"]).to(torch.float32))
+            if form == "gae_kernel":
+                gae_fused(b["rew"], b["val"], b["done"], last_value.contiguous(), self.gamma, self.lam, b["adv"], b["ret"])
             else:
-                adv, ret = gae(b["rew"], b["val"], b["done"], last_value, self.gamma, self.lam)
-            b["adv"].copy_(adv); b["ret"].copy_(ret)
-        if self.bootstrap_timeouts:
+                adv, ret = (gae_boot(b["rew"], b["val"], b["done_i"], last_value, self.gamma, self.lam) if boot else
+                            gae(b["rew"], b["val"], b["done"], last_value, self.gamma, self.lam))
+                b["adv"].copy_(adv); b["ret"].copy_(ret)
+        if boot:
             b["trunc"].copy_((b["done_i"] == 2).to(torch.float32))
-        self._carry_over(b, T)
-
-    def _rollout_tail_boot(self, b):
-        """``_rollout_tail`` with ``bootstrap_timeouts`` and without reward normalisation: with the fused policy step one launch
-        of rp_rollout_tail_boot_dev under identity statistics (its sums are discarded, its return carry is private); otherwise the
-        torch statements and ``gae_boot``."""
-        T = self.n_steps
-        if self._fused is not None:
-            self._step_base += T
-        with torch.no_grad():
-            last_value = self.policy.value(self._value_rows(b, T))
-        if self._fused is not None:
-            self._boot_tail.tail(b["rew_raw"], b["done_i"], b["val"], last_value.contiguous(), self.reward_scale, self.lam, b["rew"],
-                                 b["done"], b["adv"], b["ret"], boot=True, identity=True)
-        else:
-            b["rew"].copy_(b["rew_raw"] * self.reward_scale)
-            b["done"].copy_((b["done_i"] != 0).to(torch.float32))
-            adv, ret = gae_boot(b["rew"], b["val"], b["done_i"], last_value, self.gamma, self.lam)
-            b["adv"].copy_(adv); b["ret"].copy_(ret)
-        b["trunc"].copy_((b["done_i"] == 2).to(torch.float32))
-        self._carry_over(b, T)
-
-    def _rollout_tail(self, b):
-        if self.reward_norm is not None:
-            return self._rollout_tail_norm(b)
-        if self.bootstrap_timeouts:
-            return self._rollout_tail_boot(b)
-        T = self.n_steps
-        if self._fused is not None:
-            self._step_base += T                                             # fresh noise on the next replay
-        b["rew"].copy_(b["rew_raw"] * self.reward_scale)
-        b["done"].copy_(b["done_i"].to(torch.float32))
-        with torch.no_grad():
-            last_value = self.policy.value(self._value_rows(b, T))
-        if self._fused is not None:
-            gae_fused(b["rew"], b["val"], b["done"], last_value.contiguous(), self.gamma, self.lam, b["adv"], b["ret"])
-        else:
-            adv, ret = gae(b["rew"], b["val"], b["done"], last_value, self.gamma, self.lam)
-            b["adv"].copy_(adv); b["ret"].copy_(ret)
-        self._carry_over(b, T)
-
-    def _value_rows(self, b, t):
-        """the rows the value net reads at step t of the graph's buffers"""
-        return b["cobs"][t] if self.asymmetric_critic else b["obs"][t]
-
-    def _carry_over(self, b, T):
-        b["carry"].copy_(b["obs"][T])
-        if self.asymmetric_critic:
-            b["ccarry"].copy_(b["cobs"][T])
+        if not eager:
+            b["carry"].copy_(b["obs"][T])
+            if self.asymmetric_critic:
+                b["ccarry"].copy_(b["cobs"][T])
 
     def _rollout_body(self, b):
         self._rollout_steps(b, 0, b["carry"].shape[0])
@@ -1245,13 +1229,9 @@ class PPO:
             if self._fused is not None:       # its one-time launch configuration must not fall into the capture either
                 self._fused.act_into(b["carry"], b["act"][0], b["logp"][0], b["val"][0], deterministic=True, norm=self.obs_norm,
                                      cobs=b["ccarry"] if asym else None, cnorm=self.cobs_norm)
-                if self.reward_norm is not None:  # nor the tail kernel's (on a copy of the returns: they must not move)
-                    self.reward_norm.tail(b["rew_raw"], b["done_i"], b["val"], b["val"][0], self.reward_scale, self.lam, b["rew"],
-                                          b["done"], b["adv"], b["ret"], ret_carry=self.reward_norm.ret_carry.clone(),
-                                          boot=self.bootstrap_timeouts)
-                elif self._boot_tail is not None:
-                    self._boot_tail.tail(b["rew_raw"], b["done_i"], b["val"], b["val"][0], self.reward_scale, self.lam, b["rew"],
-                                         b["done"], b["adv"], b["ret"], boot=True, identity=True)
+                tail = self.reward_norm if self.reward_norm is not None else self._boot_tail
+                if tail is not None:          # nor the tail kernel's (on a copy of the returns: they must not move)
+                    self._tail_kernel(b, b["val"][0], ret_carry=tail.ret_carry.clone())
         side.synchronize()
         self.rollout_chains = self._pick_chains(N)
         # thread-local capture mode: another thread of the process (RCCL's watchdog in a multi-rank run) may call into
@@ -1338,6 +1318,8 @@ class PPO:
         return self._collect_rollout()
 
     def _collect_rollout(self):
+        """One rollout: the captured graph's replay, or - eager, on any device, torch or fused policy step - T (policy step,
+        ``env.step``) pairs and the tail the captured rollout runs too (``_rollout_tail``)."""
         if self.use_graphs:
             return self._collect_graph()
         env, T = self.env, self.n_steps
@@ -1349,101 +1331,35 @@ class PPO:
             if self.reward_norm is not None:
                 self.reward_norm.reset_returns(self._obs.shape[0])
         N = self._obs.shape[0]
-        buf = {k: [] for k in ("obs", "act", "logp", "val", "rew", "done") + (("cobs",) if asym else ())}
-        raw, codes = [], []
-        boot = self.bootstrap_timeouts
-        if boot and self._fused is not None:
-            return self._collect_rollout_boot_fused()
-        packed = self._fused.pack() if self._fused is not None else None
-        for t in range(T):
-            if self._fused is not None:
-                o = self._obs.contiguous()
-                a = torch.empty(N, self._fused.act_dim, device=self.device)
-                logp, v = torch.empty(N, device=self.device), torch.empty(N, device=self.device)
-                self._fused.act_into(o, a, logp, v, step=t, packed=packed, step_base=self._step_base, norm=self.obs_norm,
-                                     cobs=self._cobs.contiguous() if asym else None, cnorm=self.cobs_norm)
-            else:
-                a, logp, v = self.policy.act(self._obs, cobs=self._cobs) if asym else self.policy.act(self._obs)
-            clipped = a.clamp(-1.0, 1.0).contiguous()        # the env's action box (roboy_env.py:31)
-            obs, rew, done, _ = env.step(clipped if self.device.type == "cuda" else clipped.cpu().numpy())
-            buf["obs"].append(self._obs); buf["act"].append(a); buf["logp"].append(logp); buf["val"].append(v)
-            if asym:
-                buf["cobs"].append(self._cobs)
-                self._cobs = self._critic_rows()
-            rew = self._to_tensor(rew)
-            if self.reward_norm is not None:
-                raw.append(rew)
-            buf["rew"].append(rew * self.reward_scale)
-            buf["done"].append(self._to_tensor(done))
-            if boot:                                         # the codes: 0, 1 terminated, 2 truncated
-                codes.append(self._to_tensor(done, torch.int32) + self._to_tensor(env.truncated(), torch.int32))
-            self._obs = self._to_tensor(obs)
-        if self._fused is not None:
-            self._step_base += T
-        roll = {k: torch.stack(v) for k, v in buf.items()}
-        if self.reward_norm is not None:
-            # the torch statement of the fused tail: the returns' scan on the scaled reward, the statistics frozen through it
-            self._rew_raw = torch.stack(raw)
-            self.reward_norm.scan(roll["rew"], roll["done"])
-            roll["rew"] = self.reward_norm.apply(roll["rew"])
-            self.reward_norm.update(self.dist)
-        with torch.no_grad():
-            last_value = self.policy.value(self._cobs if asym else self._obs)
-        if boot:
-            codes = torch.stack(codes)
-            roll["trunc"] = (codes == 2).to(torch.float32)
-            roll["adv"], roll["ret"] = gae_boot(roll["rew"], roll["val"], codes, last_value, self.gamma, self.lam)
-        elif asym and self._fused is not None and self.reward_norm is None:
-            # the tail as the graph modes run it (rp_gae_dev, not the torch loop, whose roundings differ): with an asymmetric critic
-            # eager and captured rollouts agree bit for bit, as they do under bootstrap_timeouts
-            roll["adv"], roll["ret"] = gae_fused(roll["rew"].contiguous(), roll["val"].contiguous(), roll["done"].contiguous(),
-                                                 last_value.contiguous(), self.gamma, self.lam)
-        else:
-            roll["adv"], roll["ret"] = gae(roll["rew"], roll["val"], roll["done"], last_value, self.gamma, self.lam)
-        self.num_timesteps += T * N
-        return roll
-
-    def _collect_rollout_boot_fused(self):
-        """The eager rollout with the fused policy step and ``bootstrap_timeouts``: the steps through ``env.step``, then the tail as
-        the graph modes run it - one launch of rp_rollout_tail_boot_dev over the stacked rollout - so that eager and captured
-        rollouts agree bit for bit."""
-        env, T = self.env, self.n_steps
-        N = self._obs.shape[0]
         if self._boot_tail is not None and self._boot_tail.n_envs != N:
             self._boot_tail.reset_returns(N)
+        boot = self.bootstrap_timeouts
+        # fresh tensors on every call, filled step by step: a caller may keep an eager rollout beyond the next one
         z = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=self.device)
-        roll = {"obs": z(T, N, self._obs.shape[1]), "act": z(T, N, self._fused.act_dim), "logp": z(T, N), "val": z(T, N),
-                "rew": z(T, N), "done": z(T, N), "adv": z(T, N), "ret": z(T, N)}
-        rew_raw, codes = z(T, N), z(T, N, dtype=torch.int32)
-        asym = self.asymmetric_critic
+        roll = {"obs": z(T, N, self._obs.shape[1]), "act": z(T, N, env.action_space.shape[0])}
+        roll.update({k: z(T, N) for k in ("logp", "val", "rew", "done", "adv", "ret") + (("trunc",) if boot else ())})
         if asym:
             roll["cobs"] = z(T, N, self.cobs_dim)
-        packed = self._fused.pack()
+        rew_raw, codes = z(T, N), z(T, N, dtype=torch.int32)
+        packed = self._fused.pack() if self._fused is not None else None
         for t in range(T):
             roll["obs"][t].copy_(self._obs)
             if asym:
                 roll["cobs"][t].copy_(self._cobs)
-            self._fused.act_into(roll["obs"][t], roll["act"][t], roll["logp"][t], roll["val"][t], step=t, packed=packed,
-                                 step_base=self._step_base, norm=self.obs_norm, cobs=roll["cobs"][t] if asym else None,
-                                 cnorm=self.cobs_norm)
-            obs, rew, done, _ = env.step(roll["act"][t].clamp(-1.0, 1.0).contiguous())
-            rew_raw[t].copy_(rew)
-            codes[t].copy_(done.to(torch.int32) + env.truncated().to(torch.int32))
-            self._obs = obs
+            self._policy_step(roll["obs"][t], roll["cobs"][t] if asym else None, roll["act"][t], roll["logp"][t], roll["val"][t], t, packed)
+            clipped = roll["act"][t].clamp(-1.0, 1.0).contiguous()      # the env's action box (roboy_env.py:31)
+            obs, rew, done, _ = env.step(clipped if self.device.type == "cuda" else clipped.cpu().numpy())
+            rew_raw[t].copy_(torch.as_tensor(rew))           # (copy_ converts dtype and device in its one launch)
+            codes[t].copy_(torch.as_tensor(done))
+            if boot:                                         # the codes: 0, 1 terminated, 2 truncated
+                codes[t] += torch.as_tensor(env.truncated()).to(self.device)
+            self._obs = self._to_tensor(obs)
             if asym:
                 self._cobs = self._critic_rows()
-        self._step_base += T
-        with torch.no_grad():
-            last_value = self.policy.value(self._cobs if asym else self._obs).contiguous()
+        self._rollout_tail(dict(roll, rew_raw=rew_raw, done_i=codes), self._cobs if asym else self._obs, eager=True)
         if self.reward_norm is not None:
             self._rew_raw = rew_raw
-            self.reward_norm.tail(rew_raw, codes, roll["val"], last_value, self.reward_scale, self.lam, roll["rew"], roll["done"],
-                                  roll["adv"], roll["ret"], boot=True)
             self.reward_norm.update(self.dist)
-        else:
-            self._boot_tail.tail(rew_raw, codes, roll["val"], last_value, self.reward_scale, self.lam, roll["rew"], roll["done"],
-                                 roll["adv"], roll["ret"], boot=True, identity=True)
-        roll["trunc"] = (codes == 2).to(torch.float32)
         self.num_timesteps += T * N
         return roll
 
@@ -1494,7 +1410,7 @@ class PPO:
         average_gradients(self.policy, self.dist)
         nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
         dist = self.dist
-        if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        if dist_ranks(dist) > 1:
             # what update() reports is the mean over the ranks, as the fused path's slots are (one small all-reduce); the KL with it
             terms = torch.stack([pg.detach(), vf.detach()] + ([kl, cf] if self.diagnostics else []))
             dist.all_reduce(terms)

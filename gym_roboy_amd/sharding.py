@@ -23,10 +23,18 @@ def shard_bounds(n_total: int, world: int, rank: int):
     return start, base + (1 if rank < extra else 0)
 
 
+def dist_ranks(dist=None):
+    """The number of ranks of ``dist``'s process group; 0 without an initialised one (``dist`` None, unavailable or not
+    initialised).  ``> 1``: there is something to reduce over; ``> 0``: a group exists, be it of one rank."""
+    if dist is None or not dist.is_available() or not dist.is_initialized():
+        return 0
+    return dist.get_world_size()
+
+
 def allreduce_stats(stats, dist=None):
     """Sum a rank's statistics tensor over all ranks (in place); no-op without
     an initialised process group."""
-    if dist is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    if dist_ranks(dist) > 1:
         dist.all_reduce(stats, op=dist.ReduceOp.SUM)
     return stats
 
