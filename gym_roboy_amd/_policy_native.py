@@ -81,6 +81,11 @@ SIGNATURES["rp_clip_adam_kl_asym_dev"] = (_i, [_vp] * 4 + [_i, _i, _i, _vp] + [_
 # mirror-symmetry augmentation: the streaming pass that writes the mirrored half of the update's rows
 # (looked up by name: the ABI version stays 5)
 SIGNATURES["rp_mirror_rows_dev"] = (_i, [_vp, _vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp])
+# the mirror-symmetry loss on the action mean: the pair-tile instances of the gradient kernel + their reduction
+SIGNATURES["rp_sym_grad_dev"] = (_i, [_vp, _vp, _vp, _vp, ctypes.c_int64, _i, _i, _vp, _f, _vp, _i, _vp, _vp])
+SIGNATURES["rp_sym_grad_norm_dev"] = (_i, [_vp, _vp, _vp, _vp, ctypes.c_int64, _i, _i, _vp, _f, _vp, _f, _vp, _i, _vp, _vp])
+SIGNATURES["rp_sym_workspace_floats"] = (ctypes.c_int64, [_i, _i, ctypes.c_int64])
+SIGNATURES["rp_sym_grad_form"] = (_i, [_i, _i])
 
 
 def library_path():
@@ -156,6 +161,7 @@ def _grad_layout(obs_dim, vf_dim, act_dim, gs, total):
         out["%s_loss" % net] = (o, ())
         if net == "pi":
             out["approx_kl"], out["clip_frac"] = (o + 1, ()), (o + 2, ())
+            out["symmetry_loss"] = (o + 3, ())         # L_sym (rp_sym_grad_dev); rp_ppo_grad_*_dev leave 0 there
     return out, total
 
 

@@ -11,7 +11,30 @@
 // instead of a register the tile loop has not got - and clip_frac = #{rc != ratio} / B at loss + 2, counted per tile over the wave (a
 // ballot of the live lanes the clamp acted on: the running count is wave-uniform and costs no vector register).  RP_DIAG 0 expands
 // to the text as it was.
-#if RP_NORM && RP_DIAG
+// RP_SYM 1 (the action net only; DESIGN.md §26): mlp_sym_kernel / mlp_sym_norm_kernel, the gradient of the mirror-symmetry loss
+//     L_sym = coef / (B A) sum_i sum_j (mu(M s_i)[j] - mu(s_i)[P j])^2
+// A wave tile is 32 PAIRS: column tile 0 holds the rows s_i of `obs`, column tile 1 the same rows of `obs_image` (M s_i), through the
+// same staged, direct or prefetched operand paths.  After the forward pass lane l holds mu(s_l) and lane l ^ 32 mu(M s_l): every lane
+// stages its output row in S3, reads its partner's entry P[j] and forms d3[j] = c' (out[j] - partner[P j]), c' = 2 coef / (B A) - the
+// derivative for BOTH branches (P is an involution).  The image half adds the loss term, so a pair counts once.  Everything behind d3
+// is the text of the PPO kernel.  P comes in the kernel arguments (scalar loads at constant offsets: no vector register holds it).
+// RP_SYM 0 expands to the text as it was.
+#if RP_SYM
+#define RP_TW 32                                           /* samples (pairs) of a wave tile */
+#define RP_IN_TILE(l) ((l) & 31)                           /* a lane's sample within the tile */
+#define RP_OBS_OF(t) ((t) ? sym.obs_image : a.obs)         /* the rows of column tile t */
+#define RP_SYM_PARAMS , const SymArgs sym
+#else
+#define RP_TW 64
+#define RP_IN_TILE(l) (l)
+#define RP_OBS_OF(t) a.obs
+#define RP_SYM_PARAMS
+#endif
+#if RP_SYM && RP_NORM
+#define RP_KERNEL mlp_sym_norm_kernel
+#elif RP_SYM
+#define RP_KERNEL mlp_sym_kernel
+#elif RP_NORM && RP_DIAG
 #define RP_KERNEL mlp_grad_norm_diag_kernel
 #elif RP_NORM
 #define RP_KERNEL mlp_grad_norm_kernel
@@ -27,10 +50,13 @@
 #endif
 template <int NET, int KX, int NJ, bool PF>
 __global__ void __launch_bounds__(256, 1)
-RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
+RP_KERNEL(const TrainArgs a RP_NORM_PARAMS RP_SYM_PARAMS) {
     static_assert(!PF || KX == 1, "the prefetching form is the small instance's");
 #if RP_DIAG
     static_assert(NET == 0, "the diagnostics are the action net's");
+#endif
+#if RP_SYM
+    static_assert(NET == 0, "the symmetry loss is the action net's");
 #endif
     constexpr int OT = (NJ + 31) / 32;                     // 32-row tiles of the outputs
     extern __shared__ float4 lds4[];
@@ -63,14 +89,18 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
     constexpr int S3S = NJ + 1;                            // row stride of the delta3 staging (odd)
     // KX == 1: the tile's observations [64 samples][33], staged once - or (PF) two buffers of pf_rows rows of the tile's inputs:
     // rows [0, obs_dim) observation columns, then NET 0: act_dim action columns, advantage, old log-probability; NET 1: old value, return;
+#if RP_SYM
+    const int pf_rows = obs_dim + 2;                       // the observation columns (rows of obs | of obs_image) and the next tile's row index
+#else
     const int pf_rows = obs_dim + (NET == 0 ? act_dim + 2 : 2) + 2;   // (+ 2: the next tile's row index, low and high words)
+#endif
     const int XSN = PF ? 2 * pf_rows * PFS : (KX == 1 ? 64 * 33 : 0);
     float *T = lds + lds_used + wave * (32 * 33 + 64 * S3S + XSN);   // transpose scratch, the delta3 staging [64][S3S], observations
     float *S3 = T + 32 * 33;
     float *XS = S3 + 64 * S3S;
     const float onehot = half ? 0.0f : 1.0f;
     const f32x16 zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const long B = a.B, n_tiles = (B + 63) / 64;
+    const long B = a.B, n_tiles = (B + RP_TW - 1) / RP_TW;
     const int mrow = 0;                                     // (the staged layer-1 block holds this net's two row tiles)
     const int k3s = L.k3s[NET];
 
@@ -105,14 +135,15 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
 
     const long tile0 = long(blockIdx.x) * nw + wave, tstep = long(gridDim.x) * nw;
     // (PF) this lane's sample of tile t: position in the minibatch and row in the rollout tensors
-    auto pos_of = [&](long t) { const long p = t * 64 + lane; return p < B ? p : B - 1; };
+    auto pos_of = [&](long t) { const long p = t * RP_TW + RP_IN_TILE(lane); return p < B ? p : B - 1; };
     auto row_of = [&](long t) { const long p = pos_of(t); return a.index ? long(a.index[p]) : p; };
     auto prefetch = [&](long t, long row, int buf) {        // tile t's rows (this lane's sample at `row`) + the sample order of the tile after it
         float *dst = XS + buf * pf_rows * PFS;
-        const float *xr = a.obs + row * obs_dim;
+        const float *xr = RP_OBS_OF(lane >> 5) + row * obs_dim;
         for (int k = 0; k < obs_dim; ++k) dma_dword(xr + k, dst + k * PFS);
         dst += obs_dim * PFS;
-        if (NET == 0) {
+        if (RP_SYM) {
+        } else if (NET == 0) {
             const float *ar = a.act + row * act_dim;
             for (int j = 0; j < act_dim; ++j) dma_dword(ar + j, dst + j * PFS);
             dma_dword(a.adv + (a.adv_stats ? row : pos_of(t)), dst + act_dim * PFS);
@@ -166,18 +197,18 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
             }
         }
         // ================= forward =================
-        long s0 = tile * 64 + col, s1 = s0 + 32;
+        long s0 = tile * RP_TW + col, s1 = s0 + (RP_SYM ? 0 : 32);     // (RP_SYM: the pair - row s0 of obs and of obs_image)
         s0 = s0 < B ? s0 : B - 1; s1 = s1 < B ? s1 : B - 1;
         if (!PF && a.index) { s0 = a.index[s0]; s1 = a.index[s1]; }
-        const float *x0 = a.obs + s0 * obs_dim, *x1 = a.obs + s1 * obs_dim;
+        const float *x0 = a.obs + s0 * obs_dim, *x1 = RP_OBS_OF(1) + s1 * obs_dim;
         if (KX == 1 && !PF) {
             // the tile's observation rows (gathered when indexed) go to LDS once: lane = sample reads its whole row with
             // all loads in flight together; the K loop of layer 1 and the dW1 operands then come from LDS instead of
             // one dependent global load per step (the indexed minibatch cost 10.4 ms against 7.6 contiguous before)
-            long sr = tile * 64 + lane;
+            long sr = tile * RP_TW + RP_IN_TILE(lane);
             sr = sr < B ? sr : B - 1;
             if (a.index) sr = a.index[sr];
-            const float *xr = a.obs + sr * obs_dim;
+            const float *xr = RP_OBS_OF(half) + sr * obs_dim;
 #pragma unroll
             for (int k0 = 0; k0 < 32; k0 += 8) {                 // eight loads in flight at a time (registers are scarce here)
                 float v[8];
@@ -276,13 +307,33 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
             }
         }
         // ================= loss derivative of this lane's sample =================
-        const long i = tile * 64 + lane;
+        const long i = tile * RP_TW + RP_IN_TILE(lane);
         const bool live = i < B;
         const long im = live ? i : B - 1;                    // position in the minibatch
         const long ii = PF ? im : (a.index ? long(a.index[im]) : im);     // row in the rollout tensors (PF: the inputs are in PB)
         float d3[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) d3[j] = 0.0f;
+#if RP_SYM
+        {
+            // every lane's output row to its S3 row; the partner (the pair's other branch) is lane ^ 32
+            (void)ii; (void)adv_mean; (void)adv_istd;        // (the PPO epilogue's)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                if (j < act_dim) S3[lane * S3S + j] = out[j];
+            wave_fence();
+            float e2 = 0.0f;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                if (j < act_dim) {
+                    const float e = out[j] - S3[(lane ^ 32) * S3S + sym.act_src[j]];
+                    d3[j] = live ? sym.c2 * e : 0.0f;
+                    e2 += e * e;
+                }
+            if (live && half) loss_sum += sym.lscale * e2;   // the image half alone: each pair once
+            wave_fence();                                    // the partner reads above, the delta3 staging below
+        }
+#else
         if (NET == 0) {
             float lp = -0.91893853320467274f * float(act_dim);
             float z[NJ], iv[NJ];
@@ -324,6 +375,7 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
             d3[0] = live ? a.vf_coef * a.inv_B * dvl : 0.0f;
             if (live) loss_sum += 0.5f * fmaxf(e1, e2) * a.inv_B;
         }
+#endif
 #pragma unroll
         for (int j = 0; j < NJ; ++j) db3[j] += d3[j];
         // delta3 staged [sample][row] for the transposed (row-on-lane) reads of dW3
@@ -433,7 +485,7 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
 #endif
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                long sn = tile * 64 + 32 * t + unit_of(r) + 4 * half;          // sample of this K slot
+                long sn = tile * RP_TW + (RP_SYM ? 0 : 32 * t) + unit_of(r) + 4 * half;    // sample of this K slot (RP_SYM: the pair)
                 sn = sn < B ? sn : B - 1;
                 if (KX != 1 && a.index) sn = a.index[sn];
 #pragma unroll
@@ -445,7 +497,7 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
                         xv = col < obs_dim ? v : (col == obs_dim ? 1.0f : 0.0f);
                     } else
                         xv = KX == 1 ? XS[(32 * t + unit_of(r) + 4 * half) * 33 + col]
-                                     : (k < obs_dim ? a.obs[sn * obs_dim + k] : (k == obs_dim ? 1.0f : 0.0f));
+                                     : (k < obs_dim ? RP_OBS_OF(t)[sn * obs_dim + k] : (k == obs_dim ? 1.0f : 0.0f));
 #if RP_NORM
                     if ((PF || KX != 1) && k < obs_dim) xv = obs_operand<true>(xv, nmu[kx], nrs[kx], clip);
 #endif
@@ -512,7 +564,7 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
     float ls = loss_sum;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ls += __shfl_xor(ls, off, 64);
-    if (lane == 0) P[g.loss] = ls;
+    if (lane == 0) P[g.loss + (RP_SYM ? RP_SYM_LOSS_SLOT : 0)] = ls;
 #if RP_DIAG
     float kl = S3[lane * S3S + NJ];
 #pragma unroll
@@ -531,5 +583,10 @@ RP_KERNEL(const TrainArgs a RP_NORM_PARAMS) {
 }
 #undef RP_KERNEL
 #undef RP_NORM_PARAMS
+#undef RP_SYM_PARAMS
+#undef RP_OBS_OF
+#undef RP_TW
+#undef RP_IN_TILE
 #undef RP_NORM
 #undef RP_DIAG
+#undef RP_SYM

@@ -58,7 +58,8 @@ int cu_count(int dev) {
 }
 
 namespace {
-constexpr int GRANT_KERNELS = 36, GRANT_DEVICES = 64;        // 0 .. 8, + 9 for the normalising instance of each, + 18 / + 27 for the diagnostics instances
+constexpr int GRANT_KERNELS = 42, GRANT_DEVICES = 64;        // 0 .. 8, + 9 for the normalising instance of each, + 18 / + 27 for the diagnostics instances,
+                                                              // 36 .. 41 for the symmetry-loss instances (mlp_train.hip: launch_sym)
 std::mutex g_grant_mutex;
 size_t g_granted[GRANT_KERNELS][GRANT_DEVICES];            // bytes granted so far (0: the default 64 KB)
 }

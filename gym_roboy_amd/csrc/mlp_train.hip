@@ -79,17 +79,39 @@ struct TrainArgs {
 // of 8 388 608 samples: 4.4 ms against 3.5 contiguous, 29 % of the wave cycles waiting)
 // the instances of one kernel text (KX: 32-column tiles of [obs | 1]; NJ: bound of the outputs; PF: inputs by LDS-DMA - see the text):
 // without normalisation and with it; and the action net's diagnostics instances of both (RP_DIAG 1: approx_kl and clip_frac)
+// the mirror-symmetry loss: what the RP_SYM 1 instances take beside TrainArgs - a struct of its own, so that the
+// kernel arguments of the instances above are what they were
+struct SymArgs {
+    const float *obs_image;                               // [rows][obs_dim]: row r is the mirror image M obs[r]
+    float c2, lscale;                                     // 2 coef / (B A): the factor of d3;  coef / (B A): of the loss term
+    int act_src[64];                                      // P: image action j is action act_src[j] (an involution; entries >= act_dim: 0)
+};
+constexpr int RP_SYM_LOSS_SLOT = 3;                       // L_sym's slot behind the action net's loss slot (roboy_policy.h: rp_sym_grad_dev)
 #define RP_NORM 0
 #define RP_DIAG 0
+#define RP_SYM 0
 #include "mlp_grad_kernel.inc"
 #define RP_NORM 1
 #define RP_DIAG 0
+#define RP_SYM 0
 #include "mlp_grad_kernel.inc"
 #define RP_NORM 0
 #define RP_DIAG 1
+#define RP_SYM 0
 #include "mlp_grad_kernel.inc"
 #define RP_NORM 1
 #define RP_DIAG 1
+#define RP_SYM 0
+#include "mlp_grad_kernel.inc"
+
+// the symmetry-loss instances of the same text (RP_SYM 1)
+#define RP_NORM 0
+#define RP_DIAG 0
+#define RP_SYM 1
+#include "mlp_grad_kernel.inc"
+#define RP_NORM 1
+#define RP_DIAG 0
+#define RP_SYM 1
 #include "mlp_grad_kernel.inc"
 
 // out[k] = sum over the partials (one per workgroup, `gstride` apart)
@@ -104,6 +126,25 @@ __global__ void reduce_partials_kernel(const float *__restrict__ partials, int n
     }
     for (; w < n_waves; ++w) s0 += partials[long(w) * gstride + k];
     out[k] = (s0 + s1) + (s2 + s3);
+}
+
+// reduce_partials_kernel's sums in its order for the symmetry loss's block: the parameter entries [0, n_params) and the one slot
+// `slot` (L_sym) - the slots between them (pg loss, approx_kl, clip_frac) are neither read nor written.  The sum over the partials is
+// formed first and added to what is there last (accumulate), so that accumulate = 1 onto g0 is exactly g0 + (accumulate = 0).
+__global__ void reduce_sym_kernel(const float *__restrict__ partials, int n_waves, int gstride, int n_params, int slot, int accumulate,
+                                  float *__restrict__ out) {
+    int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > n_params) return;
+    if (k == n_params) k = slot;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+    int w = 0;
+    for (; w + 3 < n_waves; w += 4) {
+        s0 += partials[long(w) * gstride + k]; s1 += partials[long(w + 1) * gstride + k];
+        s2 += partials[long(w + 2) * gstride + k]; s3 += partials[long(w + 3) * gstride + k];
+    }
+    for (; w < n_waves; ++w) s0 += partials[long(w) * gstride + k];
+    const float sum = (s0 + s1) + (s2 + s3);
+    out[k] = accumulate ? out[k] + sum : sum;
 }
 
 // generalised advantage estimation over a [T][N] rollout, one env per thread, backwards in time (ppo.py: gae())
@@ -174,6 +215,22 @@ int launch_grad(const TrainArgs &a, const float *norm, float clip, long blocks, 
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(RP_EHIP, std::string("mlp_grad_kernel: ") + hipGetErrorString(e));
+    return RP_OK;
+}
+
+// the symmetry-loss instances: FORM 2 = small + prefetch, 1 = small (staged), 0 = general; kernels and LDS grants of their own
+template <int KX, int NJ, bool PF>
+int launch_sym(const TrainArgs &a, const SymArgs &sym, const float *norm, float clip, long blocks, size_t lds, int dev, hipStream_t stream) {
+    constexpr int kernel_id = 36 + (KX - 1) + (PF ? 2 : 0);
+    if (norm) {
+        if (int rc = grant_lds(reinterpret_cast<const void *>(&mlp_sym_norm_kernel<0, KX, NJ, PF>), kernel_id + 3, dev, lds)) return rc;
+        hipLaunchKernelGGL((mlp_sym_norm_kernel<0, KX, NJ, PF>), dim3(unsigned(blocks)), dim3(64 * WAVES_PER_BLOCK), lds, stream, a, norm, clip, sym);
+    } else {
+        if (int rc = grant_lds(reinterpret_cast<const void *>(&mlp_sym_kernel<0, KX, NJ, PF>), kernel_id, dev, lds)) return rc;
+        hipLaunchKernelGGL((mlp_sym_kernel<0, KX, NJ, PF>), dim3(unsigned(blocks)), dim3(64 * WAVES_PER_BLOCK), lds, stream, a, sym);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RP_EHIP, std::string("mlp_sym_kernel: ") + hipGetErrorString(e));
     return RP_OK;
 }
 
@@ -341,6 +398,74 @@ int rp_ppo_grad_diag_dev(const float *d_packed_train, const float *d_obs, const 
                          const float *d_norm, float clip, float *d_grad, float *d_workspace, void *stream) {
     return ppo_grad_launch(true, d_packed_train, d_packed_train, d_obs, d_obs, d_act, d_adv, d_adv_stats, d_logp_old, d_val_old, d_ret, d_index, batch,
                            obs_dim, obs_dim, act_dim, cliprange, vf_coef, d_norm, clip, d_norm, clip, d_grad, d_workspace, stream);
+}
+
+// ---- the mirror-symmetry loss: one launch of an RP_SYM instance over ceil(batch / 32) pair tiles + its reduction ----
+// the small instance's two variants: the prefetching one wherever its two input buffers per wave (obs_dim + 2 rows each: fewer than
+// the PPO kernel's, which also carry the actions, the advantage and the old log-probability) fit beside the operands - that is every
+// small policy - unless ROBOY_POLICY_PREFETCH=0
+int rp_sym_grad_form(int obs_dim, int act_dim) {
+    if (rp_train_packed_floats(obs_dim, act_dim) < 0) return RP_EUNSUPPORTED;
+    const Layout L = layout_of(obs_dim, act_dim);
+    if (!((obs_dim + 1 + 31) / 32 == 1 && act_dim <= 8)) return 0;
+    static const bool prefetch_off = [] { const char *e = getenv("ROBOY_POLICY_PREFETCH"); return e && e[0] == '0'; }();
+    return !prefetch_off && grad_lds_bytes(L, 0, 8, 1, obs_dim + 2) <= 160 * 1024 ? 2 : 1;
+}
+
+int64_t rp_sym_workspace_floats(int obs_dim, int act_dim, int64_t batch) {
+    if (rp_train_packed_floats(obs_dim, act_dim) < 0 || batch < 1) return RP_EUNSUPPORTED;
+    return grad_blocks(2 * batch) * WAVES_PER_BLOCK * int64_t(gstride_of(obs_dim, act_dim));
+}
+
+int rp_sym_grad_norm_dev(const float *d_packed_train, const float *d_obs, const float *d_obs_image, const int64_t *d_index, int64_t batch,
+                         int obs_dim, int act_dim, const int32_t *act_src, float coef, const float *d_norm, float clip, float *d_grad_pi,
+                         int accumulate, float *d_workspace, void *stream) {
+    if (d_norm && !(clip > 0.0f)) return fail(RP_EINVAL, "clip must be > 0");
+    if (!d_packed_train || !d_obs || !d_obs_image || !act_src || !d_grad_pi || !d_workspace) return fail(RP_EINVAL, "null argument");
+    if (batch < 1) return fail(RP_EINVAL, "batch must be >= 1");
+    if (!(coef >= 0.0f) || !(coef <= 3.0e38f)) return fail(RP_EINVAL, "coef must be finite and >= 0");
+    if (rp_train_packed_floats(obs_dim, act_dim) < 0) return RP_EUNSUPPORTED;
+    SymArgs sym;
+    for (int j = 0; j < 64; ++j) sym.act_src[j] = 0;
+    for (int j = 0; j < act_dim; ++j) {
+        const int p = act_src[j];
+        if (p < 0 || p >= act_dim || act_src[p] != j)
+            return fail(RP_EINVAL, "act_src must be an involution of [0, act_dim): act_src[act_src[j]] == j for every j");
+        sym.act_src[j] = p;
+    }
+    sym.obs_image = d_obs_image;
+    sym.lscale = float(double(coef) / (double(batch) * double(act_dim)));
+    sym.c2 = float(2.0 * double(coef) / (double(batch) * double(act_dim)));
+    DeviceScope scope(d_packed_train); if (scope.rc) return scope.rc;
+    const int dev = scope.dev;
+    const int gs = gstride_of(obs_dim, act_dim);
+    const long blocks = grad_blocks(2 * batch);                         // ceil(batch / 32) pair tiles, four waves per workgroup
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    TrainArgs a;
+    a.packed = d_packed_train; a.obs = d_obs; a.act = nullptr; a.adv = nullptr; a.adv_stats = nullptr; a.logp_old = nullptr; a.val_old = nullptr;
+    a.ret = nullptr; a.index = reinterpret_cast<const long long *>(d_index); a.B = batch; a.obs_dim = obs_dim; a.act_dim = act_dim; a.gstride = gs;
+    a.cliprange = 0.0f; a.vf_coef = 0.0f; a.inv_B = 1.0f / float(batch);
+    a.partials = d_workspace;
+    const Layout L = layout_of(obs_dim, act_dim);
+    const int form = rp_sym_grad_form(obs_dim, act_dim);
+    int rc;
+    if (form == 2) rc = launch_sym<1, 8, true>(a, sym, d_norm, clip, blocks, grad_lds_bytes(L, 0, 8, 1, obs_dim + 2), dev, st);
+    else if (form == 1) rc = launch_sym<1, 8, false>(a, sym, d_norm, clip, blocks, grad_lds_bytes(L, 0, 8, 1), dev, st);
+    else rc = launch_sym<2, 64, false>(a, sym, d_norm, clip, blocks, grad_lds_bytes(L, 0, 64, 2), dev, st);
+    if (rc) return rc;
+    const GOff g = goff_of(obs_dim, act_dim);
+    hipLaunchKernelGGL(reduce_sym_kernel, dim3((g.loss + 1 + 255) / 256), dim3(256), 0, st, d_workspace, int(blocks), WAVES_PER_BLOCK * gs, g.loss,
+                       g.loss + RP_SYM_LOSS_SLOT, accumulate != 0 ? 1 : 0, d_grad_pi);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RP_EHIP, std::string("reduce_sym_kernel: ") + hipGetErrorString(e));
+    return RP_OK;
+}
+
+int rp_sym_grad_dev(const float *d_packed_train, const float *d_obs, const float *d_obs_image, const int64_t *d_index, int64_t batch,
+                    int obs_dim, int act_dim, const int32_t *act_src, float coef, float *d_grad_pi, int accumulate, float *d_workspace,
+                    void *stream) {
+    return rp_sym_grad_norm_dev(d_packed_train, d_obs, d_obs_image, d_index, batch, obs_dim, act_dim, act_src, coef, nullptr, 0.0f, d_grad_pi,
+                                accumulate, d_workspace, stream);
 }
 
 // ---- the asymmetric critic: the value net on rows and a blob of its own, the same kernel instances ----

@@ -40,6 +40,10 @@ with that rollout's moments after the update's last minibatch.
 ``symmetry="augment"`` (an env with ``mirror_map()``: a robot with a mirror plane) runs every update on the rollout's samples and
 their mirror images: one streaming kernel (``rp_mirror_rows_dev``) writes the mirrored half of the [2 n, ...] sample set, and the
 gradient, statistics, sample-order and optimiser kernels run unchanged on twice the rows.
+``symmetry="loss"`` keeps the samples and adds ``symmetry_coef`` x the mean squared distance of the action mean from the symmetry to
+every minibatch's loss, the gradient through both branches: one more gradient kernel per minibatch (``rp_sym_grad_dev``) whose wave
+tile is 32 (sample, image) pairs, added into the PPO gradient in front of clip + Adam.  It reads the action net and the actor's rows
+only and combines with ``asymmetric_critic``.
 """
 import math
 
@@ -50,7 +54,7 @@ from torch import nn
 from .sharding import dist_ranks
 
 LR_SCHEDULES = ("adaptive",)
-SYMMETRY_MODES = ("augment",)
+SYMMETRY_MODES = ("augment", "loss")
 
 
 def adapt_lr(lr, kl, desired_kl, lr_factor, lr_min, lr_max):
@@ -595,6 +599,7 @@ class FusedPolicyGrad:
         B = int(index.shape[0]) if (index is not None and adv_stats is not None) else int(adv.shape[0])
         flat = torch.cat([self._named[k].detach().reshape(-1) for k in self._pn.PARAM_ORDER] + [self._zero])
         packed = flat[self._map]
+        self._packed_pi = packed if self.cobs_dim is None else packed[:self._split]      # (kept for sym_run() on the same parameters)
         if self.cobs_dim is None:
             need = int(self._lib.rp_ppo_workspace_floats(self.obs_dim, self.act_dim, B))
         else:
@@ -642,6 +647,41 @@ class FusedPolicyGrad:
         pg = self._g[self._layout["pi_loss"][0]]
         vf = self._g[self._layout["vf_loss"][0]]
         return pg, vf
+
+    @torch.no_grad()
+    def sym_run(self, obs, obs_image, act_src, coef, index=None, norm=None, accumulate=False, repack=True):
+        """The mirror-symmetry loss of the action mean (rp_sym_grad_dev) on the minibatch ``index`` of obs and of
+        obs_image (the rows M obs).  accumulate=False (the C ABI's 0) overwrites the action block's parameter entries and L_sym's
+        slot; accumulate=True, behind ``run()`` on the same parameters, adds its gradient into the vector ``run()`` left, in front of
+        ``FusedAdam.step``.  act_src: the action map P, a sequence of act_dim ints.  Returns the
+        view of L_sym's slot.  repack=False: the operand blob ``run()`` packed is read again (the parameters have not moved since)."""
+        c = self._ct
+        if repack or getattr(self, "_packed_pi", None) is None:
+            flat = torch.cat([self._named[k].detach().reshape(-1) for k in self._pn.PARAM_ORDER] + [self._zero])
+            packed = flat[self._map]
+            self._packed_pi = packed if self.cobs_dim is None else packed[:self._split]
+        B = int(index.shape[0]) if index is not None else int(obs.shape[0])
+        need = int(self._lib.rp_sym_workspace_floats(self.obs_dim, self.act_dim, B))
+        if getattr(self, "_sym_ws", None) is None or self._sym_ws.numel() < need:
+            self._sym_ws = torch.empty(need, device=obs.device)
+        for name, t in (("obs", obs), ("obs_image", obs_image)):
+            if t.dim() != 2 or t.shape[1] != self.obs_dim or not t.is_contiguous() or t.dtype != torch.float32 or t.device != self._g.device:
+                raise ValueError("%s must be contiguous float32 rows of %d columns on %s" % (name, self.obs_dim, self._g.device))
+        if tuple(obs_image.shape) != tuple(obs.shape):
+            raise ValueError("the image rows must have the observation rows' shape")
+        if index is not None and (index.dim() != 1 or index.dtype != torch.int64 or not index.is_contiguous() or index.device != self._g.device):
+            raise ValueError("index must be a contiguous int64 vector on %s" % (self._g.device,))
+        src = (c.c_int32 * self.act_dim)(*[int(j) for j in act_src])
+        ptr = lambda t: c.c_void_p(t.data_ptr()) if t is not None else None
+        stream = c.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+        head = (ptr(self._packed_pi), ptr(obs), ptr(obs_image), ptr(index), B, self.obs_dim, self.act_dim, src, float(coef))
+        tail = (ptr(self._g), int(bool(accumulate)), ptr(self._sym_ws), stream)
+        if norm is None:
+            self._pn.check(self._lib.rp_sym_grad_dev(*head, *tail))
+        else:
+            _check_norm(norm, self.obs_dim, obs.device)
+            self._pn.check(self._lib.rp_sym_grad_norm_dev(*head, ptr(norm.norm), float(norm.clip), *tail))
+        return self._g[self._layout["symmetry_loss"][0]]
 
     def diag(self):
         """(approx_kl, clip_frac) of the last ``run(diagnostics=True)``: views of the gradient vector's two slots."""
@@ -878,14 +918,15 @@ class _MirrorMaps:
         return True
 
     @torch.no_grad()
-    def rows_into(self, src, out, kind):
+    def rows_into(self, src, out, kind, plain=True):
         """out [2 n, width] (or [2 n]) <- [src; image of src], src [n, width] (or [n]) contiguous float32 on the GPU; kind: "obs",
-        "act", or "one" - the per-sample scalars, which are copied"""
+        "act", or "one" - the per-sample scalars, which are copied.  plain=False: out [n, width] <- the image alone"""
         pn, c, lib = self._native
         n = int(src.shape[0])
         width = int(src.shape[1]) if src.dim() == 2 else 1
         ptr = lambda t: c.c_void_p(t.data_ptr())
-        pn.check(lib.rp_mirror_rows_dev(ptr(src), ptr(out), ptr(out[n:]), n, width, ptr(self._src32[kind]), ptr(self._sign32[kind]),
+        pn.check(lib.rp_mirror_rows_dev(ptr(src), ptr(out) if plain else None, ptr(out[n:]) if plain else ptr(out), n, width,
+                                        ptr(self._src32[kind]), ptr(self._sign32[kind]),
                                         c.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)))
 
 
@@ -896,7 +937,7 @@ class PPO:
                  fused_update=None, rollout_chains=None, normalize_obs=False, clip_obs=10.0, obs_norm_prime=True,
                  normalize_reward=False, clip_reward=10.0, reward_norm_prime=True, bootstrap_timeouts=False,
                  lr_schedule=None, desired_kl=0.01, lr_factor=1.5, lr_min=1e-5, lr_max=1e-2, diagnostics=False,
-                 asymmetric_critic=False, symmetry=None):
+                 asymmetric_critic=False, symmetry=None, symmetry_coef=1.0):
         """fused_policy / fused_update: None = the fused MFMA kernels whenever they apply (a GPU, MlpPolicy's shape,
         dimensions the kernels support), True = insist, False = the torch path (the statement the kernels are
         tested against).  The gradient kernel takes up to 63 observation columns: an env with ``action_obs=K`` stays fused while
@@ -938,10 +979,21 @@ class PPO:
         statistics of ``normalize_obs`` are merged over the rows and their images.  Needs an env with ``mirror_map()`` (RoboyVecEnv on
         a robot with a mirror plane); not with ``asymmetric_critic``, whose critic rows have no map yet.  ``symmetry_gap(roll)``
         measures how far the policy is from the symmetry.  Eager and graph modes, torch and fused paths; the augmentation is
-        rank-local and sits in front of the collectives.  DESIGN.md §25."""
+        rank-local and sits in front of the collectives.  DESIGN.md §25.
+        "loss" - the samples stay the rollout's; every minibatch's loss gains
+        ``symmetry_coef * mean_i,j (mu(M s_i)[j] - mu(s_i)[P j])^2`` (mu: the action mean, M / P: the env's observation / action maps),
+        with the gradient through both branches: ``symmetry_coef * symmetry_gap(...)["action"]`` on the minibatch's rows.  It touches the
+        action net and the actor's rows only, so it combines with ``asymmetric_critic``; log_std and the value net get no gradient from
+        it.  On the fused path one more gradient kernel per minibatch (rp_sym_grad_dev) adds into the PPO gradient in front of
+        clip + Adam; the image rows are written once per update.  ``normalize_obs`` merges the rows and their images, as "augment" does.
+        ``update()`` also returns ``"symmetry_loss"``, the last minibatch's term.  symmetry_coef (>= 0) is used by "loss" only; the
+        checkpoint records it, and ``load`` keeps the constructor's value, warning where the checkpoint's differs.
+        DESIGN.md §26."""
         if symmetry not in (None,) + SYMMETRY_MODES:
             raise ValueError("unknown symmetry %r: None or one of %r" % (symmetry, SYMMETRY_MODES))
-        if symmetry is not None and asymmetric_critic:
+        if not float(symmetry_coef) >= 0.0 or math.isinf(float(symmetry_coef)):
+            raise ValueError("symmetry_coef must be finite and >= 0")
+        if symmetry == "augment" and asymmetric_critic:
             raise ValueError("symmetry=%r does not combine with asymmetric_critic: the critic rows (parameters, delay, age) have no "
                              "mirror map yet" % (symmetry,))
         if symmetry is not None and not callable(getattr(env, "mirror_map", None)):
@@ -1046,9 +1098,11 @@ class PPO:
                              "step_dev, which the captured rollout reads as 0 / 1: pass bootstrap_timeouts=True or build the env without it")
         self._rew_raw = None                  # the last rollout's raw reward (kept with normalize_reward: learn() reports it)
         self.symmetry = symmetry
+        self.symmetry_coef = float(symmetry_coef)
         self._mirror = None                   # symmetry: the env's row maps on the agent's device (_MirrorMaps)
         if symmetry is not None:
             self._mirror = _MirrorMaps(env.mirror_map(), obs_dim, act_dim, self.device)
+            self._act_src_host = [int(j) for j in np.asarray(env.mirror_map()[2])]      # P for rp_sym_grad_dev (a host array)
         self.last_rollout = None              # learn(): the rollout of its last update (graph mode: views of the graph's buffers)
         self.num_timesteps = 0
         self._obs = None
@@ -1058,13 +1112,22 @@ class PPO:
         """the env's critic rows of the observation last returned, on the agent's device"""
         return self._to_tensor(self.env.critic_obs())
 
-    def _update_obs_norms(self, obs_rows, cobs_rows):
+    def _update_obs_norms(self, obs_rows, cobs_rows, image_rows=None):
         """Merge a rollout's moments into the observation statistics - and the critic rows' into theirs, the two sets of sums
-        all-reduced over the ranks as ONE tensor."""
-        if self.cobs_norm is None:
-            return self.obs_norm.update(obs_rows, self.dist)
+        all-reduced over the ranks as ONE tensor.  image_rows (``symmetry="loss"``): the rows' mirror images join the observation's
+        moments - both sets of sums are taken around the same mean, so they add, and no [2 n, obs_dim] copy is made."""
         a, c = self.obs_norm, self.cobs_norm
-        sa, sc = a.moments(obs_rows.to(a.device)), c.moments(cobs_rows.to(c.device))
+        if image_rows is not None:
+            sa = a.moments(obs_rows.to(a.device)).clone()            # (moments() hands out one buffer)
+            sa += a.moments(image_rows.to(a.device))
+            if c is None:
+                _all_reduce_sums(sa, self.dist)
+                return a.merge(sa)
+        elif c is None:
+            return a.update(obs_rows, self.dist)
+        else:
+            sa = a.moments(obs_rows.to(a.device))
+        sc = c.moments(cobs_rows.to(c.device))
         if dist_ranks(self.dist) > 1:
             both = torch.cat([sa, sc])
             _all_reduce_sums(both, self.dist)
@@ -1311,7 +1374,8 @@ class PPO:
                 roll = self._collect_rollout()
                 self.num_timesteps = before
                 if prime_obs and self.symmetry is not None:      # every merge is over the rows and their images: this one too
-                    self._update_obs_norms(self._with_images(roll["obs"].reshape(-1, roll["obs"].shape[-1])), None)
+                    self._update_obs_norms(self._with_images(roll["obs"].reshape(-1, roll["obs"].shape[-1])),
+                                           roll["cobs"].reshape(-1, roll["cobs"].shape[-1]) if self.asymmetric_critic else None)
                 elif prime_obs:
                     self._update_obs_norms(roll["obs"].reshape(-1, roll["obs"].shape[-1]),
                                            roll["cobs"].reshape(-1, roll["cobs"].shape[-1]) if self.asymmetric_critic else None)
@@ -1381,7 +1445,14 @@ class PPO:
                 x = logp - flat["logp"][idx]
                 kl = (0.5 * x * x).mean()
                 cf = ((ratio < 1 - self.cliprange) | (ratio > 1 + self.cliprange)).to(x.dtype).mean()
-        return pg - self.ent_coef * ent + self.vf_coef * vf, pg, vf, ent, kl, cf
+        loss = pg - self.ent_coef * ent + self.vf_coef * vf
+        sym = None
+        if self.symmetry == "loss":
+            # the statement rp_sym_grad_dev is tested against: symmetry_coef * symmetry_gap's "action" on these rows, both branches live
+            e = self.policy.dist(flat["obs_image"][idx]).mean - d.mean[:, self._mirror.src["act"]]
+            sym = self.symmetry_coef * (e ** 2).mean()
+            loss = loss + sym
+        return loss, pg, vf, ent, kl, cf, sym
 
     def _minibatch_step_fused(self, flat, idx):
         """Four launches + two small reductions per minibatch: advantage statistics, the two gradient kernels (which
@@ -1391,6 +1462,11 @@ class PPO:
                                  self.vf_coef, self.ent_coef, index=idx, adv_stats=stats, entropy_grad=False, norm=self.obs_norm,
                                  diagnostics=self.diagnostics, cobs=flat["cobs"] if self.asymmetric_critic else None,
                                  cnorm=self.cobs_norm)
+        sym = None
+        if self.symmetry == "loss":
+            # one more gradient kernel on the same rows, added into the vector the optimiser (and the all-reduce in front of it) reads
+            sym = self._fgrad.sym_run(flat["obs"], flat["obs_image"], self._act_src_host, self.symmetry_coef, index=idx, norm=self.obs_norm,
+                                     accumulate=True, repack=False)
         scale = self._fadam.step(self.ent_coef, self.dist)          # all-reduces the gradient vector first when ranks > 1
         ent = (0.5 + 0.5 * math.log(2 * math.pi) + self.policy.log_std.detach()).sum()
         pg, vf = pg * scale, vf * scale                              # (the loss slots were summed over the ranks with the rest)
@@ -1399,12 +1475,16 @@ class PPO:
             kl, cf = (t * scale for t in self._fgrad.diag())         # (... and so were the diagnostics' slots)
             if self.lr_history is not None and self.lr_schedule is not None:
                 self.lr_history.append((kl, self._fadam.lr_dev[0].clone()))
-        return pg - self.ent_coef * ent + self.vf_coef * vf, pg, vf, ent, kl, cf
+        loss = pg - self.ent_coef * ent + self.vf_coef * vf
+        if sym is not None:
+            sym = sym * scale                                        # (L_sym's slot too)
+            loss = loss + sym
+        return loss, pg, vf, ent, kl, cf, sym
 
     def _minibatch_step(self, flat, idx):
         if self._fgrad is not None:
             return self._minibatch_step_fused(flat, idx)
-        loss, pg, vf, ent, kl, cf = self._minibatch_loss(flat, idx)
+        loss, pg, vf, ent, kl, cf, sym = self._minibatch_loss(flat, idx)
         self.opt.zero_grad(set_to_none=True)
         loss.backward()
         average_gradients(self.policy, self.dist)
@@ -1412,13 +1492,16 @@ class PPO:
         dist = self.dist
         if dist_ranks(dist) > 1:
             # what update() reports is the mean over the ranks, as the fused path's slots are (one small all-reduce); the KL with it
-            terms = torch.stack([pg.detach(), vf.detach()] + ([kl, cf] if self.diagnostics else []))
+            terms = torch.stack([pg.detach(), vf.detach()] + ([kl, cf] if self.diagnostics else []) + ([sym.detach()] if sym is not None else []))
             dist.all_reduce(terms)
             terms = terms / dist.get_world_size()
             pg, vf = terms[0], terms[1]
             if self.diagnostics:
                 kl, cf = terms[2], terms[3]
             loss = pg - self.ent_coef * ent.detach() + self.vf_coef * vf
+            if sym is not None:
+                sym = terms[-1]
+                loss = loss + sym
         if self.lr_schedule is not None:
             # the rule, in front of the step of the same minibatch; with ranks on their mean KL: the same decision everywhere
             self._lr32 = adapt_lr(self._lr32, kl.item(), self.desired_kl, self.lr_factor, self.lr_min, self.lr_max)
@@ -1426,7 +1509,7 @@ class PPO:
             if self.lr_history is not None:
                 self.lr_history.append((float(kl.item()), float(self._lr32)))
         self.opt.step()
-        return loss, pg, vf, ent, kl, cf
+        return loss, pg, vf, ent, kl, cf, sym
 
     def _sample_order(self, n):
         """The epoch's sample order.  Torch path: torch.randperm (a sort of n random keys).  Fused path: a keyed bijection
@@ -1455,7 +1538,7 @@ class PPO:
         next ``augment`` overwrites them); on the CPU by the torch statement, the same numbers bit for bit."""
         mm = self._mirror
         if mm is None:
-            raise RuntimeError("this agent was built without symmetry=\"augment\"")
+            raise RuntimeError("this agent was built without symmetry")
         flat = {k: roll[k].reshape(-1, *roll[k].shape[2:]) for k, _ in self.AUGMENTED_KEYS}
         if not mm.kernel_applies():
             return {k: torch.cat([flat[k], flat[k] if kind == "one" else mm.rows(flat[k], kind)]).contiguous()
@@ -1468,6 +1551,20 @@ class PPO:
         for k, kind in self.AUGMENTED_KEYS:
             mm.rows_into(flat[k].to(torch.float32).contiguous(), bufs[k], kind)
         return dict(bufs)
+
+    @torch.no_grad()
+    def _obs_images(self, obs_rows):
+        """the image rows M obs of [n, obs_dim] rows (``symmetry="loss"``): on a GPU one launch of rp_mirror_rows_dev into a buffer
+        kept between updates (the next update overwrites it), on the CPU the torch statement - the same numbers bit for bit"""
+        mm = self._mirror
+        if not mm.kernel_applies():
+            return mm.rows(obs_rows, "obs").contiguous()
+        src = obs_rows.to(torch.float32).contiguous()
+        buf = getattr(self, "_image_buf", None)
+        if buf is None or tuple(buf.shape) != tuple(src.shape):
+            buf = self._image_buf = torch.empty_like(src)
+        mm.rows_into(src, buf, "obs", plain=False)
+        return buf
 
     @torch.no_grad()
     def _with_images(self, obs_rows):
@@ -1490,11 +1587,15 @@ class PPO:
     def symmetry_gap(self, roll, max_rows=65536):
         """How far the policy is from the robot's mirror symmetry on the first ``max_rows`` observation rows s of a rollout:
         ``{"action": mean |mu(M s) - P mu(s)|^2 / act_dim, "value": mean |V(M s) - V(s)|}`` (0, 0 for an equivariant actor and an
-        invariant critic).  Needs ``symmetry="augment"``, which is where the maps come from."""
+        invariant critic).  Needs ``symmetry``, either mode, which is where the maps come from.  With an asymmetric critic, whose rows
+        have no mirror map, the value gap is not defined: NaN."""
         mm = self._mirror
         if mm is None:
-            raise RuntimeError("this agent was built without symmetry=\"augment\"")
+            raise RuntimeError("this agent was built without symmetry")
         obs = roll["obs"].reshape(-1, roll["obs"].shape[-1])[:int(max_rows)].to(self.device, torch.float32).contiguous()
+        if self.asymmetric_critic:
+            d = self.policy.dist(mm.rows(obs, "obs")).mean - mm.rows(self.policy.dist(obs).mean, "act")
+            return {"action": ((d * d).sum(-1).mean() / d.shape[-1]).item(), "value": float("nan")}
         mu, v = self._means_values(obs)
         mu_m, v_m = self._means_values(mm.rows(obs, "obs").contiguous())
         d = mu_m - mm.rows(mu, "act")
@@ -1503,13 +1604,15 @@ class PPO:
     def update(self, roll, sample_orders=None):
         """sample_orders (optional): one int64 index tensor per epoch instead of the generated order (tests feed the
         same orders to both optimiser paths)."""
-        if self.symmetry is not None:
+        if self.symmetry == "augment":
             # everything below is the update it always was, on 2 n samples: the rollout's and their mirror images
             flat = self.augment(roll)
         else:
             flat = {k: v.reshape(-1, *v.shape[2:]) for k, v in roll.items()}
             if self._fgrad is not None:          # the gradient kernels index the rollout tensors directly
                 flat = {k: v.contiguous() for k, v in flat.items()}
+            if self.symmetry == "loss":          # the image rows M obs of all n rows, once per update
+                flat["obs_image"] = self._obs_images(flat["obs"])
         n = flat["obs"].shape[0]
         mb = max(n // self.nminibatches, 1)
         out = None
@@ -1519,11 +1622,16 @@ class PPO:
                 out = self._minibatch_step(flat, perm[s:s + mb])
         if self.obs_norm is not None:
             # the statistics move only now: rollout and update saw the same ones (old and new log-probabilities of the same inputs)
-            self._update_obs_norms(flat["obs"], flat["cobs"] if self.asymmetric_critic else None)
+            # (symmetry="loss": over the rows and their images, as "augment"'s 2 n rows are - a policy cannot be equivariant under
+            # statistics that are not mirror-consistent)
+            self._update_obs_norms(flat["obs"], flat["cobs"] if self.asymmetric_critic else None,
+                                   flat["obs_image"] if self.symmetry == "loss" else None)
         if out is None:
             return {}
-        loss, pg, vf, ent, kl, cf = out
+        loss, pg, vf, ent, kl, cf, sym = out
         stats = {"loss": loss.item(), "pg_loss": pg.item(), "vf_loss": vf.item(), "entropy": ent.item()}
+        if sym is not None:
+            stats["symmetry_loss"] = sym.item()
         if self.diagnostics:
             stats["approx_kl"], stats["clip_frac"] = kl.item(), cf.item()
         if self.lr_schedule is not None:
@@ -1569,6 +1677,8 @@ class PPO:
             ck["goal_row_stats"] = {k: torch.from_numpy(counts[k].astype("int64")) for k in ("attempts", "reached")}
         if self.symmetry is not None:                # (an agent without the option writes the checkpoint it always wrote)
             ck["symmetry"] = self.symmetry
+            if self.symmetry == "loss":
+                ck["symmetry_coef"] = self.symmetry_coef
         if self.lr_schedule is not None:             # (an agent without a schedule writes the checkpoint it always wrote)
             ck["lr_schedule"] = {"kind": self.lr_schedule, "desired_kl": self.desired_kl, "lr_factor": self.lr_factor,
                                  "lr_min": self.lr_min, "lr_max": self.lr_max, "lr": self.learning_rate}
@@ -1585,6 +1695,11 @@ class PPO:
         if ck.get("symmetry") != self.symmetry:
             raise ValueError("the checkpoint was trained with symmetry=%r, this agent runs symmetry=%r (PPO's symmetry)"
                              % (ck.get("symmetry"), self.symmetry))
+        if self.symmetry == "loss" and float(ck.get("symmetry_coef", self.symmetry_coef)) != self.symmetry_coef:
+            # the coefficient is a weight, not a layout: the constructor's holds (a run may be resumed under another one), and says so
+            import warnings
+            warnings.warn("the checkpoint was trained with symmetry_coef=%r, this agent goes on with symmetry_coef=%r"
+                          % (float(ck["symmetry_coef"]), self.symmetry_coef))
         if self.asymmetric_critic and (ck["critic_obs"] != _critic_obs_of(self.env) or int(ck["critic_obs_dim"]) != self.cobs_dim):
             raise ValueError("the checkpoint's critic was trained on the rows %r (%d columns), this env writes %r (%d; RoboyVecEnv's "
                              "critic_obs)" % (ck["critic_obs"], int(ck["critic_obs_dim"]), _critic_obs_of(self.env), self.cobs_dim))

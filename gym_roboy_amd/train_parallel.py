@@ -21,7 +21,7 @@ TRAINING_STEPS_BETWEEN_BACKUPS = 100000
 def log_line(stats):
     """An update's statistics as they are printed: four decimals, and three significant digits for the small ones (the approximate KL
     and the learning rate of --lr-schedule, which four decimals would print as 0.0003 or 0)."""
-    return {k: float("%.3g" % v) if k in ("approx_kl", "lr") else round(v, 4) for k, v in stats.items()}
+    return {k: float("%.3g" % v) if k in ("approx_kl", "lr", "symmetry_loss") else round(v, 4) for k, v in stats.items()}
 
 
 DEFAULT_GOAL_POOL = 16384
@@ -153,10 +153,14 @@ def main(argv=None):
     ap.add_argument("--desired-kl", type=float, default=0.01, metavar="KL", help="the KL the adaptive schedule steers to (default 0.01)")
     ap.add_argument("--lr-min", type=float, default=1e-5, metavar="LR", help="lower bound of the scheduled learning rate (default 1e-5)")
     ap.add_argument("--lr-max", type=float, default=1e-2, metavar="LR", help="upper bound of the scheduled learning rate (default 1e-2)")
-    ap.add_argument("--symmetry", default=None, choices=("augment",),
+    ap.add_argument("--symmetry", default=None, choices=("augment", "loss"),
                     help="augment = every update runs on the rollout's samples and their images in the robot's mirror plane (twice the "
-                         "samples per env step, no more simulation; not with --critic-obs); the round's statistics then show "
-                         "symmetry_gap_action, the policy's distance from the symmetry; recorded in the checkpoint")
+                         "samples per env step, no more simulation; not with --critic-obs); loss = every minibatch's loss gains "
+                         "--symmetry-coef x the mean squared distance of the action mean from the symmetry (the action net only: works "
+                         "with --critic-obs); the round's statistics then show symmetry_gap_action, the policy's distance from the "
+                         "symmetry, and with loss symmetry_loss, the last minibatch's term; recorded in the checkpoint")
+    ap.add_argument("--symmetry-coef", type=float, default=1.0, metavar="C",
+                    help="the weight of --symmetry loss's term (>= 0, default 1)")
     args = ap.parse_args(argv)
     sensor_noise = {k: float(v) for k, v in (item.split("=", 1) for item in args.sensor_noise.split(",") if item)}
     action_delay = None
@@ -214,12 +218,13 @@ def main(argv=None):
                 normalize_reward=args.normalize_reward, clip_reward=args.clip_reward,
                 bootstrap_timeouts=args.bootstrap_timeouts, lr_schedule=args.lr_schedule, desired_kl=args.desired_kl,
                 lr_min=args.lr_min, lr_max=args.lr_max, asymmetric_critic=bool(critic_obs),
-                symmetry=args.symmetry)
+                symmetry=args.symmetry, symmetry_coef=args.symmetry_coef)
     if os.path.exists(model_file):
         agent.load(model_file)                  # resume from the last backup
+    last_stats = {}
     for round_no in range(args.rounds):
         agent.learn(total_timesteps=args.steps_per_round,
-                    log=(lambda s: print(log_line(s))) if rank == 0 else None)
+                    log=(lambda s: (last_stats.update(s), print(log_line(s)))) if rank == 0 else None)
         # episode statistics of ALL ranks' envs: the 8-double block of every rank, summed (RCCL; gloo: through the host)
         from .sharding import STAT_KEYS, allreduce_stats, summarize
         local = env.stats()
@@ -249,6 +254,8 @@ def main(argv=None):
                 summary.update(reach_rate_summary(row_counts[0], row_counts[1], goals_m // goal_curriculum["levels"]))
             if args.symmetry and agent.last_rollout is not None:      # (rank 0's policy on rank 0's last rollout: the policy is shared)
                 summary["symmetry_gap_action"] = float("%.3g" % agent.symmetry_gap(agent.last_rollout)["action"])
+                if "symmetry_loss" in last_stats:                     # (symmetry="loss": the term of the round's last minibatch)
+                    summary["symmetry_loss"] = float("%.3g" % last_stats["symmetry_loss"])
             print("episode statistics (all ranks):", summary)
     if world > 1:
         dist.destroy_process_group()

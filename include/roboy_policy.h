@@ -269,6 +269,42 @@ int rp_clip_adam_kl_asym_dev(float *d_params, const float *d_grad, float *d_m, f
  * map, sign +1 - the per-sample scalars.  rows == 0: nothing is launched.  Added by name: the ABI version stays 5. */
 int rp_mirror_rows_dev(const float *d_src, float *d_plain /* NULL: not written */, float *d_mirror, int64_t rows, int width,
                        const int32_t *d_col_src, const float *d_col_sign, void *stream);
+/* ---- the mirror-symmetry loss on the action mean (gym_roboy_amd/ppo.py: PPO(symmetry="loss")) ----
+ * For a minibatch of B rows s_i, A = act_dim, M / P the env's observation / action mirror maps:
+ *     e_i[j] = mu(M s_i)[j] - mu(s_i)[P j]        L_sym = coef / (B A) sum_i sum_j e_i[j]^2
+ * mu is the action net's mean; the gradient flows through BOTH branches; log_std and the value net get none (the log_std entries of
+ * the block are exact zeros).  It touches the action net and the actor's rows only: no critic-row map is needed.
+ * One launch of a further instance family of the gradient kernel's text (mlp_sym_kernel / mlp_sym_norm_kernel) + a reduction.  A
+ * wave tile is 32 PAIRS: column tile 0 reads row d_index[p] (or p) of d_obs, column tile 1 the same row of d_obs_image (the rows
+ * M s, e.g. from rp_mirror_rows_dev); after the forward pass lane l holds mu(s_l) and lane l ^ 32 holds mu(M s_l), and with
+ * c' = 2 coef / (B A) the loss derivative of both branches is the one expression d3[j] = c' (out[j] - partner[P j]) - no second
+ * forward pass, no target buffer, no stop-gradient.  Everything behind d3 is the PPO kernel's text on the matrix cores in exact f32.
+ *   d_packed_train: the action net's rp_pack_train blob (the asymmetric layout: d_packed_pi).
+ *   act_src: HOST array of act_dim int32, P as envs.symmetry's act_src; it must be an involution of [0, act_dim) (fixed points are
+ *     legal; act_dim = 1 with {0} works), otherwise RP_EINVAL.  It travels in the kernel arguments.
+ *   coef: finite and >= 0.  coef = 0 gives an all-zero block.
+ *   d_grad_pi: the action net's block of rp_ppo_grad_dev's / rp_ppo_grad_asym_dev's gradient vector (rp_grad_floats() / 2 floats; the
+ *     action block comes first in both layouts, so the vector itself may be handed in).  Written: the parameter entries [0, L) and
+ *     L_sym at d_grad_pi[L + 3], L = the action net's loss slot - its third spare slot, a slot of L_sym's own.  d_grad_pi[L], [L + 1],
+ *     [L + 2] (the surrogate loss, approx_kl, clip_frac) are neither read nor written.  rp_ppo_grad_*_dev leave 0 at [L + 3].
+ *   accumulate: 0 overwrites those entries, 1 adds to what is there: the sum over the partials is formed first and added LAST, so
+ *     accumulate = 1 onto g0 is exactly g0 + (the accumulate = 0 result), element by element.  Behind rp_ppo_grad_*_dev on the same
+ *     stream this puts L_sym's gradient into the PPO gradient in front of clip + Adam with no add launch.
+ *   d_workspace: rp_sym_workspace_floats() floats.  Sums in a fixed order: bit-reproducible, and the same minibatch addressed through
+ *     d_index into longer tensors gives the same bits.
+ * rp_sym_grad_norm_dev: both branches' observation operands normalised (d_norm, clip as rp_ppo_grad_norm_dev; d_norm == NULL launches
+ * rp_sym_grad_dev's kernels).  Limits: rp_train_packed_floats()'s (obs_dim <= 63, up to 64 actions, the same LDS budget rule).
+ * rp_sym_grad_form: 2 = the small instance (obs_dim <= 31, up to 8 actions) with its rows prefetched by LDS-DMA - every small policy:
+ * the two input buffers hold obs_dim + 2 rows each and always fit - 1 = the small instance staging its rows at the start of each tile
+ * (ROBOY_POLICY_PREFETCH=0 only), 0 = the general instance; < 0: unsupported.  Added by name: the ABI version stays 5. */
+int rp_sym_grad_dev(const float *d_packed_train, const float *d_obs, const float *d_obs_image, const int64_t *d_index /* or NULL */,
+                    int64_t batch, int obs_dim, int act_dim, const int32_t *act_src /* host, [act_dim] */, float coef,
+                    float *d_grad_pi, int accumulate /* 0: overwrite, 1: add to what is there */, float *d_workspace, void *stream);
+int rp_sym_grad_norm_dev(const float *d_packed_train, const float *d_obs, const float *d_obs_image, const int64_t *d_index, int64_t batch,
+                         int obs_dim, int act_dim, const int32_t *act_src, float coef, const float *d_norm, float clip, float *d_grad_pi,
+                         int accumulate, float *d_workspace, void *stream);
+int64_t rp_sym_workspace_floats(int obs_dim, int act_dim, int64_t batch);
+int rp_sym_grad_form(int obs_dim, int act_dim);
 /* test hook: would a grant of lds_bytes of dynamic LDS be issued for (kernel id, device) now?  Records it. */
 int rp_debug_lds_grant_needed(int kernel_id, int dev, int64_t lds_bytes);
 /* which form of the gradient kernels rp_ppo_grad_dev launches for this policy: 2 = the small instance (obs_dim <= 31, up to 8
