@@ -495,8 +495,8 @@ inline const Row *row_for(rb_sim *s, int entry, bool build, std::string *why = n
 // parameters are enabled (rb_params_enable: env_params.hpp), the env step while tendon channels (rb_env_obs_configure: env_obs.hpp)
 // an io configuration (rb_env_io_configure: env_io.hpp) or action rows (rb_env_action_obs_configure: env_hist.hpp) are set.  Those
 // kernels take sub-ranges.
-inline bool extension_serves(const rb_sim *s, int entry) { return s->params || (entry == ENTRY_ENV && (s->obs_mask || s->io || s->hist_rows)); }
-int extension_launch(rb_sim *s, int entry, const Launch &L);      // (roboy_sim.hip)
+inline bool extension_serves(const rb_sim *s, int entry) { return s->par.on || (entry == ENTRY_ENV && (s->chan.mask || s->io.on || s->hist.rows)); }
+int extension_launch(rb_sim *s, int entry, const Launch &L);      // (env_host.hpp)
 
 // every launch of the library's three entry kinds
 inline int dispatch(rb_sim *s, int entry, const Launch &L) {

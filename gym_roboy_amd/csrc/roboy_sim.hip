@@ -14,9 +14,11 @@
 // eight lanes per link, working set in LDS (tree_aba.hpp).  DESIGN.md §4-§5.
 // Which kernel instance a call launches is ONE table (roboy_dispatch.hpp, included below): rows keyed by robot class / entry kind /
 // kernel form / integrator / workgroup size / constants source / variant, RB_KERNEL_AUTO's thresholds as a list of rules - but for a
-// handle with per-env parameters, tendon channels or an io configuration, whose kernels (env_params.hpp, env_obs.hpp, env_io.hpp) one
-// launch path below chooses (extension_launch).  This file holds the kernels that are not in a header of their own, the handle, the
-// availability predicates and the C ABI.
+// handle with per-env parameters, tendon channels, an io configuration or action rows, whose kernels (env_params.hpp, env_obs.hpp,
+// env_io.hpp, env_hist.hpp) one launch path chooses (extension_launch, env_host.hpp).  This file holds the kernels that are not in a
+// header of their own, the handle, the run-time builds, the streams, chains and graphs, the core C ABI (rb_create, rb_step*,
+// rb_rollout*), the tendon-state readout and the dispatch exports; the fused env layer's host side - rb_env_*, rb_params_*, the
+// statistics - is env_host.hpp, included behind the dispatch table.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -459,6 +461,64 @@ __global__ void env_reset_kernel(const GoalBox box, float *q, float *qd, uint32_
 
 inline unsigned blocks_for(long n, int block) { return unsigned((n + block - 1) / block); }
 
+// The options of the fused env layer (env_host.hpp; DESIGN.md §6 has the table): ONE record each, a member of the handle below - what
+// the option owns, release() to free and null it, need*() for the entry points that are refused without it.  rb_destroy releases them all.
+// Per-env physical parameters (env_params.hpp; rb_params_*): while on, the step and env-step entries launch the parameter kernels
+// instead of the dispatch table's row.  Planes [n][n_envs], draw counters [n_envs], ranges lo[n] | hi[n] (device and host copies)
+struct OptParams {
+    bool on = false, resample = false; int n = 0;
+    float *d_planes = nullptr, *d_ranges = nullptr; uint32_t *d_draws = nullptr;
+    std::vector<float> ranges;
+    void release() { (void)hipFree(d_planes); (void)hipFree(d_draws); (void)hipFree(d_ranges); *this = OptParams{}; }
+    int need() const { return on ? RB_OK : fail(RB_EINVAL, "per-env parameters are not enabled (rb_params_enable)"); }
+};
+// Tendon channels in the env step's observation (env_obs.hpp; rb_env_obs_*): while the mask is set, the env-step entry launches
+// the extended kernels - the nominal or the parameter form
+struct OptChannels { int mask = 0; float scale[4] = {1.0f, 1.0f, 1.0f, 1.0f}; void release() { *this = OptChannels{}; } };
+// Action latency and sensor noise of the env step (env_io.hpp; rb_env_io_*): while on, the env-step entry launches the io kernels -
+// nominal or parameter form, with or without channels.  Planes [n_envs] each; the ring [slots][n_envs][n_t] exists with
+// delay_hi > 0 or with action rows: slots above max(delay_hi, K - 1)
+struct OptIo {
+    bool on = false; rb_env_io_config cfg = {};
+    uint32_t *d_delay = nullptr, *d_draws = nullptr, *d_rows = nullptr;
+    float *d_ring = nullptr; int slots = 0;
+    void release() { (void)hipFree(d_delay); (void)hipFree(d_draws); (void)hipFree(d_rows); (void)hipFree(d_ring); *this = OptIo{}; }
+};
+// The last K handed action rows as observation columns (env_hist.hpp; rb_env_action_obs_*): while rows > 0 the env-step entry
+// launches the history kernels, with or without any of the above; the ring is the io record's
+struct OptActionRows { int rows = 0; void release() { rows = 0; } };
+// Episode-end codes (rb_env_done_kind_*): while on, every env-step launch is followed by done_kind_kernel over its range.
+// Planes [n_envs] each: the goal counter d_ep_cnt[2n + i] as of env i's last episode end, and the last step's codes
+struct OptDoneKind {
+    bool on = false; uint32_t *d_seen = nullptr, *d_kind = nullptr;
+    void release() { (void)hipFree(d_seen); (void)hipFree(d_kind); *this = OptDoneKind{}; }
+    int need() const { return on ? RB_OK : fail(RB_EINVAL, "episode-end codes are not enabled (rb_env_done_kind_configure)"); }
+};
+// Privileged critic rows (env_critic.hpp; rb_env_critic_obs_*): while the mask is set, every env-step launch and every reset is
+// followed by critic_rows_kernel over its range.  dim: the row width the mask had when it was configured; the plane [n_envs][dim]
+struct OptCritic {
+    int mask = 0, dim = 0; float *d_rows = nullptr;
+    void release() { (void)hipFree(d_rows); *this = OptCritic{}; }
+    int need() const { return mask ? RB_OK : fail(RB_EINVAL, "critic rows are not enabled (rb_env_critic_obs_configure)"); }
+};
+// Goal pool (env_goal.hpp; rb_env_goal_pool_*): while set, every env-step launch and every reset is followed by ONE goal kernel
+// over its range, and rb_sample_goals(_dev) return pool rows.  Rows [m][n_q]; m is fixed by the first call, the pointer never moves.
+// Curriculum over the pool's row order (rb_env_goal_curriculum_*): while L > 0 that kernel is goal_curriculum_kernel.  Planes
+// [n_envs] each, one allocation starting at d_level: the env's level, the row it holds, and the goals-reached counter
+// d_ep_cnt[2n + i] as of its last episode end (a copy of its own: episode-end codes may be off); d_hist: [L] counts behind them,
+// rb_env_goal_level_hist's device buffer.  Outcome counts per pool row (rb_env_goal_row_stats_*): while d_row_stats is set the
+// kernel is goal_curriculum_stats_kernel.  [2][m]: attempts, then reached
+struct OptGoals {
+    float *d_pool = nullptr; int64_t m = 0;
+    uint32_t L = 0, up = 0, down = 0;
+    uint32_t *d_level = nullptr, *d_index = nullptr, *d_seen = nullptr;
+    uint64_t *d_hist = nullptr, *d_row_stats = nullptr;
+    void release() { (void)hipFree(d_pool); (void)hipFree(d_level); (void)hipFree(d_row_stats); *this = OptGoals{}; }
+    int need_pool() const { return d_pool ? RB_OK : fail(RB_EINVAL, "no goal pool is set (rb_env_goal_pool_set)"); }
+    int need_curriculum() const { return L ? RB_OK : fail(RB_EINVAL, "no goal curriculum is configured (rb_env_goal_curriculum_configure)"); }
+    int need_row_stats() const { return d_row_stats ? RB_OK : fail(RB_EINVAL, "goal row stats are not enabled (rb_env_goal_row_stats_enable)"); }
+};
+
 }  // namespace
 
 // --------------------------------------------------------------------- handle
@@ -549,53 +609,9 @@ struct rb_sim {
     std::vector<float> ts_tree_lconst;
     float *d_ts_lconst = nullptr, *d_ts_out = nullptr;
     bool ts_attr_set = false;
-    // per-env physical parameters (env_params.hpp; rb_params_*): while enabled, the step and env-step entries launch the parameter
-    // kernels instead of the dispatch table's row.  Planes [P][n], draw counters [n], ranges lo[P] | hi[P] (device and host copies)
-    bool params = false;
-    int n_params = 0;
-    float *d_params = nullptr, *d_param_ranges = nullptr;
-    uint32_t *d_param_draws = nullptr;
-    std::vector<float> param_ranges;
-    bool param_resample = false;
-    // tendon channels in the env step's observation (env_obs.hpp; rb_env_obs_*): while the mask is set, the env-step entry launches
-    // the extended kernels - the nominal or the parameter form - instead of the dispatch table's row / the parameter kernel
-    int obs_mask = 0;
-    float obs_scale[4] = {1.0f, 1.0f, 1.0f, 1.0f};
-    int obs_dim() const { return 3 * n_q + rbo::n_channels(obs_mask) * n_t + hist_rows * n_t; }
-    // action latency and sensor noise of the env step (env_io.hpp; rb_env_io_*): while configured, the env-step entry launches the io
-    // kernels - nominal or parameter form, with or without channels.  Planes [n] each; the ring [io_slots][n][n_t] only with delay_hi > 0
-    bool io = false;
-    rb_env_io_config io_cfg = {};
-    uint32_t *d_io_delay = nullptr, *d_io_draws = nullptr, *d_io_rows = nullptr;
-    float *d_io_hist = nullptr;
-    int io_slots = 0;
-    // the last K handed action rows as observation columns (env_hist.hpp; rb_env_action_obs_*): while K > 0 the env-step entry launches
-    // the history kernels, with or without any of the above, and the ring exists whatever delay_hi is (io_slots above max(delay_hi, K - 1))
-    int hist_rows = 0;
-    // episode-end codes (rb_env_done_kind_*): while enabled, every env-step launch is followed by done_kind_kernel over its range.
-    // Planes [n] each: the goal counter d_ep_cnt[2n + i] as of env i's last episode end, and the last step's codes
-    bool done_kind = false;
-    uint32_t *d_done_seen = nullptr, *d_done_kind = nullptr;
-    // privileged critic rows (env_critic.hpp; rb_env_critic_obs_*): while the mask is set, every env-step launch and every reset is
-    // followed by critic_rows_kernel over its range.  critic_dim: the row width the mask had when it was configured; the plane [n][Dc]
-    int critic_mask = 0, critic_dim = 0;
-    float *d_critic = nullptr;
-    int critic_width() const {
-        return rbc::row_dim(critic_mask, n_q, params ? n_params : 0, hist_rows * n_t);
-    }
-    // goal pool (env_goal.hpp; rb_env_goal_pool_*): while set, every env-step launch and every reset is followed by goal_pool_kernel
-    // over its range, and rb_sample_goals(_dev) return pool rows.  Rows [m][n_q]; m is fixed by the first call, the pointer never moves
-    float *d_goal_pool = nullptr;
-    int64_t goal_pool_m = 0;
-    // goal curriculum over the pool's row order (env_goal.hpp; rb_env_goal_curriculum_*): while curr_L > 0, goal_pool_launch enqueues
-    // goal_curriculum_kernel in place of goal_pool_kernel.  Planes [n] each: the env's level, the row it holds, and the goals-reached
-    // counter d_ep_cnt[2n + i] as of its last episode end (a copy of its own: episode-end codes may be off)
-    uint32_t curr_L = 0, curr_up = 0, curr_down = 0;
-    uint32_t *d_goal_level = nullptr, *d_goal_index = nullptr, *d_goal_seen = nullptr;      // one allocation, d_goal_level its start
-    uint64_t *d_goal_hist = nullptr;          // [L] counts behind the planes: rb_env_goal_level_hist's device buffer
-    // outcome counts per pool row (env_goal.hpp; rb_env_goal_row_stats_*): while non-null, goal_pool_launch enqueues
-    // goal_curriculum_stats_kernel in place of goal_curriculum_kernel.  [2][m]: attempts, then reached
-    uint64_t *d_goal_row_stats = nullptr;
+    OptParams par; OptChannels chan; OptIo io; OptActionRows hist; OptDoneKind done; OptCritic critic; OptGoals goals;      // the env layer's options (above)
+    int obs_dim() const { return 3 * n_q + rbo::n_channels(chan.mask) * n_t + hist.rows * n_t; }
+    int critic_width() const { return rbc::row_dim(critic.mask, n_q, par.on ? par.n : 0, hist.rows * n_t); }
 };
 
 namespace {
@@ -646,7 +662,7 @@ bool tree_form_ready(rb_sim *s, int kernel, int kind, bool build) {
     return false;
 }
 void maybe_jit(rb_sim *s) {
-    if (s->params) return;                        // the parameter kernels are ahead of time (and a later call builds after rb_params_disable)
+    if (s->par.on) return;                        // the parameter kernels are ahead of time (and a later call builds after rb_params_disable)
     if (s->tree) { if (tree_wants_lane(s)) (void)tree_form_ready(s, RB_KERNEL_ENV_PER_LANE, 0, true); return; }
     if (s->jit_state != 0) return;
     if (s->ntx || s->baked || s->n <= RB_SMALL_BATCH || !rbj::enabled() || jit_level() == 0) { s->jit_state = -1; return; }
@@ -826,228 +842,16 @@ int drop_graphs(rb_sim *s) {
     return RB_OK;
 }
 
-// ---- tendon channels in the observation (env_obs.hpp): the arguments of a launch while a mask is set ----
-// dynamic LDS of an extended env-step launch: the rows of its workgroup's envs, where they fit beside the instance's own columns (0: per-lane stores)
-size_t obs_stage_bytes(const rb_sim *s, int block = 256) {
-    const size_t columns = (s->baked ? 0 : s->ntx ? 4 * block * NTX : 4 * block * NT8) * (s->params ? 2 : 1);
-    const size_t rows = size_t(4) * block * s->obs_dim();
-    return columns + rows <= 65536 ? rows : 0;
-}
-template <int NT>
-rbo::ObsArgs<NT> obs_args(const rb_sim *s, bool staged = false) {
-    rbo::ObsArgs<NT> oa;
-    oa.mask = s->obs_mask; oa.obs_dim = s->obs_dim(); oa.staged = staged ? 1 : 0; oa.pad_ = 0;
-    for (int c = 0; c < 4; ++c) oa.scale[c] = s->obs_scale[c];
-    for (int k = 0; k < NT; ++k) oa.units[k] = s->ts_units.u[k];
-    return oa;
-}
-// ---- action latency and sensor noise (env_io.hpp): the argument of a launch while rb_env_io_configure holds ----
-// first: the launch's first env (the planes and the ring inside each slot are shifted by it)
-rbio::IoArgs io_args(const rb_sim *s, long first) {
-    rbio::IoArgs io;
-    std::memset(&io, 0, sizeof(io));
-    const rb_env_io_config cfg = s->io ? s->io_cfg : rb_env_io_config{};      // (no io configuration, K > 0: zeros and the ring)
-    if (s->io) { io.delay = s->d_io_delay + first; io.delay_draws = s->d_io_draws + first; io.rows = s->d_io_rows + first; }
-    io.hist = s->d_io_hist ? s->d_io_hist + first * s->n_t : nullptr;
-    io.slot_stride = long(s->n) * s->n_t;
-    io.slot_mask = s->io_slots ? s->io_slots - 1 : 0;
-    io.delay_lo = cfg.delay_lo; io.delay_hi = cfg.delay_hi; io.resample = cfg.resample_on_reset ? 1 : 0;
-    // row positions: q, qd, (goal: never), then the selected channels in row order, each sigma in the units the column reports (x scale)
-    const int nq = s->n_q;
-    for (int j = 0; j < nq; ++j) { io.colsig[j] = cfg.sigma_q; io.colsig[nq + j] = cfg.sigma_qd; }
-    int col = 3 * nq;
-    for (int ch = 0; ch < 4; ++ch)
-        if (s->obs_mask >> ch & 1)
-            for (int k = 0; k < s->n_t; ++k) io.colsig[col++] = cfg.sigma_tendon[ch] * s->obs_scale[ch];
-    for (int c = 0; c < col; ++c)
-        if (io.colsig[c] != 0.0f) io.noise_blocks |= 1u << (c >> 2);
-    return io;
-}
-void io_free(rb_sim *s) {
-    (void)hipFree(s->d_io_delay); (void)hipFree(s->d_io_draws); (void)hipFree(s->d_io_rows); (void)hipFree(s->d_io_hist);
-    s->d_io_delay = nullptr; s->d_io_draws = nullptr; s->d_io_rows = nullptr; s->d_io_hist = nullptr;
-    s->io = false; s->io_slots = 0;
-}
-// the ring both options share: S slots, the smallest power of two above max(delay_hi, K - 1); none without a delay range and K = 0
-int ring_slots_wanted(int delay_hi, int hist_rows) {
-    if (delay_hi <= 0 && hist_rows <= 0) return 0;
-    const int reach = delay_hi > hist_rows - 1 ? delay_hi : hist_rows - 1;
-    int slots = 1;
-    while (slots <= reach) slots *= 2;
-    return slots;
-}
-// ... rebuilt (zeroed) for the handle as configured
-int ring_rebuild(rb_sim *s) {
-    (void)hipFree(s->d_io_hist);
-    s->d_io_hist = nullptr;
-    s->io_slots = ring_slots_wanted(s->io ? s->io_cfg.delay_hi : 0, s->hist_rows);
-    if (!s->io_slots) return RB_OK;
-    const size_t bytes = sizeof(float) * size_t(s->io_slots) * size_t(s->n) * size_t(s->n_t);
-    const hipError_t e = hipMalloc(&s->d_io_hist, bytes);
-    if (e != hipSuccess) {                   // no ring: neither a delay range nor action rows (their kernels index it unasked)
-        s->d_io_hist = nullptr; s->io_slots = 0; s->hist_rows = 0;
-        if (s->io) s->io_cfg.delay_lo = s->io_cfg.delay_hi = 0;
-        return fail(RB_EHIP, std::string("the action history ring: ") + hipGetErrorString(e));
-    }
-    RB_HIP(hipMemsetAsync(s->d_io_hist, 0, bytes, s->stream));
+// a sub-range on a stream of the caller's choice: envs are independent, so disjoint ranges may be stepped concurrently
+int range_ok(const rb_sim *s, int64_t first, int64_t count) {
+    if (first < 0 || count < 1 || first + count > s->n) return fail(RB_EINVAL, "range outside the batch");
+    if (first % 256) return fail(RB_EINVAL, "a range starts at a multiple of 256 envs");
     return RB_OK;
-}
-// rb_env_reset_dev's observation rows on such a handle: the state the reset kernel has just written, every set-point 0
-void obs_rows_launch(rb_sim *s, float *d_obs) {
-    const dim3 grid(blocks_for(s->n, 256)), block(256);
-    const float *par = s->params ? s->d_params : nullptr;
-    if (s->ntx)
-        hipLaunchKernelGGL((rbo::msj_obs_rows<256, ConstX>), grid, block, 0, s->stream, s->cx, obs_args<NTX>(s), s->d_q, s->d_qd, s->d_goal, par, d_obs, s->n);
-    else
-        hipLaunchKernelGGL((rbo::msj_obs_rows<256, Const8>), grid, block, 0, s->stream, s->c8, obs_args<NT8>(s), s->d_q, s->d_qd, s->d_goal, par, d_obs, s->n);
-}
-
-// ---- what dispatch() launches where extension_serves() (roboy_dispatch.hpp): the kernels of env_params.hpp, env_obs.hpp, env_io.hpp ----
-// The constants an instance is compiled for, chosen here and nowhere else: f(the constants object, BK as a type) with BK = the
-// constants are MsjRobot's literals (msj_baked.hpp), the object then only fills the argument's place
-template <typename F>
-int with_consts(const rb_sim *s, F &&f) {
-    if (s->ntx) return f(s->cx, std::false_type{});
-    if (s->baked) return f(s->c8, std::true_type{});
-    return f(s->c8, std::false_type{});
-}
-rbp::ParamArgs param_args(const rb_sim *s, const Launch &L) {
-    return rbp::ParamArgs{s->d_params + L.i0, s->d_param_draws + L.i0, s->d_param_ranges, s->n, s->n_params, s->param_resample ? 1 : 0};
-}
-// the plain step under parameters: three argument lists of their own
-template <int INTEG>
-int params_step_launch(rb_sim *s, const Launch &L) {
-    constexpr int B = 256;
-    const dim3 grid(blocks_for(L.cnt, B)), block(B);
-    float *q = s->d_q + L.i0, *qd = s->d_qd + L.i0, *par = s->d_params + L.i0;
-    uint32_t *feas = s->d_feas + L.i0;
-    const float *act = L.act + size_t(L.i0) * s->n_t;
-    return with_consts(s, [&](const auto &c, auto bk) {
-        if constexpr (std::is_same<std::decay_t<decltype(c)>, ConstX>::value)
-            hipLaunchKernelGGL((rbp::msj_params_step_nt<INTEG, B>), grid, block, 0, L.stream, c, q, qd, feas, act, L.act_scale, par, s->n, L.cnt);
-        else
-            hipLaunchKernelGGL((rbp::msj_params_step<INTEG, B, decltype(bk)::value>), grid, block, 0, L.stream, c, q, qd, feas, act, scale8(s, L.act_scale), par, s->n, L.cnt);
-        return RB_OK;
-    });
-}
-// The env step of a handle with any combination of parameters, channels and io: the env-step body with the extension of the last
-// header that applies (io over channels over none), in its parameter form where parameters are enabled.
-template <int INTEG>
-int ext_env_launch(rb_sim *s, const Launch &L) {
-    MsjEnvArgs a = msj_env_args(s, L);
-    a.obs = L.obs + L.i0 * s->obs_dim();                 // the row stride is the handle's obs_dim (9 without channels)
-    const int K = s->hist_rows;                           // > 0: the history kernels (env_hist.hpp), an io argument of zeros without io
-    const bool par = s->params, io = s->io || K > 0, rows = io || s->obs_mask;       // rows: TendonObs writes them (env_obs.hpp)
-    return with_consts(s, [&](const auto &c, auto bk) {
-        using CONST = std::decay_t<decltype(c)>;
-        constexpr bool BK = decltype(bk)::value;
-        constexpr int NT = rbo::NtOf<CONST>::N;
-        // the unroll factors of the large-batch env-per-lane rows (0: run-time tendon count)
-        constexpr int U = NT == NTX ? 0 : BK ? (INTEG == 0 ? UBE : UBR) : (INTEG == 0 ? UKE : UKR);
-        // An io kernel is the text of the kernel it stands in for.  Without parameters and channels that is the table's env-per-lane
-        // row, which for MsjRobot's baked constants at small batches is the 64-thread instance with tendons AND integrator stages written
-        // out - another summation order of the RK4 stages than the large-batch text (rolled stages): a configuration of zeros steps like
-        // no configuration there too.  (Kernarg constants: the large-batch text's rolled tendon loop adds the same terms in the same order
-        // as the written-out 64-thread row, and that row has no scalar register to spare - with the io arguments it would spill.)
-        const bool small = BK && io && !par && !s->obs_mask && s->n <= RB_SMALL_BATCH;
-        const int B = small ? 64 : 256;
-        const size_t lds = rows ? obs_stage_bytes(s, B) : 0;
-        const rbo::ObsArgs<NT> oa = obs_args<NT>(s, lds != 0);
-        auto go = [&](auto kernel, const auto &...behind) {      // every instance takes (constants, MsjEnvArgs, ...)
-            hipLaunchKernelGGL(kernel, dim3(blocks_for(L.cnt, B)), dim3(B), lds, L.stream, c, a, behind...);
-            return RB_OK;
-        };
-        auto io_step = [&](auto block, auto unroll) {
-            return go(rbio::msj_io_env_step<INTEG, decltype(block)::value, decltype(unroll)::value, CONST, BK>, oa, io_args(s, L.i0));
-        };
-        if (K > 0) {
-            const rbh::HistIoArgs hio{io_args(s, L.i0), {K, s->obs_dim() - K * s->n_t}};
-            if (par) return go(rbh::msj_hist_params_env_step<INTEG, 256, CONST, BK>, param_args(s, L), oa, hio);
-            if constexpr (BK) if (small) return go(rbh::msj_hist_env_step<INTEG, 64, 8, CONST, BK>, oa, hio);
-            return go(rbh::msj_hist_env_step<INTEG, 256, U, CONST, BK>, oa, hio);
-        }
-        if (par && io) return go(rbio::msj_io_params_env_step<INTEG, 256, CONST, BK>, param_args(s, L), oa, io_args(s, L.i0));
-        if (io) {
-            if constexpr (BK) if (small) return io_step(std::integral_constant<int, 64>{}, std::integral_constant<int, 8>{});
-            return io_step(std::integral_constant<int, 256>{}, std::integral_constant<int, U>{});
-        }
-        if (par && rows) return go(rbo::msj_obs_params_env_step<INTEG, 256, CONST, BK>, param_args(s, L), oa);
-        if (rows) return go(rbo::msj_obs_env_step<INTEG, 256, U, CONST, BK>, oa);
-        return go(rbp::msj_params_env_step<INTEG, 256, CONST, BK>, param_args(s, L));
-    });
-}
-int extension_launch(rb_sim *s, int entry, const Launch &L) {
-    if (L.cnt <= 0) return RB_OK;
-    const bool euler = s->integrator == RB_EULER;
-    if (entry == ENTRY_STEP) return euler ? params_step_launch<0>(s, L) : params_step_launch<1>(s, L);
-    if (entry == ENTRY_ENV) return euler ? ext_env_launch<0>(s, L) : ext_env_launch<1>(s, L);
-    return fail(RB_EUNSUPPORTED, "per-env parameters have no fused-rollout kernel (rb_params_disable first)");
-}
-// ---- privileged critic rows (env_critic.hpp): one launch behind an env step or a reset, over the envs [i0, i0 + cnt) ----
-// the options the mask was configured against are still there, and the row is as wide as the plane's
-int critic_check(rb_sim *s) {
-    const int m = s->critic_mask;
-    if ((m & rbc::PARAMS && !s->params) || (m & rbc::DELAY && !s->io) || (m & rbc::ACTIONS && !s->hist_rows) || s->critic_width() != s->critic_dim)
-        return fail(RB_EINVAL, "an option the critic rows depend on changed after rb_env_critic_obs_configure: configure the rows again");
-    return RB_OK;
-}
-// d_obs: the observation rows the step has just written (null: no rows, zero action blocks); out: rows [n][Dc] of the whole batch
-int critic_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float *d_obs, float *out) {
-    if (cnt <= 0) return RB_OK;
-    rbc::CriticArgs a;
-    a.q = s->d_q; a.qd = s->d_qd; a.goal = s->d_goal; a.step_num = s->d_step_num;
-    a.par = s->params ? s->d_params : nullptr;
-    a.delay = s->io ? s->d_io_delay : nullptr;
-    a.obs = d_obs; a.out = out;
-    a.n = s->n; a.i0 = i0; a.i1 = i0 + cnt;
-    a.max_len = float(s->env.max_len);
-    a.nq = s->n_q; a.np = s->params ? s->n_params : 0; a.mask = s->critic_mask; a.dc = s->critic_dim;
-    a.od = s->obs_dim(); a.act_cols = s->hist_rows * s->n_t; a.lead = a.od - a.act_cols;
-    a.flat = reinterpret_cast<uintptr_t>(out) % 16 == 0 ? 1 : 0;
-    hipLaunchKernelGGL(rbc::critic_rows_kernel, dim3(blocks_for(cnt, 256)), dim3(256), sizeof(float) * 256 * size_t(a.dc), stream, a);
-    RB_HIP(hipGetLastError());
-    return RB_OK;
-}
-// ---- goal pool (env_goal.hpp): one launch behind an env step (d_done: its done words) or a reset (null: every env), over [i0, i0 + cnt) ----
-int goal_pool_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const uint32_t *d_done, float *d_obs) {
-    rbg::GoalPoolArgs a;
-    a.pool = s->d_goal_pool; a.done = d_done; a.goal_count = s->d_goal_count; a.goal = s->d_goal; a.obs = d_obs;
-    a.n = s->n; a.i0 = i0; a.i1 = i0 + cnt;
-    a.seed = s->seed; a.env0 = uint64_t(s->env0);
-    a.m = uint32_t(s->goal_pool_m);
-    a.nq = s->n_q; a.od = s->obs_dim(); a.rows = s->tree ? 1 : 0;
-    if (s->curr_L) {                          // a curriculum: the same launch, the row drawn inside the env's window
-        rbg::GoalCurriculumArgs c;
-        c.p = a;
-        c.level = s->d_goal_level; c.index = s->d_goal_index; c.seen = s->d_goal_seen;
-        c.reached = s->d_ep_cnt + 2 * size_t(s->n);
-        c.L = s->curr_L; c.up = s->curr_up; c.down = s->curr_down;
-        if (s->d_goal_row_stats) {            // outcome counts per row: the same launch again, two adds per episode end more
-            rbg::GoalCurriculumStatsArgs t;
-            t.c = c; t.counts = reinterpret_cast<unsigned long long *>(s->d_goal_row_stats);
-            hipLaunchKernelGGL(rbg::goal_curriculum_stats_kernel, dim3(blocks_for(cnt, RBG_STATS_BLOCK)), dim3(RBG_STATS_BLOCK), 0, stream, t);
-        } else
-            hipLaunchKernelGGL(rbg::goal_curriculum_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, c);
-    } else
-        hipLaunchKernelGGL(rbg::goal_pool_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, a);
-    RB_HIP(hipGetLastError());
-    return RB_OK;
-}
-void params_free(rb_sim *s) {
-    (void)hipFree(s->d_params); (void)hipFree(s->d_param_draws); (void)hipFree(s->d_param_ranges);
-    s->d_params = nullptr; s->d_param_draws = nullptr; s->d_param_ranges = nullptr;
-    s->params = false; s->n_params = 0; s->param_resample = false; s->param_ranges.clear();
-}
-// refusal of the entry points that have no parameter form
-int params_refuse(rb_sim *s, const char *what) {
-    return fail(RB_EUNSUPPORTED, std::string(what) + " has no per-env-parameter form: the handle has parameters enabled (rb_params_disable first)");
-}
-// rb_sample_goals(_dev) on a handle with a goal curriculum: without an env step there is no episode outcome to move a level
-int curriculum_refuse_sample(rb_sim *) {
-    return fail(RB_EUNSUPPORTED, "rb_sample_goals: the handle has a goal curriculum, whose levels move with the env layer's episode ends");
 }
 
 }  // namespace
+
+#include "env_host.hpp"       // the fused env layer and its options on the host: launch arguments, rb_env_*, rb_params_*, the statistics
 
 // ----------------------------------------------------------------------- C ABI
 extern "C" {
@@ -1227,13 +1031,7 @@ void rb_destroy(rb_sim *s) {
     (void)hipFree(s->d_state_rows); (void)hipHostFree(s->h_state_rows);
     (void)hipFree(s->d_goal); (void)hipFree(s->d_ep_ret); (void)hipFree(s->d_ep_sum); (void)hipFree(s->d_ep_cnt);
     (void)hipFree(s->d_step_num); (void)hipFree(s->d_infeas_n); (void)hipFree(s->d_stats);
-    params_free(s);
-    io_free(s);
-    (void)hipFree(s->d_done_seen); (void)hipFree(s->d_done_kind);
-    (void)hipFree(s->d_critic);
-    (void)hipFree(s->d_goal_pool);
-    (void)hipFree(s->d_goal_level);          // (with it the index plane, the seen plane and the histogram counts)
-    (void)hipFree(s->d_goal_row_stats);
+    s->par.release(); s->chan.release(); s->io.release(); s->hist.release(); s->done.release(); s->critic.release(); s->goals.release();
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1461,7 +1259,7 @@ int rb_step(rb_sim *s, const float *act, float act_scale, float *q, float *qd, u
 
 int rb_sample_goals(rb_sim *s, const uint8_t *mask, float *goal_q) {
     if (check(s) || !goal_q) return fail(RB_EINVAL, "null argument");
-    if (s->curr_L) return curriculum_refuse_sample(s);
+    if (s->goals.L) return curriculum_refuse_sample(s);
     RB_HIP(hipSetDevice(s->device));
     const uint8_t *d_mask = nullptr;
     if (mask) {
@@ -1469,9 +1267,9 @@ int rb_sample_goals(rb_sim *s, const uint8_t *mask, float *goal_q) {
         d_mask = s->d_u8;
     }
     if (mask) RB_HIP(hipMemsetAsync(s->d_rows, 0, sizeof(float) * s->n * s->n_q, s->stream));
-    if (s->d_goal_pool)
-        hipLaunchKernelGGL(rbg::goal_pool_sample_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->d_goal_pool,
-                           uint32_t(s->goal_pool_m), s->d_rows, s->d_goal_count, d_mask, s->n_q, s->n, s->seed, uint64_t(s->env0), 1);
+    if (s->goals.d_pool)
+        hipLaunchKernelGGL(rbg::goal_pool_sample_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->goals.d_pool,
+                           uint32_t(s->goals.m), s->d_rows, s->d_goal_count, d_mask, s->n_q, s->n, s->seed, uint64_t(s->env0), 1);
     else
         hipLaunchKernelGGL(sample_goals_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream,
                            s->d_rows, s->d_goal_count, d_mask, s->box, s->n_q, s->n, s->seed, uint64_t(s->env0), 1);
@@ -1636,8 +1434,8 @@ int rb_rollout_fused_dev(rb_sim *s, const float *d_ring, int ring, int n_steps, 
     if (ring < 1 || n_steps < 0) return fail(RB_EINVAL, "ring must be >= 1 and n_steps >= 0");
     if (reinterpret_cast<uintptr_t>(d_ring) % 16) return fail(RB_EINVAL, "action ring must be 16-byte aligned");
     if (s->tree || s->ntx) return fail(RB_EUNSUPPORTED, "fused rollout is built for 8-tendon ball-joint robots");
-    if (s->params) return params_refuse(s, "the fused rollout (rb_rollout_fused_dev)");
-    if (s->d_goal_pool)
+    if (s->par.on) return params_refuse(s, "the fused rollout (rb_rollout_fused_dev)");
+    if (s->goals.d_pool)
         return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) redraws goals inside one kernel and cannot draw them from a goal pool");
     if (n_steps == 0) return RB_OK;
     const long n = s->n;
@@ -1660,11 +1458,11 @@ int rb_fill_actions_dev(rb_sim *s, float *d_act, uint32_t step) {
 
 int rb_sample_goals_dev(rb_sim *s, const uint8_t *d_mask, float *d_goal_q) {
     if (check(s) || !d_goal_q) return fail(RB_EINVAL, "null argument");
-    if (s->curr_L) return curriculum_refuse_sample(s);
+    if (s->goals.L) return curriculum_refuse_sample(s);
     RB_HIP(hipSetDevice(s->device));
-    if (s->d_goal_pool)
-        hipLaunchKernelGGL(rbg::goal_pool_sample_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->d_goal_pool,
-                           uint32_t(s->goal_pool_m), d_goal_q, s->d_goal_count, d_mask, s->n_q, s->n, s->seed, uint64_t(s->env0), 0);
+    if (s->goals.d_pool)
+        hipLaunchKernelGGL(rbg::goal_pool_sample_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->goals.d_pool,
+                           uint32_t(s->goals.m), d_goal_q, s->d_goal_count, d_mask, s->n_q, s->n, s->seed, uint64_t(s->env0), 0);
     else
         hipLaunchKernelGGL(sample_goals_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream,
                            d_goal_q, s->d_goal_count, d_mask, s->box, s->n_q, s->n, s->seed, uint64_t(s->env0), 0);
@@ -1672,623 +1470,6 @@ int rb_sample_goals_dev(rb_sim *s, const uint8_t *d_mask, float *d_goal_q) {
     return RB_OK;
 }
 
-int rb_env_configure(rb_sim *s, const rb_env_config *cfg) {
-    if (check(s) || !cfg) return fail(RB_EINVAL, "null argument");
-    if (!s->tree && s->n_q != 3) return fail(RB_EUNSUPPORTED, "fused env layer: unsupported robot");
-    if (cfg->max_episode_length < 1) return fail(RB_EINVAL, "max_episode_length must be >= 1");
-    if (!(cfg->angle_hi > cfg->angle_lo) || !(cfg->vel_hi > cfg->vel_lo) || !(cfg->action_hi > cfg->action_lo))
-        return fail(RB_EINVAL, "empty box in env config");
-    RB_HIP(hipSetDevice(s->device));
-    EnvParams &e = s->env;
-    e.vel_penalty = cfg->joint_vel_penalty != 0; e.bonus = cfg->goal_bonus != 0;
-    e.max_len = cfg->max_episode_length; e.auto_reset = cfg->auto_reset != 0;
-    e.penalty = cfg->penalty_boundary; e.bonus_val = cfg->bonus_goal;
-    e.a_lo = cfg->angle_lo; e.a_hi = cfg->angle_hi; e.v_lo = cfg->vel_lo; e.v_hi = cfg->vel_hi;
-    e.act_hi = cfg->action_hi;
-    // (out.high - out.low) / (in.high - in.low) evaluated in fp32 like the reference's float32 Boxes
-    e.slope = (cfg->action_hi - cfg->action_lo) / (1.0f - (-1.0f));
-    e.tol_a2 = cfg->goal_angle_tol * cfg->goal_angle_tol; e.tol_v2 = cfg->goal_vel_tol * cfg->goal_vel_tol;
-    e.a_scale = 2.0f / (cfg->angle_hi - cfg->angle_lo); e.v_scale = 2.0f / (cfg->vel_hi - cfg->vel_lo);
-    if (!s->d_goal) {
-        const size_t plane = sizeof(float) * size_t(s->n);
-        RB_HIP(hipMalloc(&s->d_goal, plane * s->n_q));
-        RB_HIP(hipMalloc(&s->d_ep_ret, plane));
-        RB_HIP(hipMalloc(&s->d_step_num, sizeof(uint32_t) * size_t(s->n)));
-        RB_HIP(hipMalloc(&s->d_ep_sum, sizeof(double) * size_t(s->n) * 2));
-        RB_HIP(hipMalloc(&s->d_ep_cnt, sizeof(uint32_t) * size_t(s->n) * 3));
-    }
-    RB_HIP(hipMemsetAsync(s->d_ep_sum, 0, sizeof(double) * size_t(s->n) * 2, s->stream));
-    RB_HIP(hipMemsetAsync(s->d_ep_cnt, 0, sizeof(uint32_t) * size_t(s->n) * 3, s->stream));
-    if (s->done_kind) RB_HIP(hipMemsetAsync(s->d_done_seen, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
-    if (s->curr_L) RB_HIP(hipMemsetAsync(s->d_goal_seen, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
-    RB_HIP(hipMemsetAsync(s->d_infeas_n, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
-    s->env_steps = 0.0;
-    s->env_ready = true;
-    // the run-time specialised kernels are built here, outside any capture a caller may wrap around its first step
-    maybe_jit(s);
-    if (s->tree) (void)resolve_form(s, ENTRY_ENV, /*build=*/true, nullptr);      // (the env step's kernel of the generated form it runs)
-    return rb_env_reset_dev(s, nullptr);
-}
-
-int rb_env_reset_dev(rb_sim *s, float *d_obs) {
-    if (check(s)) return RB_EINVAL;
-    RB_HIP(hipSetDevice(s->device));
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    if (s->tree)
-        hipLaunchKernelGGL(rbt::tree_env_reset_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream,
-                           s->box, s->d_q, s->d_qd, s->d_feas, s->d_goal, s->d_step_num, s->d_ep_ret,
-                           s->d_goal_count, d_obs, s->n_q, s->n, s->seed, uint64_t(s->env0));
-    else
-        hipLaunchKernelGGL(env_reset_kernel, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream,
-                           s->box, s->d_q, s->d_qd, s->d_feas, s->d_goal, s->d_step_num, s->d_ep_ret,
-                           s->d_goal_count, s->obs_mask || s->hist_rows ? nullptr : d_obs, s->n, s->seed, uint64_t(s->env0));
-    RB_HIP(hipGetLastError());
-    if ((s->obs_mask || s->hist_rows) && d_obs) {      // rows of obs_dim floats: the tendon columns at the zero pose, every set-point 0
-        obs_rows_launch(s, d_obs);
-        RB_HIP(hipGetLastError());
-    }
-    if (s->done_kind) {                       // a reset is no episode end: the next one is judged against the counters as they stand, and nothing is reported
-        RB_HIP(hipMemcpyAsync(s->d_done_seen, s->d_ep_cnt + 2 * size_t(s->n), sizeof(uint32_t) * size_t(s->n), hipMemcpyDeviceToDevice, s->stream));
-        RB_HIP(hipMemsetAsync(s->d_done_kind, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
-    }
-    if (s->io && d_obs) {                     // sensor readings too: the rows' noise, in place (the episode restarts, the history needs nothing)
-        const rbio::IoArgs io = io_args(s, 0);
-        if (io.noise_blocks) {
-            const int od = s->obs_dim();
-            if (s->hist_rows)                 // (the noise stops in front of the action blocks: row stride and noised width apart)
-                hipLaunchKernelGGL(rbh::hist_noise_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, od, od - s->hist_rows * s->n_t, io,
-                                   long(s->n), s->seed, uint64_t(s->env0));
-            else
-                hipLaunchKernelGGL(rbio::io_noise_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, od, io, s->n, s->seed, uint64_t(s->env0));
-            RB_HIP(hipGetLastError());
-        }
-    }
-    if (s->hist_rows && d_obs) {              // nothing has been handed yet: K zero blocks
-        const int od = s->obs_dim();
-        hipLaunchKernelGGL(rbh::hist_zero_rows, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, d_obs, od, od - s->hist_rows * s->n_t, long(s->n));
-        RB_HIP(hipGetLastError());
-    }
-    if (s->d_goal_pool) {                     // every env's goal becomes the pool row of the draw the reset kernel made (a curriculum:
-        // inside the env's window, levels as they stand, and its `seen` plane re-based to the counters like d_done_seen above)
-        const int rc = goal_pool_launch(s, 0, s->n, s->stream, nullptr, d_obs);
-        if (rc) return rc;
-    }
-    if (s->critic_mask) {                     // the privileged rows of the reset state, behind every kernel that wrote the rows above
-        int rc = critic_check(s);
-        if (rc == RB_OK) rc = critic_launch(s, 0, s->n, s->stream, d_obs, s->d_critic);
-        if (rc) return rc;
-    }
-    return RB_OK;
-}
-
-// ---- tendon channels in the fused env step's observation (env_obs.hpp) ----
-int32_t rb_env_obs_count(int32_t n_q, int32_t n_t, uint32_t channel_mask) {
-    if (n_q < 0 || n_t < 0 || (channel_mask & ~uint32_t(RB_OBS_ALL))) return -1;
-    return 3 * n_q + rbo::n_channels(int(channel_mask)) * n_t;
-}
-int rb_env_obs_configure(rb_sim *s, uint32_t channel_mask, const float *scale) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    if (channel_mask & ~uint32_t(RB_OBS_ALL)) return fail(RB_EINVAL, "unknown bits in the channel mask (RB_OBS_LENGTH | RB_OBS_RATE | RB_OBS_ACTIVATION | RB_OBS_FORCE)");
-    if (scale)
-        for (int c = 0; c < 4; ++c)
-            if (!std::isfinite(scale[c])) return fail(RB_EINVAL, "channel scales must be finite");
-    if (s->tree && channel_mask)
-        return fail(RB_EUNSUPPORTED, "tendon channels in the observation are built for ball-joint robots (1-16 tendons); a joint tree's readout is "
-                                     "rb_tendon_state_dev");
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);                       // nothing in flight may still write rows of the old width
-    if (rc) return rc;
-    rc = drop_graphs(s);
-    if (rc) return rc;
-    s->obs_mask = int(channel_mask);
-    for (int c = 0; c < 4; ++c) s->obs_scale[c] = scale ? scale[c] : 1.0f;
-    return RB_OK;
-}
-// ---- per-env action latency and sensor noise in the fused env step (env_io.hpp) ----
-int rb_env_io_configure(rb_sim *s, const rb_env_io_config *cfg) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    if (cfg) {
-        const float sig[6] = {cfg->sigma_q, cfg->sigma_qd, cfg->sigma_tendon[0], cfg->sigma_tendon[1], cfg->sigma_tendon[2], cfg->sigma_tendon[3]};
-        for (float v : sig)
-            if (!std::isfinite(v) || v < 0.0f) return fail(RB_EINVAL, "sensor-noise standard deviations must be finite and >= 0");
-        if (cfg->delay_lo < 0 || cfg->delay_lo > cfg->delay_hi || cfg->delay_hi > RB_IO_MAX_DELAY)
-            return fail(RB_EINVAL, "action delay: 0 <= delay_lo <= delay_hi <= RB_IO_MAX_DELAY");
-        if (s->tree)
-            return fail(RB_EUNSUPPORTED, "action latency and sensor noise are built for ball-joint robots (1-16 tendons); joint trees have none");
-    }
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);                       // nothing in flight may still use the planes or the ring
-    if (rc) return rc;
-    rc = drop_graphs(s);
-    if (rc) return rc;
-    io_free(s);
-    if (!cfg) return ring_rebuild(s);        // (the ring stays for the action columns, rb_env_action_obs_configure)
-    const size_t n = size_t(s->n);
-    auto planes = [&]() -> int {
-        RB_HIP(hipMalloc(&s->d_io_delay, sizeof(uint32_t) * n));
-        RB_HIP(hipMalloc(&s->d_io_draws, sizeof(uint32_t) * n));
-        RB_HIP(hipMalloc(&s->d_io_rows, sizeof(uint32_t) * n));
-        RB_HIP(hipMemsetAsync(s->d_io_draws, 0, sizeof(uint32_t) * n, s->stream));
-        RB_HIP(hipMemsetAsync(s->d_io_rows, 0, sizeof(uint32_t) * n, s->stream));
-        return RB_OK;
-    };
-    rc = planes();
-    if (rc) {                                // no io configuration; action rows keep a ring of their own (or are switched off with it)
-        io_free(s);
-        (void)ring_rebuild(s);               // (clears the action rows itself where it fails too)
-        return rc;
-    }
-    s->io_cfg = *cfg;
-    s->io = true;
-    rc = ring_rebuild(s);
-    if (rc) return rc;
-    return rb_env_io_sample_delay_dev(s, nullptr);      // draw 0 of every env
-}
-// ---- the last K commanded actions as observation columns (env_hist.hpp) ----
-int32_t rb_env_action_obs_count(int32_t n_q, int32_t n_t, uint32_t channel_mask, int32_t rows) {
-    if (rows < 0 || rows > RB_ACTION_OBS_MAX) return -1;
-    const int32_t lead = rb_env_obs_count(n_q, n_t, channel_mask);
-    return lead < 0 ? -1 : lead + rows * n_t;
-}
-int rb_env_action_obs_configure(rb_sim *s, int32_t rows) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    if (rows < 0 || rows > RB_ACTION_OBS_MAX) return fail(RB_EINVAL, "action rows in the observation: 0 <= rows <= RB_ACTION_OBS_MAX");
-    if (s->tree && rows)
-        return fail(RB_EUNSUPPORTED, "action columns in the observation are built for ball-joint robots (1-16 tendons); joint trees have none");
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);                       // nothing in flight may still write rows of the old width or use the ring
-    if (rc) return rc;
-    rc = drop_graphs(s);
-    if (rc) return rc;
-    const int delay_hi = s->io ? s->io_cfg.delay_hi : 0;
-    const bool resize = ring_slots_wanted(delay_hi, rows) != s->io_slots;
-    s->hist_rows = rows;
-    if (!resize) return RB_OK;
-    if (s->io) {                             // another S: planes, counters and ring as a fresh io configuration leaves them
-        const rb_env_io_config cfg = s->io_cfg;
-        return rb_env_io_configure(s, &cfg);
-    }
-    return ring_rebuild(s);
-}
-int rb_env_action_obs_rows(rb_sim *s, int32_t *rows) {
-    if (check(s) || !rows) return fail(RB_EINVAL, "null argument");
-    *rows = s->hist_rows;
-    return RB_OK;
-}
-int rb_env_io_ptr(rb_sim *s, uint32_t **d_delay, uint32_t **d_delay_draws, uint32_t **d_rows, float **d_history, int32_t *slots) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->io && !s->hist_rows) return fail(RB_EINVAL, "no io configuration (rb_env_io_configure)");
-    if (d_delay) *d_delay = s->d_io_delay;
-    if (d_delay_draws) *d_delay_draws = s->d_io_draws;
-    if (d_rows) *d_rows = s->d_io_rows;
-    if (d_history) *d_history = s->d_io_hist;
-    if (slots) *slots = s->io_slots;
-    return RB_OK;
-}
-int rb_env_io_sample_delay_dev(rb_sim *s, const uint8_t *d_mask) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->io) return fail(RB_EINVAL, "no io configuration (rb_env_io_configure)");
-    RB_HIP(hipSetDevice(s->device));
-    hipLaunchKernelGGL(rbio::io_sample_delay, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->d_io_delay, s->d_io_draws, d_mask,
-                       s->io_cfg.delay_lo, s->io_cfg.delay_hi, long(s->n), s->seed, uint64_t(s->env0));
-    RB_HIP(hipGetLastError());
-    return RB_OK;
-}
-
-// ---- episode-end codes of the fused env step (done_kind_kernel) ----
-int rb_env_done_kind_configure(rb_sim *s, int enable) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);                       // nothing in flight may still write the planes
-    if (rc) return rc;
-    rc = drop_graphs(s);
-    if (rc) return rc;
-    s->done_kind = false;
-    (void)hipFree(s->d_done_seen); (void)hipFree(s->d_done_kind);
-    s->d_done_seen = nullptr; s->d_done_kind = nullptr;
-    if (!enable) return RB_OK;
-    const size_t plane = sizeof(uint32_t) * size_t(s->n);
-    RB_HIP(hipMalloc(&s->d_done_seen, plane));
-    RB_HIP(hipMalloc(&s->d_done_kind, plane));
-    RB_HIP(hipMemcpyAsync(s->d_done_seen, s->d_ep_cnt + 2 * size_t(s->n), plane, hipMemcpyDeviceToDevice, s->stream));
-    RB_HIP(hipMemsetAsync(s->d_done_kind, 0, plane, s->stream));
-    s->done_kind = true;
-    return RB_OK;
-}
-int rb_env_done_kind_ptr(rb_sim *s, uint32_t **d_kind) {
-    if (check(s) || !d_kind) return fail(RB_EINVAL, "null argument");
-    if (!s->done_kind) return fail(RB_EINVAL, "episode-end codes are not enabled (rb_env_done_kind_configure)");
-    *d_kind = s->d_done_kind;
-    return RB_OK;
-}
-
-// ---- privileged critic rows behind the fused env step (env_critic.hpp) ----
-int32_t rb_env_critic_obs_count(int32_t n_q, int32_t n_t, uint32_t mask, int32_t n_params, int32_t action_rows) {
-    if (n_q < 0 || n_t < 0 || n_params < 0 || action_rows < 0 || (mask & ~uint32_t(RB_CRITIC_ALL))) return -1;
-    return mask ? rbc::row_dim(int(mask | RB_CRITIC_STATE), n_q, n_params, action_rows * n_t) : 0;
-}
-int rb_env_critic_obs_configure(rb_sim *s, uint32_t mask) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    if (mask & ~uint32_t(RB_CRITIC_ALL))
-        return fail(RB_EINVAL, "unknown bits in the critic-row mask (RB_CRITIC_STATE | _AGE | _PARAMS | _DELAY | _ACTIONS)");
-    if (s->tree && mask)
-        return fail(RB_EUNSUPPORTED, "critic rows are built for ball-joint robots (1-16 tendons); joint trees have none");
-    if (mask) mask |= RB_CRITIC_STATE;       // (always selected)
-    if (mask & RB_CRITIC_PARAMS && !s->params) return fail(RB_EINVAL, "critic rows: RB_CRITIC_PARAMS needs per-env parameters (rb_params_enable first)");
-    if (mask & RB_CRITIC_DELAY && !s->io) return fail(RB_EINVAL, "critic rows: RB_CRITIC_DELAY needs an io configuration (rb_env_io_configure first)");
-    if (mask & RB_CRITIC_ACTIONS && !s->hist_rows)
-        return fail(RB_EINVAL, "critic rows: RB_CRITIC_ACTIONS needs action rows in the observation (rb_env_action_obs_configure first)");
-    const int dim = rbc::row_dim(int(mask), s->n_q, s->params ? s->n_params : 0, s->hist_rows * s->n_t);
-    if (dim > RB_CRITIC_OBS_MAX_DIM)
-        return fail(RB_EINVAL, "critic rows: " + std::to_string(dim) + " columns, at most RB_CRITIC_OBS_MAX_DIM = 63 (the PPO gradient kernels' input limit)");
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);                       // nothing in flight may still write rows of the old width
-    if (rc) return rc;
-    rc = drop_graphs(s);
-    if (rc) return rc;
-    (void)hipFree(s->d_critic);
-    s->d_critic = nullptr; s->critic_mask = 0; s->critic_dim = 0;
-    if (!mask) return RB_OK;
-    const size_t bytes = sizeof(float) * size_t(s->n) * size_t(dim);
-    RB_HIP(hipMalloc(&s->d_critic, bytes));
-    s->critic_mask = int(mask); s->critic_dim = dim;
-    // the rows of the envs as they stand (no observation rows at hand: zero action blocks, as behind a reset)
-    return critic_launch(s, 0, s->n, s->stream, nullptr, s->d_critic);
-}
-int rb_env_critic_obs_dim(rb_sim *s, int32_t *dim) {
-    if (check(s) || !dim) return fail(RB_EINVAL, "null argument");
-    *dim = s->critic_dim;
-    return RB_OK;
-}
-int rb_env_critic_obs_ptr(rb_sim *s, float **d_rows) {
-    if (check(s) || !d_rows) return fail(RB_EINVAL, "null argument");
-    if (!s->critic_mask) return fail(RB_EINVAL, "critic rows are not enabled (rb_env_critic_obs_configure)");
-    *d_rows = s->d_critic;
-    return RB_OK;
-}
-
-// ---- goal pool: env goals drawn from a set of poses instead of the box (env_goal.hpp) ----
-int rb_env_goal_pool_set(rb_sim *s, const float *goal_q, int64_t m) {
-    if (check(s) || !goal_q) return fail(RB_EINVAL, "null argument");
-    if (m < 1 || m > int64_t(UINT32_MAX)) return fail(RB_EINVAL, "goal pool: m must be >= 1 (and below 2^32)");
-    if (s->d_goal_pool && m != s->goal_pool_m)
-        return fail(RB_EINVAL, "goal pool: the handle's pool has " + std::to_string(s->goal_pool_m) + " rows, fixed by the first call; got " + std::to_string(m));
-    // the angle box of rb_env_configure, or the robot's own box (what rb_sample_goals draws from) without an env layer
-    for (int64_t r = 0; r < m; ++r)
-        for (int j = 0; j < s->n_q; ++j) {
-            const float v = goal_q[r * s->n_q + j];
-            const float lo = s->env_ready ? s->env.a_lo : s->box.lo[j], hi = s->env_ready ? s->env.a_hi : s->box.hi[j];
-            if (!std::isfinite(v) || v < lo || v > hi)
-                return fail(RB_EINVAL, "goal pool: row " + std::to_string(r) + ", joint " + std::to_string(j) + " is not finite or outside the angle box");
-        }
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);                       // nothing in flight may still read the rows
-    if (rc) return rc;
-    const size_t bytes = sizeof(float) * size_t(m) * size_t(s->n_q);
-    if (!s->d_goal_pool) {
-        float *d = nullptr;
-        hipError_t e = hipMalloc(&d, bytes);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RB_ENOMEM : RB_EHIP, std::string("hipMalloc (goal pool): ") + hipGetErrorString(e));
-        e = hipMemcpy(d, goal_q, bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d); return fail(RB_EHIP, std::string("hipMemcpy (goal pool): ") + hipGetErrorString(e)); }
-        s->d_goal_pool = d; s->goal_pool_m = m;      // (from here on the env step and the reset launch goal_pool_kernel)
-        // an env layer already drew every env's goal from the box (rb_env_configure resets): that draw's pool row takes its place,
-        // counters untouched, so from here on every goal of the handle is a row of the pool
-        return s->env_ready ? goal_pool_launch(s, 0, s->n, s->stream, nullptr, nullptr) : RB_OK;
-    }
-    RB_HIP(hipMemcpy(s->d_goal_pool, goal_q, bytes, hipMemcpyHostToDevice));      // in place: a captured graph reads the new rows on its next replay
-    return RB_OK;
-}
-int rb_env_goal_pool_ptr(rb_sim *s, float **d_pool, int64_t *m) {
-    if (check(s) || !d_pool || !m) return fail(RB_EINVAL, "null argument");
-    if (!s->d_goal_pool) return fail(RB_EINVAL, "no goal pool is set (rb_env_goal_pool_set)");
-    *d_pool = s->d_goal_pool; *m = s->goal_pool_m;
-    return RB_OK;
-}
-
-// ---- goal curriculum: a level per env over the pool's row order (env_goal.hpp) ----
-int rb_env_goal_curriculum_configure(rb_sim *s, int32_t levels, int32_t up, int32_t down, int32_t level0) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    if (!s->d_goal_pool) return fail(RB_EINVAL, "goal curriculum: no goal pool is set (rb_env_goal_pool_set first)");
-    if (s->curr_L) return fail(RB_EINVAL, "goal curriculum: already configured (once per handle: a captured graph holds the arguments by value)");
-    const int64_t most = s->goal_pool_m < RB_GOAL_LEVELS_MAX ? s->goal_pool_m : int64_t(RB_GOAL_LEVELS_MAX);
-    if (levels < 1 || levels > most)
-        return fail(RB_EINVAL, "goal curriculum: levels must be in 1.." + std::to_string(most) + " (at most the pool's rows and RB_GOAL_LEVELS_MAX = 256), got " +
-                                   std::to_string(levels));
-    if (up < 0 || down < 0) return fail(RB_EINVAL, "goal curriculum: up and down must be >= 0");
-    if (level0 < 0 || level0 >= levels) return fail(RB_EINVAL, "goal curriculum: level0 must be in 0..levels - 1");
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);                       // nothing in flight may still launch the pool's own kernel
-    if (rc) return rc;
-    rc = drop_graphs(s);
-    if (rc) return rc;
-    const size_t plane = sizeof(uint32_t) * size_t(s->n);
-    if (!s->d_goal_level) {                  // (one block: the three planes, then the host histogram's L counts)
-        uint32_t *d = nullptr;
-        const hipError_t e = hipMalloc(&d, 3 * plane + sizeof(uint64_t) * RB_GOAL_LEVELS_MAX + 8);
-        if (e != hipSuccess)
-            return fail(e == hipErrorOutOfMemory ? RB_ENOMEM : RB_EHIP, std::string("hipMalloc (goal curriculum): ") + hipGetErrorString(e));
-        s->d_goal_level = d; s->d_goal_index = d + s->n; s->d_goal_seen = d + 2 * s->n;
-        s->d_goal_hist = reinterpret_cast<uint64_t *>((reinterpret_cast<uintptr_t>(d + 3 * s->n) + 7) & ~uintptr_t(7));
-    }
-    {
-        std::vector<uint32_t> l0(size_t(s->n), uint32_t(level0));
-        RB_HIP(hipMemcpy(s->d_goal_level, l0.data(), plane, hipMemcpyHostToDevice));
-    }
-    s->curr_L = uint32_t(levels); s->curr_up = uint32_t(up); s->curr_down = uint32_t(down);      // (from here on goal_pool_launch enqueues goal_curriculum_kernel)
-    // every env's current goal, a row of the whole pool, becomes the row of that same draw inside its window (counters untouched);
-    // the launch also sets `seen` to the counters as they stand and fills the index plane
-    return goal_pool_launch(s, 0, s->n, s->stream, nullptr, nullptr);
-}
-static int curriculum_check(rb_sim *s) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->curr_L) return fail(RB_EINVAL, "no goal curriculum is configured (rb_env_goal_curriculum_configure)");
-    return RB_OK;
-}
-int rb_env_goal_level_ptr(rb_sim *s, uint32_t **d_level) {
-    if (curriculum_check(s)) return RB_EINVAL;
-    if (!d_level) return fail(RB_EINVAL, "null argument");
-    *d_level = s->d_goal_level;
-    return RB_OK;
-}
-int rb_env_goal_index_ptr(rb_sim *s, uint32_t **d_index) {
-    if (curriculum_check(s)) return RB_EINVAL;
-    if (!d_index) return fail(RB_EINVAL, "null argument");
-    *d_index = s->d_goal_index;
-    return RB_OK;
-}
-int rb_env_goal_levels_set(rb_sim *s, const uint32_t *levels) {
-    if (curriculum_check(s)) return RB_EINVAL;
-    if (!levels) return fail(RB_EINVAL, "null argument");
-    for (long i = 0; i < s->n; ++i)
-        if (levels[i] >= s->curr_L)
-            return fail(RB_EINVAL, "goal levels: env " + std::to_string(i) + " has level " + std::to_string(levels[i]) + ", the curriculum has " +
-                                       std::to_string(s->curr_L) + " levels");
-    RB_HIP(hipSetDevice(s->device));
-    const int rc = drain(s);                 // nothing in flight may still move a level
-    if (rc) return rc;
-    RB_HIP(hipMemcpy(s->d_goal_level, levels, sizeof(uint32_t) * size_t(s->n), hipMemcpyHostToDevice));
-    return RB_OK;
-}
-int rb_env_goal_level_hist_dev(rb_sim *s, uint64_t *d_out, void *hip_stream) {
-    if (curriculum_check(s)) return RB_EINVAL;
-    if (!d_out) return fail(RB_EINVAL, "null argument");
-    RB_HIP(hipSetDevice(s->device));
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
-    RB_HIP(hipMemsetAsync(d_out, 0, sizeof(uint64_t) * s->curr_L, st));
-    unsigned g = blocks_for(s->n, 256);
-    if (g > 1024u) g = 1024u;                // (grid-stride beyond: at most 1024 x L atomics into the output)
-    hipLaunchKernelGGL(rbg::goal_level_hist_kernel, dim3(g), dim3(256), 0, st, s->d_goal_level, long(s->n), s->curr_L,
-                       reinterpret_cast<unsigned long long *>(d_out));
-    RB_HIP(hipGetLastError());
-    return RB_OK;
-}
-int rb_env_goal_level_hist(rb_sim *s, uint64_t *out) {
-    if (curriculum_check(s)) return RB_EINVAL;
-    if (!out) return fail(RB_EINVAL, "null argument");
-    RB_HIP(hipSetDevice(s->device));
-    const int rc = rb_env_goal_level_hist_dev(s, s->d_goal_hist, nullptr);
-    if (rc) return rc;
-    RB_HIP(hipMemcpyAsync(out, s->d_goal_hist, sizeof(uint64_t) * s->curr_L, hipMemcpyDeviceToHost, s->stream));
-    RB_HIP(hipStreamSynchronize(s->stream));
-    return RB_OK;
-}
-
-// ---- outcome counts per pool row, and re-ordering a live pool (env_goal.hpp) ----
-int rb_env_goal_row_stats_enable(rb_sim *s) {
-    if (curriculum_check(s)) return RB_EINVAL;
-    if (s->d_goal_row_stats) return fail(RB_EINVAL, "goal row stats: already enabled (once per handle: a captured graph holds the kernel it was captured with)");
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);                       // nothing in flight may still launch the curriculum's own kernel
-    if (rc) return rc;
-    rc = drop_graphs(s);
-    if (rc) return rc;
-    const size_t bytes = sizeof(uint64_t) * 2 * size_t(s->goal_pool_m);
-    uint64_t *d = nullptr;
-    hipError_t e = hipMalloc(&d, bytes);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RB_ENOMEM : RB_EHIP, std::string("hipMalloc (goal row stats): ") + hipGetErrorString(e));
-    e = hipMemset(d, 0, bytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { (void)hipFree(d); return fail(RB_EHIP, std::string("hipMemset (goal row stats): ") + hipGetErrorString(e)); }
-    s->d_goal_row_stats = d;                 // (from here on goal_pool_launch enqueues goal_curriculum_stats_kernel)
-    return RB_OK;
-}
-static int row_stats_check(rb_sim *s) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->d_goal_row_stats) return fail(RB_EINVAL, "goal row stats are not enabled (rb_env_goal_row_stats_enable)");
-    return RB_OK;
-}
-int rb_env_goal_row_stats_ptr(rb_sim *s, uint64_t **d_counts, int64_t *m) {
-    if (row_stats_check(s)) return RB_EINVAL;
-    if (!d_counts || !m) return fail(RB_EINVAL, "null argument");
-    *d_counts = s->d_goal_row_stats; *m = s->goal_pool_m;
-    return RB_OK;
-}
-int rb_env_goal_row_stats_read(rb_sim *s, uint64_t *host, int clear) {
-    if (row_stats_check(s)) return RB_EINVAL;
-    if (!host) return fail(RB_EINVAL, "null argument");
-    RB_HIP(hipSetDevice(s->device));
-    const int rc = drain(s);                 // every count enqueued so far is in
-    if (rc) return rc;
-    const size_t bytes = sizeof(uint64_t) * 2 * size_t(s->goal_pool_m);
-    RB_HIP(hipMemcpy(host, s->d_goal_row_stats, bytes, hipMemcpyDeviceToHost));
-    if (clear) {
-        RB_HIP(hipMemset(s->d_goal_row_stats, 0, bytes));
-        RB_HIP(hipDeviceSynchronize());
-    }
-    return RB_OK;
-}
-int rb_env_goal_row_stats_set(rb_sim *s, const uint64_t *host) {
-    if (row_stats_check(s)) return RB_EINVAL;
-    if (!host) return fail(RB_EINVAL, "null argument");
-    const int64_t m = s->goal_pool_m;
-    for (int64_t k = 0; k < m; ++k)
-        if (host[m + k] > host[k])
-            return fail(RB_EINVAL, "goal row stats: row " + std::to_string(k) + " has reached " + std::to_string(host[m + k]) + " > attempts " +
-                                       std::to_string(host[k]));
-    RB_HIP(hipSetDevice(s->device));
-    const int rc = drain(s);                 // nothing in flight may still add to the planes
-    if (rc) return rc;
-    RB_HIP(hipMemcpy(s->d_goal_row_stats, host, sizeof(uint64_t) * 2 * size_t(m), hipMemcpyHostToDevice));
-    return RB_OK;
-}
-int rb_env_goal_pool_permute(rb_sim *s, const uint32_t *order) {
-    if (check(s) || !order) return fail(RB_EINVAL, "null argument");
-    if (!s->d_goal_pool) return fail(RB_EINVAL, "no goal pool is set (rb_env_goal_pool_set)");
-    const size_t m = size_t(s->goal_pool_m), nq = size_t(s->n_q);
-    std::vector<uint32_t> inv(m, UINT32_MAX);        // inv[old row] = new row
-    for (size_t j = 0; j < m; ++j) {
-        if (order[j] >= m) return fail(RB_EINVAL, "goal pool permute: entry " + std::to_string(j) + " is " + std::to_string(order[j]) + ", the pool has " + std::to_string(m) + " rows");
-        if (inv[order[j]] != UINT32_MAX) return fail(RB_EINVAL, "goal pool permute: row " + std::to_string(order[j]) + " occurs twice (not a permutation)");
-        inv[order[j]] = uint32_t(j);
-    }
-    RB_HIP(hipSetDevice(s->device));
-    const int rc = drain(s);                 // nothing in flight may still read the rows, the indices or the counts
-    if (rc) return rc;
-    uint32_t *d_inv = nullptr;
-    if (s->curr_L) {                         // (everything that can fail for want of memory: before anything changes)
-        const hipError_t e = hipMalloc(&d_inv, sizeof(uint32_t) * m);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? RB_ENOMEM : RB_EHIP, std::string("hipMalloc (goal pool permute): ") + hipGetErrorString(e));
-    }
-    auto done = [&](hipError_t e, const char *what) {
-        (void)hipFree(d_inv);
-        return e == hipSuccess ? RB_OK : fail(RB_EHIP, std::string(what) + " (goal pool permute): " + hipGetErrorString(e));
-    };
-    // the rows through the host, back IN PLACE: the pointer never moves, so a graph captured earlier reads the new order
-    std::vector<float> rows(m * nq), out(m * nq);
-    hipError_t e = hipMemcpy(rows.data(), s->d_goal_pool, sizeof(float) * m * nq, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return done(e, "hipMemcpy");
-    for (size_t j = 0; j < m; ++j) std::memcpy(&out[j * nq], &rows[size_t(order[j]) * nq], sizeof(float) * nq);
-    e = hipMemcpy(s->d_goal_pool, out.data(), sizeof(float) * m * nq, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return done(e, "hipMemcpy");
-    if (s->d_goal_row_stats) {               // both count planes travel with their rows
-        std::vector<uint64_t> cnt(2 * m), cout2(2 * m);
-        e = hipMemcpy(cnt.data(), s->d_goal_row_stats, sizeof(uint64_t) * 2 * m, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return done(e, "hipMemcpy");
-        for (size_t j = 0; j < m; ++j) { cout2[j] = cnt[order[j]]; cout2[m + j] = cnt[m + order[j]]; }
-        e = hipMemcpy(s->d_goal_row_stats, cout2.data(), sizeof(uint64_t) * 2 * m, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return done(e, "hipMemcpy");
-    }
-    if (s->curr_L) {                         // every env keeps the pose it holds: its index becomes that row's new number
-        e = hipMemcpy(d_inv, inv.data(), sizeof(uint32_t) * m, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return done(e, "hipMemcpy");
-        unsigned g = blocks_for(s->n, 256);
-        if (g > 1024u) g = 1024u;            // (grid-stride beyond)
-        hipLaunchKernelGGL(rbg::goal_index_permute_kernel, dim3(g), dim3(256), 0, s->stream, s->d_goal_index, d_inv, long(s->n), uint32_t(m));
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-        if (e != hipSuccess) return done(e, "index kernel");
-    }
-    return done(hipSuccess, "");
-}
-
-int rb_env_obs_dim(rb_sim *s, int32_t *obs_dim) {
-    if (check(s) || !obs_dim) return fail(RB_EINVAL, "null argument");
-    *obs_dim = s->obs_dim();
-    return RB_OK;
-}
-
-int rb_env_set_goal(rb_sim *s, const float *goal_q, const uint32_t *step_num) {
-    if (check(s) || !goal_q) return fail(RB_EINVAL, "null argument");
-    RB_HIP(hipSetDevice(s->device));
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    const long n = s->n;
-    RB_HIP(hipMemcpyAsync(s->d_rows, goal_q, sizeof(float) * n * s->n_q, hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(unpack_rows_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s->stream, s->d_rows, s->d_goal, s->n_q, n, s->tree ? 1 : 0);
-    RB_HIP(hipGetLastError());
-    if (step_num)
-        RB_HIP(hipMemcpyAsync(s->d_step_num, step_num, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s->stream));
-    if (s->curr_L)                            // these goals are no row of the pool: RB_GOAL_INDEX_NONE, every byte 0xFF
-        RB_HIP(hipMemsetAsync(s->d_goal_index, 0xFF, sizeof(uint32_t) * n, s->stream));
-    RB_HIP(hipStreamSynchronize(s->stream));
-    return RB_OK;
-}
-
-// RoboyEnv.step for envs [i0, i0 + cnt) on `stream`; the array arguments are those of the whole batch (the launchers apply the
-// offsets).  Sub-ranges: every ball-joint form and the joint trees' one-wave-per-64-envs form (Row::ranges).
-// d_cobs: where the range's critic rows go while rb_env_critic_obs_configure holds (null: the handle's plane)
-static int env_step_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done,
-                           float *d_cobs = nullptr) {
-    if (s->critic_mask) { const int rc = critic_check(s); if (rc) return rc; }       // (before anything is enqueued)
-    Launch L;
-    L.i0 = i0; L.cnt = cnt; L.stream = stream; L.act = d_act; L.obs = d_obs; L.reward = d_reward; L.done = d_done;
-    const int rc = dispatch(s, ENTRY_ENV, L);
-    if (rc != RB_OK) return rc;
-    if (s->d_goal_pool) {                     // the done envs' new goal becomes a pool row, in front of everything that reads the goal (same stream)
-        const int rc1 = goal_pool_launch(s, i0, cnt, stream, d_done, d_obs);
-        if (rc1) return rc1;
-    }
-    if (s->critic_mask) {                     // the privileged rows of the range, from the planes as the step left them (same stream)
-        const int rc2 = critic_launch(s, i0, cnt, stream, d_obs, d_cobs ? d_cobs : s->d_critic);
-        if (rc2) return rc2;
-    }
-    if (!s->done_kind) return RB_OK;
-    // the episode-end codes of the range, behind whichever kernel stepped it (same stream)
-    hipLaunchKernelGGL(done_kind_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, d_done, s->d_ep_cnt + 2 * size_t(s->n),
-                       s->d_done_seen, s->d_done_kind, i0, i0 + cnt);
-    RB_HIP(hipGetLastError());
-    return RB_OK;
-}
-
-int rb_env_step_dev(rb_sim *s, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done) {
-    if (check(s) || !d_act || !d_obs || !d_reward || !d_done) return fail(RB_EINVAL, "null argument");
-    RB_HIP(hipSetDevice(s->device));
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    if (!s->tree && reinterpret_cast<uintptr_t>(d_act) % 16) return fail(RB_EINVAL, "action slab must be 16-byte aligned");
-    int rc = env_step_launch(s, 0, s->n, s->stream, d_act, d_obs, d_reward, d_done);
-    if (rc == RB_OK) s->env_steps += double(s->n);
-    return rc;
-}
-
-int rb_env_step_critic_dev(rb_sim *s, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done, float *d_cobs) {
-    if (check(s) || !d_act || !d_obs || !d_reward || !d_done || !d_cobs) return fail(RB_EINVAL, "null argument");
-    RB_HIP(hipSetDevice(s->device));
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    if (!s->critic_mask) return fail(RB_EINVAL, "critic rows are not enabled (rb_env_critic_obs_configure)");
-    if (reinterpret_cast<uintptr_t>(d_act) % 16) return fail(RB_EINVAL, "action slab must be 16-byte aligned");
-    int rc = env_step_launch(s, 0, s->n, s->stream, d_act, d_obs, d_reward, d_done, d_cobs);
-    if (rc == RB_OK) s->env_steps += double(s->n);
-    return rc;
-}
-
-// a sub-range on a stream of the caller's choice: envs are independent, so disjoint ranges may be stepped concurrently
-static int range_ok(const rb_sim *s, int64_t first, int64_t count) {
-    if (first < 0 || count < 1 || first + count > s->n) return fail(RB_EINVAL, "range outside the batch");
-    if (first % 256) return fail(RB_EINVAL, "a range starts at a multiple of 256 envs");
-    return RB_OK;
-}
-int rb_env_step_range_dev(rb_sim *s, int64_t first_env, int64_t n_envs, void *hip_stream, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done) {
-    if (check(s) || !d_act || !d_obs || !d_reward || !d_done) return fail(RB_EINVAL, "null argument");
-    RB_HIP(hipSetDevice(s->device));
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    if (!s->tree && reinterpret_cast<uintptr_t>(d_act) % 16) return fail(RB_EINVAL, "action slab must be 16-byte aligned");
-    if (range_ok(s, first_env, n_envs)) return RB_EINVAL;
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
-    CallStreamScope scope(s, st);          // a first call captured on the caller's stream defers the run-time builds (capturing())
-    int rc = env_step_launch(s, long(first_env), long(n_envs), st, d_act, d_obs, d_reward, d_done);
-    if (rc == RB_OK) { s->env_steps += double(n_envs); rc = note_caller_stream(s, st); }
-    return rc;
-}
-int rb_env_step_range_critic_dev(rb_sim *s, int64_t first_env, int64_t n_envs, void *hip_stream, const float *d_act, float *d_obs, float *d_reward,
-                                 uint32_t *d_done, float *d_cobs) {
-    if (check(s) || !d_act || !d_obs || !d_reward || !d_done || !d_cobs) return fail(RB_EINVAL, "null argument");
-    RB_HIP(hipSetDevice(s->device));
-    if (!s->env_ready) return fail(RB_EINVAL, "rb_env_configure has not been called");
-    if (!s->critic_mask) return fail(RB_EINVAL, "critic rows are not enabled (rb_env_critic_obs_configure)");
-    if (reinterpret_cast<uintptr_t>(d_act) % 16) return fail(RB_EINVAL, "action slab must be 16-byte aligned");
-    if (range_ok(s, first_env, n_envs)) return RB_EINVAL;
-    hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : s->stream;
-    CallStreamScope scope(s, st);          // a first call captured on the caller's stream defers the run-time builds (capturing())
-    int rc = env_step_launch(s, long(first_env), long(n_envs), st, d_act, d_obs, d_reward, d_done, d_cobs);
-    if (rc == RB_OK) { s->env_steps += double(n_envs); rc = note_caller_stream(s, st); }
-    return rc;
-}
 int rb_step_range_dev(rb_sim *s, int64_t first_env, int64_t n_envs, void *hip_stream, const float *d_act, float act_scale) {
     if (check(s) || !d_act) return fail(RB_EINVAL, "null argument");
     RB_HIP(hipSetDevice(s->device));
@@ -2315,55 +1496,11 @@ int rb_range_capable(rb_sim *s) {
     return (ranges(ENTRY_STEP, true) ? 1 : 0) | (ranges(ENTRY_ENV, s->env_ready) ? 2 : 0);
 }
 
-static int stats_launch(rb_sim *s, double *d_out2) {
-    unsigned g = blocks_for(s->n, 256);
-    if (g > unsigned(STATS_BLOCKS)) g = STATS_BLOCKS;
-    double *partials = s->d_stats + 8;
-    unsigned int *ticket = reinterpret_cast<unsigned int *>(s->d_stats + 8 * (STATS_BLOCKS + 1));
-    if (s->env_ready)
-        hipLaunchKernelGGL(stats_reduce_kernel<true>, dim3(g), dim3(256), 0, s->stream, s->d_ep_sum, s->d_ep_cnt, s->d_ep_ret,
-                           s->d_infeas_n, s->d_feas, partials, ticket, s->d_stats, d_out2, s->env_steps, s->n);
-    else
-        hipLaunchKernelGGL(stats_reduce_kernel<false>, dim3(g), dim3(256), 0, s->stream, nullptr, s->d_ep_cnt, s->d_ep_ret,
-                           s->d_infeas_n, s->d_feas, partials, ticket, s->d_stats, d_out2, s->env_steps, s->n);
-    RB_HIP(hipGetLastError());
-    return RB_OK;
-}
-static int stats_reset(rb_sim *s) {
-    if (s->env_ready) {
-        RB_HIP(hipMemsetAsync(s->d_ep_sum, 0, sizeof(double) * size_t(s->n) * 2, s->stream));
-        RB_HIP(hipMemsetAsync(s->d_ep_cnt, 0, sizeof(uint32_t) * size_t(s->n) * 3, s->stream));
-        if (s->done_kind) RB_HIP(hipMemsetAsync(s->d_done_seen, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
-        if (s->curr_L) RB_HIP(hipMemsetAsync(s->d_goal_seen, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
-    }
-    RB_HIP(hipMemsetAsync(s->d_infeas_n, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
-    s->env_steps = 0.0;
-    return RB_OK;
-}
-
-int rb_env_stats_dev(rb_sim *s, double *d_stats8, int reset) {
-    if (check(s) || !d_stats8) return fail(RB_EINVAL, "null argument");
-    RB_HIP(hipSetDevice(s->device));
-    int rc = stats_launch(s, d_stats8);
-    if (rc) return rc;
-    return reset ? stats_reset(s) : RB_OK;
-}
-
-int rb_env_stats(rb_sim *s, double *stats8, int reset) {
-    if (check(s) || !stats8) return fail(RB_EINVAL, "null argument");
-    RB_HIP(hipSetDevice(s->device));
-    int rc = stats_launch(s, nullptr);
-    if (rc) return rc;
-    RB_HIP(hipMemcpyAsync(stats8, s->d_stats, sizeof(double) * 8, hipMemcpyDeviceToHost, s->stream));
-    RB_HIP(hipStreamSynchronize(s->stream));
-    return reset ? stats_reset(s) : RB_OK;
-}
-
 // ---- tendon state readout (tendon_state.hpp): one kernel per robot class, not a row of the dispatch table ----
 namespace {
 int tendon_state_check(rb_sim *s, const float *act, int mode, float act_scale) {
     if (check(s)) return RB_EINVAL;
-    if (s->params) return params_refuse(s, "the tendon-state readout (rb_tendon_state_dev)");
+    if (s->par.on) return params_refuse(s, "the tendon-state readout (rb_tendon_state_dev)");
     if (mode != RB_SP_SCALED && mode != RB_SP_ENV) return fail(RB_EINVAL, "unknown set-point mode (RB_SP_SCALED or RB_SP_ENV)");
     if (mode == RB_SP_ENV && !s->env_ready) return fail(RB_EINVAL, "RB_SP_ENV needs the env layer's action box: call rb_env_configure first");
     if (mode == RB_SP_SCALED && act && !(act_scale > 0.0f)) return fail(RB_EINVAL, "act_scale must be > 0 under RB_SP_SCALED");
@@ -2458,10 +1595,10 @@ int rb_dispatch_current(rb_sim *s, int entry, rb_dispatch_row *out) {
     if (entry == ENTRY_FUSED && (s->tree || s->ntx)) return fail(RB_EUNSUPPORTED, "fused rollout is built for 8-tendon ball-joint robots");
     if (extension_serves(s, entry))
         return fail(RB_EUNSUPPORTED,
-                    s->hist_rows && entry == ENTRY_ENV
+                    s->hist.rows && entry == ENTRY_ENV
                         ? "action rows are set (rb_env_action_obs_configure): the history env-step kernels (env_hist.hpp) are not rows of the dispatch table"
-                    : s->params ? "per-env parameters are enabled: the parameter kernels (env_params.hpp) are not rows of the dispatch table"
-                    : s->io   ? "an io configuration is set (rb_env_io_configure): the io env-step kernels (env_io.hpp) are not rows of the dispatch table"
+                    : s->par.on ? "per-env parameters are enabled: the parameter kernels (env_params.hpp) are not rows of the dispatch table"
+                    : s->io.on ? "an io configuration is set (rb_env_io_configure): the io env-step kernels (env_io.hpp) are not rows of the dispatch table"
                               : "tendon channels are set (rb_env_obs_configure): the extended env-step kernels (env_obs.hpp) are not rows of the dispatch table");
     RB_HIP(hipSetDevice(s->device));
     if (entry != ENTRY_ENV || s->env_ready) maybe_jit(s);
@@ -2469,92 +1606,6 @@ int rb_dispatch_current(rb_sim *s, int entry, rb_dispatch_row *out) {
     const Row *r = row_for(s, entry, /*build=*/entry != ENTRY_ENV || s->env_ready, &why);
     if (!r) return fail(RB_EUNSUPPORTED, why);
     *out = public_row(*r);
-    return RB_OK;
-}
-
-// ---- per-env physical parameters (env_params.hpp) ----
-int rb_params_enable(rb_sim *s, int32_t *n_params) {
-    if (check(s)) return RB_EINVAL;
-    if (s->tree) return fail(RB_EUNSUPPORTED, "per-env parameters are built for ball-joint robots (the closed-form kernels); joint trees have none");
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);                       // nothing in flight may read the planes while they are reset
-    if (rc) return rc;
-    rc = drop_graphs(s);                     // captured graphs hold the nominal kernels' nodes
-    if (rc) return rc;
-    const int nt = s->n_t, P = rbp::n_params(nt);
-    const size_t n = size_t(s->n);
-    if (!s->d_params) {
-        hipError_t e = hipMalloc(&s->d_params, sizeof(float) * size_t(P) * n);
-        if (e == hipSuccess) e = hipMalloc(&s->d_param_draws, sizeof(uint32_t) * n);
-        if (e == hipSuccess) e = hipMalloc(&s->d_param_ranges, sizeof(float) * 2 * size_t(P));
-        if (e != hipSuccess) {
-            params_free(s);
-            return fail(e == hipErrorOutOfMemory ? RB_ENOMEM : RB_EHIP, std::string("parameter planes: ") + hipGetErrorString(e));
-        }
-    }
-    // nominal values: force scales 1, offsets 0, mass scale 1, damping scales 1; counters 0; ranges lo = hi = nominal, no redraw
-    uint32_t one, zero = 0u;
-    const float onef = 1.0f;
-    std::memcpy(&one, &onef, 4);
-    RB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->d_params), int(one), size_t(nt) * n, s->stream));
-    RB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->d_params + size_t(nt) * n), int(zero), size_t(nt) * n, s->stream));
-    RB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->d_params + size_t(2 * nt) * n), int(one), 4 * n, s->stream));
-    RB_HIP(hipMemsetAsync(s->d_param_draws, 0, sizeof(uint32_t) * n, s->stream));
-    s->param_ranges.assign(2 * size_t(P), 1.0f);
-    for (int k = 0; k < nt; ++k) s->param_ranges[nt + k] = s->param_ranges[P + nt + k] = 0.0f;
-    RB_HIP(hipMemcpyAsync(s->d_param_ranges, s->param_ranges.data(), sizeof(float) * 2 * size_t(P), hipMemcpyHostToDevice, s->stream));
-    RB_HIP(hipStreamSynchronize(s->stream));
-    s->n_params = P;
-    s->param_resample = false;
-    s->params = true;
-    if (n_params) *n_params = P;
-    return RB_OK;
-}
-int rb_params_disable(rb_sim *s) {
-    if (check(s)) return RB_EINVAL;
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);
-    if (rc) return rc;
-    rc = drop_graphs(s);                     // captured graphs hold the parameter kernels' nodes
-    if (rc) return rc;
-    params_free(s);
-    return RB_OK;
-}
-int rb_params_ptr(rb_sim *s, float **d_params, uint32_t **d_draws) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->params) return fail(RB_EINVAL, "per-env parameters are not enabled (rb_params_enable)");
-    if (d_params) *d_params = s->d_params;
-    if (d_draws) *d_draws = s->d_param_draws;
-    return RB_OK;
-}
-int rb_params_set_ranges(rb_sim *s, const float *lo, const float *hi, int resample_on_reset) {
-    if (check(s) || !lo || !hi) return fail(RB_EINVAL, "null argument");
-    if (!s->params) return fail(RB_EINVAL, "per-env parameters are not enabled (rb_params_enable)");
-    const int nt = s->n_t, P = s->n_params;
-    for (int p = 0; p < P; ++p) {
-        const std::string at = "parameter " + std::to_string(p) + ": ";
-        if (!std::isfinite(lo[p]) || !std::isfinite(hi[p])) return fail(RB_EINVAL, at + "range bounds must be finite");
-        if (lo[p] > hi[p]) return fail(RB_EINVAL, at + "lo > hi");
-        if (p == 2 * nt && !(lo[p] > 0.0f)) return fail(RB_EINVAL, at + "mass_scale must stay > 0");
-        if ((p < nt || p > 2 * nt) && lo[p] < 0.0f) return fail(RB_EINVAL, at + "force_scale and damping_scale must stay >= 0");
-    }
-    RB_HIP(hipSetDevice(s->device));
-    int rc = drain(s);                       // (a kernel in flight may be reading the ranges)
-    if (rc) return rc;
-    s->param_ranges.assign(lo, lo + P);
-    s->param_ranges.insert(s->param_ranges.end(), hi, hi + P);
-    RB_HIP(hipMemcpyAsync(s->d_param_ranges, s->param_ranges.data(), sizeof(float) * 2 * size_t(P), hipMemcpyHostToDevice, s->stream));
-    RB_HIP(hipStreamSynchronize(s->stream));
-    s->param_resample = resample_on_reset != 0;
-    return RB_OK;
-}
-int rb_params_sample_dev(rb_sim *s, const uint8_t *d_mask) {
-    if (check(s)) return RB_EINVAL;
-    if (!s->params) return fail(RB_EINVAL, "per-env parameters are not enabled (rb_params_enable)");
-    RB_HIP(hipSetDevice(s->device));
-    hipLaunchKernelGGL(rbp::params_sample, dim3(blocks_for(s->n, 256)), dim3(256), 0, s->stream, s->d_params, s->d_param_draws, s->d_param_ranges,
-                       d_mask, s->n_params, s->n, s->seed, uint64_t(s->env0));
-    RB_HIP(hipGetLastError());
     return RB_OK;
 }
 
