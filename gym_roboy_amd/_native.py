@@ -96,6 +96,13 @@ class EnvIoConfig(ctypes.Structure):
                 ("delay_lo", ctypes.c_int32), ("delay_hi", ctypes.c_int32), ("resample_on_reset", ctypes.c_int32), ("_pad", ctypes.c_int32)]
 
 
+class EnvShapingConfig(ctypes.Structure):
+    """rb_env_shaping_config: the weights of the reward-shaping terms around the fused env step"""
+    _fields_ = [("action_rate", ctypes.c_float), ("tension", ctypes.c_float), ("activation", ctypes.c_float), ("_pad", ctypes.c_float)]
+
+
+REWARD_SHAPING_TERMS = ("action_rate", "tension", "activation")      # RoboyVecEnv(reward_shaping=...): the keys, in the record's order
+
 _vp = ctypes.c_void_p
 _fp = ctypes.POINTER(ctypes.c_float)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -180,6 +187,9 @@ SIGNATURES = {
     "rb_env_goal_row_stats_read": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "rb_env_goal_row_stats_set": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_uint64)]),
     "rb_env_goal_pool_permute": (ctypes.c_int, [_sim, _u32p]),
+    "rb_env_shaping_configure": (ctypes.c_int, [_sim, ctypes.POINTER(EnvShapingConfig)]),
+    "rb_env_shaping_cost_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp)]),
+    "rb_env_shaping_stats": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

@@ -1,7 +1,7 @@
 // env_host.hpp - the fused env layer and its options on the host.
 // Part of roboy_sim.hip (included there once, at file scope, behind the dispatch table; not a stand-alone header): everything
 // RoboyEnv.step's layer (rb_env_*) and its options - per-env parameters, tendon channels, io and the action ring, action rows,
-// episode-end codes, critic rows, the goal pool with its curriculum and row counts - do outside a kernel.  Each option is ONE record in
+// episode-end codes, critic rows, the goal pool with its curriculum and row counts, reward shaping - do outside a kernel.  Each option is ONE record in
 // rb_sim (roboy_sim.hip), is switched by ONE entry point that opens with reconfigure(), and has ONE line in behind_step() /
 // behind_reset() if it launches anything there.  The kernels are in env_*.hpp and roboy_sim.hip; which env-step kernel runs is the
 // dispatch table's business, or extension_launch()'s where extension_serves().  DESIGN.md §6 has the table of options.
@@ -251,12 +251,87 @@ int goal_pool_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const uin
     return RB_OK;
 }
 
+// ---- reward shaping (env_shaping.hpp): one launch in front of an env step and one behind it, over the envs [i0, i0 + cnt) ----
+const char *const SHAPING_TENDON_TERMS = "the reward-shaping tendon terms (rb_env_shaping_configure: tension, activation)";
+int shaping_refuse_delay() {
+    return fail(RB_EUNSUPPORTED, std::string(SHAPING_TENDON_TERMS) + " need the row applied to be the row handed: the handle's action-delay range "
+                                 "reaches above 0 (action_rate alone combines with a delay)");
+}
+// what holds between the option and the others, asked by whichever of two calls comes second (w: the weights asked for or configured)
+int shaping_compatible(rb_sim *s, const rb_env_shaping_config &w, bool params, int delay_hi) {
+    if (w.tension == 0.0f && w.activation == 0.0f) return RB_OK;
+    if (params) return params_refuse(s, SHAPING_TENDON_TERMS);
+    return delay_hi > 0 ? shaping_refuse_delay() : RB_OK;
+}
+// before anything of a step is enqueued: the options as they stand now, and the step's own refusals (a step that is refused
+// behind the cost kernel would have moved the previous rows)
+int shaping_check(rb_sim *s, long i0, long cnt) {
+    RB_RC(shaping_compatible(s, s->shaping.cfg, s->par.on, s->io.on ? s->io.cfg.delay_hi : 0));
+    if (extension_serves(s, ENTRY_ENV)) return RB_OK;
+    std::string why;
+    const Row *r = row_for(s, ENTRY_ENV, true, &why);
+    if (!r) return fail(RB_EUNSUPPORTED, why);
+    if (!r->ranges && !(i0 == 0 && cnt == s->n)) return fail(RB_EUNSUPPORTED, "this kernel form steps whole batches only (rb_range_capable)");
+    return RB_OK;
+}
+size_t shaping_tree_lds(const rb_sim *s, int waves) {
+    return rbt::tree_lds_bytes(s->tree_host, waves) + sizeof(float) * size_t(waves) * 3 * rbt::TREE_E * size_t(s->n_t);
+}
+int shaping_cost_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float *d_act) {
+    if (cnt <= 0) return RB_OK;
+    const OptShaping &o = s->shaping;
+    rbs::CostArgs a;
+    a.q = s->d_q; a.qd = s->d_qd; a.act = d_act; a.step_num = s->d_step_num; a.prev = o.d_prev; a.cost = o.d_cost;
+    a.w_rate = o.cfg.action_rate; a.w_tension = o.cfg.tension; a.w_act = o.cfg.activation;
+    a.slope = s->env.slope; a.act_hi = s->env.act_hi;
+    a.n = s->n; a.i0 = i0; a.i1 = i0 + cnt;
+    constexpr int BLOCK = 256;
+    if (s->tree) {
+        const int wv = o.tree_waves;
+        const long per_block = long(wv) * rbt::TREE_E;
+        const dim3 grid(unsigned((cnt + per_block - 1) / per_block)), block(64 * wv);
+        if (s->tree_host.dev.single_pass)
+            hipLaunchKernelGGL((rbt::tree_shaping_cost<rbt::TREE_E, true>), grid, block, shaping_tree_lds(s, wv), stream, s->tree_host.dev, s->d_ts_lconst, a);
+        else
+            hipLaunchKernelGGL((rbt::tree_shaping_cost<rbt::TREE_E, false>), grid, block, shaping_tree_lds(s, wv), stream, s->tree_host.dev, s->d_ts_lconst, a);
+    } else if (s->ntx) {
+        hipLaunchKernelGGL(rbs::msj_shaping_cost_nt<BLOCK>, dim3(blocks_for(cnt, BLOCK)), dim3(BLOCK), 0, stream, s->cx, s->ts_units, a);
+    } else {
+        rbts::Units<NT8> u8;
+        for (int k = 0; k < NT8; ++k) u8.u[k] = s->ts_units.u[k];
+        hipLaunchKernelGGL(rbs::msj_shaping_cost8<BLOCK>, dim3(blocks_for(cnt, BLOCK)), dim3(BLOCK), 0, stream, s->c8, u8, a);
+    }
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
+int shaping_apply_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, float *d_reward, const uint32_t *d_done) {
+    if (cnt <= 0) return RB_OK;
+    const OptShaping &o = s->shaping;
+    const rbs::ApplyArgs a{d_reward, o.d_cost, d_done, o.d_run, o.d_sums, o.d_cnt, s->n, i0, i0 + cnt};
+    hipLaunchKernelGGL(rbs::shaping_apply, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, a);
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
+// the sums and counts to zero (rb_env_configure, rb_env_shaping_stats with reset); the running episode costs and the cost plane to
+// zero (a reset: the episodes it abandons are not counted)
+int shaping_clear_sums(rb_sim *s) {
+    RB_HIP(hipMemsetAsync(s->shaping.d_sums, 0, sizeof(double) * 2 * size_t(s->n), s->stream));
+    RB_HIP(hipMemsetAsync(s->shaping.d_cnt, 0, sizeof(uint32_t) * 2 * size_t(s->n), s->stream));
+    return RB_OK;
+}
+int shaping_restart(rb_sim *s) {
+    RB_HIP(hipMemsetAsync(s->shaping.d_run, 0, sizeof(double) * size_t(s->n), s->stream));
+    RB_HIP(hipMemsetAsync(s->shaping.d_cost, 0, sizeof(float) * size_t(s->n), s->stream));
+    return RB_OK;
+}
+
 // ---- the episode counters and the planes that mirror them ----
 // d_ep_sum, d_ep_cnt (episodes, lengths, goals reached), d_infeas_n and env_steps count since the last clear; d_done_seen (episode-end
 // codes) and d_goal_seen (curriculum) hold each env's goals-reached counter as of its last episode end, so they follow it.  A new
 // plane that mirrors a counter is added HERE.  Everything is enqueued on the handle's stream.
 //   COUNTERS_CONFIGURE (rb_env_configure) and COUNTERS_CLEAR (rb_env_stats*(reset)): counters and mirrors to zero; the latter on a
-//     handle without the env layer has only d_infeas_n and env_steps to clear
+//     handle without the env layer has only d_infeas_n and env_steps to clear.  The shaping sums are cleared by the former only:
+//     rb_env_stats(reset) leaves them to rb_env_shaping_stats(reset)
 //   COUNTERS_REBASE (rb_env_reset_dev): a reset is no episode end - the counters stand, d_done_seen is set to them and no code is
 //     reported; d_goal_seen is re-based by the curriculum's own kernel, which behind_reset launches
 enum CounterSite { COUNTERS_CONFIGURE, COUNTERS_CLEAR, COUNTERS_REBASE };
@@ -277,12 +352,15 @@ int episode_counters(rb_sim *s, CounterSite site) {
     }
     RB_HIP(hipMemsetAsync(s->d_infeas_n, 0, sizeof(uint32_t) * n, s->stream));
     s->env_steps = 0.0;
+    if (site == COUNTERS_CONFIGURE && s->shaping.on) RB_RC(shaping_clear_sums(s));
     return RB_OK;
 }
 
 // ---- what runs behind an env step and behind a reset ----
 // ONE stream each, so every kernel sees what those in front of it wrote.  The order, and why:
-//   step:   the env-step kernel (dispatch)
+//   step:   the shaping cost of (s_t, a_t) - IN FRONT of the env-step kernel (env_step_launch), which overwrites the state it reads
+//           the env-step kernel (dispatch)
+//           0. shaping apply - reward -= cost, the cost statistics; reads the done words as flags, like 1.
 //           1. goal pool / curriculum / row counts - the done envs' new goal becomes a pool row, IN FRONT of everything that reads the goal
 //           2. critic rows - from the planes as 1. left them
 //           3. episode-end codes - last: it turns the range's done words, which 1. reads as flags, into codes
@@ -293,8 +371,10 @@ int episode_counters(rb_sim *s, CounterSite site) {
 //           4. zero action blocks - nothing has been handed yet
 //           5. goal pool / curriculum - every env's goal becomes the pool row of the draw the reset kernel made, in the rows too
 //           6. critic rows - behind every kernel that wrote the rows above
+//           7. shaping - the running episode costs and the cost plane to zero (step_num is 1: the rate term restarts by itself)
 // A new option that launches behind either adds its line here.
-int behind_step(rb_sim *s, long i0, long cnt, hipStream_t stream, float *d_obs, uint32_t *d_done, float *d_cobs) {
+int behind_step(rb_sim *s, long i0, long cnt, hipStream_t stream, float *d_obs, float *d_reward, uint32_t *d_done, float *d_cobs) {
+    if (s->shaping.on) RB_RC(shaping_apply_launch(s, i0, cnt, stream, d_reward, d_done));
     if (s->goals.d_pool) RB_RC(goal_pool_launch(s, i0, cnt, stream, d_done, d_obs));
     if (s->critic.mask) RB_RC(critic_launch(s, i0, cnt, stream, d_obs, d_cobs ? d_cobs : s->critic.d_rows));
     if (s->done.on) {
@@ -331,6 +411,7 @@ int behind_reset(rb_sim *s, float *d_obs) {
         RB_RC(critic_check(s));
         RB_RC(critic_launch(s, 0, s->n, s->stream, d_obs, s->critic.d_rows));
     }
+    if (s->shaping.on) RB_RC(shaping_restart(s));
     return RB_OK;
 }
 
@@ -339,10 +420,12 @@ int behind_reset(rb_sim *s, float *d_obs) {
 // d_cobs: where the range's critic rows go while rb_env_critic_obs_configure holds (null: the handle's plane)
 int env_step_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done, float *d_cobs) {
     if (s->critic.mask) RB_RC(critic_check(s));          // (before anything is enqueued)
+    if (s->shaping.on) RB_RC(shaping_check(s, i0, cnt));
     Launch L;
     L.i0 = i0; L.cnt = cnt; L.stream = stream; L.act = d_act; L.obs = d_obs; L.reward = d_reward; L.done = d_done;
+    if (s->shaping.on) RB_RC(shaping_cost_launch(s, i0, cnt, stream, d_act));
     RB_RC(dispatch(s, ENTRY_ENV, L));
-    return behind_step(s, i0, cnt, stream, d_obs, d_done, d_cobs);
+    return behind_step(s, i0, cnt, stream, d_obs, d_reward, d_done, d_cobs);
 }
 // The one function behind the four rb_env_step*_dev exports.  range: envs [first, first + count) on hip_stream (null: the handle's) -
 // the call's stream is visible to the build guards for its duration (a first call captured on the caller's stream defers the run-time
@@ -516,6 +599,7 @@ int rb_env_io_configure(rb_sim *s, const rb_env_io_config *cfg) {
             return fail(RB_EINVAL, "action delay: 0 <= delay_lo <= delay_hi <= RB_IO_MAX_DELAY");
         if (s->tree)
             return fail(RB_EUNSUPPORTED, "action latency and sensor noise are built for ball-joint robots (1-16 tendons); joint trees have none");
+        if (s->shaping.on) RB_RC(shaping_compatible(s, s->shaping.cfg, false, cfg->delay_hi));
         return RB_OK;
     }));
     s->io.release();
@@ -865,12 +949,72 @@ int rb_env_goal_pool_permute(rb_sim *s, const uint32_t *order) {
     return done(hipSuccess, "");
 }
 
+// ---- reward shaping around the fused env step (env_shaping.hpp) ----
+int rb_env_shaping_configure(rb_sim *s, const rb_env_shaping_config *cfg) {
+    rb_env_shaping_config w = {};
+    if (cfg) { w.action_rate = cfg->action_rate; w.tension = cfg->tension; w.activation = cfg->activation; }
+    const bool off = w.action_rate == 0.0f && w.tension == 0.0f && w.activation == 0.0f;      // (also -0.0)
+    int waves = 1;
+    // nothing in flight may still use the planes, and a captured graph holds the launches of the handle as it was
+    RB_RC(reconfigure(s, NEEDS_ENV | DROP_GRAPHS, [&]() -> int {
+        for (float v : {w.action_rate, w.tension, w.activation})
+            if (!std::isfinite(v) || v < 0.0f) return fail(RB_EINVAL, "reward shaping: the weights must be finite and >= 0");
+        if (off) return RB_OK;
+        RB_RC(shaping_compatible(s, w, s->par.on, s->io.on ? s->io.cfg.delay_hi : 0));
+        if (s->tree) {                          // the cost kernel's workgroup: the readout's, fewer waves where the terms do not fit beside them
+            waves = s->tree_waves;
+            while (waves > 0 && shaping_tree_lds(s, waves) > 160 * 1024) --waves;
+            if (!waves) return fail(RB_EUNSUPPORTED, "reward shaping: the robot's working set and the per-tendon terms exceed the 160 KiB LDS of a CU");
+        }
+        return RB_OK;
+    }));
+    OptShaping &o = s->shaping;
+    if (off) { o.release(); return RB_OK; }
+    const size_t n = size_t(s->n);
+    if (!o.d_prev) {
+        auto alloc = [](auto **d, size_t bytes) { return dev_alloc(d, bytes, "hipMalloc (reward shaping): "); };
+        int rc = alloc(&o.d_prev, sizeof(float) * n * size_t(s->n_t));
+        if (rc == RB_OK) rc = alloc(&o.d_cost, sizeof(float) * n);
+        if (rc == RB_OK) rc = alloc(&o.d_run, sizeof(double) * n);
+        if (rc == RB_OK) rc = alloc(&o.d_sums, sizeof(double) * 2 * n);
+        if (rc == RB_OK) rc = alloc(&o.d_cnt, sizeof(uint32_t) * 2 * n);
+        if (rc == RB_OK) rc = alloc(&o.d_red, sizeof(double) * 4 * (rbs::REDUCE_BLOCKS + 1));
+        if (rc) { o.release(); return rc; }
+    }
+    o.cfg = w; o.tree_waves = waves; o.on = true;
+    // the episodes as they stand: no cost so far, and a previous row of zeros where an episode is already under way
+    RB_HIP(hipMemsetAsync(o.d_prev, 0, sizeof(float) * n * size_t(s->n_t), s->stream));
+    RB_RC(shaping_restart(s));
+    return shaping_clear_sums(s);
+}
+int rb_env_shaping_cost_ptr(rb_sim *s, float **d_cost) {
+    if (check(s) || !d_cost) return fail(RB_EINVAL, "null argument");
+    if (s->shaping.need()) return RB_EINVAL;
+    *d_cost = s->shaping.d_cost;
+    return RB_OK;
+}
+int rb_env_shaping_stats(rb_sim *s, double *out, int reset) {
+    // every cost enqueued so far is in.  The graphs stay: a read changes nothing they hold, a clear writes the planes in place
+    RB_RC(reconfigure(s, KEEP_GRAPHS, [&]() -> int { return s->shaping.need() ? RB_EINVAL : out ? RB_OK : fail(RB_EINVAL, "null argument"); }));
+    const OptShaping &o = s->shaping;
+    unsigned g = blocks_for(s->n, 256);
+    if (g > unsigned(rbs::REDUCE_BLOCKS)) g = rbs::REDUCE_BLOCKS;
+    double *result = o.d_red + 4 * rbs::REDUCE_BLOCKS;
+    hipLaunchKernelGGL(rbs::shaping_reduce, dim3(g), dim3(256), 0, s->stream, o.d_sums, o.d_cnt, o.d_red, long(s->n));
+    hipLaunchKernelGGL(rbs::shaping_reduce_final, dim3(1), dim3(256), 0, s->stream, o.d_red, int(g), result);
+    RB_HIP(hipGetLastError());
+    RB_HIP(hipMemcpyAsync(out, result, sizeof(double) * 4, hipMemcpyDeviceToHost, s->stream));
+    RB_HIP(hipStreamSynchronize(s->stream));
+    return reset ? shaping_clear_sums(s) : RB_OK;
+}
+
 // ---- per-env physical parameters (env_params.hpp) ----
 int rb_params_enable(rb_sim *s, int32_t *n_params) {
     // (no env layer needed: the plain step has a parameter form.)  Nothing in flight may read the planes while they are reset, and
     // captured graphs hold the nominal kernels' nodes
     RB_RC(reconfigure(s, DROP_GRAPHS, [&]() -> int {
-        return s->tree ? fail(RB_EUNSUPPORTED, "per-env parameters are built for ball-joint robots (the closed-form kernels); joint trees have none") : RB_OK;
+        if (s->tree) return fail(RB_EUNSUPPORTED, "per-env parameters are built for ball-joint robots (the closed-form kernels); joint trees have none");
+        return s->shaping.on ? shaping_compatible(s, s->shaping.cfg, true, 0) : RB_OK;
     }));
     OptParams &p = s->par;
     const int nt = s->n_t, P = rbp::n_params(nt);

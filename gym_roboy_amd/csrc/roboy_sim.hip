@@ -54,6 +54,7 @@
 #include "env_hist.hpp"               // the last K commanded actions as observation columns (rb_env_action_obs_*)
 #include "env_critic.hpp"             // privileged critic rows behind the fused env step (rb_env_critic_obs_*)
 #include "env_goal.hpp"               // goals drawn from a pool of poses (rb_env_goal_pool_*)
+#include "env_shaping.hpp"            // action-rate and effort reward terms around the fused env step (rb_env_shaping_*)
 
 namespace {
 
@@ -518,6 +519,22 @@ struct OptGoals {
     int need_curriculum() const { return L ? RB_OK : fail(RB_EINVAL, "no goal curriculum is configured (rb_env_goal_curriculum_configure)"); }
     int need_row_stats() const { return d_row_stats ? RB_OK : fail(RB_EINVAL, "goal row stats are not enabled (rb_env_goal_row_stats_enable)"); }
 };
+// Reward shaping (env_shaping.hpp; rb_env_shaping_*): while on, every env-step launch has shaping_cost in front of it and
+// shaping_apply behind it, over its range.  Planes: the previous clamped action rows [n_envs][n_t], the last step's costs [n_envs],
+// the running episode costs [n_envs] (fp64), sums [2][n_envs] (finished episodes' costs, all step costs; fp64) and counts [2][n_envs]
+// (finished episodes, steps); d_red: the reduction's block partials [REDUCE_BLOCKS][4], then its result [4]
+struct OptShaping {
+    bool on = false; rb_env_shaping_config cfg = {};
+    float *d_prev = nullptr, *d_cost = nullptr;
+    double *d_run = nullptr, *d_sums = nullptr, *d_red = nullptr; uint32_t *d_cnt = nullptr;
+    int tree_waves = 1;                  // joint trees: waves per workgroup of the cost kernel (its LDS holds the per-tendon terms too)
+    bool tendons() const { return on && (cfg.tension != 0.0f || cfg.activation != 0.0f); }
+    void release() {
+        (void)hipFree(d_prev); (void)hipFree(d_cost); (void)hipFree(d_run); (void)hipFree(d_sums); (void)hipFree(d_red); (void)hipFree(d_cnt);
+        *this = OptShaping{};
+    }
+    int need() const { return on ? RB_OK : fail(RB_EINVAL, "reward shaping is not configured (rb_env_shaping_configure)"); }
+};
 
 }  // namespace
 
@@ -610,6 +627,7 @@ struct rb_sim {
     float *d_ts_lconst = nullptr, *d_ts_out = nullptr;
     bool ts_attr_set = false;
     OptParams par; OptChannels chan; OptIo io; OptActionRows hist; OptDoneKind done; OptCritic critic; OptGoals goals;      // the env layer's options (above)
+    OptShaping shaping;
     int obs_dim() const { return 3 * n_q + rbo::n_channels(chan.mask) * n_t + hist.rows * n_t; }
     int critic_width() const { return rbc::row_dim(critic.mask, n_q, par.on ? par.n : 0, hist.rows * n_t); }
 };
@@ -996,6 +1014,7 @@ int rb_create(const rb_robot_desc *robot, int64_t n_envs, int integrator, double
         RB_TREE_ATTR((rbt::tree_env_step_aba<0, rbt::TREE_E, true>)); RB_TREE_ATTR((rbt::tree_env_step_aba<1, rbt::TREE_E, true>));
         RB_TREE_ATTR((rbt::tree_env_step_aba<0, rbt::TREE_E, false>)); RB_TREE_ATTR((rbt::tree_env_step_aba<1, rbt::TREE_E, false>));
         RB_TREE_ATTR((rbt::tree_tendon_state<rbt::TREE_E, true>)); RB_TREE_ATTR((rbt::tree_tendon_state<rbt::TREE_E, false>));
+        RB_TREE_ATTR((rbt::tree_shaping_cost<rbt::TREE_E, true>)); RB_TREE_ATTR((rbt::tree_shaping_cost<rbt::TREE_E, false>));
         RB_TRY(hipMalloc(&s->d_ts_lconst, sizeof(float) * s->ts_tree_lconst.size()));
         RB_TRY(hipMemcpy(s->d_ts_lconst, s->ts_tree_lconst.data(), sizeof(float) * s->ts_tree_lconst.size(), hipMemcpyHostToDevice));
         if (s->form(RB_KERNEL_ENV_PER_LANE_SPLIT).baked) {
@@ -1031,7 +1050,7 @@ void rb_destroy(rb_sim *s) {
     (void)hipFree(s->d_state_rows); (void)hipHostFree(s->h_state_rows);
     (void)hipFree(s->d_goal); (void)hipFree(s->d_ep_ret); (void)hipFree(s->d_ep_sum); (void)hipFree(s->d_ep_cnt);
     (void)hipFree(s->d_step_num); (void)hipFree(s->d_infeas_n); (void)hipFree(s->d_stats);
-    s->par.release(); s->chan.release(); s->io.release(); s->hist.release(); s->done.release(); s->critic.release(); s->goals.release();
+    s->par.release(); s->chan.release(); s->io.release(); s->hist.release(); s->done.release(); s->critic.release(); s->goals.release(); s->shaping.release();
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1435,6 +1454,9 @@ int rb_rollout_fused_dev(rb_sim *s, const float *d_ring, int ring, int n_steps, 
     if (reinterpret_cast<uintptr_t>(d_ring) % 16) return fail(RB_EINVAL, "action ring must be 16-byte aligned");
     if (s->tree || s->ntx) return fail(RB_EUNSUPPORTED, "fused rollout is built for 8-tendon ball-joint robots");
     if (s->par.on) return params_refuse(s, "the fused rollout (rb_rollout_fused_dev)");
+    if (s->shaping.on)
+        return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) forms its rewards inside one kernel and cannot apply reward shaping "
+                                     "(rb_env_shaping_configure(sim, NULL) first)");
     if (s->goals.d_pool)
         return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) redraws goals inside one kernel and cannot draw them from a goal pool");
     if (n_steps == 0) return RB_OK;

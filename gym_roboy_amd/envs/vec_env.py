@@ -135,6 +135,39 @@ def critic_obs_spec(critic_obs, n_q: int, n_t: int, randomization: bool = False,
     return names, sum(1 << nat.CRITIC_OBS_BLOCKS.index(c) for c in names), dim
 
 
+def reward_shaping_weights(reward_shaping):
+    """``{"action_rate": 0.05, "tension": 0.01}`` (or None) -> the dict with all three keys of ``_native.REWARD_SHAPING_TERMS`` as
+    floats, 0 where not given - or None where every weight is 0 (the option is off).  ``ValueError`` for an unknown key and for a
+    weight that is negative or not finite."""
+    if reward_shaping is None:
+        return None
+    out = dict.fromkeys(nat.REWARD_SHAPING_TERMS, 0.0)
+    for k, v in dict(reward_shaping).items():
+        if k not in nat.REWARD_SHAPING_TERMS:
+            raise ValueError("reward_shaping: unknown term %r (takes %s)" % (k, nat.REWARD_SHAPING_TERMS))
+        if isinstance(v, bool) or not np.isfinite(v) or v < 0:
+            raise ValueError("reward_shaping[%r] must be finite and >= 0, got %r" % (k, v))
+        out[k] = float(np.float32(v))
+    return out if any(out.values()) else None
+
+
+def parse_reward_shaping(text):
+    """The command line's ``action_rate=0.05,tension=0.01`` -> the dict ``reward_shaping_weights`` takes ('' -> None)."""
+    items = [item for item in (text or "").split(",") if item]
+    if not items:
+        return None
+    out = {}
+    for item in items:
+        if "=" not in item:
+            raise ValueError("reward shaping: expected TERM=WEIGHT, got %r" % (item,))
+        k, v = item.split("=", 1)
+        if k in out:
+            raise ValueError("reward shaping: %r given twice" % (k,))
+        out[k] = float(v)
+    reward_shaping_weights(out)
+    return out
+
+
 class RoboyVecEnv:
 
     def __init__(self, robot: RoboyRobot, num_envs: int, seed: int = 0,
@@ -144,7 +177,7 @@ class RoboyVecEnv:
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
                  randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None,
                  report_truncation: bool = False, action_obs=None, critic_obs=None, goals=None, goal_curriculum=None,
-                 goal_row_stats: bool = False):
+                 goal_row_stats: bool = False, reward_shaping=None):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
@@ -190,13 +223,22 @@ class RoboyVecEnv:
         needs ``goal_curriculum`` - ``goal_curriculum=1`` counts without a staircase).  ``goal_row_stats()`` reads the counts,
         ``set_goal_row_stats`` writes them, ``permute_goal_pool(order)`` re-orders the live pool (any env with ``goals``) and
         ``reorder_goals_by_reach_rate()`` re-orders it by the measured reach rate.  False: the env launches exactly what it launched
-        before."""
+        before.
+        ``reward_shaping``: ``{"action_rate": w_r, "tension": w_f, "activation": w_a}`` (finite, >= 0, a missing key is 0) - the reward
+        becomes ``r_step - (w_r c_rate + w_f c_tension + w_a c_activation)`` with the costs of the state before the step and the
+        action handed to it: the mean squared change of the clamped action against the same episode's previous step (0 on an
+        episode's first step), the mean squared tendon force over its maximum, the mean squared activation (every
+        robot, every kernel form).  Observations, dones, the state and ``stats()`` are those of an env without the option.
+        ``shaping_cost()`` returns the last step's costs, ``shaping_stats()`` their sums.  ``tension`` and ``activation`` do not
+        combine with ``randomization`` nor with an ``action_delay`` above 0; ``action_rate`` does.  None or all zeros: the env
+        launches exactly what it launched before."""
         desc = robot.get_description()
         crit_names, crit_mask, crit_dim = critic_obs_spec(critic_obs, desc.n_q, desc.n_t, randomization is not None, action_delay, action_obs)
         obs_names = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
         sig = sensor_noise_sigmas(sensor_noise, obs_names)               # (bad options: before anything is allocated)
         d_lo, d_hi, ranged = action_delay_range(action_delay)
         n_action_rows = action_obs_rows(action_obs)
+        shaping = reward_shaping_weights(reward_shaping)
         curriculum = envgoals.goal_curriculum_spec(goal_curriculum)
         if curriculum is not None:
             if goals is None:
@@ -330,6 +372,13 @@ class RoboyVecEnv:
             nat.check(self.sim._lib.rb_env_critic_obs_dim(self.sim.handle, ctypes.byref(dim)))
             self.critic_obs_dim = int(dim.value)
             assert self.critic_obs_dim == crit_dim
+        self.reward_shaping = None
+        if shaping is not None:
+            # after the options it has to agree with, before anything is captured into a graph: every env-step launch gets the cost
+            # kernel in front of it and the kernel that applies the cost behind it
+            cfg = nat.EnvShapingConfig(shaping["action_rate"], shaping["tension"], shaping["activation"], 0.0)
+            self._or_close(lambda: nat.check(self.sim._lib.rb_env_shaping_configure(self.sim.handle, ctypes.byref(cfg))))
+            self.reward_shaping = shaping
 
     def _or_close(self, configure):
         """an option the library refuses (a joint tree asked for a ball-joint option) must not leave the simulation's handle behind"""
@@ -610,6 +659,34 @@ class RoboyVecEnv:
         self.sim.synchronize()
         return self.sim.download(rows.value, (self.num_envs, self.critic_obs_dim))
 
+    # -- reward shaping (rb_env_shaping_*) -----------------
+    def _shaping_plane(self):
+        if self.reward_shaping is None:
+            raise RuntimeError("this RoboyVecEnv has no reward shaping (reward_shaping=None)")
+        ptr = ctypes.c_void_p()
+        nat.check(self.sim._lib.rb_env_shaping_cost_ptr(self.sim.handle, ctypes.byref(ptr)))
+        return ptr.value
+
+    def shaping_cost(self):
+        """``[N]``: the cost the last step subtracted from every env's reward (zeros behind a reset).  numpy after a numpy step, read
+        from the handle's plane after a synchronisation; after a torch step a CUDA tensor VIEW of that plane - the next step
+        overwrites it, clone it to keep it.  Needs ``reward_shaping``."""
+        d_cost = self._shaping_plane()
+        if _is_cuda_tensor(self._last_actions):
+            return _device_view_f32(d_cost, self.num_envs, self._last_actions.device)
+        self.sim.synchronize()
+        return self.sim.download(d_cost, (self.num_envs,))
+
+    def shaping_stats(self, reset: bool = False) -> dict:
+        """``{"sum_episode_cost", "n_episodes", "sum_step_cost", "n_steps"}``: the summed shaping costs of the episodes that ended and
+        their number, the sum of all step costs and the number of env steps, since these sums were last cleared (``reset=True``
+        clears them behind the read; ``stats(reset=True)`` does not).  Counted on the device, so steps replayed from a captured
+        graph are in.  Needs ``reward_shaping``."""
+        self._shaping_plane()
+        out = (ctypes.c_double * 4)()
+        nat.check(self.sim._lib.rb_env_shaping_stats(self.sim.handle, out, int(bool(reset))))
+        return dict(zip(("sum_episode_cost", "n_episodes", "sum_step_cost", "n_steps"), list(out)))
+
     def tendon_state(self, actions=None):
         """Per-tendon state of every env at its current state (``HipBatchSimulation.tendon_state``), the set-points formed
         from ``actions`` ``[N, n_t]`` in [-1, 1] as ``step`` forms them (``RB_SP_ENV``): ``{'length', 'rate', 'activation',
@@ -676,6 +753,9 @@ class RoboyVecEnv:
             self._stream = stream_ptr
 
     def stats(self, reset: bool = False) -> dict:
+        """The task's statistics.  With ``reward_shaping`` they are untouched: returns and ``sum_reward`` are those of the step's own
+        reward, without the shaping cost, so the weights change them only through the policy and runs with different weights stay
+        comparable (the costs: ``shaping_stats()``)."""
         out = (ctypes.c_double * 8)()
         nat.check(self.sim._lib.rb_env_stats(self.sim.handle, out, int(reset)))
         keys = ("sum_return", "sum_return_sq", "n_episodes", "sum_length", "n_goal_reached",
@@ -720,6 +800,15 @@ class RoboyVecEnv:
 
     def close(self):
         self.sim.close()
+
+
+def _device_view_f32(ptr: int, n: int, device):
+    """a float32 CUDA tensor [n] over device memory this library owns (no copy; the memory outlives the tensor's use by contract)"""
+    import torch
+
+    class _Plane:
+        __cuda_array_interface__ = {"shape": (int(n),), "typestr": "<f4", "data": (int(ptr), False), "version": 2, "strides": None}
+    return torch.as_tensor(_Plane(), device=device)
 
 
 def _is_cuda_tensor(x):

@@ -1675,6 +1675,9 @@ class PPO:
         if getattr(self.env, "goal_row_stats_enabled", False):      # (an env without the counts writes the checkpoint it always wrote)
             counts = self.env.goal_row_stats()       # per row of ck["goals"]["q"], which is the pool in its current order
             ck["goal_row_stats"] = {k: torch.from_numpy(counts[k].astype("int64")) for k in ("attempts", "reached")}
+        shaping = getattr(self.env, "reward_shaping", None)
+        if shaping is not None:                      # (an env without reward shaping writes the checkpoint it always wrote)
+            ck["reward_shaping"] = {k: float(v) for k, v in shaping.items()}
         if self.symmetry is not None:                # (an agent without the option writes the checkpoint it always wrote)
             ck["symmetry"] = self.symmetry
             if self.symmetry == "loss":
@@ -1703,6 +1706,11 @@ class PPO:
         if self.asymmetric_critic and (ck["critic_obs"] != _critic_obs_of(self.env) or int(ck["critic_obs_dim"]) != self.cobs_dim):
             raise ValueError("the checkpoint's critic was trained on the rows %r (%d columns), this env writes %r (%d; RoboyVecEnv's "
                              "critic_obs)" % (ck["critic_obs"], int(ck["critic_obs_dim"]), _critic_obs_of(self.env), self.cobs_dim))
+        if ck.get("reward_shaping") != getattr(self.env, "reward_shaping", None):
+            # the weights shape the reward, not a layout: the env's hold (a run may be resumed under other weights), and says so
+            import warnings
+            warnings.warn("the checkpoint was trained with reward_shaping=%r, this env runs reward_shaping=%r"
+                          % (ck.get("reward_shaping"), getattr(self.env, "reward_shaping", None)))
         # the goal pool the checkpoint was trained on (rows and recipe; None: box goals), for a caller that wants the same goals again:
         # visualize_agent replays with them.  The env keeps its own pool - the policy reads a goal as columns, whichever way it was drawn
         self.checkpoint_goals = ck.get("goals")

@@ -161,6 +161,11 @@ def main(argv=None):
                          "symmetry, and with loss symmetry_loss, the last minibatch's term; recorded in the checkpoint")
     ap.add_argument("--symmetry-coef", type=float, default=1.0, metavar="C",
                     help="the weight of --symmetry loss's term (>= 0, default 1)")
+    ap.add_argument("--reward-shaping", default="", metavar="TERM=WEIGHT,...",
+                    help="regularising reward terms, subtracted from the step's reward on the device: action_rate (mean squared change "
+                         "of the clamped action within an episode), tension (mean squared tendon force over its maximum), activation "
+                         "(mean squared muscle activation), e.g. action_rate=0.05,tension=0.01; the round's statistics then show "
+                         "shaping_cost_per_step, while return and goals reached stay the task's; recorded in the checkpoint")
     args = ap.parse_args(argv)
     sensor_noise = {k: float(v) for k, v in (item.split("=", 1) for item in args.sensor_noise.split(",") if item)}
     action_delay = None
@@ -173,6 +178,8 @@ def main(argv=None):
     goals_m = parse_goals(args.goals)
     goal_curriculum = parse_goal_curriculum(args.goal_levels, args.goal_up, args.goal_down, goals_m)
     by_reach_rate = parse_goal_order(args.goal_order, args.goal_reorder_every, goal_curriculum)
+    from .envs.vec_env import parse_reward_shaping
+    reward_shaping = parse_reward_shaping(args.reward_shaping)
 
     import numpy as np
     import torch
@@ -210,7 +217,8 @@ def main(argv=None):
                       env_id_offset=rank * args.num_envs, tendon_obs=tendon_obs or None, tendon_obs_scale=tendon_obs_scale or None,
                       sensor_noise=sensor_noise or None, action_delay=action_delay,
                       report_truncation=args.bootstrap_timeouts, action_obs=args.action_obs or None,
-                      critic_obs=critic_obs or None, goal_curriculum=goal_curriculum, **({"goal_row_stats": True} if by_reach_rate else {}))
+                      critic_obs=critic_obs or None, goal_curriculum=goal_curriculum, **({"goal_row_stats": True} if by_reach_rate else {}),
+                      **({"reward_shaping": reward_shaping} if reward_shaping else {}))
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,
@@ -239,10 +247,13 @@ def main(argv=None):
             counts = env.goal_row_stats()
             rows = torch.from_numpy(np.concatenate((counts["attempts"], counts["reached"])).astype(np.float64))
             block = torch.cat((block, rows.to(block)))
+        if env.reward_shaping is not None:      # the round's shaping costs ride along at the end: [... | sum of step costs | steps]
+            cost = env.shaping_stats(reset=True)
+            block = torch.cat((block, torch.tensor([cost["sum_step_cost"], cost["n_steps"]], dtype=torch.float64).to(block)))
         allreduce_stats(block, dist)
         row_counts = None
         if by_reach_rate:
-            row_counts = block[n_head:].cpu().numpy().astype(np.uint64).reshape(2, goals_m)
+            row_counts = block[n_head:n_head + 2 * goals_m].cpu().numpy().astype(np.uint64).reshape(2, goals_m)
             if (round_no + 1) % args.goal_reorder_every == 0:      # every rank orders by the same sums: all ranks keep the same pool
                 env.reorder_goals_by_reach_rate(attempts=row_counts[0], reached=row_counts[1])
         if rank == 0:
@@ -256,6 +267,8 @@ def main(argv=None):
                 summary["symmetry_gap_action"] = float("%.3g" % agent.symmetry_gap(agent.last_rollout)["action"])
                 if "symmetry_loss" in last_stats:                     # (symmetry="loss": the term of the round's last minibatch)
                     summary["symmetry_loss"] = float("%.3g" % last_stats["symmetry_loss"])
+            if env.reward_shaping is not None:
+                summary["shaping_cost_per_step"] = float("%.4g" % (float(block[-2]) / max(float(block[-1]), 1.0)))
             print("episode statistics (all ranks):", summary)
     if world > 1:
         dist.destroy_process_group()

@@ -645,6 +645,42 @@ int rb_env_goal_row_stats_read(rb_sim *sim, uint64_t *host /* [2][m] */, int cle
 int rb_env_goal_row_stats_set(rb_sim *sim, const uint64_t *host /* [2][m] */);
 int rb_env_goal_pool_permute(rb_sim *sim, const uint32_t *order /* host, [m] */);
 
+/* ---- reward shaping: an action-rate term and two effort terms around the fused env step ----
+ * Every robot, every kernel form, every env-step entry: no env-step kernel changes; one kernel is launched in front of it and one
+ * behind it, on its stream, over its envs.  With weights w_r = action_rate, w_f = tension, w_a = activation (finite, >= 0), the reward
+ * an env step returns is
+ *     reward[i] = fl32( r_step[i] - cost[i] )                 r_step: the reward of a handle without the option, bit for bit
+ *     cost[i]   = w_r c_rate + w_f c_tension + w_a c_activation
+ * at the state s_t the env is in BEFORE the step and the action row a_t handed to this step (an auto-reset inside the step does not
+ * disturb it):
+ *     c_rate       = mean over tendons of (â_k - p_k)^2: â = clamp(a_t, -1, 1) as the step clamps, p = the clamped row of the same
+ *                    episode's previous step; 0 on an episode's first step (the step entered with step counter 1, which a reset and an
+ *                    auto-reset leave there).  p lives in a plane of its own, [n][n_t].
+ *     c_tension    = mean over tendons of (F_k / F_max,k)^2
+ *     c_activation = mean over tendons of act_k^2       F, act: what rb_tendon_state_dev(RB_SP_ENV) reports for s_t and a_t
+ * Each mean is summed over k ascending in fp32 by one lane: a cost does not depend on the batch size, the launch range or the kernel
+ * form.  Observations, done words, the state, rb_env_stats (which keeps reporting the task's return) and every random draw are those
+ * of a handle without the option.
+ *   configure: needs rb_env_configure.  NULL or all-zero weights: off, the planes are freed, the handle launches exactly what it
+ *        launched before.  Drains the handle's streams and drops its graphs; call it before a caller captures env steps.  Zeroes the
+ *        statistics below.  RB_EINVAL for a negative or non-finite weight; RB_EUNSUPPORTED for tension or activation while per-env
+ *        parameters are enabled (the readout has no parameter form) or while the action-delay range reaches above 0 (the row applied
+ *        is then not the row handed) - in either order of the two calls; action_rate alone combines with both.  A refusal leaves the
+ *        handle as it was.  rb_rollout_fused_dev is RB_EUNSUPPORTED while the option is on.
+ *   cost_ptr: the device plane [n] of the last step's costs.
+ *   stats: {sum of finished episodes' costs, finished episodes, sum of all step costs, steps} since these sums were last cleared
+ *        (reset != 0 clears them behind the read; rb_env_configure clears them; rb_env_stats(reset) does not).  fp64, a fixed order
+ *        of additions: bit-reproducible.  Synchronous.  rb_env_reset_dev zeroes the running episode costs and the cost plane; the
+ *        episodes it abandons are not counted.
+ * RB_ABI_VERSION is still 6 (nothing that existed changed): look rb_env_shaping_configure up before relying on it. */
+typedef struct rb_env_shaping_config {
+    float action_rate, tension, activation;
+    float _pad;
+} rb_env_shaping_config;
+int rb_env_shaping_configure(rb_sim *sim, const rb_env_shaping_config *cfg);
+int rb_env_shaping_cost_ptr(rb_sim *sim, float **d_cost /* [n] */);
+int rb_env_shaping_stats(rb_sim *sim, double out[4], int reset);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
