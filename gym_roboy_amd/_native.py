@@ -101,6 +101,11 @@ class EnvShapingConfig(ctypes.Structure):
     _fields_ = [("action_rate", ctypes.c_float), ("tension", ctypes.c_float), ("activation", ctypes.c_float), ("_pad", ctypes.c_float)]
 
 
+class EnvPushConfig(ctypes.Structure):
+    """rb_env_push_config: the threshold (P(push per env step) = threshold / 2^24) and the per-joint sigmas of the random pushes"""
+    _fields_ = [("threshold", ctypes.c_uint32), ("_pad", ctypes.c_uint32), ("sigma", ctypes.c_float * 32)]
+
+
 REWARD_SHAPING_TERMS = ("action_rate", "tension", "activation")      # RoboyVecEnv(reward_shaping=...): the keys, in the record's order
 
 _vp = ctypes.c_void_p
@@ -190,6 +195,9 @@ SIGNATURES = {
     "rb_env_shaping_configure": (ctypes.c_int, [_sim, ctypes.POINTER(EnvShapingConfig)]),
     "rb_env_shaping_cost_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp)]),
     "rb_env_shaping_stats": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_double), ctypes.c_int]),
+    "rb_env_push_configure": (ctypes.c_int, [_sim, ctypes.POINTER(EnvPushConfig)]),
+    "rb_env_push_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rb_env_push_count": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

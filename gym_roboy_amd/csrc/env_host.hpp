@@ -1,7 +1,7 @@
 // env_host.hpp - the fused env layer and its options on the host.
 // Part of roboy_sim.hip (included there once, at file scope, behind the dispatch table; not a stand-alone header): everything
 // RoboyEnv.step's layer (rb_env_*) and its options - per-env parameters, tendon channels, io and the action ring, action rows,
-// episode-end codes, critic rows, the goal pool with its curriculum and row counts, reward shaping - do outside a kernel.  Each option is ONE record in
+// episode-end codes, critic rows, the goal pool with its curriculum and row counts, reward shaping, random pushes - do outside a kernel.  Each option is ONE record in
 // rb_sim (roboy_sim.hip), is switched by ONE entry point that opens with reconfigure(), and has ONE line in behind_step() /
 // behind_reset() if it launches anything there.  The kernels are in env_*.hpp and roboy_sim.hip; which env-step kernel runs is the
 // dispatch table's business, or extension_launch()'s where extension_serves().  DESIGN.md §6 has the table of options.
@@ -264,15 +264,19 @@ int shaping_compatible(rb_sim *s, const rb_env_shaping_config &w, bool params, i
     return delay_hi > 0 ? shaping_refuse_delay() : RB_OK;
 }
 // before anything of a step is enqueued: the options as they stand now, and the step's own refusals (a step that is refused
-// behind the cost kernel would have moved the previous rows)
-int shaping_check(rb_sim *s, long i0, long cnt) {
-    RB_RC(shaping_compatible(s, s->shaping.cfg, s->par.on, s->io.on ? s->io.cfg.delay_hi : 0));
+// behind the cost kernel would have moved the previous rows; behind the push kernel, velocities and counters).  step_form_check: what
+// dispatch() would refuse - shared by every option that launches in front of the step
+int step_form_check(rb_sim *s, long i0, long cnt) {
     if (extension_serves(s, ENTRY_ENV)) return RB_OK;
     std::string why;
     const Row *r = row_for(s, ENTRY_ENV, true, &why);
     if (!r) return fail(RB_EUNSUPPORTED, why);
     if (!r->ranges && !(i0 == 0 && cnt == s->n)) return fail(RB_EUNSUPPORTED, "this kernel form steps whole batches only (rb_range_capable)");
     return RB_OK;
+}
+int shaping_check(rb_sim *s, long i0, long cnt) {
+    RB_RC(shaping_compatible(s, s->shaping.cfg, s->par.on, s->io.on ? s->io.cfg.delay_hi : 0));
+    return step_form_check(s, i0, cnt);
 }
 size_t shaping_tree_lds(const rb_sim *s, int waves) {
     return rbt::tree_lds_bytes(s->tree_host, waves) + sizeof(float) * size_t(waves) * 3 * rbt::TREE_E * size_t(s->n_t);
@@ -302,6 +306,30 @@ int shaping_cost_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const 
         hipLaunchKernelGGL(rbs::msj_shaping_cost8<BLOCK>, dim3(blocks_for(cnt, BLOCK)), dim3(BLOCK), 0, stream, s->c8, u8, a);
     }
     RB_HIP(hipGetLastError());
+    return RB_OK;
+}
+// ---- random pushes (env_push.hpp): one launch in front of an env step (and of its shaping cost), over the envs [i0, i0 + cnt) ----
+int push_launch(rb_sim *s, long i0, long cnt, hipStream_t stream) {
+    if (cnt <= 0) return RB_OK;
+    const OptPush &o = s->push;
+    rbpush::PushArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.qd = s->d_qd; a.count = o.d_count; a.last = o.d_last; a.n_pushes = o.d_n; a.impulse = o.d_impulse;
+    a.n = s->n; a.i0 = i0; a.i1 = i0 + cnt;
+    a.seed = s->seed; a.env0 = uint64_t(s->env0);
+    a.threshold = o.cfg.threshold; a.nq = s->n_q; a.rows = s->tree ? 1 : 0;
+    for (int j = 0; j < s->n_q; ++j) { a.sigma[j] = o.cfg.sigma[j]; a.qd_max[j] = s->qd_max[j]; }
+    hipLaunchKernelGGL(rbpush::env_push, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, a);
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
+int push_clear(rb_sim *s) {
+    const OptPush &o = s->push;
+    const size_t plane = sizeof(uint32_t) * size_t(s->n);
+    RB_HIP(hipMemsetAsync(o.d_count, 0, plane, s->stream));
+    RB_HIP(hipMemsetAsync(o.d_last, 0, plane, s->stream));
+    RB_HIP(hipMemsetAsync(o.d_n, 0, plane, s->stream));
+    RB_HIP(hipMemsetAsync(o.d_impulse, 0, sizeof(float) * size_t(s->n) * size_t(s->n_q), s->stream));
     return RB_OK;
 }
 int shaping_apply_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, float *d_reward, const uint32_t *d_done) {
@@ -358,7 +386,8 @@ int episode_counters(rb_sim *s, CounterSite site) {
 
 // ---- what runs behind an env step and behind a reset ----
 // ONE stream each, so every kernel sees what those in front of it wrote.  The order, and why:
-//   step:   the shaping cost of (s_t, a_t) - IN FRONT of the env-step kernel (env_step_launch), which overwrites the state it reads
+//   step:   the random push - IN FRONT of everything (env_step_launch): it makes the state s_t the step really starts from
+//           the shaping cost of (s_t, a_t) - IN FRONT of the env-step kernel (env_step_launch), which overwrites the state it reads
 //           the env-step kernel (dispatch)
 //           0. shaping apply - reward -= cost, the cost statistics; reads the done words as flags, like 1.
 //           1. goal pool / curriculum / row counts - the done envs' new goal becomes a pool row, IN FRONT of everything that reads the goal
@@ -421,8 +450,10 @@ int behind_reset(rb_sim *s, float *d_obs) {
 int env_step_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float *d_act, float *d_obs, float *d_reward, uint32_t *d_done, float *d_cobs) {
     if (s->critic.mask) RB_RC(critic_check(s));          // (before anything is enqueued)
     if (s->shaping.on) RB_RC(shaping_check(s, i0, cnt));
+    else if (s->push.on) RB_RC(step_form_check(s, i0, cnt));
     Launch L;
     L.i0 = i0; L.cnt = cnt; L.stream = stream; L.act = d_act; L.obs = d_obs; L.reward = d_reward; L.done = d_done;
+    if (s->push.on) RB_RC(push_launch(s, i0, cnt, stream));
     if (s->shaping.on) RB_RC(shaping_cost_launch(s, i0, cnt, stream, d_act));
     RB_RC(dispatch(s, ENTRY_ENV, L));
     return behind_step(s, i0, cnt, stream, d_obs, d_reward, d_done, d_cobs);
@@ -1006,6 +1037,65 @@ int rb_env_shaping_stats(rb_sim *s, double *out, int reset) {
     RB_HIP(hipMemcpyAsync(out, result, sizeof(double) * 4, hipMemcpyDeviceToHost, s->stream));
     RB_HIP(hipStreamSynchronize(s->stream));
     return reset ? shaping_clear_sums(s) : RB_OK;
+}
+
+// ---- random velocity pushes in front of the fused env step (env_push.hpp) ----
+int rb_env_push_configure(rb_sim *s, const rb_env_push_config *cfg) {
+    rb_env_push_config c = {};
+    bool off = true;
+    // nothing in flight may still use the planes, and a captured graph holds the launches of the handle as it was
+    RB_RC(reconfigure(s, NEEDS_ENV | DROP_GRAPHS, [&]() -> int {
+        if (!cfg) return RB_OK;
+        if (cfg->threshold > (1u << 24)) return fail(RB_EINVAL, "random pushes: threshold must be in 0 .. 2^24 (P(push per env step) = threshold / 2^24)");
+        c.threshold = cfg->threshold;
+        bool any = false;
+        for (int j = 0; j < s->n_q; ++j) {
+            const float v = cfg->sigma[j];
+            if (!std::isfinite(v) || v < 0.0f) return fail(RB_EINVAL, "random pushes: the sigmas of the robot's joints must be finite and >= 0");
+            c.sigma[j] = v;
+            any = any || v != 0.0f;
+        }
+        off = c.threshold == 0u || !any;
+        return RB_OK;
+    }));
+    OptPush &o = s->push;
+    if (off) { o.release(); return RB_OK; }
+    const size_t n = size_t(s->n);
+    if (!o.d_count) {
+        auto alloc = [](auto **d, size_t bytes) { return dev_alloc(d, bytes, "hipMalloc (random pushes): "); };
+        OptPush fresh;
+        int rc = alloc(&fresh.d_count, sizeof(uint32_t) * n);
+        if (rc == RB_OK) rc = alloc(&fresh.d_last, sizeof(uint32_t) * n);
+        if (rc == RB_OK) rc = alloc(&fresh.d_n, sizeof(uint32_t) * n);
+        if (rc == RB_OK) rc = alloc(&fresh.d_impulse, sizeof(float) * n * size_t(s->n_q));
+        if (rc == RB_OK) rc = alloc(&fresh.d_total, sizeof(unsigned long long));
+        if (rc) { fresh.release(); return rc; }      // (the handle as it was: the option was off)
+        o = fresh;
+    }
+    o.cfg = c; o.on = true;
+    return push_clear(s);
+}
+int rb_env_push_ptr(rb_sim *s, uint32_t **d_count, uint32_t **d_last, uint32_t **d_n_pushes, float **d_impulse) {
+    if (check(s) || s->push.need()) return RB_EINVAL;
+    if (d_count) *d_count = s->push.d_count;
+    if (d_last) *d_last = s->push.d_last;
+    if (d_n_pushes) *d_n_pushes = s->push.d_n;
+    if (d_impulse) *d_impulse = s->push.d_impulse;
+    return RB_OK;
+}
+int rb_env_push_count(rb_sim *s, uint64_t *pushes, int reset) {
+    // every push enqueued so far is in.  The graphs stay: a read changes nothing they hold, a clear writes the plane in place
+    RB_RC(reconfigure(s, KEEP_GRAPHS, [&]() -> int { return s->push.need() ? RB_EINVAL : pushes ? RB_OK : fail(RB_EINVAL, "null argument"); }));
+    const OptPush &o = s->push;
+    unsigned long long total = 0;
+    RB_HIP(hipMemsetAsync(o.d_total, 0, sizeof(total), s->stream));
+    hipLaunchKernelGGL(rbpush::push_count_sum, dim3(stride_grid(s->n)), dim3(256), 0, s->stream, o.d_n, long(s->n), o.d_total);
+    RB_HIP(hipGetLastError());
+    RB_HIP(hipMemcpyAsync(&total, o.d_total, sizeof(total), hipMemcpyDeviceToHost, s->stream));
+    RB_HIP(hipStreamSynchronize(s->stream));
+    *pushes = uint64_t(total);
+    if (reset) RB_HIP(hipMemsetAsync(o.d_n, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
+    return RB_OK;
 }
 
 // ---- per-env physical parameters (env_params.hpp) ----

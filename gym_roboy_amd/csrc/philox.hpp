@@ -21,7 +21,7 @@
 namespace rb {
 
 // (stream 2 is the policy's sampling noise, mlp_common.hpp; 3 the per-env physical parameters, env_params.hpp; 4 the row of a goal
-// pool, env_goal.hpp)
+// pool, env_goal.hpp, and the sensor noise, env_io.hpp; 5 the action delay, env_io.hpp; 6 the random pushes, env_push.hpp)
 enum { STREAM_ACTIONS = 0, STREAM_GOALS = 1, STREAM_PARAMS = 3, STREAM_GOAL_POOL = 4 };
 
 struct Philox4 { uint32_t v[4]; };

@@ -55,6 +55,7 @@
 #include "env_critic.hpp"             // privileged critic rows behind the fused env step (rb_env_critic_obs_*)
 #include "env_goal.hpp"               // goals drawn from a pool of poses (rb_env_goal_pool_*)
 #include "env_shaping.hpp"            // action-rate and effort reward terms around the fused env step (rb_env_shaping_*)
+#include "env_push.hpp"               // random velocity pushes in front of the fused env step (rb_env_push_*)
 
 namespace {
 
@@ -535,6 +536,19 @@ struct OptShaping {
     }
     int need() const { return on ? RB_OK : fail(RB_EINVAL, "reward shaping is not configured (rb_env_shaping_configure)"); }
 };
+// Random velocity pushes (env_push.hpp; rb_env_push_*): while on, every env-step launch has env_push in front of it (and in front of
+// shaping_cost), over its range.  Planes [n_envs] each: steps counted, the count at the env's last push, pushes; the last impulses
+// [n_envs][n_q]; d_total: rb_env_push_count's device word
+struct OptPush {
+    bool on = false; rb_env_push_config cfg = {};
+    uint32_t *d_count = nullptr, *d_last = nullptr, *d_n = nullptr;
+    float *d_impulse = nullptr; unsigned long long *d_total = nullptr;
+    void release() {
+        (void)hipFree(d_count); (void)hipFree(d_last); (void)hipFree(d_n); (void)hipFree(d_impulse); (void)hipFree(d_total);
+        *this = OptPush{};
+    }
+    int need() const { return on ? RB_OK : fail(RB_EINVAL, "random pushes are not configured (rb_env_push_configure)"); }
+};
 
 }  // namespace
 
@@ -628,6 +642,8 @@ struct rb_sim {
     bool ts_attr_set = false;
     OptParams par; OptChannels chan; OptIo io; OptActionRows hist; OptDoneKind done; OptCritic critic; OptGoals goals;      // the env layer's options (above)
     OptShaping shaping;
+    OptPush push;
+    float qd_max[32] = {};               // the description's velocity bounds, as every step kernel holds them (fp32)
     int obs_dim() const { return 3 * n_q + rbo::n_channels(chan.mask) * n_t + hist.rows * n_t; }
     int critic_width() const { return rbc::row_dim(critic.mask, n_q, par.on ? par.n : 0, hist.rows * n_t); }
 };
@@ -964,7 +980,7 @@ int rb_create(const rb_robot_desc *robot, int64_t n_envs, int integrator, double
     s->device = device; s->n = n_envs; s->n_q = robot->n_q; s->n_t = robot->n_t;
     s->integrator = integrator; s->nsub = n_substeps; s->step_size = step_size;
     s->seed = seed; s->env0 = env_id_offset;
-    for (int j = 0; j < s->n_q; ++j) { s->box.lo[j] = float(robot->q_lo[j]); s->box.hi[j] = float(robot->q_hi[j]); }
+    for (int j = 0; j < s->n_q; ++j) { s->box.lo[j] = float(robot->q_lo[j]); s->box.hi[j] = float(robot->q_hi[j]); s->qd_max[j] = float(robot->qd_max[j]); }
 
 #define RB_TRY(call)                                                                      \
     do {                                                                                  \
@@ -1050,7 +1066,7 @@ void rb_destroy(rb_sim *s) {
     (void)hipFree(s->d_state_rows); (void)hipHostFree(s->h_state_rows);
     (void)hipFree(s->d_goal); (void)hipFree(s->d_ep_ret); (void)hipFree(s->d_ep_sum); (void)hipFree(s->d_ep_cnt);
     (void)hipFree(s->d_step_num); (void)hipFree(s->d_infeas_n); (void)hipFree(s->d_stats);
-    s->par.release(); s->chan.release(); s->io.release(); s->hist.release(); s->done.release(); s->critic.release(); s->goals.release(); s->shaping.release();
+    s->par.release(); s->chan.release(); s->io.release(); s->hist.release(); s->done.release(); s->critic.release(); s->goals.release(); s->shaping.release(); s->push.release();
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1457,6 +1473,9 @@ int rb_rollout_fused_dev(rb_sim *s, const float *d_ring, int ring, int n_steps, 
     if (s->shaping.on)
         return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) forms its rewards inside one kernel and cannot apply reward shaping "
                                      "(rb_env_shaping_configure(sim, NULL) first)");
+    if (s->push.on)
+        return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) steps inside one kernel and cannot apply random pushes "
+                                     "(rb_env_push_configure(sim, NULL) first)");
     if (s->goals.d_pool)
         return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) redraws goals inside one kernel and cannot draw them from a goal pool");
     if (n_steps == 0) return RB_OK;

@@ -168,6 +168,53 @@ def parse_reward_shaping(text):
     return out
 
 
+def push_spec(push, n_q: int):
+    """``{"prob": p, "sigma": s}`` (or None) -> ``{"prob": p, "sigma": [n_q floats], "threshold": round(p * 2**24)}`` - or None where
+    the option is off (``prob`` rounds to a threshold of 0, or every sigma is 0).  ``sigma``: a scalar or ``n_q`` entries, rad/s, as
+    the library holds them (float32).  ``ValueError`` for an unknown or missing key, a ``prob`` outside [0, 1], a sigma that is negative
+    or not finite, or a sigma vector of another length."""
+    if push is None:
+        return None
+    push = dict(push)
+    for k in push:
+        if k not in ("prob", "sigma"):
+            raise ValueError("push: unknown key %r (takes 'prob' and 'sigma')" % (k,))
+    if "prob" not in push or "sigma" not in push:
+        raise ValueError("push: needs both 'prob' and 'sigma', got %r" % (sorted(push),))
+    p = push["prob"]
+    if isinstance(p, bool) or not np.isscalar(p) or not np.isfinite(p) or p < 0 or p > 1:
+        raise ValueError("push['prob'] must be in [0, 1], got %r" % (p,))
+    sig = np.asarray(push["sigma"], dtype=np.float64)
+    if sig.ndim == 0:
+        sig = np.full(n_q, float(sig))
+    if sig.shape != (n_q,):
+        raise ValueError("push['sigma'] must be a scalar or have %d entries (one per joint), got shape %r" % (n_q, sig.shape))
+    if not np.all(np.isfinite(sig)) or np.any(sig < 0):
+        raise ValueError("push['sigma'] must be finite and >= 0, got %r" % (push["sigma"],))
+    sig = sig.astype(np.float32)
+    threshold = int(round(float(p) * 2 ** 24))
+    if threshold == 0 or not sig.any():
+        return None
+    return {"prob": float(p), "sigma": [float(v) for v in sig], "threshold": threshold}
+
+
+def parse_push(text):
+    """The command line's ``prob=0.02,sigma=0.5`` -> the dict ``RoboyVecEnv(push=...)`` takes ('' -> None); one sigma for every joint."""
+    items = [item for item in (text or "").split(",") if item]
+    if not items:
+        return None
+    out = {}
+    for item in items:
+        if "=" not in item:
+            raise ValueError("push: expected KEY=VALUE, got %r" % (item,))
+        k, v = item.split("=", 1)
+        if k in out:
+            raise ValueError("push: %r given twice" % (k,))
+        out[k] = float(v)
+    push_spec(out, 1)
+    return out
+
+
 class RoboyVecEnv:
 
     def __init__(self, robot: RoboyRobot, num_envs: int, seed: int = 0,
@@ -177,7 +224,7 @@ class RoboyVecEnv:
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
                  randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None,
                  report_truncation: bool = False, action_obs=None, critic_obs=None, goals=None, goal_curriculum=None,
-                 goal_row_stats: bool = False, reward_shaping=None):
+                 goal_row_stats: bool = False, reward_shaping=None, push=None):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
@@ -231,7 +278,14 @@ class RoboyVecEnv:
         robot, every kernel form).  Observations, dones, the state and ``stats()`` are those of an env without the option.
         ``shaping_cost()`` returns the last step's costs, ``shaping_stats()`` their sums.  ``tension`` and ``activation`` do not
         combine with ``randomization`` nor with an ``action_delay`` above 0; ``action_rate`` does.  None or all zeros: the env
-        launches exactly what it launched before."""
+        launches exactly what it launched before.
+        ``push``: ``{"prob": p, "sigma": s}`` - random velocity pushes, an external disturbance: in front of every env step each env
+        is pushed with probability ``round(p * 2**24) / 2**24``; a pushed env's joint velocities get ``sigma_j z_j`` added (``z``
+        standard normal, ``s`` a scalar or ``n_q`` entries in rad/s) and are clamped to the robot's velocity bounds; the step then
+        runs from that state as it always did (every robot, every kernel form, every option above).  ``push`` holds
+        the record (None without the option), ``last_push()`` returns who was pushed in the last step and by how much,
+        ``push_count()`` the number of pushes so far.  None, ``prob`` 0 or all-zero sigmas: the env launches exactly what it launched
+        before."""
         desc = robot.get_description()
         crit_names, crit_mask, crit_dim = critic_obs_spec(critic_obs, desc.n_q, desc.n_t, randomization is not None, action_delay, action_obs)
         obs_names = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
@@ -239,6 +293,7 @@ class RoboyVecEnv:
         d_lo, d_hi, ranged = action_delay_range(action_delay)
         n_action_rows = action_obs_rows(action_obs)
         shaping = reward_shaping_weights(reward_shaping)
+        push_rec = push_spec(push, desc.n_q)
         curriculum = envgoals.goal_curriculum_spec(goal_curriculum)
         if curriculum is not None:
             if goals is None:
@@ -379,6 +434,15 @@ class RoboyVecEnv:
             cfg = nat.EnvShapingConfig(shaping["action_rate"], shaping["tension"], shaping["activation"], 0.0)
             self._or_close(lambda: nat.check(self.sim._lib.rb_env_shaping_configure(self.sim.handle, ctypes.byref(cfg))))
             self.reward_shaping = shaping
+        self.push = None
+        if push_rec is not None:
+            # before anything is captured into a graph: every env-step launch gets the push kernel in front of it
+            pcfg = nat.EnvPushConfig()
+            pcfg.threshold = push_rec["threshold"]
+            for j, v in enumerate(push_rec["sigma"]):
+                pcfg.sigma[j] = v
+            self._or_close(lambda: nat.check(self.sim._lib.rb_env_push_configure(self.sim.handle, ctypes.byref(pcfg))))
+            self.push = push_rec
 
     def _or_close(self, configure):
         """an option the library refuses (a joint tree asked for a ball-joint option) must not leave the simulation's handle behind"""
@@ -686,6 +750,39 @@ class RoboyVecEnv:
         out = (ctypes.c_double * 4)()
         nat.check(self.sim._lib.rb_env_shaping_stats(self.sim.handle, out, int(bool(reset))))
         return dict(zip(("sum_episode_cost", "n_episodes", "sum_step_cost", "n_steps"), list(out)))
+
+    # -- random pushes (rb_env_push_*) ----------------------
+    def _push_planes(self):
+        if self.push is None:
+            raise RuntimeError("this RoboyVecEnv has no random pushes (push=None)")
+        p = [ctypes.c_void_p() for _ in range(4)]
+        nat.check(self.sim._lib.rb_env_push_ptr(self.sim.handle, *[ctypes.byref(x) for x in p]))
+        return [x.value for x in p]            # count, last, n_pushes, impulse
+
+    def last_push(self):
+        """``(pushed [N] bool, impulse [N, n_q])``: the envs the last step pushed, and every env's impulse row (rad/s, exactly what
+        was added before the clamp) - an env that was not pushed keeps the row of its last push, zeros before its first.  numpy
+        after a numpy step, read after a synchronisation; after a torch step CUDA tensors, ``impulse`` a VIEW of the handle's plane
+        that the next step overwrites (clone it to keep it).  Before the first step behind the configuration nobody was pushed (the
+        step counter is 0).  Needs ``push``."""
+        d_count, d_last, _, d_imp = self._push_planes()
+        n = self.num_envs
+        if _is_cuda_tensor(self._last_actions):
+            import torch
+            dev = self._last_actions.device
+            count, last = (_device_view_f32(p, n, dev).view(torch.int32) for p in (d_count, d_last))
+            return (count == last) & (count != 0), _device_view_f32(d_imp, n * self.n_q, dev).view(n, self.n_q)
+        self.sim.synchronize()
+        count, last = (self.sim.download(p, (n,), np.uint32) for p in (d_count, d_last))
+        return (count == last) & (count != 0), self.sim.download(d_imp, (n, self.n_q))
+
+    def push_count(self, reset: bool = False) -> int:
+        """The number of pushes over all envs since the count was last cleared (``reset=True`` clears it behind the read).  Counted
+        on the device, so steps replayed from a captured graph are in.  Needs ``push``."""
+        self._push_planes()
+        out = ctypes.c_uint64()
+        nat.check(self.sim._lib.rb_env_push_count(self.sim.handle, ctypes.byref(out), int(bool(reset))))
+        return int(out.value)
 
     def tendon_state(self, actions=None):
         """Per-tendon state of every env at its current state (``HipBatchSimulation.tendon_state``), the set-points formed

@@ -1678,6 +1678,9 @@ class PPO:
         shaping = getattr(self.env, "reward_shaping", None)
         if shaping is not None:                      # (an env without reward shaping writes the checkpoint it always wrote)
             ck["reward_shaping"] = {k: float(v) for k, v in shaping.items()}
+        push = getattr(self.env, "push", None)
+        if push is not None:                         # (an env without random pushes writes the checkpoint it always wrote)
+            ck["env_push"] = {"prob": float(push["prob"]), "sigma": [float(v) for v in push["sigma"]], "threshold": int(push["threshold"])}
         if self.symmetry is not None:                # (an agent without the option writes the checkpoint it always wrote)
             ck["symmetry"] = self.symmetry
             if self.symmetry == "loss":
@@ -1711,6 +1714,9 @@ class PPO:
             import warnings
             warnings.warn("the checkpoint was trained with reward_shaping=%r, this env runs reward_shaping=%r"
                           % (ck.get("reward_shaping"), getattr(self.env, "reward_shaping", None)))
+        # the pushes the checkpoint was trained under (None: none), for a caller that wants the same again: visualize_agent replays with
+        # them.  The env keeps its own - a disturbance is a condition of the run, not a layout
+        self.checkpoint_env_push = ck.get("env_push")
         # the goal pool the checkpoint was trained on (rows and recipe; None: box goals), for a caller that wants the same goals again:
         # visualize_agent replays with them.  The env keeps its own pool - the policy reads a goal as columns, whichever way it was drawn
         self.checkpoint_goals = ck.get("goals")

@@ -166,6 +166,11 @@ def main(argv=None):
                          "of the clamped action within an episode), tension (mean squared tendon force over its maximum), activation "
                          "(mean squared muscle activation), e.g. action_rate=0.05,tension=0.01; the round's statistics then show "
                          "shaping_cost_per_step, while return and goals reached stay the task's; recorded in the checkpoint")
+    ap.add_argument("--push", default="", metavar="prob=P,sigma=S",
+                    help="random velocity pushes, an external disturbance on the device: in front of every env step each env is pushed "
+                         "with probability P, a pushed env's joint velocities get S * z added (z standard normal, S in rad/s) and are "
+                         "clamped to the robot's bounds, e.g. prob=0.02,sigma=0.5; the round's statistics then show pushes_per_step; "
+                         "recorded in the checkpoint")
     args = ap.parse_args(argv)
     sensor_noise = {k: float(v) for k, v in (item.split("=", 1) for item in args.sensor_noise.split(",") if item)}
     action_delay = None
@@ -180,6 +185,8 @@ def main(argv=None):
     by_reach_rate = parse_goal_order(args.goal_order, args.goal_reorder_every, goal_curriculum)
     from .envs.vec_env import parse_reward_shaping
     reward_shaping = parse_reward_shaping(args.reward_shaping)
+    from .envs.vec_env import parse_push
+    push = parse_push(args.push)
 
     import numpy as np
     import torch
@@ -218,7 +225,7 @@ def main(argv=None):
                       sensor_noise=sensor_noise or None, action_delay=action_delay,
                       report_truncation=args.bootstrap_timeouts, action_obs=args.action_obs or None,
                       critic_obs=critic_obs or None, goal_curriculum=goal_curriculum, **({"goal_row_stats": True} if by_reach_rate else {}),
-                      **({"reward_shaping": reward_shaping} if reward_shaping else {}))
+                      **({"reward_shaping": reward_shaping} if reward_shaping else {}), **({"push": push} if push else {}))
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
                 reward_scale=0.01, use_graphs=not args.no_graphs, fused_policy=not args.torch_policy,
@@ -230,6 +237,7 @@ def main(argv=None):
     if os.path.exists(model_file):
         agent.load(model_file)                  # resume from the last backup
     last_stats = {}
+    push_steps_seen = 0.0                       # (--push: the env steps counted up to the last round's end)
     for round_no in range(args.rounds):
         agent.learn(total_timesteps=args.steps_per_round,
                     log=(lambda s: (last_stats.update(s), print(log_line(s)))) if rank == 0 else None)
@@ -247,6 +255,11 @@ def main(argv=None):
             counts = env.goal_row_stats()
             rows = torch.from_numpy(np.concatenate((counts["attempts"], counts["reached"])).astype(np.float64))
             block = torch.cat((block, rows.to(block)))
+        i_push = block.numel()
+        if env.push is not None:                # the round's pushes ride along: [... | pushes | env steps of the round]
+            steps_now = float(local["n_env_steps"])
+            block = torch.cat((block, torch.tensor([env.push_count(reset=True), steps_now - push_steps_seen], dtype=torch.float64).to(block)))
+            push_steps_seen = steps_now
         if env.reward_shaping is not None:      # the round's shaping costs ride along at the end: [... | sum of step costs | steps]
             cost = env.shaping_stats(reset=True)
             block = torch.cat((block, torch.tensor([cost["sum_step_cost"], cost["n_steps"]], dtype=torch.float64).to(block)))
@@ -267,6 +280,8 @@ def main(argv=None):
                 summary["symmetry_gap_action"] = float("%.3g" % agent.symmetry_gap(agent.last_rollout)["action"])
                 if "symmetry_loss" in last_stats:                     # (symmetry="loss": the term of the round's last minibatch)
                     summary["symmetry_loss"] = float("%.3g" % last_stats["symmetry_loss"])
+            if env.push is not None:
+                summary["pushes_per_step"] = float("%.4g" % (float(block[i_push]) / max(float(block[i_push + 1]), 1.0)))
             if env.reward_shaping is not None:
                 summary["shaping_cost_per_step"] = float("%.4g" % (float(block[-2]) / max(float(block[-1]), 1.0)))
             print("episode statistics (all ranks):", summary)

@@ -48,14 +48,17 @@ def main(argv=None):
         action_delay = tuple(action_delay)
     goals = ck.get("goals")                       # trained on a goal pool (train_parallel --goals): replay draws from the stored rows
     goal_rows = None if goals is None else np.asarray(goals["q"], dtype=np.float32)
-    if tendon_obs or sensor_noise or action_delay or action_obs:
+    env_push = ck.get("env_push")                 # trained under random pushes (train_parallel --push): replayed under the same
+    push = None if env_push is None else {"prob": env_push["prob"], "sigma": env_push["sigma"]}
+    if tendon_obs or sensor_noise or action_delay or action_obs or push:
         # trained with tendon channels in the observation (train_parallel --tendon-obs), sensor noise, an action delay or the last
         # actions in the observation (--sensor-noise, --action-delay, --action-obs): the same row, under the same conditions, comes from a RoboyVecEnv of one env, which resets
-        # itself on done and returns the reset observation.  RoboyEnv, one env stepped from the host, offers neither noise nor delay.
+        # itself on done and returns the reset observation.  RoboyEnv, one env stepped from the host, offers neither noise nor delay
+        # nor pushes (--push).
         from .envs.vec_env import TENDON_OBS_CHANNELS, RoboyVecEnv
         scale = dict(zip(TENDON_OBS_CHANNELS, ck["tendon_obs"]["scale"])) if tendon_obs else None
         vec = RoboyVecEnv(MsjRobot(), 1, tendon_obs=tendon_obs or None, tendon_obs_scale=scale, sensor_noise=sensor_noise,
-                          action_delay=action_delay, action_obs=action_obs or None, goals=goal_rows)
+                          action_delay=action_delay, action_obs=action_obs or None, goals=goal_rows, push=push)
         reset = lambda: vec.reset()[0]
 
         def step(a):

@@ -681,6 +681,47 @@ int rb_env_shaping_configure(rb_sim *sim, const rb_env_shaping_config *cfg);
 int rb_env_shaping_cost_ptr(rb_sim *sim, float **d_cost /* [n] */);
 int rb_env_shaping_stats(rb_sim *sim, double out[4], int reset);
 
+/* ---- random velocity pushes: an external disturbance in front of the fused env step ----
+ * Every robot, every kernel form, every env-step entry, every option above: no env-step kernel changes; ONE kernel is launched in
+ * front of every env-step launch over envs [i0, i0 + cnt), on its stream, over the same envs.  The step that follows integrates,
+ * clamps, writes the row, adds noise, accounts reward and done and auto-resets as it always did, from the state it finds.
+ * A handle with the option holds four planes: count, last, n_pushes (uint32 [n]) and impulse (float [n][n_q], env-major for every
+ * robot class).  For env i of the handle, global id g = env_id_offset + i, the kernel does:
+ *   1. m = count[i]; count[i] = m + 1.  The counter wraps as a uint32; nothing but rb_env_push_configure resets it (neither a reset
+ *      nor an episode end does).
+ *   2. w = philox_draw(seed, g, m, STREAM_PUSH = 6, block 0).v[0] (csrc/philox.hpp).  The env is PUSHED iff (w >> 8) < threshold:
+ *      integer arithmetic only, P(push per env step) = threshold / 2^24.
+ *   3. pushed: for every joint j < n_q, z_j is component j & 3 of block 1 + (j >> 2) of the same draw (same seed, g, m, stream),
+ *      turned into a normal deviate by the sensor noise's Box-Muller expression (pairs (0,1) and (2,3); u1 = ((w >> 8) + 1) / 2^24,
+ *      u2 = (w >> 8) / 2^24; radius sqrt(-2 ln u1), angle 2 pi u2; cosine to the even component, sine to the odd), in fp32;
+ *          impulse[i][j] = fl32(sigma_j z_j)
+ *          qd_j          = clamp(fl32(qd_j + impulse[i][j]), -qd_max_j, +qd_max_j)       qd_max: the description's, the bound every
+ *                                                                                        step kernel clamps to
+ *      - product and sum are two roundings, never one fused multiply-add: the stored impulse is exactly what was added.  Then
+ *      last[i] = m + 1 and n_pushes[i] += 1.  The velocity lives in the handle's own layout; q is not touched.
+ *   4. not pushed: nothing but count[i] is touched; the env's impulse row keeps its old content.
+ * After a step, "env i was pushed in this step" reads last[i] == count[i].
+ * Order in front of the step: the push kernel, then the reward-shaping cost (the cost of the state the step really starts from),
+ * then the env-step kernel.  All of a step's own refusals (a whole-batch-only form given a sub-range, the critic rows' and the
+ * shaping checks) are tested BEFORE the push kernel is enqueued: a refused step has moved neither velocities nor counters.
+ * rb_env_reset_dev leaves the four planes alone; rb_step* and rb_rollout_dev never push (pushes belong to the env layer).
+ *   configure: needs rb_env_configure (RB_EINVAL without).  NULL, threshold == 0 or all of the first n_q sigmas zero: off, the
+ *        planes are freed, the handle launches exactly what it launched before.  RB_EINVAL for threshold > 2^24 and for a negative
+ *        or non-finite sigma among the first n_q.  RB_ENOMEM when the planes cannot be allocated.  A refusal leaves the handle as it
+ *        was.  A successful call zeroes all four planes.  Drains the handle's streams and drops its graphs; call it before a caller
+ *        captures env steps.  rb_rollout_fused_dev is RB_EUNSUPPORTED while the option is on.
+ *   ptr: the four device planes (any argument may be NULL); RB_EINVAL without the option.
+ *   count: the sum of n_pushes over the handle's envs; reset != 0 zeroes that plane behind the read.  Synchronous.
+ * RB_ABI_VERSION is still 6 (nothing that existed changed): look rb_env_push_configure up before relying on it. */
+typedef struct rb_env_push_config {
+    uint32_t threshold;                  /* 0 .. 2^24: P(push per env step) = threshold / 2^24 */
+    uint32_t _pad;
+    float sigma[32];                     /* rad/s per joint, the first n_q are read */
+} rb_env_push_config;
+int rb_env_push_configure(rb_sim *sim, const rb_env_push_config *cfg);
+int rb_env_push_ptr(rb_sim *sim, uint32_t **d_count, uint32_t **d_last, uint32_t **d_n_pushes, float **d_impulse);
+int rb_env_push_count(rb_sim *sim, uint64_t *pushes, int reset);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
