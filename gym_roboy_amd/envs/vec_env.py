@@ -25,194 +25,13 @@ from .. import _native as nat
 from .._gymcompat import spaces
 from . import goals as envgoals
 from . import reward as rw
+from .options import (SENSOR_NOISE_KEYS, TENDON_OBS_CHANNELS, _TENDON_OBS_BOUNDS, action_delay_range, action_obs_bounds,  # noqa: F401
+                      action_obs_rows, critic_obs_spec, parse_push, parse_reward_shaping, push_spec, reward_shaping_weights,
+                      sensor_noise_sigmas, tendon_obs_mask, tendon_obs_scales)
 from .robots import RoboyRobot
 from .simulations.hip_simulation_client import HipBatchSimulation
 
 _IN_SLAB = object()      # RoboyVecEnv._last_actions: the last step's numpy actions, uploaded into the action slab
-
-# tendon channels of the observation, in row order, with their bits (rb_obs_channel) and physical bounds
-TENDON_OBS_CHANNELS = ("length", "rate", "activation", "force")
-_TENDON_OBS_BOUNDS = {"length": (0.0, np.inf), "rate": (-np.inf, np.inf), "activation": (0.0, 1.0), "force": (0.0, np.inf)}
-
-
-def tendon_obs_mask(channels) -> int:
-    """Channel names (any order, no repeats) -> the mask of ``rb_env_obs_configure``."""
-    names = [channels] if isinstance(channels, str) else list(channels)
-    unknown = [c for c in names if c not in TENDON_OBS_CHANNELS]
-    if unknown or len(set(names)) != len(names):
-        raise ValueError("tendon_obs takes distinct names out of %s, got %r" % (TENDON_OBS_CHANNELS, channels))
-    return sum(1 << TENDON_OBS_CHANNELS.index(c) for c in names)
-
-
-def tendon_obs_scales(scale) -> np.ndarray:
-    """``{"force": 1/400, ...}`` (or None) -> the four finite fp32 scales in channel order, 1 where not given."""
-    out = np.ones(4, np.float32)
-    for k, v in dict(scale or {}).items():
-        if k not in TENDON_OBS_CHANNELS:
-            raise ValueError("tendon_obs_scale: unknown channel %r" % (k,))
-        out[TENDON_OBS_CHANNELS.index(k)] = v
-    if not np.all(np.isfinite(out)):
-        raise ValueError("tendon_obs_scale must be finite")
-    return out
-
-
-SENSOR_NOISE_KEYS = ("q", "qd") + TENDON_OBS_CHANNELS
-
-
-def sensor_noise_sigmas(sensor_noise, tendon_obs=()) -> np.ndarray:
-    """``{"q": 0.01, "force": 2.0, ...}`` (or None) -> six fp32 standard deviations ``[q, qd, length, rate, activation, force]``
-    in physical units, 0 where not given.  Keys: ``q``, ``qd`` and the channel names; a channel must be one of ``tendon_obs``."""
-    out = np.zeros(6, np.float32)
-    for k, v in dict(sensor_noise or {}).items():
-        if k not in SENSOR_NOISE_KEYS:
-            raise ValueError("sensor_noise: unknown key %r (takes %s)" % (k, SENSOR_NOISE_KEYS))
-        if k in TENDON_OBS_CHANNELS and k not in tuple(tendon_obs or ()):
-            raise ValueError("sensor_noise: channel %r is not in tendon_obs" % (k,))
-        if not np.isfinite(v) or v < 0:
-            raise ValueError("sensor_noise[%r] must be finite and >= 0" % (k,))
-        out[SENSOR_NOISE_KEYS.index(k)] = v
-    return out
-
-
-def action_delay_range(action_delay):
-    """``2`` -> ``(2, 2, False)``, ``(0, 3)`` -> ``(0, 3, True)`` (a range is redrawn on auto-reset), None -> ``(0, 0, False)``"""
-    if action_delay is None:
-        return 0, 0, False
-    if isinstance(action_delay, (int, np.integer)):
-        lo = hi = int(action_delay)
-        ranged = False
-    else:
-        lo, hi = (int(x) for x in action_delay)
-        ranged = True
-    if not 0 <= lo <= hi <= nat.RB_IO_MAX_DELAY:
-        raise ValueError("action_delay: 0 <= lo <= hi <= %d, got %r" % (nat.RB_IO_MAX_DELAY, action_delay))
-    return lo, hi, ranged
-
-
-def action_obs_rows(action_obs) -> int:
-    """None -> 0, K -> K: the number of action rows behind the observation, 0 <= K <= 8"""
-    if action_obs is None:
-        return 0
-    if isinstance(action_obs, bool) or not isinstance(action_obs, (int, np.integer)) or not 0 <= int(action_obs) <= nat.RB_ACTION_OBS_MAX:
-        raise ValueError("action_obs: an int, 0 <= K <= %d, got %r" % (nat.RB_ACTION_OBS_MAX, action_obs))
-    return int(action_obs)
-
-
-def action_obs_bounds(low, high, n_t: int, rows: int):
-    """The observation box with K = ``rows`` action rows behind it: ``rows * n_t`` more columns, each within [-1, 1] (the clamp
-    the env step applies to an action).  Returns ``(low, high)`` as float32 arrays."""
-    extra = int(rows) * int(n_t)
-    return (np.concatenate((np.asarray(low, np.float32), np.full(extra, -1.0, np.float32))),
-            np.concatenate((np.asarray(high, np.float32), np.full(extra, 1.0, np.float32))))
-
-
-def critic_obs_spec(critic_obs, n_q: int, n_t: int, randomization: bool = False, action_delay=None, action_obs=None):
-    """Block names of a privileged critic row (``RoboyVecEnv(critic_obs=...)``; any order, no repeats; ``"state"`` is always part of the
-    row, named or not) -> ``(names in row order, the mask of rb_env_critic_obs_configure, Dc)`` for a ball-joint robot with ``n_q``
-    joints and ``n_t`` tendons.  None or an empty list: ``((), 0, 0)``.  ``ValueError`` for an unknown name, for a block whose option
-    the env does not have (``params``: ``randomization``; ``delay``: an ``action_delay`` above 0; ``actions``: ``action_obs=K``) and
-    for a row wider than 63 columns, the PPO gradient kernels' input limit."""
-    if critic_obs is None:
-        return (), 0, 0
-    names = [critic_obs] if isinstance(critic_obs, str) else list(critic_obs)
-    unknown = [c for c in names if c not in nat.CRITIC_OBS_BLOCKS]
-    if unknown or len(set(names)) != len(names):
-        raise ValueError("critic_obs takes distinct names out of %s, got %r" % (nat.CRITIC_OBS_BLOCKS, critic_obs))
-    if not names:
-        return (), 0, 0
-    rows = action_obs_rows(action_obs)
-    needs = {"params": (bool(randomization), "randomization"), "delay": (action_delay_range(action_delay)[1] > 0, "an action_delay above 0"),
-             "actions": (rows > 0, "action_obs=K")}
-    for c in names:
-        if c in needs and not needs[c][0]:
-            raise ValueError("critic_obs: %r needs %s" % (c, needs[c][1]))
-    names = tuple(c for c in nat.CRITIC_OBS_BLOCKS if c == "state" or c in names)
-    width = {"state": 3 * n_q, "age": 1, "params": 2 * n_t + 4, "delay": 1, "actions": rows * n_t}
-    dim = sum(width[c] for c in names)
-    if dim > nat.RB_CRITIC_OBS_MAX_DIM:
-        raise ValueError("critic_obs: %s is %d columns wide, at most %d (the PPO gradient kernels' input limit)"
-                         % (names, dim, nat.RB_CRITIC_OBS_MAX_DIM))
-    return names, sum(1 << nat.CRITIC_OBS_BLOCKS.index(c) for c in names), dim
-
-
-def reward_shaping_weights(reward_shaping):
-    """``{"action_rate": 0.05, "tension": 0.01}`` (or None) -> the dict with all three keys of ``_native.REWARD_SHAPING_TERMS`` as
-    floats, 0 where not given - or None where every weight is 0 (the option is off).  ``ValueError`` for an unknown key and for a
-    weight that is negative or not finite."""
-    if reward_shaping is None:
-        return None
-    out = dict.fromkeys(nat.REWARD_SHAPING_TERMS, 0.0)
-    for k, v in dict(reward_shaping).items():
-        if k not in nat.REWARD_SHAPING_TERMS:
-            raise ValueError("reward_shaping: unknown term %r (takes %s)" % (k, nat.REWARD_SHAPING_TERMS))
-        if isinstance(v, bool) or not np.isfinite(v) or v < 0:
-            raise ValueError("reward_shaping[%r] must be finite and >= 0, got %r" % (k, v))
-        out[k] = float(np.float32(v))
-    return out if any(out.values()) else None
-
-
-def parse_reward_shaping(text):
-    """The command line's ``action_rate=0.05,tension=0.01`` -> the dict ``reward_shaping_weights`` takes ('' -> None)."""
-    items = [item for item in (text or "").split(",") if item]
-    if not items:
-        return None
-    out = {}
-    for item in items:
-        if "=" not in item:
-            raise ValueError("reward shaping: expected TERM=WEIGHT, got %r" % (item,))
-        k, v = item.split("=", 1)
-        if k in out:
-            raise ValueError("reward shaping: %r given twice" % (k,))
-        out[k] = float(v)
-    reward_shaping_weights(out)
-    return out
-
-
-def push_spec(push, n_q: int):
-    """``{"prob": p, "sigma": s}`` (or None) -> ``{"prob": p, "sigma": [n_q floats], "threshold": round(p * 2**24)}`` - or None where
-    the option is off (``prob`` rounds to a threshold of 0, or every sigma is 0).  ``sigma``: a scalar or ``n_q`` entries, rad/s, as
-    the library holds them (float32).  ``ValueError`` for an unknown or missing key, a ``prob`` outside [0, 1], a sigma that is negative
-    or not finite, or a sigma vector of another length."""
-    if push is None:
-        return None
-    push = dict(push)
-    for k in push:
-        if k not in ("prob", "sigma"):
-            raise ValueError("push: unknown key %r (takes 'prob' and 'sigma')" % (k,))
-    if "prob" not in push or "sigma" not in push:
-        raise ValueError("push: needs both 'prob' and 'sigma', got %r" % (sorted(push),))
-    p = push["prob"]
-    if isinstance(p, bool) or not np.isscalar(p) or not np.isfinite(p) or p < 0 or p > 1:
-        raise ValueError("push['prob'] must be in [0, 1], got %r" % (p,))
-    sig = np.asarray(push["sigma"], dtype=np.float64)
-    if sig.ndim == 0:
-        sig = np.full(n_q, float(sig))
-    if sig.shape != (n_q,):
-        raise ValueError("push['sigma'] must be a scalar or have %d entries (one per joint), got shape %r" % (n_q, sig.shape))
-    if not np.all(np.isfinite(sig)) or np.any(sig < 0):
-        raise ValueError("push['sigma'] must be finite and >= 0, got %r" % (push["sigma"],))
-    sig = sig.astype(np.float32)
-    threshold = int(round(float(p) * 2 ** 24))
-    if threshold == 0 or not sig.any():
-        return None
-    return {"prob": float(p), "sigma": [float(v) for v in sig], "threshold": threshold}
-
-
-def parse_push(text):
-    """The command line's ``prob=0.02,sigma=0.5`` -> the dict ``RoboyVecEnv(push=...)`` takes ('' -> None); one sigma for every joint."""
-    items = [item for item in (text or "").split(",") if item]
-    if not items:
-        return None
-    out = {}
-    for item in items:
-        if "=" not in item:
-            raise ValueError("push: expected KEY=VALUE, got %r" % (item,))
-        k, v = item.split("=", 1)
-        if k in out:
-            raise ValueError("push: %r given twice" % (k,))
-        out[k] = float(v)
-    push_spec(out, 1)
-    return out
 
 
 class RoboyVecEnv:
@@ -287,10 +106,12 @@ class RoboyVecEnv:
         ``push_count()`` the number of pushes so far.  None, ``prob`` 0 or all-zero sigmas: the env launches exactly what it launched
         before."""
         desc = robot.get_description()
+        # 1. every ValueError of a bad option, before anything is allocated
         crit_names, crit_mask, crit_dim = critic_obs_spec(critic_obs, desc.n_q, desc.n_t, randomization is not None, action_delay, action_obs)
         obs_names = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
-        sig = sensor_noise_sigmas(sensor_noise, obs_names)               # (bad options: before anything is allocated)
-        d_lo, d_hi, ranged = action_delay_range(action_delay)
+        obs_scale = tendon_obs_scales(tendon_obs_scale)
+        sig = sensor_noise_sigmas(sensor_noise, obs_names)
+        delay = action_delay_range(action_delay)
         n_action_rows = action_obs_rows(action_obs)
         shaping = reward_shaping_weights(reward_shaping)
         push_rec = push_spec(push, desc.n_q)
@@ -304,103 +125,114 @@ class RoboyVecEnv:
         if goal_row_stats and curriculum is None:
             raise ValueError("goal_row_stats needs goal_curriculum= (the counts are kept by the row each env holds, the curriculum's index "
                              "plane; goal_curriculum=1 is the plain pool plus that plane)")
-        self.robot = robot
-        self.num_envs = int(num_envs)
-        self.sim = HipBatchSimulation(robot, num_envs, integrator=integrator, n_substeps=n_substeps,
-                                      device=device, seed=seed, env_id_offset=env_id_offset)
-        angles, vels, acts = (robot.get_joint_angles_space(), robot.get_joint_vels_space(),
-                              robot.get_action_space())
-        self.n_q, self.n_t = self.sim.n_q, self.sim.n_t
+        # 2. the simulation and the plain env layer (rb_env_configure)
+        self.robot, self.num_envs = robot, int(num_envs)
+        self.sim = HipBatchSimulation(robot, num_envs, integrator=integrator, n_substeps=n_substeps, device=device, seed=seed, env_id_offset=env_id_offset)
+        angles, vels, acts = robot.get_joint_angles_space(), robot.get_joint_vels_space(), robot.get_action_space()
+        self.n_q, self.n_t, self.obs_dim = self.sim.n_q, self.sim.n_t, 3 * self.sim.n_q
         self.action_space = spaces.Box(low=-1, high=1, shape=acts.shape, dtype="float32")
-        self.observation_space = spaces.Box(
-            low=np.concatenate((angles.low, vels.low, angles.low)),
-            high=np.concatenate((angles.high, vels.high, angles.high)), dtype="float32")
-        # thresholds exactly as the reference forms them (roboy_env.py:24-25,127,130)
-        max_dist_angle = rw.l2_distance(angles.low, angles.high)
-        max_dist_vel = rw.l2_distance(vels.low, vels.high)
-        cfg = nat.EnvConfig()
-        cfg.joint_vel_penalty = int(bool(joint_vel_penalty))
-        cfg.goal_bonus = int(bool(is_agent_getting_bonus_for_reaching_goal))
-        cfg.max_episode_length = int(max_episode_length)
-        cfg.auto_reset = int(bool(auto_reset))
-        cfg.penalty_boundary = 1.0
-        cfg.bonus_goal = 1000.0
-        cfg.angle_lo, cfg.angle_hi = float(angles.low[0]), float(angles.high[0])
-        cfg.vel_lo, cfg.vel_hi = float(vels.low[0]), float(vels.high[0])
+        self.observation_space = spaces.Box(low=np.concatenate((angles.low, vels.low, angles.low)),
+                                            high=np.concatenate((angles.high, vels.high, angles.high)), dtype="float32")
+        cfg = self._cfg = nat.EnvConfig()
+        cfg.joint_vel_penalty, cfg.goal_bonus = int(bool(joint_vel_penalty)), int(bool(is_agent_getting_bonus_for_reaching_goal))
+        cfg.max_episode_length, cfg.auto_reset = int(max_episode_length), int(bool(auto_reset))
+        cfg.penalty_boundary, cfg.bonus_goal = 1.0, 1000.0
+        cfg.angle_lo, cfg.angle_hi, cfg.vel_lo, cfg.vel_hi = float(angles.low[0]), float(angles.high[0]), float(vels.low[0]), float(vels.high[0])
         cfg.action_lo, cfg.action_hi = float(acts.low[0]), float(acts.high[0])
-        cfg.goal_angle_tol = float(max_dist_angle / 200)
-        cfg.goal_vel_tol = float(max_dist_vel / 5)
+        # thresholds exactly as the reference forms them (roboy_env.py:24-25,127,130)
+        cfg.goal_angle_tol, cfg.goal_vel_tol = float(rw.l2_distance(angles.low, angles.high) / 200), float(rw.l2_distance(vels.low, vels.high) / 5)
         for box in (angles, vels, acts):
             if not (np.all(box.low == box.low[0]) and np.all(box.high == box.high[0])):
                 raise NotImplementedError("fused env layer expects uniform per-joint boxes")
-        self._cfg = cfg
         # (bad rows: before anything is configured)
         pool_rows = None if goals is None else self._or_close(lambda: envgoals.goal_rows(goals, self.n_q, angles.low, angles.high))
         self.goal_recipe = dict(goals.recipe) if isinstance(goals, envgoals.GoalPool) else {}
         nat.check(self.sim._lib.rb_env_configure(self.sim.handle, ctypes.byref(cfg)))
-        self._goal_pool_m = 0
+        # 3. the options, in the one order they take (a call puts its kernels in the place of, in front of or behind those of the calls before
+        # it): pool, curriculum, row counts, tendon channels, action rows, buffers, randomization, io, truncation, critic rows, shaping, pushes
+        self._configure_goal_pool(pool_rows)
+        self._configure_goal_curriculum(curriculum)
+        self._configure_goal_row_stats(goal_row_stats)
+        self._configure_tendon_obs(obs_names, obs_scale)
+        self._configure_action_obs(n_action_rows)
+        self._allocate_buffers(seed)
+        self._configure_randomization(randomization)
+        self._configure_io(sensor_noise, action_delay, sig, *delay)
+        self._configure_truncation(report_truncation)
+        self._configure_critic_obs(crit_names, crit_mask, crit_dim)
+        self._configure_shaping(shaping)
+        self._configure_push(push_rec)
+
+    def _configure_goal_pool(self, pool_rows):
+        self.goal_pool_size = 0               # the pool's number of rows m; 0: the env draws its goals from the box
         if pool_rows is not None:
             # before anything is captured into a graph: every env-step launch and reset is followed by the small kernel that puts the
             # pool's rows in place of the box goals (the first call also turns the goal rb_env_configure's reset drew, draw 0, into its
             # pool row: the draw counters stay those of an env without a pool)
             self._or_close(lambda: self._set_goal_pool_rows(pool_rows))
-        self.goal_curriculum = None
+
+    def _configure_goal_curriculum(self, curriculum):
+        self.goal_curriculum = None if curriculum is None else dict(curriculum)
         if curriculum is not None:
             # directly behind the pool, before anything is captured into a graph: from here on the curriculum's kernel stands in the
             # pool kernel's place (the call also redraws every env's goal inside its window; the draw counters stay as they are)
-            self._or_close(lambda: envgoals.goal_curriculum_spec(curriculum, m=self._goal_pool_m))
+            self._or_close(lambda: envgoals.goal_curriculum_spec(curriculum, m=self.goal_pool_size))
             self._or_close(lambda: nat.check(self.sim._lib.rb_env_goal_curriculum_configure(
                 self.sim.handle, curriculum["levels"], curriculum["up"], curriculum["down"], curriculum["start"])))
-            self.goal_curriculum = dict(curriculum)
-        self.goal_row_stats_enabled = False
+
+    def _configure_goal_row_stats(self, goal_row_stats):
+        self.goal_row_stats_enabled = bool(goal_row_stats)
         if goal_row_stats:
             # directly behind the curriculum, before anything is captured into a graph: the counting kernel stands in its kernel's place
             self._or_close(lambda: nat.check(self.sim._lib.rb_env_goal_row_stats_enable(self.sim.handle)))
-            self.goal_row_stats_enabled = True
-        self.tendon_obs = tuple(c for c in TENDON_OBS_CHANNELS if tendon_obs and tendon_obs_mask(tendon_obs) >> TENDON_OBS_CHANNELS.index(c) & 1)
-        self.tendon_obs_scale = tendon_obs_scales(tendon_obs_scale)
-        self.obs_dim = 3 * self.n_q
+
+    def _configure_tendon_obs(self, obs_names, obs_scale):
+        self.tendon_obs, self.tendon_obs_scale = obs_names, obs_scale
         if self.tendon_obs:
             # before anything is captured into a graph: the extended kernels replace the handle's env-step kernels from here on
             self._or_close(lambda: nat.check(self.sim._lib.rb_env_obs_configure(self.sim.handle, tendon_obs_mask(self.tendon_obs),
                                                                                 nat.fptr(self.tendon_obs_scale))))
-            dim = ctypes.c_int32()
-            nat.check(self.sim._lib.rb_env_obs_dim(self.sim.handle, ctypes.byref(dim)))
-            self.obs_dim = int(dim.value)
             lo, hi = [self.observation_space.low], [self.observation_space.high]
             for c in self.tendon_obs:
                 b = np.sort(np.float32(_TENDON_OBS_BOUNDS[c]) * self.tendon_obs_scale[TENDON_OBS_CHANNELS.index(c)]) \
                     if self.tendon_obs_scale[TENDON_OBS_CHANNELS.index(c)] != 0 else np.zeros(2, np.float32)
                 lo.append(np.full(self.n_t, b[0], np.float32))
                 hi.append(np.full(self.n_t, b[1], np.float32))
-            self.observation_space = spaces.Box(low=np.concatenate(lo), high=np.concatenate(hi), dtype="float32")
-            assert self.observation_space.shape == (self.obs_dim,)
+            self._grow_observation(np.concatenate(lo), np.concatenate(hi))
+
+    def _configure_action_obs(self, n_action_rows):
         self.action_obs = n_action_rows
         if self.action_obs:
             # before anything is captured into a graph: the history kernels replace the env-step kernels from here on
             self._or_close(lambda: self.sim.configure_action_obs(self.action_obs))
-            dim = ctypes.c_int32()
-            nat.check(self.sim._lib.rb_env_obs_dim(self.sim.handle, ctypes.byref(dim)))
-            self.obs_dim = int(dim.value)
-            lo, hi = action_obs_bounds(self.observation_space.low, self.observation_space.high, self.n_t, self.action_obs)
-            self.observation_space = spaces.Box(low=lo, high=hi, dtype="float32")
-            assert self.observation_space.shape == (self.obs_dim,)
-        n = self.num_envs
-        self._d_act = self.sim.malloc(4 * n * self.n_t)
-        self._d_obs = self.sim.malloc(4 * n * self.obs_dim)
-        self._d_rew = self.sim.malloc(4 * n)
-        self._d_done = self.sim.malloc(4 * n)
+            self._grow_observation(*action_obs_bounds(self.observation_space.low, self.observation_space.high, self.n_t, self.action_obs))
+
+    def _grow_observation(self, low, high):
+        """an option has widened the row: ``obs_dim`` is read back from the library, and the caller's box has to be as wide"""
+        dim = ctypes.c_int32()
+        nat.check(self.sim._lib.rb_env_obs_dim(self.sim.handle, ctypes.byref(dim)))
+        self.obs_dim = int(dim.value)
+        self.observation_space = spaces.Box(low=low, high=high, dtype="float32")
+        assert self.observation_space.shape == (self.obs_dim,)
+
+    def _allocate_buffers(self, seed):
+        n = self.num_envs                  # (behind the options that set obs_dim)
+        self._d_act, self._d_obs = self.sim.malloc(4 * n * self.n_t), self.sim.malloc(4 * n * self.obs_dim)
+        self._d_rew, self._d_done = self.sim.malloc(4 * n), self.sim.malloc(4 * n)
         self._pending_actions = None
         self._last_actions = None      # tendon_state(): the last step's actions - _IN_SLAB (numpy: in _d_act) or the torch tensor
         self._d_ts = None              # tendon_state(): device outputs of the numpy path (4 x [N, n_t], first use)
-        self._seed = int(seed)
-        self._replayed_env_steps = 0.0
+        self._seed, self._replayed_env_steps = int(seed), 0.0
         self._stream = None            # the simulation's own stream
+
+    def _configure_randomization(self, randomization):
         self.randomization = randomization
         if randomization is not None:
             # before anything is captured into a graph: the parameter kernels replace the handle's step kernels from here on
             self._or_close(self.sim.enable_params)
             self._or_close(lambda: self.sim.set_param_ranges(randomization, resample_on_reset=True))
+
+    def _configure_io(self, sensor_noise, action_delay, sig, d_lo, d_hi, ranged):
         self.sensor_noise = dict(sensor_noise or {})
         self.action_delay = None if action_delay is None else ((d_lo, d_hi) if ranged else d_lo)
         self._io = bool(sig.any() or d_hi > 0)
@@ -412,11 +244,15 @@ class RoboyVecEnv:
                 io.sigma_tendon[c] = float(sig[2 + c])
             io.delay_lo, io.delay_hi, io.resample_on_reset = d_lo, d_hi, int(ranged)
             self._or_close(lambda: self.sim.configure_io(io))
+
+    def _configure_truncation(self, report_truncation):
         self.report_truncation = bool(report_truncation)
         self._last_done_codes = None   # truncated(): the last torch step's int32 codes (None: the last step was not a torch step)
         if self.report_truncation:
             # before anything is captured into a graph: every env-step launch is followed by the small kernel that writes the codes
             nat.check(self.sim._lib.rb_env_done_kind_configure(self.sim.handle, 1))
+
+    def _configure_critic_obs(self, crit_names, crit_mask, crit_dim):
         self.critic_obs_names, self.critic_obs_dim = crit_names, 0
         self._last_cobs = None         # critic_obs(): the last torch step's rows (None: the handle's plane holds the last rows)
         if crit_mask:
@@ -427,14 +263,17 @@ class RoboyVecEnv:
             nat.check(self.sim._lib.rb_env_critic_obs_dim(self.sim.handle, ctypes.byref(dim)))
             self.critic_obs_dim = int(dim.value)
             assert self.critic_obs_dim == crit_dim
-        self.reward_shaping = None
+
+    def _configure_shaping(self, shaping):
+        self.reward_shaping = shaping
         if shaping is not None:
             # after the options it has to agree with, before anything is captured into a graph: every env-step launch gets the cost
             # kernel in front of it and the kernel that applies the cost behind it
             cfg = nat.EnvShapingConfig(shaping["action_rate"], shaping["tension"], shaping["activation"], 0.0)
             self._or_close(lambda: nat.check(self.sim._lib.rb_env_shaping_configure(self.sim.handle, ctypes.byref(cfg))))
-            self.reward_shaping = shaping
-        self.push = None
+
+    def _configure_push(self, push_rec):
+        self.push = push_rec
         if push_rec is not None:
             # before anything is captured into a graph: every env-step launch gets the push kernel in front of it
             pcfg = nat.EnvPushConfig()
@@ -442,7 +281,6 @@ class RoboyVecEnv:
             for j, v in enumerate(push_rec["sigma"]):
                 pcfg.sigma[j] = v
             self._or_close(lambda: nat.check(self.sim._lib.rb_env_push_configure(self.sim.handle, ctypes.byref(pcfg))))
-            self.push = push_rec
 
     def _or_close(self, configure):
         """an option the library refuses (a joint tree asked for a ball-joint option) must not leave the simulation's handle behind"""
@@ -452,15 +290,19 @@ class RoboyVecEnv:
             self.sim.close()
             raise
 
+    @staticmethod
+    def _need(has_option, message):             # the guard of every accessor that belongs to an option
+        if not has_option:
+            raise RuntimeError(message)
+
     # -- goal pool (rb_env_goal_pool_*) -------------------
     def _set_goal_pool_rows(self, rows):
         nat.check(self.sim._lib.rb_env_goal_pool_set(self.sim.handle, nat.fptr(rows), rows.shape[0]))
-        self._goal_pool_m = int(rows.shape[0])
+        self.goal_pool_size = int(rows.shape[0])
 
     def goal_pool(self) -> np.ndarray:
         """The pool's rows ``[m, n_q]`` as the device holds them; needs ``goals``."""
-        if not self._goal_pool_m:
-            raise RuntimeError("this RoboyVecEnv draws its goals from the box (goals=None)")
+        self._need(self.goal_pool_size, "this RoboyVecEnv draws its goals from the box (goals=None)")
         d_pool, m = ctypes.c_void_p(), ctypes.c_int64()
         nat.check(self.sim._lib.rb_env_goal_pool_ptr(self.sim.handle, ctypes.byref(d_pool), ctypes.byref(m)))
         self.sim.synchronize()
@@ -470,18 +312,16 @@ class RoboyVecEnv:
         """Replace the pool's rows in place by as many others (a ``GoalPool`` or an array ``[m, n_q]``), between steps: goals drawn from
         now on - also by a captured graph's next replay, the device rows do not move - are rows of the new pool; goals already drawn
         stay until their env draws again.  Needs ``goals``; ``ValueError`` for another size."""
-        if not self._goal_pool_m:
-            raise RuntimeError("this RoboyVecEnv draws its goals from the box (goals=None): a pool is given at construction")
+        self._need(self.goal_pool_size, "this RoboyVecEnv draws its goals from the box (goals=None): a pool is given at construction")
         angles = self.robot.get_joint_angles_space()
-        rows = envgoals.goal_rows(goals, self.n_q, angles.low, angles.high, m=self._goal_pool_m)
+        rows = envgoals.goal_rows(goals, self.n_q, angles.low, angles.high, m=self.goal_pool_size)
         self._set_goal_pool_rows(rows)
         self.goal_recipe = dict(goals.recipe) if isinstance(goals, envgoals.GoalPool) else {}
 
     # -- goal curriculum (rb_env_goal_curriculum_*; DESIGN.md §23) --------
     def _curriculum_plane(self, getter):
         """a uint32 plane [N] of the curriculum: numpy, or a CUDA int64 tensor when the last step was a torch step"""
-        if self.goal_curriculum is None:
-            raise RuntimeError("this RoboyVecEnv has no goal curriculum (goal_curriculum=None)")
+        self._need(self.goal_curriculum is not None, "this RoboyVecEnv has no goal curriculum (goal_curriculum=None)")
         ptr = ctypes.c_void_p()
         nat.check(getter(self.sim.handle, ctypes.byref(ptr)))
         self.sim.synchronize()
@@ -502,8 +342,7 @@ class RoboyVecEnv:
     def set_goal_levels(self, levels):
         """Write every env's level ``[N]`` (ints below ``levels``), between steps: goals already drawn stay until their env draws
         again.  ``ValueError`` for a level out of range, and nothing has changed then."""
-        if self.goal_curriculum is None:
-            raise RuntimeError("this RoboyVecEnv has no goal curriculum (goal_curriculum=None)")
+        self._need(self.goal_curriculum is not None, "this RoboyVecEnv has no goal curriculum (goal_curriculum=None)")
         if _is_cuda_tensor(levels):
             levels = levels.cpu().numpy()
         lv = np.asarray(levels)
@@ -516,8 +355,7 @@ class RoboyVecEnv:
 
     def goal_level_histogram(self):
         """``[levels]`` counts: how many envs sit at each level (one small kernel; numpy int64, or a CUDA tensor after a torch step)."""
-        if self.goal_curriculum is None:
-            raise RuntimeError("this RoboyVecEnv has no goal curriculum (goal_curriculum=None)")
+        self._need(self.goal_curriculum is not None, "this RoboyVecEnv has no goal curriculum (goal_curriculum=None)")
         n_levels = self.goal_curriculum["levels"]
         if _is_cuda_tensor(self._last_actions):
             import torch
@@ -531,28 +369,24 @@ class RoboyVecEnv:
         return out.astype(np.int64)
 
     # -- outcome counts per pool row (rb_env_goal_row_stats_*, rb_env_goal_pool_permute) --------
-    def _need_row_stats(self):
-        if not self.goal_row_stats_enabled:
-            raise RuntimeError("this RoboyVecEnv keeps no goal row stats (goal_row_stats=False)")
-
     def goal_row_stats(self, reset: bool = False):
         """``{"attempts": uint64 [m], "reached": uint64 [m]}``: per pool row, the episodes that ended while aimed at it and those of
         them that reached it, since the counts were last cleared (``reset=True`` clears them behind the read).  Needs
         ``goal_row_stats``."""
-        self._need_row_stats()
-        out = np.empty((2, self._goal_pool_m), np.uint64)
+        self._need(self.goal_row_stats_enabled, "this RoboyVecEnv keeps no goal row stats (goal_row_stats=False)")
+        out = np.empty((2, self.goal_pool_size), np.uint64)
         nat.check(self.sim._lib.rb_env_goal_row_stats_read(self.sim.handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(bool(reset))))
         return {"attempts": out[0].copy(), "reached": out[1].copy()}
 
     def set_goal_row_stats(self, attempts, reached):
         """Write the counts ``[m]`` each (non-negative ints, ``reached <= attempts``), between steps.  ``ValueError`` otherwise, and
         nothing has changed then."""
-        self._need_row_stats()
+        self._need(self.goal_row_stats_enabled, "this RoboyVecEnv keeps no goal row stats (goal_row_stats=False)")
         planes = []
         for name, x in (("attempts", attempts), ("reached", reached)):
             a = np.asarray(x.cpu().numpy() if _is_cuda_tensor(x) else x)
-            if a.shape != (self._goal_pool_m,) or a.dtype.kind not in "iu":
-                raise ValueError("%s must be %d ints" % (name, self._goal_pool_m))
+            if a.shape != (self.goal_pool_size,) or a.dtype.kind not in "iu":
+                raise ValueError("%s must be %d ints" % (name, self.goal_pool_size))
             if a.dtype.kind == "i" and np.any(a < 0):
                 raise ValueError("%s must be >= 0" % name)
             planes.append(a.astype(np.uint64))
@@ -566,10 +400,9 @@ class RoboyVecEnv:
         otherwise and nothing has changed).  The device rows are permuted in place, so a captured graph's next replay reads the new
         order; every env keeps the goal it holds, ``goal_index()`` follows the rows, and the row counts travel with them.  Levels
         stay.  Needs ``goals``; the recipe's ``"ordered"`` mark becomes ``"custom"``."""
-        if not self._goal_pool_m:
-            raise RuntimeError("this RoboyVecEnv draws its goals from the box (goals=None)")
+        self._need(self.goal_pool_size, "this RoboyVecEnv draws its goals from the box (goals=None)")
         a = np.asarray(order.cpu().numpy() if _is_cuda_tensor(order) else order)
-        m = self._goal_pool_m
+        m = self.goal_pool_size
         if a.shape != (m,) or a.dtype.kind not in "iu":
             raise ValueError("order must be %d ints, a permutation of 0..%d" % (m, m - 1))
         if np.any(a < 0) or np.any(a >= m) or np.unique(a).size != m:
@@ -584,15 +417,15 @@ class RoboyVecEnv:
         applied.  The rates come from this env's counts, or from ``attempts`` / ``reached`` where given (a multi-rank run passes the
         sums over its ranks, so that every rank applies the same order).  ``halve``: afterwards every count of this env is shifted
         right by one, so an older policy's outcomes fade by a fixed rule.  Needs ``goal_row_stats``."""
-        self._need_row_stats()
+        self._need(self.goal_row_stats_enabled, "this RoboyVecEnv keeps no goal row stats (goal_row_stats=False)")
         if (attempts is None) != (reached is None):
             raise ValueError("give both attempts and reached, or neither")
         if attempts is None:
             own = self.goal_row_stats()
             attempts, reached = own["attempts"], own["reached"]
         order = envgoals.reach_rate_order(attempts, reached, prior)
-        if order.shape != (self._goal_pool_m,):
-            raise ValueError("the pool has %d rows, the counts have %d" % (self._goal_pool_m, order.shape[0]))
+        if order.shape != (self.goal_pool_size,):
+            raise ValueError("the pool has %d rows, the counts have %d" % (self.goal_pool_size, order.shape[0]))
         self.permute_goal_pool(order)
         self.goal_recipe["ordered"] = "reach_rate"
         if halve:
@@ -692,8 +525,7 @@ class RoboyVecEnv:
         """``[N]`` bools of the last step: True where the episode ended at the time limit without reaching its goal.  numpy after a
         numpy step (or ``step_dev`` / ``step_range_dev``, read from the handle's code plane after a synchronisation), a CUDA tensor
         after a torch step.  Needs ``report_truncation=True``."""
-        if not self.report_truncation:
-            raise RuntimeError("this RoboyVecEnv does not report truncation (report_truncation=False)")
+        self._need(self.report_truncation, "this RoboyVecEnv does not report truncation (report_truncation=False)")
         if self._last_done_codes is not None:
             return self._last_done_codes == nat.RB_DONE_TRUNCATED
         kind = ctypes.c_void_p()
@@ -714,8 +546,7 @@ class RoboyVecEnv:
         """``[N, critic_obs_dim]``: the privileged rows that belong to the observation rows last returned.  A CUDA tensor after a torch
         step; otherwise numpy, read from the handle's plane after a synchronisation (a reset, a numpy step, ``step_dev`` /
         ``step_range_dev`` without ``d_cobs``).  Needs ``critic_obs``."""
-        if not self.critic_obs_dim:
-            raise RuntimeError("this RoboyVecEnv writes no critic rows (critic_obs=None)")
+        self._need(self.critic_obs_dim, "this RoboyVecEnv writes no critic rows (critic_obs=None)")
         if self._last_cobs is not None:
             return self._last_cobs
         rows = ctypes.c_void_p()
@@ -725,8 +556,7 @@ class RoboyVecEnv:
 
     # -- reward shaping (rb_env_shaping_*) -----------------
     def _shaping_plane(self):
-        if self.reward_shaping is None:
-            raise RuntimeError("this RoboyVecEnv has no reward shaping (reward_shaping=None)")
+        self._need(self.reward_shaping is not None, "this RoboyVecEnv has no reward shaping (reward_shaping=None)")
         ptr = ctypes.c_void_p()
         nat.check(self.sim._lib.rb_env_shaping_cost_ptr(self.sim.handle, ctypes.byref(ptr)))
         return ptr.value
@@ -753,8 +583,7 @@ class RoboyVecEnv:
 
     # -- random pushes (rb_env_push_*) ----------------------
     def _push_planes(self):
-        if self.push is None:
-            raise RuntimeError("this RoboyVecEnv has no random pushes (push=None)")
+        self._need(self.push is not None, "this RoboyVecEnv has no random pushes (push=None)")
         p = [ctypes.c_void_p() for _ in range(4)]
         nat.check(self.sim._lib.rb_env_push_ptr(self.sim.handle, *[ctypes.byref(x) for x in p]))
         return [x.value for x in p]            # count, last, n_pushes, impulse
@@ -873,15 +702,13 @@ class RoboyVecEnv:
 
     def get_action_delay(self) -> np.ndarray:
         """Every env's action delay ``[N]`` (steps); needs ``sensor_noise`` or ``action_delay``."""
-        if not self._io:
-            raise RuntimeError("this RoboyVecEnv has no action delay (action_delay=None)")
+        self._need(self._io, "this RoboyVecEnv has no action delay (action_delay=None)")
         self.sim.synchronize()
         return self.sim.download(self.sim.io_ptrs()["delay"], (self.num_envs,), np.uint32).astype(np.int64)
 
     def set_action_delay(self, delay):
         """Overwrite every env's delay ``[N]``: integers in ``[0, hi]`` of the configured ``action_delay``."""
-        if not self._io:
-            raise RuntimeError("this RoboyVecEnv has no action delay (action_delay=None)")
+        self._need(self._io, "this RoboyVecEnv has no action delay (action_delay=None)")
         d = np.asarray(delay)
         hi = action_delay_range(self.action_delay)[1]
         if d.shape != (self.num_envs,) or np.any(d < 0) or np.any(d > hi) or np.any(d != np.floor(d)):
@@ -891,8 +718,7 @@ class RoboyVecEnv:
 
     def get_params(self) -> dict:
         """Every env's physical parameters (``HipBatchSimulation.get_params``); needs ``randomization``."""
-        if self.randomization is None:
-            raise RuntimeError("this RoboyVecEnv has no per-env parameters (randomization=None)")
+        self._need(self.randomization is not None, "this RoboyVecEnv has no per-env parameters (randomization=None)")
         return self.sim.get_params()
 
     def close(self):

@@ -51,6 +51,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .envs.options import check_env_checkpoint, env_checkpoint_record, env_io_record as _env_io_of  # noqa: F401 (the last: old name)
 from .sharding import dist_ranks
 
 LR_SCHEDULES = ("adaptive",)
@@ -838,31 +839,6 @@ def average_gradients(module, dist=None):
             n = p.grad.numel()
             p.grad.copy_(flat[off:off + n].view_as(p.grad))
             off += n
-
-
-def _tendon_obs_of(env):
-    """What a checkpoint records about the env's observation (RoboyVecEnv's tendon channels and their scales): a policy only
-    makes sense on the observation it was trained on.  An env without the option - or an older checkpoint - has no channels."""
-    channels = tuple(getattr(env, "tendon_obs", ()) or ())
-    scale = [float(x) for x in getattr(env, "tendon_obs_scale", (1.0, 1.0, 1.0, 1.0))] if channels else [1.0] * 4
-    return {"channels": list(channels), "scale": scale}
-
-
-def _env_io_of(env):
-    """What a checkpoint records about the conditions the policy was trained under (RoboyVecEnv's sensor_noise, action_delay and
-    action_obs - the last of them IS part of the row's layout: K n_t more columns): playback (visualize_agent) reads them back."""
-    delay = getattr(env, "action_delay", None)
-    out = {"sensor_noise": {k: float(v) for k, v in dict(getattr(env, "sensor_noise", None) or {}).items()},
-           "action_delay": list(delay) if isinstance(delay, tuple) else delay}
-    if getattr(env, "action_obs", 0):          # (an env without the option records what it always recorded)
-        out["action_obs"] = int(env.action_obs)
-    return out
-
-
-def _critic_obs_of(env):
-    """What a checkpoint records about the critic's rows (RoboyVecEnv's critic_obs): the value net only makes sense on the row it
-    was trained on.  An env without the option has no names."""
-    return list(getattr(env, "critic_obs_names", ()) or ())
 
 
 def _fused_kernels_apply(policy, obs_dim, act_dim):
@@ -1657,30 +1633,13 @@ class PPO:
     def save(self, path):
         opt = self._fadam.state_dict() if self._fgrad is not None else self.opt.state_dict()
         ck = {"policy": self.policy.state_dict(), "optimizer": opt, "num_timesteps": self.num_timesteps,
-              "epoch": self._epoch, "tendon_obs": _tendon_obs_of(self.env), "env_io": _env_io_of(self.env),
+              "epoch": self._epoch, **env_checkpoint_record(self.env, critic=self.asymmetric_critic),
               "obs_norm": self.obs_norm.state_dict() if self.obs_norm is not None else None,
               "reward_norm": self.reward_norm.state_dict() if self.reward_norm is not None else None,
               "bootstrap_timeouts": self.bootstrap_timeouts}
         if self.asymmetric_critic:                   # (an agent without the option writes the checkpoint it always wrote)
-            ck["critic_obs"] = _critic_obs_of(self.env)
             ck["critic_obs_dim"] = self.cobs_dim
             ck["critic_obs_norm"] = self.cobs_norm.state_dict() if self.cobs_norm is not None else None
-        if getattr(self.env, "_goal_pool_m", 0):     # (an env that draws its goals from the box writes the checkpoint it always wrote)
-            ck["goals"] = {"q": torch.from_numpy(self.env.goal_pool()), "recipe": dict(getattr(self.env, "goal_recipe", {}) or {})}
-        curriculum = getattr(self.env, "goal_curriculum", None)
-        if curriculum is not None:                   # (an env without a goal curriculum writes the checkpoint it always wrote)
-            level = self.env.goal_levels()
-            ck["goal_curriculum"] = {"levels": curriculum["levels"], "up": curriculum["up"], "down": curriculum["down"],
-                                     "level": (level if torch.is_tensor(level) else torch.from_numpy(level.astype("int64"))).cpu()}
-        if getattr(self.env, "goal_row_stats_enabled", False):      # (an env without the counts writes the checkpoint it always wrote)
-            counts = self.env.goal_row_stats()       # per row of ck["goals"]["q"], which is the pool in its current order
-            ck["goal_row_stats"] = {k: torch.from_numpy(counts[k].astype("int64")) for k in ("attempts", "reached")}
-        shaping = getattr(self.env, "reward_shaping", None)
-        if shaping is not None:                      # (an env without reward shaping writes the checkpoint it always wrote)
-            ck["reward_shaping"] = {k: float(v) for k, v in shaping.items()}
-        push = getattr(self.env, "push", None)
-        if push is not None:                         # (an env without random pushes writes the checkpoint it always wrote)
-            ck["env_push"] = {"prob": float(push["prob"]), "sigma": [float(v) for v in push["sigma"]], "threshold": int(push["threshold"])}
         if self.symmetry is not None:                # (an agent without the option writes the checkpoint it always wrote)
             ck["symmetry"] = self.symmetry
             if self.symmetry == "loss":
@@ -1692,9 +1651,6 @@ class PPO:
 
     def load(self, path):
         ck = torch.load(path, map_location=self.device)
-        if ck.get("tendon_obs", _tendon_obs_of(None)) != _tendon_obs_of(self.env):
-            raise ValueError("the checkpoint was trained on the observation %r, this env gives %r (RoboyVecEnv's tendon_obs / "
-                             "tendon_obs_scale)" % (ck.get("tendon_obs", _tendon_obs_of(None)), _tendon_obs_of(self.env)))
         if ("critic_obs" in ck) != self.asymmetric_critic:
             raise ValueError("the checkpoint was trained %s an asymmetric critic, this agent runs %s one (PPO's asymmetric_critic)"
                              % (("with", "without") if not self.asymmetric_critic else ("without", "with")))
@@ -1706,32 +1662,9 @@ class PPO:
             import warnings
             warnings.warn("the checkpoint was trained with symmetry_coef=%r, this agent goes on with symmetry_coef=%r"
                           % (float(ck["symmetry_coef"]), self.symmetry_coef))
-        if self.asymmetric_critic and (ck["critic_obs"] != _critic_obs_of(self.env) or int(ck["critic_obs_dim"]) != self.cobs_dim):
-            raise ValueError("the checkpoint's critic was trained on the rows %r (%d columns), this env writes %r (%d; RoboyVecEnv's "
-                             "critic_obs)" % (ck["critic_obs"], int(ck["critic_obs_dim"]), _critic_obs_of(self.env), self.cobs_dim))
-        if ck.get("reward_shaping") != getattr(self.env, "reward_shaping", None):
-            # the weights shape the reward, not a layout: the env's hold (a run may be resumed under other weights), and says so
-            import warnings
-            warnings.warn("the checkpoint was trained with reward_shaping=%r, this env runs reward_shaping=%r"
-                          % (ck.get("reward_shaping"), getattr(self.env, "reward_shaping", None)))
-        # the pushes the checkpoint was trained under (None: none), for a caller that wants the same again: visualize_agent replays with
-        # them.  The env keeps its own - a disturbance is a condition of the run, not a layout
-        self.checkpoint_env_push = ck.get("env_push")
-        # the goal pool the checkpoint was trained on (rows and recipe; None: box goals), for a caller that wants the same goals again:
-        # visualize_agent replays with them.  The env keeps its own pool - the policy reads a goal as columns, whichever way it was drawn
-        self.checkpoint_goals = ck.get("goals")
-        # the outcome counts per row of that pool (None: the checkpoint's env kept none), kept here like the goals: the env keeps its own
-        self.checkpoint_goal_row_stats = ck.get("goal_row_stats")
-        # the goal curriculum's levels go back into an env with as many levels and envs; otherwise the env keeps its own and the
-        # checkpoint's are kept here, as the goals above
-        self.checkpoint_goal_curriculum = None
-        saved = ck.get("goal_curriculum")
-        if saved is not None:
-            own = getattr(self.env, "goal_curriculum", None)
-            if own is not None and own["levels"] == int(saved["levels"]) and int(saved["level"].numel()) == self.env.num_envs:
-                self.env.set_goal_levels(saved["level"].cpu().numpy())
-            else:
-                self.checkpoint_goal_curriculum = saved
+        # the env's side; what the env does not take over is kept as checkpoint_goals, _goal_row_stats, _goal_curriculum and _env_push
+        for key, value in check_env_checkpoint(self.env, ck, self.cobs_dim).items():
+            setattr(self, "checkpoint_" + key, value)
         if (ck.get("obs_norm") is not None) != (self.obs_norm is not None):      # (a checkpoint without the key: written without it)
             raise ValueError("the checkpoint was trained %s observation normalisation, this agent runs %s it (PPO's normalize_obs)"
                              % (("with", "without") if self.obs_norm is None else ("without", "with")))

@@ -39,6 +39,20 @@ def allreduce_stats(stats, dist=None):
     return stats
 
 
+def join_segments(segments, device="cpu"):
+    """``[(name, values), ...]`` -> ``(block, layout)``: the values laid end to end in one float64 tensor on ``device`` (counts are exact
+    below 2^53), what ``allreduce_stats`` takes in one call, and ``{name: (start, end)}``, where each name lies in it."""
+    import torch
+    parts = [torch.as_tensor(values, dtype=torch.float64).reshape(-1).to(device) for _, values in segments]
+    ends = [sum(p.numel() for p in parts[:i]) for i in range(len(parts) + 1)]
+    return torch.cat(parts), {name: (ends[i], ends[i + 1]) for i, (name, _) in enumerate(segments)}
+
+
+def split_segments(block, layout) -> dict:
+    """The block of ``join_segments`` (summed over the ranks or not) -> ``{name: its part}``, views into ``block``."""
+    return {name: block[start:end] for name, (start, end) in layout.items()}
+
+
 def summarize(stats) -> dict:
     """Mean return / length / rates from the summed vector."""
     s = [float(x) for x in stats]

@@ -35,30 +35,18 @@ def main(argv=None):
     import numpy as np
     import torch
     from .envs import RoboyEnv
+    from .envs.options import env_kwargs_from_checkpoint
     from .envs.robots import MsjRobot
     from .envs.simulations import HipSimulationClient
     from .ppo import MlpPolicy
 
     ck = torch.load(args.model, map_location="cpu")
-    tendon_obs = ck.get("tendon_obs", {}).get("channels", [])
-    env_io = ck.get("env_io", {})
-    sensor_noise, action_delay = env_io.get("sensor_noise") or None, env_io.get("action_delay")
-    action_obs = int(env_io.get("action_obs") or 0)
-    if isinstance(action_delay, list):
-        action_delay = tuple(action_delay)
-    goals = ck.get("goals")                       # trained on a goal pool (train_parallel --goals): replay draws from the stored rows
-    goal_rows = None if goals is None else np.asarray(goals["q"], dtype=np.float32)
-    env_push = ck.get("env_push")                 # trained under random pushes (train_parallel --push): replayed under the same
-    push = None if env_push is None else {"prob": env_push["prob"], "sigma": env_push["sigma"]}
-    if tendon_obs or sensor_noise or action_delay or action_obs or push:
-        # trained with tendon channels in the observation (train_parallel --tendon-obs), sensor noise, an action delay or the last
-        # actions in the observation (--sensor-noise, --action-delay, --action-obs): the same row, under the same conditions, comes from a RoboyVecEnv of one env, which resets
-        # itself on done and returns the reset observation.  RoboyEnv, one env stepped from the host, offers neither noise nor delay
-        # nor pushes (--push).
-        from .envs.vec_env import TENDON_OBS_CHANNELS, RoboyVecEnv
-        scale = dict(zip(TENDON_OBS_CHANNELS, ck["tendon_obs"]["scale"])) if tendon_obs else None
-        vec = RoboyVecEnv(MsjRobot(), 1, tendon_obs=tendon_obs or None, tendon_obs_scale=scale, sensor_noise=sensor_noise,
-                          action_delay=action_delay, action_obs=action_obs or None, goals=goal_rows, push=push)
+    env_kw, needs_vec_env = env_kwargs_from_checkpoint(ck)
+    if needs_vec_env:
+        # trained with tendon channels or the last actions in the observation, under sensor noise, an action delay or random pushes: the
+        # same row, under the same conditions, comes from a RoboyVecEnv of one env, which resets itself on done and returns the reset row
+        from .envs.vec_env import RoboyVecEnv
+        vec = RoboyVecEnv(MsjRobot(), 1, **env_kw)
         reset = lambda: vec.reset()[0]
 
         def step(a):
@@ -66,7 +54,7 @@ def main(argv=None):
             return o[0], float(r[0]), False
         n_obs, n_act = vec.observation_space.shape[0], vec.action_space.shape[0]
     else:
-        env = RoboyEnv(simulation_client=HipSimulationClient(robot=MsjRobot(), goals=goal_rows))
+        env = RoboyEnv(simulation_client=HipSimulationClient(robot=MsjRobot(), goals=env_kw["goals"]))
         reset = env.reset
 
         def step(a):
