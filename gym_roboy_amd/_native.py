@@ -80,6 +80,7 @@ class EnvConfig(ctypes.Structure):
 RB_IO_MAX_DELAY = 7
 RB_ACTION_OBS_MAX = 8      # rb_env_action_obs_configure: at most this many action rows behind the observation
 RB_DONE_NONE, RB_DONE_TERMINATED, RB_DONE_TRUNCATED = 0, 1, 2      # the done words while rb_env_done_kind_configure holds
+RB_EPISODE_LOG_MAX = 64     # rb_env_episode_log_configure: at most this many records per env
 
 # rb_env_critic_obs_configure: the blocks of a privileged critic row, in row order, with their bits; the widest row
 CRITIC_OBS_BLOCKS = ("state", "age", "params", "delay", "actions")
@@ -198,6 +199,12 @@ SIGNATURES = {
     "rb_env_push_configure": (ctypes.c_int, [_sim, ctypes.POINTER(EnvPushConfig)]),
     "rb_env_push_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "rb_env_push_count": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]),
+    "rb_env_episode_log_configure": (ctypes.c_int, [_sim, ctypes.c_int32]),
+    "rb_env_episode_log_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                              ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int32)]),
+    "rb_env_episode_log_clear": (ctypes.c_int, [_sim]),
+    "rb_env_episode_log_summary": (ctypes.c_int, [_sim, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
+    "rb_env_episode_log_summary_dev": (ctypes.c_int, [_sim, ctypes.c_int32, _vp]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

@@ -1,7 +1,7 @@
 // env_host.hpp - the fused env layer and its options on the host.
 // Part of roboy_sim.hip (included there once, at file scope, behind the dispatch table; not a stand-alone header): everything
 // RoboyEnv.step's layer (rb_env_*) and its options - per-env parameters, tendon channels, io and the action ring, action rows,
-// episode-end codes, critic rows, the goal pool with its curriculum and row counts, reward shaping, random pushes - do outside a kernel.  Each option is ONE record in
+// episode-end codes, critic rows, the goal pool with its curriculum and row counts, reward shaping, random pushes, the episode log - do outside a kernel.  Each option is ONE record in
 // rb_sim (roboy_sim.hip), is switched by ONE entry point that opens with reconfigure(), and has ONE line in behind_step() /
 // behind_reset() if it launches anything there.  The kernels are in env_*.hpp and roboy_sim.hip; which env-step kernel runs is the
 // dispatch table's business, or extension_launch()'s where extension_serves().  DESIGN.md §6 has the table of options.
@@ -352,6 +352,39 @@ int shaping_restart(rb_sim *s) {
     RB_HIP(hipMemsetAsync(s->shaping.d_cost, 0, sizeof(float) * size_t(s->n), s->stream));
     return RB_OK;
 }
+// ---- episode log (env_episode_log.hpp): one launch behind an env step, over the envs [i0, i0 + cnt) ----
+int episode_log_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const float *d_reward, const uint32_t *d_done) {
+    if (cnt <= 0) return RB_OK;
+    const OptEpisodeLog &o = s->elog;
+    rbel::LogArgs a;
+    a.reward = d_reward; a.done = d_done; a.reached = s->d_ep_cnt + 2 * size_t(s->n);
+    a.acc = o.d_acc; a.age = o.d_age; a.seen = o.d_seen; a.count = o.d_count;
+    a.ret = o.d_ret; a.len = o.d_len; a.kind = o.d_kind; a.full = o.d_full;
+    a.n = s->n; a.i0 = i0; a.i1 = i0 + cnt;
+    a.E = uint32_t(o.E); a.pad_ = 0;
+    hipLaunchKernelGGL(rbel::episode_log_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, a);
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
+// the running episodes to zero (a reset: the episode it abandons is not recorded; records and counts stay)
+int episode_log_restart(rb_sim *s) {
+    RB_HIP(hipMemsetAsync(s->elog.d_acc, 0, sizeof(float) * size_t(s->n), s->stream));
+    RB_HIP(hipMemsetAsync(s->elog.d_age, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
+    return RB_OK;
+}
+// `seen` follows the goals-reached counters as they stand: the next episode end is judged against them
+int episode_log_rebase(rb_sim *s) {
+    RB_HIP(hipMemcpyAsync(s->elog.d_seen, s->d_ep_cnt + 2 * size_t(s->n), sizeof(uint32_t) * size_t(s->n), hipMemcpyDeviceToDevice, s->stream));
+    return RB_OK;
+}
+// no records, no episode under way (rb_env_episode_log_configure, rb_env_episode_log_clear); the record planes keep their content,
+// which nothing reads at or beyond count
+int episode_log_clear(rb_sim *s) {
+    RB_HIP(hipMemsetAsync(s->elog.d_count, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
+    RB_HIP(hipMemsetAsync(s->elog.d_full, 0, sizeof(uint32_t), s->stream));
+    RB_RC(episode_log_restart(s));
+    return episode_log_rebase(s);
+}
 
 // ---- the episode counters and the planes that mirror them ----
 // d_ep_sum, d_ep_cnt (episodes, lengths, goals reached), d_infeas_n and env_steps count since the last clear; d_done_seen (episode-end
@@ -361,7 +394,9 @@ int shaping_restart(rb_sim *s) {
 //     handle without the env layer has only d_infeas_n and env_steps to clear.  The shaping sums are cleared by the former only:
 //     rb_env_stats(reset) leaves them to rb_env_shaping_stats(reset)
 //   COUNTERS_REBASE (rb_env_reset_dev): a reset is no episode end - the counters stand, d_done_seen is set to them and no code is
-//     reported; d_goal_seen is re-based by the curriculum's own kernel, which behind_reset launches
+//     reported; d_goal_seen is re-based by the curriculum's own kernel, which behind_reset launches; the episode log's `seen` is set to
+//     them too.  The log's plane is zeroed with the others where the counters are: a clear in the middle of a run would otherwise
+//     mislabel the next outcome of every env
 enum CounterSite { COUNTERS_CONFIGURE, COUNTERS_CLEAR, COUNTERS_REBASE };
 int done_rebase(rb_sim *s) {
     const size_t plane = sizeof(uint32_t) * size_t(s->n);
@@ -370,13 +405,17 @@ int done_rebase(rb_sim *s) {
     return RB_OK;
 }
 int episode_counters(rb_sim *s, CounterSite site) {
-    if (site == COUNTERS_REBASE) return s->done.on ? done_rebase(s) : RB_OK;
+    if (site == COUNTERS_REBASE) {
+        if (s->elog.E) RB_RC(episode_log_rebase(s));
+        return s->done.on ? done_rebase(s) : RB_OK;
+    }
     const size_t n = size_t(s->n);
     if (site == COUNTERS_CONFIGURE || s->env_ready) {
         RB_HIP(hipMemsetAsync(s->d_ep_sum, 0, sizeof(double) * n * 2, s->stream));
         RB_HIP(hipMemsetAsync(s->d_ep_cnt, 0, sizeof(uint32_t) * n * 3, s->stream));
         if (s->done.on) RB_HIP(hipMemsetAsync(s->done.d_seen, 0, sizeof(uint32_t) * n, s->stream));
         if (s->goals.L) RB_HIP(hipMemsetAsync(s->goals.d_seen, 0, sizeof(uint32_t) * n, s->stream));
+        if (s->elog.E) RB_HIP(hipMemsetAsync(s->elog.d_seen, 0, sizeof(uint32_t) * n, s->stream));
     }
     RB_HIP(hipMemsetAsync(s->d_infeas_n, 0, sizeof(uint32_t) * n, s->stream));
     s->env_steps = 0.0;
@@ -392,7 +431,8 @@ int episode_counters(rb_sim *s, CounterSite site) {
 //           0. shaping apply - reward -= cost, the cost statistics; reads the done words as flags, like 1.
 //           1. goal pool / curriculum / row counts - the done envs' new goal becomes a pool row, IN FRONT of everything that reads the goal
 //           2. critic rows - from the planes as 1. left them
-//           3. episode-end codes - last: it turns the range's done words, which 1. reads as flags, into codes
+//           3. episode log - the reward as 0. left it (what the caller receives), the done words still flags
+//           4. episode-end codes - last: it turns the range's done words, which 0., 1. and 3. read as flags, into codes
 //   reset:  the reset kernel
 //           1. observation rows (channels, action rows) - the tendon columns at the zero pose, every set-point 0
 //           2. the done-seen re-base (episode_counters)
@@ -401,11 +441,13 @@ int episode_counters(rb_sim *s, CounterSite site) {
 //           5. goal pool / curriculum - every env's goal becomes the pool row of the draw the reset kernel made, in the rows too
 //           6. critic rows - behind every kernel that wrote the rows above
 //           7. shaping - the running episode costs and the cost plane to zero (step_num is 1: the rate term restarts by itself)
+//           8. episode log - the running return and age to zero: the abandoned episode is not recorded, records and counts stay
 // A new option that launches behind either adds its line here.
 int behind_step(rb_sim *s, long i0, long cnt, hipStream_t stream, float *d_obs, float *d_reward, uint32_t *d_done, float *d_cobs) {
     if (s->shaping.on) RB_RC(shaping_apply_launch(s, i0, cnt, stream, d_reward, d_done));
     if (s->goals.d_pool) RB_RC(goal_pool_launch(s, i0, cnt, stream, d_done, d_obs));
     if (s->critic.mask) RB_RC(critic_launch(s, i0, cnt, stream, d_obs, d_cobs ? d_cobs : s->critic.d_rows));
+    if (s->elog.E) RB_RC(episode_log_launch(s, i0, cnt, stream, d_reward, d_done));
     if (s->done.on) {
         hipLaunchKernelGGL(done_kind_kernel, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, d_done, s->d_ep_cnt + 2 * size_t(s->n),
                            s->done.d_seen, s->done.d_kind, i0, i0 + cnt);
@@ -441,6 +483,7 @@ int behind_reset(rb_sim *s, float *d_obs) {
         RB_RC(critic_launch(s, 0, s->n, s->stream, d_obs, s->critic.d_rows));
     }
     if (s->shaping.on) RB_RC(shaping_restart(s));
+    if (s->elog.E) RB_RC(episode_log_restart(s));
     return RB_OK;
 }
 
@@ -1095,6 +1138,79 @@ int rb_env_push_count(rb_sim *s, uint64_t *pushes, int reset) {
     RB_HIP(hipStreamSynchronize(s->stream));
     *pushes = uint64_t(total);
     if (reset) RB_HIP(hipMemsetAsync(o.d_n, 0, sizeof(uint32_t) * size_t(s->n), s->stream));
+    return RB_OK;
+}
+
+// ---- per-env episode records behind the fused env step (env_episode_log.hpp) ----
+int rb_env_episode_log_configure(rb_sim *s, int32_t capacity) {
+    // nothing in flight may still write the planes, and a captured graph holds the launches of the handle as it was
+    RB_RC(reconfigure(s, NEEDS_ENV | DROP_GRAPHS, [&]() -> int {
+        if (capacity < 0 || capacity > RB_EPISODE_LOG_MAX)
+            return fail(RB_EINVAL, "episode log: capacity must be in 0 .. RB_EPISODE_LOG_MAX = 64 (0 switches it off), got " + std::to_string(capacity));
+        return RB_OK;
+    }));
+    OptEpisodeLog &o = s->elog;
+    if (!capacity) { o.release(); return RB_OK; }
+    const size_t n = size_t(s->n), E = size_t(capacity);
+    if (o.E != capacity) {
+        auto alloc = [](auto **d, size_t bytes) { return dev_alloc(d, bytes, "hipMalloc (episode log): "); };
+        OptEpisodeLog fresh;
+        int rc = alloc(&fresh.d_acc, sizeof(float) * n);
+        if (rc == RB_OK) rc = alloc(&fresh.d_age, sizeof(uint32_t) * n);
+        if (rc == RB_OK) rc = alloc(&fresh.d_seen, sizeof(uint32_t) * n);
+        if (rc == RB_OK) rc = alloc(&fresh.d_count, sizeof(uint32_t) * n);
+        if (rc == RB_OK) rc = alloc(&fresh.d_ret, sizeof(float) * E * n);
+        if (rc == RB_OK) rc = alloc(&fresh.d_len, sizeof(uint32_t) * E * n);
+        if (rc == RB_OK) rc = alloc(&fresh.d_kind, sizeof(uint32_t) * E * n);
+        if (rc == RB_OK) rc = alloc(&fresh.d_full, sizeof(uint32_t));
+        if (rc == RB_OK) rc = alloc(&fresh.d_red, sizeof(double) * 8 * (rbel::SUMMARY_BLOCKS + 2));
+        if (rc) { fresh.release(); return rc; }      // (the handle as it was)
+        o.release();
+        o = fresh;
+        o.E = capacity;
+        RB_HIP(hipMemsetAsync(o.d_red, 0, sizeof(double) * 8 * (rbel::SUMMARY_BLOCKS + 2), s->stream));      // (the ticket word)
+    }
+    RB_HIP(hipMemsetAsync(o.d_ret, 0, sizeof(float) * E * n, s->stream));
+    RB_HIP(hipMemsetAsync(o.d_len, 0, sizeof(uint32_t) * E * n, s->stream));
+    RB_HIP(hipMemsetAsync(o.d_kind, 0, sizeof(uint32_t) * E * n, s->stream));
+    return episode_log_clear(s);
+}
+int rb_env_episode_log_ptr(rb_sim *s, uint32_t **d_count, float **d_ret, uint32_t **d_len, uint32_t **d_kind, uint32_t **d_full, int32_t *capacity) {
+    if (check(s) || s->elog.need()) return RB_EINVAL;
+    if (d_count) *d_count = s->elog.d_count;
+    if (d_ret) *d_ret = s->elog.d_ret;
+    if (d_len) *d_len = s->elog.d_len;
+    if (d_kind) *d_kind = s->elog.d_kind;
+    if (d_full) *d_full = s->elog.d_full;
+    if (capacity) *capacity = s->elog.E;
+    return RB_OK;
+}
+int rb_env_episode_log_clear(rb_sim *s) {
+    if (check(s) || s->elog.need()) return RB_EINVAL;
+    RB_HIP(hipSetDevice(s->device));
+    // (no drain, no graph dropped: memsets and one copy on the handle's stream, behind whatever was enqueued or replayed there; a
+    // captured env step holds the planes' addresses and finds them cleared)
+    return episode_log_clear(s);
+}
+int rb_env_episode_log_summary_dev(rb_sim *s, int32_t first_k, double *d_out8) {
+    if (check(s) || s->elog.need()) return RB_EINVAL;
+    if (first_k < 1) return fail(RB_EINVAL, "episode log summary: first_k must be >= 1");
+    RB_HIP(hipSetDevice(s->device));
+    const OptEpisodeLog &o = s->elog;
+    unsigned g = blocks_for(s->n, 256);
+    if (g > unsigned(rbel::SUMMARY_BLOCKS)) g = rbel::SUMMARY_BLOCKS;
+    double *partials = o.d_red + 8;
+    unsigned int *ticket = reinterpret_cast<unsigned int *>(o.d_red + 8 * (rbel::SUMMARY_BLOCKS + 1));
+    hipLaunchKernelGGL(rbel::episode_log_summary, dim3(g), dim3(256), 0, s->stream, o.d_count, o.d_ret, o.d_len, o.d_kind, uint32_t(first_k), partials,
+                       ticket, o.d_red, d_out8, long(s->n));
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
+int rb_env_episode_log_summary(rb_sim *s, int32_t first_k, double *out8) {
+    if (check(s) || !out8) return fail(RB_EINVAL, "null argument");
+    RB_RC(rb_env_episode_log_summary_dev(s, first_k, nullptr));
+    RB_HIP(hipMemcpyAsync(out8, s->elog.d_red, sizeof(double) * 8, hipMemcpyDeviceToHost, s->stream));
+    RB_HIP(hipStreamSynchronize(s->stream));
     return RB_OK;
 }
 

@@ -56,6 +56,7 @@
 #include "env_goal.hpp"               // goals drawn from a pool of poses (rb_env_goal_pool_*)
 #include "env_shaping.hpp"            // action-rate and effort reward terms around the fused env step (rb_env_shaping_*)
 #include "env_push.hpp"               // random velocity pushes in front of the fused env step (rb_env_push_*)
+#include "env_episode_log.hpp"        // per-env episode records behind the fused env step (rb_env_episode_log_*)
 
 namespace {
 
@@ -549,6 +550,22 @@ struct OptPush {
     }
     int need() const { return on ? RB_OK : fail(RB_EINVAL, "random pushes are not configured (rb_env_push_configure)"); }
 };
+// Episode log (env_episode_log.hpp; rb_env_episode_log_*): while E > 0, every env-step launch is followed by episode_log_kernel over
+// its range.  Planes [n_envs] each: the running return and age of the current episode, the goals-reached counter d_ep_cnt[2n + i] as of
+// the env's last episode end (a copy of its own, like the curriculum's), records written; records [E][n_envs] each: return, length,
+// outcome; d_full: the number of envs with E records; d_red: the summary's result [8], block partials [SUMMARY_BLOCKS][8], ticket
+struct OptEpisodeLog {
+    int E = 0;
+    float *d_acc = nullptr, *d_ret = nullptr;
+    uint32_t *d_age = nullptr, *d_seen = nullptr, *d_count = nullptr, *d_len = nullptr, *d_kind = nullptr, *d_full = nullptr;
+    double *d_red = nullptr;
+    void release() {
+        (void)hipFree(d_acc); (void)hipFree(d_ret); (void)hipFree(d_age); (void)hipFree(d_seen); (void)hipFree(d_count); (void)hipFree(d_len);
+        (void)hipFree(d_kind); (void)hipFree(d_full); (void)hipFree(d_red);
+        *this = OptEpisodeLog{};
+    }
+    int need() const { return E ? RB_OK : fail(RB_EINVAL, "the episode log is not configured (rb_env_episode_log_configure)"); }
+};
 
 }  // namespace
 
@@ -643,6 +660,7 @@ struct rb_sim {
     OptParams par; OptChannels chan; OptIo io; OptActionRows hist; OptDoneKind done; OptCritic critic; OptGoals goals;      // the env layer's options (above)
     OptShaping shaping;
     OptPush push;
+    OptEpisodeLog elog;
     float qd_max[32] = {};               // the description's velocity bounds, as every step kernel holds them (fp32)
     int obs_dim() const { return 3 * n_q + rbo::n_channels(chan.mask) * n_t + hist.rows * n_t; }
     int critic_width() const { return rbc::row_dim(critic.mask, n_q, par.on ? par.n : 0, hist.rows * n_t); }
@@ -1066,7 +1084,7 @@ void rb_destroy(rb_sim *s) {
     (void)hipFree(s->d_state_rows); (void)hipHostFree(s->h_state_rows);
     (void)hipFree(s->d_goal); (void)hipFree(s->d_ep_ret); (void)hipFree(s->d_ep_sum); (void)hipFree(s->d_ep_cnt);
     (void)hipFree(s->d_step_num); (void)hipFree(s->d_infeas_n); (void)hipFree(s->d_stats);
-    s->par.release(); s->chan.release(); s->io.release(); s->hist.release(); s->done.release(); s->critic.release(); s->goals.release(); s->shaping.release(); s->push.release();
+    s->par.release(); s->chan.release(); s->io.release(); s->hist.release(); s->done.release(); s->critic.release(); s->goals.release(); s->shaping.release(); s->push.release(); s->elog.release();
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1476,6 +1494,9 @@ int rb_rollout_fused_dev(rb_sim *s, const float *d_ring, int ring, int n_steps, 
     if (s->push.on)
         return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) steps inside one kernel and cannot apply random pushes "
                                      "(rb_env_push_configure(sim, NULL) first)");
+    if (s->elog.E)
+        return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) ends episodes inside one kernel and cannot record them in the episode log "
+                                     "(rb_env_episode_log_configure(sim, 0) first)");
     if (s->goals.d_pool)
         return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) redraws goals inside one kernel and cannot draw them from a goal pool");
     if (n_steps == 0) return RB_OK;

@@ -157,6 +157,34 @@ def push_spec(push, n_q: int):
     return {"prob": float(p), "sigma": [float(v) for v in sig], "threshold": threshold}
 
 
+def episode_log_capacity(episode_log) -> int:
+    """None -> 0 (the option is off), E -> E: the number of finished episodes the env records per env, 1 <= E <= 64.  ``ValueError``
+    for anything else (0 too: an env without the option is ``episode_log=None``)."""
+    if episode_log is None:
+        return 0
+    if isinstance(episode_log, bool) or not isinstance(episode_log, (int, np.integer)) or not 1 <= int(episode_log) <= nat.RB_EPISODE_LOG_MAX:
+        raise ValueError("episode_log: an int, 1 <= E <= %d, got %r" % (nat.RB_EPISODE_LOG_MAX, episode_log))
+    return int(episode_log)
+
+
+EPISODE_LOG_SUMS = ("n_records", "sum_return", "sum_return_sq", "sum_length", "n_terminated", "n_truncated", "n_complete")
+
+
+def episode_log_figures(sums, num_envs: int) -> dict:
+    """the eight sums of ``rb_env_episode_log_summary`` (over one env batch, or added up over several of ``num_envs`` envs in all) ->
+    ``episode_log_summary``'s dict"""
+    out = {key: float(v) for key, v in zip(EPISODE_LOG_SUMS, sums)}
+    n = out["n_records"]
+    nan = float("nan")
+    out["mean_return"] = out["sum_return"] / n if n else nan
+    out["std_return"] = max(out["sum_return_sq"] / n - out["mean_return"] ** 2, 0.0) ** 0.5 if n else nan
+    out["mean_length"] = out["sum_length"] / n if n else nan
+    out["success_rate"] = out["n_terminated"] / n if n else nan
+    out["truncated_rate"] = out["n_truncated"] / n if n else nan
+    out["complete"] = bool(out["n_complete"] == num_envs)
+    return out
+
+
 # ---- the command line (train_parallel) ----
 def parse_key_values(text, name, form="KEY=VALUE", check=lambda values: None):
     """``key=1.5,other=2`` -> ``{"key": 1.5, "other": 2.0}`` ('' -> None); ``ValueError`` in the option's ``name`` for a malformed item"""
@@ -258,18 +286,23 @@ ENV_FLAGS = (
     ("--push", str, "", "prob=P,sigma=S", "random velocity pushes, an external disturbance on the device: in front of every env step each env is "
      "pushed with probability P, a pushed env's joint velocities get S * z added (z standard normal, S in rad/s) and are clamped to the robot's "
      "bounds, e.g. prob=0.02,sigma=0.5; the round's statistics then show pushes_per_step; recorded in the checkpoint"),
+    ("--episode-log", int, 0, "E", "record every env's first E finished episodes (at most 64) on the device: return, length and whether the goal "
+     "was reached (RoboyVecEnv.episode_log, episode_log_summary); a condition of the run, recorded in the checkpoint and not replayed"),
 )
+
+N_LATE_ENV_FLAGS = 3                             # ENV_FLAGS' last rows: declared behind the agent's flags
 
 
 def add_env_arguments(ap, late: bool = False):
     """Declare the env's flags on ``ap``: the observation and goal flags, or (``late=True``) the reward and disturbance flags."""
-    for flag, kind, default, metavar, text in (ENV_FLAGS[-2:] if late else ENV_FLAGS[:-2]):
+    for flag, kind, default, metavar, text in (ENV_FLAGS[-N_LATE_ENV_FLAGS:] if late else ENV_FLAGS[:-N_LATE_ENV_FLAGS]):
         ap.add_argument(flag, type=kind, default=default, metavar=metavar, help=text)
 
 
 def env_kwargs_from_args(args) -> dict:
     """The parsed command line -> ``RoboyVecEnv``'s keyword arguments, all but what only the running process knows (``goals``, the pool
-    ``--goals`` asks for; ``device``; ``env_id_offset``).  An option that is off is None, or absent (``goal_row_stats``, ``reward_shaping``, ``push``)."""
+    ``--goals`` asks for; ``device``; ``env_id_offset``).  An option that is off is None, or absent (``goal_row_stats``, ``reward_shaping``, ``push``,
+    ``episode_log``)."""
     noise = parse_key_values(args.sensor_noise, "sensor noise", "KEY=SIGMA")         # (a bad flag is reported in this order)
     delay = [int(x) for x in args.action_delay.split(":")] if args.action_delay else None
     scale = parse_key_values(args.tendon_obs_scale, "tendon obs scale", "CHANNEL=FACTOR")
@@ -279,7 +312,8 @@ def env_kwargs_from_args(args) -> dict:
               report_truncation=args.bootstrap_timeouts, action_obs=args.action_obs or None,
               critic_obs=tuple(c for c in args.critic_obs.split(",") if c) or None, goal_curriculum=curriculum)
     late = {"goal_row_stats": parse_goal_order(args.goal_order, args.goal_reorder_every, curriculum),
-            "reward_shaping": parse_reward_shaping(args.reward_shaping), "push": parse_push(args.push)}
+            "reward_shaping": parse_reward_shaping(args.reward_shaping), "push": parse_push(args.push),
+            "episode_log": episode_log_capacity(getattr(args, "episode_log", 0) or None)}
     return dict(kw, **{key: value for key, value in late.items() if value})
 
 
@@ -322,13 +356,17 @@ def env_checkpoint_record(env, critic=None) -> dict:
         ck["reward_shaping"] = {k: float(v) for k, v in shaping.items()}
     if (push := getattr(env, "push", None)) is not None:
         ck["env_push"] = {"prob": float(push["prob"]), "sigma": [float(v) for v in push["sigma"]], "threshold": int(push["threshold"])}
+    if (capacity := getattr(env, "episode_log_capacity", 0)):
+        ck["episode_log"] = int(capacity)
     return ck
 
 
 def check_env_checkpoint(env, ck, critic_dim=None) -> dict:
     """``load()``'s env side.  ``ValueError`` where the checkpoint's rows are not this env's (tendon channels; with ``critic_dim``, the width an
     asymmetric agent reads, the critic rows); a warning where the reward-shaping weights differ (the env's hold); the curriculum's levels go into
-    an env with as many levels and envs.  Returns what the env does not take over: ``{"goals", "goal_row_stats", "goal_curriculum", "env_push"}``."""
+    an env with as many levels and envs.  Returns what the env does not take over: ``{"goals", "goal_row_stats", "goal_curriculum", "env_push"}``.  ``episode_log`` (the
+    capacity of the run that wrote the checkpoint) is a condition of that run, never a layout: it must be a capacity (``ValueError`` otherwise), is
+    neither taken over nor kept, and this env's own capacity holds, whatever it is."""
     old, own = ck.get("tendon_obs", tendon_obs_record(None)), tendon_obs_record(env)
     if old != own:
         raise ValueError("the checkpoint was trained on the observation %r, this env gives %r (RoboyVecEnv's tendon_obs / tendon_obs_scale)" % (old, own))
@@ -340,6 +378,8 @@ def check_env_checkpoint(env, ck, critic_dim=None) -> dict:
         import warnings
         warnings.warn("the checkpoint was trained with reward_shaping=%r, this env runs reward_shaping=%r"
                       % (ck.get("reward_shaping"), getattr(env, "reward_shaping", None)))
+    if "episode_log" in ck:
+        episode_log_capacity(ck["episode_log"])
     kept = {k: ck.get(k) for k in ("goals", "goal_row_stats", "goal_curriculum", "env_push")}
     saved, own = kept["goal_curriculum"], getattr(env, "goal_curriculum", None)
     if saved is not None and own is not None and own["levels"] == int(saved["levels"]) and int(saved["level"].numel()) == env.num_envs:
@@ -362,4 +402,5 @@ def env_kwargs_from_checkpoint(ck):
     # goal_curriculum: playback draws from the whole pool, the top level's draw
     # goal_row_stats: counts of the training run, nothing a step reads
     # reward_shaping: shapes the reward the trainer saw; playback prints the task's reward
+    # episode_log: a condition of the run that wrote the checkpoint, no layout; whoever evaluates asks for the capacity it needs
     return kw, any(kw[k] for k in ("tendon_obs", "sensor_noise", "action_delay", "action_obs", "push"))

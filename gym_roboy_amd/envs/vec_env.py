@@ -26,7 +26,7 @@ from .._gymcompat import spaces
 from . import goals as envgoals
 from . import reward as rw
 from .options import (SENSOR_NOISE_KEYS, TENDON_OBS_CHANNELS, _TENDON_OBS_BOUNDS, action_delay_range, action_obs_bounds,  # noqa: F401
-                      action_obs_rows, critic_obs_spec, parse_push, parse_reward_shaping, push_spec, reward_shaping_weights,
+                      action_obs_rows, critic_obs_spec, episode_log_capacity, episode_log_figures, parse_push, parse_reward_shaping, push_spec, reward_shaping_weights,
                       sensor_noise_sigmas, tendon_obs_mask, tendon_obs_scales)
 from .robots import RoboyRobot
 from .simulations.hip_simulation_client import HipBatchSimulation
@@ -43,7 +43,7 @@ class RoboyVecEnv:
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
                  randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None,
                  report_truncation: bool = False, action_obs=None, critic_obs=None, goals=None, goal_curriculum=None,
-                 goal_row_stats: bool = False, reward_shaping=None, push=None):
+                 goal_row_stats: bool = False, reward_shaping=None, push=None, episode_log=None):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
@@ -104,7 +104,16 @@ class RoboyVecEnv:
         runs from that state as it always did (every robot, every kernel form, every option above).  ``push`` holds
         the record (None without the option), ``last_push()`` returns who was pushed in the last step and by how much,
         ``push_count()`` the number of pushes so far.  None, ``prob`` 0 or all-zero sigmas: the env launches exactly what it launched
-        before."""
+        before.
+        ``episode_log``: an int ``E`` (1..64) - the device keeps each env's first E finished episodes since the log was last cleared:
+        return (the sum of the rewards ``step`` returned, so with ``reward_shaping`` the shaped ones, added up in fp32 in step order),
+        length and outcome (``_native.RB_DONE_TERMINATED``: the goal was reached, ``RB_DONE_TRUNCATED``: the time limit alone ended
+        it), written by one small kernel behind every env step (every robot, every kernel form, every option above,
+        sub-ranges and captured graphs).  Every env contributes exactly its first E episodes, so the figures are not biased towards
+        short episodes as totals over whatever ended are.  ``reset()`` drops the episode under way without recording it.
+        ``episode_log()`` reads the records, ``episode_log_summary(first_k)`` their sums and rates, ``episode_log_full()`` how many
+        envs have all E, ``clear_episode_log()`` starts over; ``episode_log_capacity`` holds E (0 without the option).  None: the env
+        launches exactly what it launched before."""
         desc = robot.get_description()
         # 1. every ValueError of a bad option, before anything is allocated
         crit_names, crit_mask, crit_dim = critic_obs_spec(critic_obs, desc.n_q, desc.n_t, randomization is not None, action_delay, action_obs)
@@ -115,6 +124,7 @@ class RoboyVecEnv:
         n_action_rows = action_obs_rows(action_obs)
         shaping = reward_shaping_weights(reward_shaping)
         push_rec = push_spec(push, desc.n_q)
+        log_capacity = episode_log_capacity(episode_log)
         curriculum = envgoals.goal_curriculum_spec(goal_curriculum)
         if curriculum is not None:
             if goals is None:
@@ -126,7 +136,7 @@ class RoboyVecEnv:
             raise ValueError("goal_row_stats needs goal_curriculum= (the counts are kept by the row each env holds, the curriculum's index "
                              "plane; goal_curriculum=1 is the plain pool plus that plane)")
         # 2. the simulation and the plain env layer (rb_env_configure)
-        self.robot, self.num_envs = robot, int(num_envs)
+        self.robot, self.num_envs, self.max_episode_length = robot, int(num_envs), int(max_episode_length)
         self.sim = HipBatchSimulation(robot, num_envs, integrator=integrator, n_substeps=n_substeps, device=device, seed=seed, env_id_offset=env_id_offset)
         angles, vels, acts = robot.get_joint_angles_space(), robot.get_joint_vels_space(), robot.get_action_space()
         self.n_q, self.n_t, self.obs_dim = self.sim.n_q, self.sim.n_t, 3 * self.sim.n_q
@@ -149,7 +159,8 @@ class RoboyVecEnv:
         self.goal_recipe = dict(goals.recipe) if isinstance(goals, envgoals.GoalPool) else {}
         nat.check(self.sim._lib.rb_env_configure(self.sim.handle, ctypes.byref(cfg)))
         # 3. the options, in the one order they take (a call puts its kernels in the place of, in front of or behind those of the calls before
-        # it): pool, curriculum, row counts, tendon channels, action rows, buffers, randomization, io, truncation, critic rows, shaping, pushes
+        # it): pool, curriculum, row counts, tendon channels, action rows, buffers, randomization, io, truncation, critic rows, shaping, pushes,
+        # episode log
         self._configure_goal_pool(pool_rows)
         self._configure_goal_curriculum(curriculum)
         self._configure_goal_row_stats(goal_row_stats)
@@ -162,6 +173,7 @@ class RoboyVecEnv:
         self._configure_critic_obs(crit_names, crit_mask, crit_dim)
         self._configure_shaping(shaping)
         self._configure_push(push_rec)
+        self._configure_episode_log(log_capacity)
 
     def _configure_goal_pool(self, pool_rows):
         self.goal_pool_size = 0               # the pool's number of rows m; 0: the env draws its goals from the box
@@ -281,6 +293,13 @@ class RoboyVecEnv:
             for j, v in enumerate(push_rec["sigma"]):
                 pcfg.sigma[j] = v
             self._or_close(lambda: nat.check(self.sim._lib.rb_env_push_configure(self.sim.handle, ctypes.byref(pcfg))))
+
+    def _configure_episode_log(self, capacity):
+        self.episode_log_capacity = capacity
+        if capacity:
+            # last, before anything is captured into a graph: every env-step launch is followed by the small kernel that keeps the
+            # records (behind the shaping apply, whose reward it adds up; in front of the kernel that writes the episode-end codes)
+            self._or_close(lambda: nat.check(self.sim._lib.rb_env_episode_log_configure(self.sim.handle, capacity)))
 
     def _or_close(self, configure):
         """an option the library refuses (a joint tree asked for a ball-joint option) must not leave the simulation's handle behind"""
@@ -612,6 +631,56 @@ class RoboyVecEnv:
         out = ctypes.c_uint64()
         nat.check(self.sim._lib.rb_env_push_count(self.sim.handle, ctypes.byref(out), int(bool(reset))))
         return int(out.value)
+
+    # -- episode log (rb_env_episode_log_*) ------------------
+    def _episode_log_planes(self):
+        self._need(self.episode_log_capacity, "this RoboyVecEnv keeps no episode log (episode_log=None)")
+        p = [ctypes.c_void_p() for _ in range(5)]
+        capacity = ctypes.c_int32()
+        nat.check(self.sim._lib.rb_env_episode_log_ptr(self.sim.handle, *[ctypes.byref(x) for x in p], ctypes.byref(capacity)))
+        assert capacity.value == self.episode_log_capacity
+        return [x.value for x in p]            # count, ret, len, kind, full
+
+    def episode_log(self) -> dict:
+        """``{"count": [N], "return": [N, E], "length": [N, E], "kind": [N, E]}`` (numpy; int64, float32, int64, int64), read after a
+        synchronisation: env ``i``'s record ``k < count[i]`` is its ``k``-th episode that ended since the log was last cleared; entries
+        at or beyond ``count`` are zero.  Needs ``episode_log``."""
+        d_count, d_ret, d_len, d_kind, _ = self._episode_log_planes()
+        n, E = self.num_envs, self.episode_log_capacity
+        self.sim.synchronize()
+        count = self.sim.download(d_count, (n,), np.uint32).astype(np.int64)
+        live = np.arange(E)[None, :] < count[:, None]
+        planes = (self.sim.download(d_ret, (E, n)), self.sim.download(d_len, (E, n), np.uint32).astype(np.int64),
+                  self.sim.download(d_kind, (E, n), np.uint32).astype(np.int64))
+        ret, length, kind = (np.where(live, np.ascontiguousarray(x.T), x.dtype.type(0)) for x in planes)
+        return {"count": count, "return": ret, "length": length, "kind": kind}
+
+    def episode_log_summary(self, first_k=None) -> dict:
+        """The records ``k < min(count[i], first_k)`` of every env, reduced on the device in a fixed order (the same planes give the
+        same bits; the counts are exact): ``{"n_records", "sum_return", "sum_return_sq", "sum_length", "n_terminated", "n_truncated",
+        "n_complete"}`` - the last the number of envs with at least ``first_k`` records - and from them ``mean_return``, ``std_return``
+        (population), ``mean_length``, ``success_rate`` (terminated over records), ``truncated_rate`` and ``complete`` (every env has
+        its ``first_k``); the means and rates are NaN without a record.  ``first_k=None``: the capacity.  Needs ``episode_log``."""
+        self._need(self.episode_log_capacity, "this RoboyVecEnv keeps no episode log (episode_log=None)")
+        k = self.episode_log_capacity if first_k is None else first_k
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError("first_k: an int >= 1, got %r" % (first_k,))
+        out = (ctypes.c_double * 8)()
+        nat.check(self.sim._lib.rb_env_episode_log_summary(self.sim.handle, int(k), out))
+        return episode_log_figures(list(out), self.num_envs)
+
+    def episode_log_full(self) -> int:
+        """The number of envs that have all ``episode_log`` records: one 4-byte read behind a synchronisation.  Needs ``episode_log``."""
+        d_full = self._episode_log_planes()[4]
+        self.sim.synchronize()
+        return int(self.sim.download(d_full, (1,), np.uint32)[0])
+
+    def clear_episode_log(self):
+        """No records, no episode under way: every env records its next E episodes that START from here - an episode under way is
+        dropped from its return and length, so call it behind a ``reset()`` (or accept a first record that is the tail of an episode).
+        Enqueued on the env's stream; between replays of a captured graph it needs no new capture.  Needs ``episode_log``."""
+        self._need(self.episode_log_capacity, "this RoboyVecEnv keeps no episode log (episode_log=None)")
+        nat.check(self.sim._lib.rb_env_episode_log_clear(self.sim.handle))
 
     def tendon_state(self, actions=None):
         """Per-tendon state of every env at its current state (``HipBatchSimulation.tendon_state``), the set-points formed

@@ -906,6 +906,62 @@ class _MirrorMaps:
                                         c.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)))
 
 
+@torch.no_grad()
+def evaluate_policy(policy, env, episodes_per_env=1, poll_every=32, fused=None, obs_norm=None, cobs_norm=None, device="cuda"):
+    """Run ``policy``'s DETERMINISTIC action (the mean) on every env of ``env`` - a ``RoboyVecEnv`` with ``episode_log >=
+    episodes_per_env`` - until each env has finished ``episodes_per_env`` episodes, and return ``env.episode_log_summary(first_k=
+    episodes_per_env)`` plus ``"steps"``.  Every env contributes exactly its first ``episodes_per_env`` episodes (envs that finish early
+    go on stepping, unrecorded), so the figures are not biased towards short episodes.  The loop: reset, clear the log, then policy
+    step and ``env.step`` on device tensors; every ``poll_every`` steps one 4-byte read tells whether every env is done.  An episode
+    has at most ``env.max_episode_length`` steps, so ``episodes_per_env * max_episode_length`` steps always suffice: a log that is not
+    complete then is an error.  fused: a ``FusedPolicyStep`` over ``policy`` (its kernel then takes the step, with ``obs_norm`` /
+    ``cobs_norm`` as ``act_into`` takes them); None: ``policy.act`` (which applies the statistics the policy holds).  No statistics are
+    updated, no noise is drawn.  An asymmetric critic's value is not needed: the env's critic rows are handed where it writes them
+    at the policy's width, else zeros, and the value is discarded."""
+    E, poll = int(episodes_per_env), int(poll_every)
+    if E < 1 or poll < 1:
+        raise ValueError("episodes_per_env and poll_every must be >= 1, got %r and %r" % (episodes_per_env, poll_every))
+    obs_dim, act_dim = policy.pi[0].in_features, policy.pi[-1].out_features
+    if env.observation_space.shape[0] != obs_dim:
+        raise ValueError("the policy reads %d observation columns, this env gives %d: the row's layout (tendon_obs, action_obs) must be "
+                         "the one the policy was trained on" % (obs_dim, env.observation_space.shape[0]))
+    if int(getattr(env, "episode_log_capacity", 0) or 0) < E:
+        raise ValueError("evaluation of %d episodes per env needs an env built with episode_log >= %d, this one has episode_log=%r"
+                         % (E, E, getattr(env, "episode_log_capacity", 0) or None))
+    device = torch.device(device)
+    n = env.num_envs
+    obs = torch.as_tensor(env.reset(), dtype=torch.float32, device=device)
+    env.clear_episode_log()
+    cobs_dim = getattr(policy, "critic_obs_dim", None)
+    own_rows = cobs_dim is not None and getattr(env, "critic_obs_dim", 0) == cobs_dim
+    cobs = None
+    if cobs_dim is not None and fused is not None:
+        cobs = torch.as_tensor(env.critic_obs(), dtype=torch.float32, device=device) if own_rows else torch.zeros((n, cobs_dim), device=device)
+    if fused is not None:
+        packed = fused.pack()
+        act, logp, val = torch.empty((n, act_dim), device=device), torch.empty(n, device=device), torch.empty(n, device=device)
+    bound = E * int(env.max_episode_length)
+    steps = 0
+    while steps < bound:
+        if fused is not None:
+            fused.act_into(obs, act, logp, val, packed=packed, deterministic=True, norm=obs_norm, cobs=cobs, cnorm=cobs_norm)
+            action = act
+        else:
+            action = policy.act(obs, deterministic=True)[0].clamp(-1.0, 1.0).contiguous()
+        obs = env.step(action)[0]
+        if own_rows and fused is not None:
+            cobs = env.critic_obs()
+        steps += 1
+        if (steps % poll == 0 or steps == bound) and env.episode_log_full() == n:
+            break
+    summary = env.episode_log_summary(first_k=E)
+    if not summary["complete"]:
+        raise RuntimeError("evaluation: after %d steps (%d episodes of at most %d steps) only %d of %d envs have their %d records"
+                           % (steps, E, env.max_episode_length, summary["n_complete"], n, E))
+    summary["steps"] = steps
+    return summary
+
+
 class PPO:
     def __init__(self, env, policy=None, n_steps=128, nminibatches=4, noptepochs=4, gamma=0.99, lam=0.95,
                  learning_rate=2.5e-4, cliprange=0.2, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5,
@@ -1613,6 +1669,19 @@ class PPO:
         if self.lr_schedule is not None:
             stats["lr"] = self.learning_rate
         return stats
+
+    def evaluate(self, env, episodes_per_env=1, poll_every=32):
+        """The agent's deterministic policy on ``env`` - a ``RoboyVecEnv`` of its own with ``episode_log >= episodes_per_env``, under
+        whatever conditions it was built with - for exactly ``episodes_per_env`` episodes of every env (``evaluate_policy``): the
+        summary of ``env.episode_log_summary`` plus ``"steps"``.  The fused policy step where the agent has one, with the frozen
+        ``obs_norm``.  ``ValueError`` for the training env itself (evaluation never touches it, its carried observation, a captured
+        rollout or the noise counters), for another observation width and for a log capacity that is too small.
+        ``num_timesteps``, the step base and every optimiser and normaliser state are as before the call.  DESIGN.md §29."""
+        if env is self.env:
+            raise ValueError("evaluate() takes an env of its own: the training env carries the rollout's observation and episodes "
+                             "(build a second RoboyVecEnv with episode_log=%d)" % int(episodes_per_env))
+        return evaluate_policy(self.policy, env, episodes_per_env, poll_every, fused=self._fused, obs_norm=self.obs_norm,
+                               cobs_norm=self.cobs_norm, device=self.device)
 
     def learn(self, total_timesteps, log=None):
         target = self.num_timesteps + total_timesteps

@@ -19,6 +19,7 @@ from .envs.options import (DEFAULT_GOAL_POOL, ENV_INTEGRATOR, GOAL_ORDERS, add_e
                            parse_goal_curriculum, parse_goal_order, parse_goals)
 
 TRAINING_STEPS_BETWEEN_BACKUPS = 100000
+EVAL_SEED_OFFSET = 7919                         # --eval-every: the evaluation env's seed is the run's plus this
 
 
 def log_line(stats):
@@ -85,8 +86,16 @@ def main(argv=None):
     ap.add_argument("--symmetry-coef", type=float, default=1.0, metavar="C",
                     help="the weight of --symmetry loss's term (>= 0, default 1)")
     add_env_arguments(ap, late=True)
+    ap.add_argument("--eval-every", type=int, default=0, metavar="R",
+                    help="after every R-th round the deterministic policy is evaluated on a second env batch under the training conditions "
+                         "(another seed; exactly --eval-episodes episodes of each of --eval-envs envs per rank, PPO.evaluate); the round's "
+                         "statistics then show eval_success_rate, eval_mean_return and eval_mean_length; 0 (default): no second env")
+    ap.add_argument("--eval-envs", type=int, default=4096, metavar="N", help="evaluation envs per rank (default 4096)")
+    ap.add_argument("--eval-episodes", type=int, default=1, metavar="E", help="episodes per evaluation env, at most 64 (default 1)")
     args = ap.parse_args(argv)
     env_kw = env_kwargs_from_args(args)         # (bad values: before torch is imported or a GPU is touched)
+    if args.eval_every < 0 or (args.eval_every and (args.eval_envs < 1 or not 1 <= args.eval_episodes <= 64)):
+        raise SystemExit("--eval-every takes R >= 0, --eval-envs N >= 1 and --eval-episodes 1..64")
     goals_m, goal_curriculum, by_reach_rate = parse_goals(args.goals), env_kw["goal_curriculum"], "goal_row_stats" in env_kw
 
     import numpy as np
@@ -130,6 +139,12 @@ def main(argv=None):
                 bootstrap_timeouts=args.bootstrap_timeouts, lr_schedule=args.lr_schedule, desired_kl=args.desired_kl,
                 lr_min=args.lr_min, lr_max=args.lr_max, asymmetric_critic=bool(env_kw["critic_obs"]),
                 symmetry=args.symmetry, symmetry_coef=args.symmetry_coef)
+    eval_env = None
+    if args.eval_every:
+        # the training conditions on a batch of its own: a seed apart from training's, this rank's shard of the evaluation's global env
+        # ids, and a log of exactly the episodes asked for (the training env's own --episode-log, if any, stays the training env's)
+        eval_env = RoboyVecEnv(MsjRobot(), args.eval_envs, goals=goals, device=local_rank, env_id_offset=rank * args.eval_envs,
+                               **dict(env_kw, seed=args.seed + EVAL_SEED_OFFSET, episode_log=args.eval_episodes, goal_row_stats=False))
     if os.path.exists(model_file):
         agent.load(model_file)                  # resume from the last backup
     last_stats = {}
@@ -153,6 +168,10 @@ def main(argv=None):
         if env.reward_shaping is not None:      # the round's sum of step costs and its steps
             cost = env.shaping_stats(reset=True)
             segments.append(("shaping", [cost["sum_step_cost"], cost["n_steps"]]))
+        if eval_env is not None and (round_no + 1) % args.eval_every == 0:      # the evaluation's eight sums (every rank evaluates its shard)
+            from .envs.options import EPISODE_LOG_SUMS
+            figures = agent.evaluate(eval_env, episodes_per_env=args.eval_episodes)
+            segments.append(("eval", [figures[k] for k in EPISODE_LOG_SUMS] + [0.0]))
         block, layout = join_segments(segments, "cuda" if (dist is not None and args.backend == "nccl") else "cpu")
         total = split_segments(allreduce_stats(block, dist).cpu(), layout)
         row_counts = total["row_counts"].numpy().astype(np.uint64).reshape(2, goals_m) if by_reach_rate else None
@@ -172,6 +191,10 @@ def main(argv=None):
             for name, key in (("pushes", "pushes_per_step"), ("shaping", "shaping_cost_per_step")):
                 if name in total:                # (a sum of the round over its env steps)
                     summary[key] = float("%.4g" % (float(total[name][0]) / max(float(total[name][1]), 1.0)))
+            if "eval" in total:                  # (exactly --eval-episodes episodes of every evaluation env of every rank)
+                from .envs.options import episode_log_figures
+                figures = episode_log_figures([float(x) for x in total["eval"]], args.eval_envs * world)
+                summary.update({"eval_" + k: float("%.6g" % figures[k]) for k in ("success_rate", "mean_return", "mean_length")})
             print("episode statistics (all ranks):", summary)
     if world > 1:
         dist.destroy_process_group()

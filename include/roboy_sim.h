@@ -722,6 +722,45 @@ int rb_env_push_configure(rb_sim *sim, const rb_env_push_config *cfg);
 int rb_env_push_ptr(rb_sim *sim, uint32_t **d_count, uint32_t **d_last, uint32_t **d_n_pushes, float **d_impulse);
 int rb_env_push_count(rb_sim *sim, uint64_t *pushes, int reset);
 
+/* ---- episode log: each env's first E finished episodes - return, length, outcome - behind the fused env step ----
+ * Every robot, every kernel form, every env-step entry, every option above: no env-step kernel changes; ONE kernel is launched
+ * behind every env-step launch over envs [i0, i0 + cnt), on its stream, over the same envs - behind the reward-shaping apply (the
+ * reward is the one the caller receives) and the goal pool, in front of the episode-end codes (the done words are read as flags,
+ * != 0, so the records are the same with and without the codes).
+ * A handle with capacity E holds, all indexed by the env's index in the handle (never by the position in a launch):
+ *   acc   float  [n]     running return of the env's current episode        age   uint32 [n]     steps seen in the current episode
+ *   seen  uint32 [n]     the goals-reached counter at the env's last episode end (a plane of the log's own)
+ *   count uint32 [n]     records written, saturates at E                     full  uint32 one     number of envs with count == E
+ *   ret   float  [E][n]  per-record return      len  uint32 [E][n]  per-record length      kind  uint32 [E][n]  per-record outcome
+ * For env i the kernel does, with r = reward[i] and g = the env's goals-reached counter:
+ *     a = fl32(acc[i] + r);  t = age[i] + 1
+ *     done[i] == 0:  acc[i] = a; age[i] = t
+ *     done[i] != 0:  k = (g != seen[i]) ? RB_DONE_TERMINATED : RB_DONE_TRUNCATED;  seen[i] = g;  c = count[i]
+ *                    c < E: ret[c][i] = a; len[c][i] = t; kind[c][i] = k; count[i] = c + 1; c + 1 == E: full += 1 (one atomic add)
+ *                    acc[i] = 0; age[i] = 0
+ * rb_env_reset_dev zeroes acc and age of every env: the abandoned episode is not recorded; records and counts stay.  Wherever
+ * the episode counters are cleared (rb_env_stats with reset, rb_env_configure) `seen` is cleared with them.
+ *   configure: capacity 0 switches the option off (the planes are freed, the handle launches exactly what it launched before);
+ *        1 .. RB_EPISODE_LOG_MAX switches it on.  Needs rb_env_configure.  RB_EINVAL outside 0 .. RB_EPISODE_LOG_MAX, RB_ENOMEM
+ *        when the planes cannot be allocated; either leaves the handle as it was.  A successful call leaves every plane zero and
+ *        `seen` equal to the counters as they stand.  Drains the handle's streams and drops its graphs; call it before a caller
+ *        captures env steps.  rb_rollout_fused_dev is RB_EUNSUPPORTED while the option is on.
+ *   ptr: the device planes and the capacity (any argument may be NULL); RB_EINVAL without the option.
+ *   clear: count, full, acc and age to zero, `seen` to the counters as they stand.  Enqueued on the handle's stream, nothing is
+ *        drained and no graph dropped: it may be called between replays of a captured env step.
+ *   summary: over the records k < min(count[i], first_k) of every env (first_k >= 1, may exceed E), eight doubles:
+ *        [records, sum of returns, sum of squared returns, sum of lengths, terminated, truncated, envs with count >= first_k, 0].
+ *        A two-stage reduction in a fixed order (block partials, then the last block adds them in block order): the same planes
+ *        give the same bits; the counts are exact.  summary is synchronous; summary_dev is enqueued on the handle's stream and
+ *        writes d_out8 (device memory, may be NULL: the result stays in the handle).
+ * RB_ABI_VERSION is still 6 (nothing that existed changed): look rb_env_episode_log_configure up before relying on it. */
+#define RB_EPISODE_LOG_MAX 64
+int rb_env_episode_log_configure(rb_sim *sim, int32_t capacity);
+int rb_env_episode_log_ptr(rb_sim *sim, uint32_t **d_count, float **d_ret, uint32_t **d_len, uint32_t **d_kind, uint32_t **d_full, int32_t *capacity);
+int rb_env_episode_log_clear(rb_sim *sim);
+int rb_env_episode_log_summary(rb_sim *sim, int32_t first_k, double out8[8]);
+int rb_env_episode_log_summary_dev(rb_sim *sim, int32_t first_k, double *d_out8);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
