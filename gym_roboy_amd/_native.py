@@ -89,6 +89,7 @@ RB_CRITIC_OBS_MAX_DIM = 63
 # rb_env_goal_curriculum_configure: the most levels; what the index plane reads behind rb_env_set_goal
 RB_GOAL_LEVELS_MAX = 256
 RB_GOAL_INDEX_NONE = 0xFFFFFFFF
+RB_START_INDEX_REST = 0xFFFFFFFF     # rb_env_start_poses_*: what the index plane reads for an episode that began at the rest pose
 
 
 class EnvIoConfig(ctypes.Structure):
@@ -205,6 +206,9 @@ SIGNATURES = {
     "rb_env_episode_log_clear": (ctypes.c_int, [_sim]),
     "rb_env_episode_log_summary": (ctypes.c_int, [_sim, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]),
     "rb_env_episode_log_summary_dev": (ctypes.c_int, [_sim, ctypes.c_int32, _vp]),
+    "rb_env_start_poses_configure": (ctypes.c_int, [_sim, _fp, ctypes.c_int64, ctypes.c_double]),
+    "rb_env_start_poses_set": (ctypes.c_int, [_sim, _fp, ctypes.c_int64]),
+    "rb_env_start_poses_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

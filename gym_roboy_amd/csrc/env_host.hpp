@@ -1,7 +1,7 @@
 // env_host.hpp - the fused env layer and its options on the host.
 // Part of roboy_sim.hip (included there once, at file scope, behind the dispatch table; not a stand-alone header): everything
 // RoboyEnv.step's layer (rb_env_*) and its options - per-env parameters, tendon channels, io and the action ring, action rows,
-// episode-end codes, critic rows, the goal pool with its curriculum and row counts, reward shaping, random pushes, the episode log - do outside a kernel.  Each option is ONE record in
+// episode-end codes, critic rows, the goal pool with its curriculum and row counts, reward shaping, random pushes, the episode log, start poses - do outside a kernel.  Each option is ONE record in
 // rb_sim (roboy_sim.hip), is switched by ONE entry point that opens with reconfigure(), and has ONE line in behind_step() /
 // behind_reset() if it launches anything there.  The kernels are in env_*.hpp and roboy_sim.hip; which env-step kernel runs is the
 // dispatch table's business, or extension_launch()'s where extension_serves().  DESIGN.md §6 has the table of options.
@@ -386,6 +386,50 @@ int episode_log_clear(rb_sim *s) {
     return episode_log_rebase(s);
 }
 
+// ---- start poses (env_start.hpp): one launch behind an env step (d_done: its done words) or the reset kernel (null: every env), over [i0, i0 + cnt) ----
+const char *const START_POSES_TENDON_OBS =
+    "start poses and tendon channels in the observation do not combine: a started env's tendon columns would have to be evaluated at "
+    "the new pose under the held command, and no readout does that yet";
+int start_launch(rb_sim *s, long i0, long cnt, hipStream_t stream, const uint32_t *d_done, float *d_obs) {
+    if (cnt <= 0) return RB_OK;
+    const OptStart &o = s->start;
+    rbstart::StartArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.pool = o.d_pool; a.done = d_done; a.q = s->d_q; a.qd = s->d_qd; a.feas = s->d_feas; a.count = o.d_count; a.index = o.d_index; a.obs = d_obs;
+    a.n = s->n; a.i0 = i0; a.i1 = i0 + cnt;
+    a.seed = s->seed; a.env0 = uint64_t(s->env0);
+    a.m = uint32_t(o.m); a.threshold = o.threshold;
+    a.nq = s->n_q; a.od = s->obs_dim(); a.rows = s->tree ? 1 : 0;
+    if (d_done && s->io.on) {                 // behind a step: the noise of the row the step has just written, on the columns replaced
+        const rbio::IoArgs io = io_args(s, 0);
+        a.noise_rows = io.noise_blocks ? s->io.d_rows : nullptr;
+        for (int c = 0; c < 2 * s->n_q; ++c) {
+            a.colsig[c] = io.colsig[c];
+            if (io.colsig[c] != 0.0f) a.noise_blocks |= 1u << (c >> 2);
+        }
+    }
+    hipLaunchKernelGGL(rbstart::env_start, dim3(blocks_for(cnt, 256)), dim3(256), 0, stream, a);
+    RB_HIP(hipGetLastError());
+    return RB_OK;
+}
+// no start counted, every running episode began at the rest pose (rb_env_start_poses_configure)
+int start_clear(rb_sim *s) {
+    const size_t plane = sizeof(uint32_t) * size_t(s->n);
+    RB_HIP(hipMemsetAsync(s->start.d_count, 0, plane, s->stream));
+    RB_HIP(hipMemsetAsync(s->start.d_index, 0xFF, plane, s->stream));      // RB_START_INDEX_REST, every byte 0xFF
+    return RB_OK;
+}
+// the rows of a pool [m][n_q]: finite and inside the robot's joint limits
+int start_rows_check(const rb_sim *s, const float *rows, int64_t m) {
+    for (int64_t r = 0; r < m; ++r)
+        for (int j = 0; j < s->n_q; ++j) {
+            const float v = rows[r * s->n_q + j];
+            if (!std::isfinite(v) || v < s->box.lo[j] || v > s->box.hi[j])
+                return fail(RB_EINVAL, "start poses: row " + std::to_string(r) + ", joint " + std::to_string(j) + " is not finite or outside the joint limits");
+        }
+    return RB_OK;
+}
+
 // ---- the episode counters and the planes that mirror them ----
 // d_ep_sum, d_ep_cnt (episodes, lengths, goals reached), d_infeas_n and env_steps count since the last clear; d_done_seen (episode-end
 // codes) and d_goal_seen (curriculum) hold each env's goals-reached counter as of its last episode end, so they follow it.  A new
@@ -430,10 +474,15 @@ int episode_counters(rb_sim *s, CounterSite site) {
 //           the env-step kernel (dispatch)
 //           0. shaping apply - reward -= cost, the cost statistics; reads the done words as flags, like 1.
 //           1. goal pool / curriculum / row counts - the done envs' new goal becomes a pool row, IN FRONT of everything that reads the goal
+//           1a. start poses (auto_reset only) - the done envs' zero pose becomes a pool row or stays, in the planes and in the row's
+//               q / qd columns (with the noise the step put on them), IN FRONT of the critic rows, which report the true start pose.
+//               Nothing of the option runs in front of the step: a refused step (step_form_check, dispatch) has enqueued nothing of it
 //           2. critic rows - from the planes as 1. left them
 //           3. episode log - the reward as 0. left it (what the caller receives), the done words still flags
 //           4. episode-end codes - last: it turns the range's done words, which 0., 1. and 3. read as flags, into codes
 //   reset:  the reset kernel
+//           0. start poses - every env's zero pose becomes a pool row or stays, IN FRONT of everything below: the row kernels, the
+//              noise and the critic rows all work from the planes and rows as it left them
 //           1. observation rows (channels, action rows) - the tendon columns at the zero pose, every set-point 0
 //           2. the done-seen re-base (episode_counters)
 //           3. sensor noise on the rows of 1., in place (the episode restarts, the history needs nothing)
@@ -446,6 +495,7 @@ int episode_counters(rb_sim *s, CounterSite site) {
 int behind_step(rb_sim *s, long i0, long cnt, hipStream_t stream, float *d_obs, float *d_reward, uint32_t *d_done, float *d_cobs) {
     if (s->shaping.on) RB_RC(shaping_apply_launch(s, i0, cnt, stream, d_reward, d_done));
     if (s->goals.d_pool) RB_RC(goal_pool_launch(s, i0, cnt, stream, d_done, d_obs));
+    if (s->start.d_pool && s->env.auto_reset) RB_RC(start_launch(s, i0, cnt, stream, d_done, d_obs));
     if (s->critic.mask) RB_RC(critic_launch(s, i0, cnt, stream, d_obs, d_cobs ? d_cobs : s->critic.d_rows));
     if (s->elog.E) RB_RC(episode_log_launch(s, i0, cnt, stream, d_reward, d_done));
     if (s->done.on) {
@@ -458,6 +508,7 @@ int behind_step(rb_sim *s, long i0, long cnt, hipStream_t stream, float *d_obs, 
 int behind_reset(rb_sim *s, float *d_obs) {
     const int od = s->obs_dim(), lead = od - s->hist.rows * s->n_t;      // (the noise stops in front of the action blocks: row stride and noised width apart)
     const dim3 grid(blocks_for(s->n, 256)), block(256);
+    if (s->start.d_pool) RB_RC(start_launch(s, 0, s->n, s->stream, nullptr, d_obs));
     if ((s->chan.mask || s->hist.rows) && d_obs) {
         obs_rows_launch(s, d_obs);
         RB_HIP(hipGetLastError());
@@ -654,6 +705,7 @@ int rb_env_obs_configure(rb_sim *s, uint32_t channel_mask, const float *scale) {
         if (s->tree && channel_mask)
             return fail(RB_EUNSUPPORTED, "tendon channels in the observation are built for ball-joint robots (1-16 tendons); a joint tree's readout is "
                                          "rb_tendon_state_dev");
+        if (s->start.d_pool && channel_mask) return fail(RB_EUNSUPPORTED, START_POSES_TENDON_OBS);
         return RB_OK;
     }));
     s->chan.mask = int(channel_mask);
@@ -1211,6 +1263,60 @@ int rb_env_episode_log_summary(rb_sim *s, int32_t first_k, double *out8) {
     RB_RC(rb_env_episode_log_summary_dev(s, first_k, nullptr));
     RB_HIP(hipMemcpyAsync(out8, s->elog.d_red, sizeof(double) * 8, hipMemcpyDeviceToHost, s->stream));
     RB_HIP(hipStreamSynchronize(s->stream));
+    return RB_OK;
+}
+
+// ---- start poses: episodes begin at a row of a pool instead of the zero pose (env_start.hpp) ----
+int rb_env_start_poses_configure(rb_sim *s, const float *rows, int64_t m, double prob) {
+    uint32_t threshold = 0;
+    // nothing in flight may still use the pool or the planes, and a captured graph holds the launches of the handle as it was
+    RB_RC(reconfigure(s, NEEDS_ENV | DROP_GRAPHS, [&]() -> int {
+        if (m == 0) return RB_OK;
+        if (m < 1 || m > int64_t(UINT32_MAX)) return fail(RB_EINVAL, "start poses: m must be >= 1 (and below 2^32; 0 switches the option off)");
+        if (!rows) return fail(RB_EINVAL, "null argument");
+        if (!(prob >= 0.0 && prob <= 1.0)) return fail(RB_EINVAL, "start poses: prob must be in [0, 1]");
+        threshold = uint32_t(std::nearbyint(prob * 16777216.0));
+        if (s->chan.mask) return fail(RB_EUNSUPPORTED, START_POSES_TENDON_OBS);
+        return start_rows_check(s, rows, m);
+    }));
+    OptStart &o = s->start;
+    if (m == 0) { o.release(); return RB_OK; }
+    const size_t bytes = sizeof(float) * size_t(m) * size_t(s->n_q), plane = sizeof(uint32_t) * size_t(s->n);
+    if (o.m != m) {
+        auto alloc = [](auto **d, size_t b) { return dev_alloc(d, b, "hipMalloc (start poses): "); };
+        OptStart fresh;
+        int rc = alloc(&fresh.d_pool, bytes);
+        if (rc == RB_OK) rc = alloc(&fresh.d_count, plane);
+        if (rc == RB_OK) rc = alloc(&fresh.d_index, plane);
+        if (rc) { fresh.release(); return rc; }      // (the handle as it was)
+        o.release();
+        o = fresh;
+        o.m = m;
+    }
+    o.threshold = threshold; o.prob = prob;
+    RB_HIP(hipMemcpy(o.d_pool, rows, bytes, hipMemcpyHostToDevice));
+    return start_clear(s);
+}
+int rb_env_start_poses_set(rb_sim *s, const float *rows, int64_t m) {
+    // nothing in flight may still read the rows.  The graphs stay: a captured env step reads the rows behind a pointer that never
+    // moves - its next replay sees the new ones
+    RB_RC(reconfigure(s, KEEP_GRAPHS, [&]() -> int {
+        if (s->start.need()) return RB_EINVAL;
+        if (!rows) return fail(RB_EINVAL, "null argument");
+        if (m != s->start.m)
+            return fail(RB_EINVAL, "start poses: the handle's pool has " + std::to_string(s->start.m) + " rows, fixed by rb_env_start_poses_configure; got " +
+                                       std::to_string(m));
+        return start_rows_check(s, rows, m);
+    }));
+    RB_HIP(hipMemcpy(s->start.d_pool, rows, sizeof(float) * size_t(m) * size_t(s->n_q), hipMemcpyHostToDevice));
+    return RB_OK;
+}
+int rb_env_start_poses_ptr(rb_sim *s, float **d_pool, int64_t *m, uint32_t **d_count, uint32_t **d_index) {
+    if (check(s) || s->start.need()) return RB_EINVAL;
+    if (d_pool) *d_pool = s->start.d_pool;
+    if (m) *m = s->start.m;
+    if (d_count) *d_count = s->start.d_count;
+    if (d_index) *d_index = s->start.d_index;
     return RB_OK;
 }
 

@@ -57,6 +57,7 @@
 #include "env_shaping.hpp"            // action-rate and effort reward terms around the fused env step (rb_env_shaping_*)
 #include "env_push.hpp"               // random velocity pushes in front of the fused env step (rb_env_push_*)
 #include "env_episode_log.hpp"        // per-env episode records behind the fused env step (rb_env_episode_log_*)
+#include "env_start.hpp"              // episodes that begin at a pose from a pool (rb_env_start_poses_*)
 
 namespace {
 
@@ -566,6 +567,16 @@ struct OptEpisodeLog {
     }
     int need() const { return E ? RB_OK : fail(RB_EINVAL, "the episode log is not configured (rb_env_episode_log_configure)"); }
 };
+// Start poses (env_start.hpp; rb_env_start_poses_*): while d_pool is set, every reset kernel and - on a handle with auto_reset - every
+// env-step launch is followed by env_start over its range.  Rows [m][n_q]; m and the pointer stay for the option's life
+// (rb_env_start_poses_set writes the rows in place).  Planes [n_envs] each: starts counted, the row the running episode began at
+struct OptStart {
+    float *d_pool = nullptr; int64_t m = 0;
+    uint32_t threshold = 0; double prob = 0.0;
+    uint32_t *d_count = nullptr, *d_index = nullptr;
+    void release() { (void)hipFree(d_pool); (void)hipFree(d_count); (void)hipFree(d_index); *this = OptStart{}; }
+    int need() const { return d_pool ? RB_OK : fail(RB_EINVAL, "start poses are not configured (rb_env_start_poses_configure)"); }
+};
 
 }  // namespace
 
@@ -661,6 +672,7 @@ struct rb_sim {
     OptShaping shaping;
     OptPush push;
     OptEpisodeLog elog;
+    OptStart start;
     float qd_max[32] = {};               // the description's velocity bounds, as every step kernel holds them (fp32)
     int obs_dim() const { return 3 * n_q + rbo::n_channels(chan.mask) * n_t + hist.rows * n_t; }
     int critic_width() const { return rbc::row_dim(critic.mask, n_q, par.on ? par.n : 0, hist.rows * n_t); }
@@ -1084,7 +1096,7 @@ void rb_destroy(rb_sim *s) {
     (void)hipFree(s->d_state_rows); (void)hipHostFree(s->h_state_rows);
     (void)hipFree(s->d_goal); (void)hipFree(s->d_ep_ret); (void)hipFree(s->d_ep_sum); (void)hipFree(s->d_ep_cnt);
     (void)hipFree(s->d_step_num); (void)hipFree(s->d_infeas_n); (void)hipFree(s->d_stats);
-    s->par.release(); s->chan.release(); s->io.release(); s->hist.release(); s->done.release(); s->critic.release(); s->goals.release(); s->shaping.release(); s->push.release(); s->elog.release();
+    s->par.release(); s->chan.release(); s->io.release(); s->hist.release(); s->done.release(); s->critic.release(); s->goals.release(); s->shaping.release(); s->push.release(); s->elog.release(); s->start.release();
     for (rb_sim::CallerStream &c : s->caller) if (c.done) (void)hipEventDestroy(c.done);
     if (s->chain_fork) (void)hipEventDestroy(s->chain_fork);
     for (int c = 1; c < rb_sim::MAX_CHAINS; ++c) {
@@ -1499,6 +1511,9 @@ int rb_rollout_fused_dev(rb_sim *s, const float *d_ring, int ring, int n_steps, 
                                      "(rb_env_episode_log_configure(sim, 0) first)");
     if (s->goals.d_pool)
         return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) redraws goals inside one kernel and cannot draw them from a goal pool");
+    if (s->start.d_pool)
+        return fail(RB_EUNSUPPORTED, "the fused rollout (rb_rollout_fused_dev) resets episodes inside one kernel and cannot start them at poses from a pool "
+                                     "(rb_env_start_poses_configure(sim, NULL, 0, 0) first)");
     if (n_steps == 0) return RB_OK;
     const long n = s->n;
     maybe_jit(s);

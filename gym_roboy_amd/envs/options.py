@@ -10,6 +10,7 @@ TENDON_OBS_CHANNELS = ("length", "rate", "activation", "force")
 _TENDON_OBS_BOUNDS = {"length": (0.0, np.inf), "rate": (-np.inf, np.inf), "activation": (0.0, 1.0), "force": (0.0, np.inf)}
 SENSOR_NOISE_KEYS = ("q", "qd") + TENDON_OBS_CHANNELS
 DEFAULT_GOAL_POOL = 16384                        # --goals reachable
+DEFAULT_START_POOL = 4096                        # --start-poses reachable
 ENV_INTEGRATOR = "euler"                         # RoboyVecEnv's default: the pool is settled with the integrator the env steps with
 GOAL_ORDERS = ("rest_distance", "reach_rate")
 
@@ -157,6 +158,28 @@ def push_spec(push, n_q: int):
     return {"prob": float(p), "sigma": [float(v) for v in sig], "threshold": threshold}
 
 
+def start_pose_spec(start_poses, start_prob, n_q: int, low, high, m=None):
+    """``RoboyVecEnv(start_poses=pool, start_prob=p)`` -> ``{"q": float32 rows [m, n_q], "prob": p, "threshold": round(p * 2**24),
+    "recipe": dict}`` - or None without a pool (the option is off; ``start_prob`` must then be left at 1).  ``start_poses``: an
+    ``envs.goals.GoalPool`` (its recipe is kept) or an array ``[m, n_q]``, every value finite and inside ``[low, high]``, the robot's
+    joint limits (``goals.goal_rows``); ``m`` given: the size of the pool the env already holds.  ``start_prob`` 0 keeps the option on
+    (every episode starts at rest, the planes are kept).  ``ValueError`` for bad rows and for a ``start_prob`` outside [0, 1]."""
+    from . import goals as envgoals
+    p = start_prob
+    if isinstance(p, (bool, str)) or not np.isscalar(p) or not np.isfinite(p) or p < 0 or p > 1:
+        raise ValueError("start_prob must be in [0, 1], got %r" % (p,))
+    if start_poses is None:
+        if float(p) != 1.0:
+            raise ValueError("start_prob needs start_poses= (a pool of poses to start from)")
+        return None
+    try:
+        rows = envgoals.goal_rows(start_poses, n_q, low, high, m=m)
+    except ValueError as e:
+        raise ValueError("start_poses: %s" % e) from None
+    recipe = dict(start_poses.recipe) if isinstance(start_poses, envgoals.GoalPool) else {}
+    return {"q": rows, "prob": float(p), "threshold": int(round(float(p) * 2 ** 24)), "recipe": recipe}
+
+
 def episode_log_capacity(episode_log) -> int:
     """None -> 0 (the option is off), E -> E: the number of finished episodes the env records per env, 1 <= E <= 64.  ``ValueError``
     for anything else (0 too: an env without the option is ``episode_log=None``)."""
@@ -218,6 +241,22 @@ def parse_goals(text):
     if kind != "reachable" or (m and (not m.isdigit() or int(m) < 1)):
         raise SystemExit("--goals takes reachable or reachable:M with M >= 1, got %r" % text)
     return int(m) if m else DEFAULT_GOAL_POOL
+
+
+def parse_start_poses(text, prob=None):
+    """``--start-poses reachable[:M] --start-prob P``: ``(0, 1.0)`` without ``--start-poses``, else ``(M, P)`` with M the pool's size
+    (default 4096) and P in [0, 1] (default 1); ``--start-prob`` needs ``--start-poses``"""
+    if not text:
+        if prob is not None:
+            raise SystemExit("--start-prob needs --start-poses")
+        return 0, 1.0
+    kind, _, m = text.partition(":")
+    if kind != "reachable" or (m and (not m.isdigit() or int(m) < 1)):
+        raise SystemExit("--start-poses takes reachable or reachable:M with M >= 1, got %r" % text)
+    prob = 1.0 if prob is None else prob
+    if not 0.0 <= prob <= 1.0:               # (NaN too)
+        raise SystemExit("--start-prob takes P in [0, 1], got %r" % (prob,))
+    return (int(m) if m else DEFAULT_START_POOL), float(prob)
 
 
 def parse_goal_curriculum(levels, up, down, goals_m):
@@ -288,9 +327,15 @@ ENV_FLAGS = (
      "bounds, e.g. prob=0.02,sigma=0.5; the round's statistics then show pushes_per_step; recorded in the checkpoint"),
     ("--episode-log", int, 0, "E", "record every env's first E finished episodes (at most 64) on the device: return, length and whether the goal "
      "was reached (RoboyVecEnv.episode_log, episode_log_summary); a condition of the run, recorded in the checkpoint and not replayed"),
+    ("--start-poses", str, "", "reachable[:M]", "begin episodes, at a reset and at every auto-reset, at a pose out of a pool of M poses (default "
+     "4096) the robot holds under constant set-points, with zero velocity, instead of the zero pose; the pool is made once at start with the "
+     "run's seed + 1 (so it is not the goal pool; every rank makes the same one); the round's statistics then show start_pool_share; rows and "
+     "recipe are recorded in the checkpoint"),
+    ("--start-prob", float, None, "P", "the probability that an episode begins at a pool pose (default 1; otherwise it begins at the zero "
+     "pose); needs --start-poses"),
 )
 
-N_LATE_ENV_FLAGS = 3                             # ENV_FLAGS' last rows: declared behind the agent's flags
+N_LATE_ENV_FLAGS = 5                             # ENV_FLAGS' last rows: declared behind the agent's flags
 
 
 def add_env_arguments(ap, late: bool = False):
@@ -302,7 +347,7 @@ def add_env_arguments(ap, late: bool = False):
 def env_kwargs_from_args(args) -> dict:
     """The parsed command line -> ``RoboyVecEnv``'s keyword arguments, all but what only the running process knows (``goals``, the pool
     ``--goals`` asks for; ``device``; ``env_id_offset``).  An option that is off is None, or absent (``goal_row_stats``, ``reward_shaping``, ``push``,
-    ``episode_log``)."""
+    ``episode_log``, ``start_poses``: here ``{"m": M, "prob": P}``, what the running process makes the pool from - ``start_pose_pool``)."""
     noise = parse_key_values(args.sensor_noise, "sensor noise", "KEY=SIGMA")         # (a bad flag is reported in this order)
     delay = [int(x) for x in args.action_delay.split(":")] if args.action_delay else None
     scale = parse_key_values(args.tendon_obs_scale, "tendon obs scale", "CHANNEL=FACTOR")
@@ -314,7 +359,17 @@ def env_kwargs_from_args(args) -> dict:
     late = {"goal_row_stats": parse_goal_order(args.goal_order, args.goal_reorder_every, curriculum),
             "reward_shaping": parse_reward_shaping(args.reward_shaping), "push": parse_push(args.push),
             "episode_log": episode_log_capacity(getattr(args, "episode_log", 0) or None)}
+    start_m, start_prob = parse_start_poses(getattr(args, "start_poses", ""), getattr(args, "start_prob", None))
+    if start_m:
+        late["start_poses"] = {"m": start_m, "prob": start_prob}
     return dict(kw, **{key: value for key, value in late.items() if value})
+
+
+def start_pose_pool(robot, request, seed: int, device: int = 0):
+    """``env_kwargs_from_args``' ``start_poses`` request ``{"m", "prob"}`` -> ``RoboyVecEnv``'s ``(start_poses, start_prob)``: the pool
+    ``reachable_goals`` makes with the run's seed + 1 - not the goal pool's rows, and every rank makes the same one."""
+    from .goals import reachable_goals
+    return reachable_goals(robot, int(request["m"]), seed=int(seed) + 1, integrator=ENV_INTEGRATOR, device=device), float(request["prob"])
 
 
 # ---- the checkpoint (PPO.save / PPO.load, visualize_agent) ----
@@ -358,13 +413,17 @@ def env_checkpoint_record(env, critic=None) -> dict:
         ck["env_push"] = {"prob": float(push["prob"]), "sigma": [float(v) for v in push["sigma"]], "threshold": int(push["threshold"])}
     if (capacity := getattr(env, "episode_log_capacity", 0)):
         ck["episode_log"] = int(capacity)
+    if getattr(env, "start_poses_size", 0):
+        ck["env_start_poses"] = {"q": torch.from_numpy(env.start_pose_pool()), "prob": float(env.start_prob),
+                                 "threshold": int(round(float(env.start_prob) * 2 ** 24)), "recipe": dict(getattr(env, "start_recipe", {}) or {})}
     return ck
 
 
 def check_env_checkpoint(env, ck, critic_dim=None) -> dict:
     """``load()``'s env side.  ``ValueError`` where the checkpoint's rows are not this env's (tendon channels; with ``critic_dim``, the width an
     asymmetric agent reads, the critic rows); a warning where the reward-shaping weights differ (the env's hold); the curriculum's levels go into
-    an env with as many levels and envs.  Returns what the env does not take over: ``{"goals", "goal_row_stats", "goal_curriculum", "env_push"}``.  ``episode_log`` (the
+    an env with as many levels and envs.  Returns what the env does not take over: ``{"goals", "goal_row_stats", "goal_curriculum", "env_push"}`` and, where the
+    checkpoint has it, ``"env_start_poses"`` (a condition of the run like the pushes).  ``episode_log`` (the
     capacity of the run that wrote the checkpoint) is a condition of that run, never a layout: it must be a capacity (``ValueError`` otherwise), is
     neither taken over nor kept, and this env's own capacity holds, whatever it is."""
     old, own = ck.get("tendon_obs", tendon_obs_record(None)), tendon_obs_record(env)
@@ -381,6 +440,8 @@ def check_env_checkpoint(env, ck, critic_dim=None) -> dict:
     if "episode_log" in ck:
         episode_log_capacity(ck["episode_log"])
     kept = {k: ck.get(k) for k in ("goals", "goal_row_stats", "goal_curriculum", "env_push")}
+    if "env_start_poses" in ck:                  # (absent when off: a checkpoint without the option returns exactly what it did)
+        kept["env_start_poses"] = ck["env_start_poses"]
     saved, own = kept["goal_curriculum"], getattr(env, "goal_curriculum", None)
     if saved is not None and own is not None and own["levels"] == int(saved["levels"]) and int(saved["level"].numel()) == env.num_envs:
         env.set_goal_levels(saved["level"].cpu().numpy())
@@ -398,6 +459,8 @@ def env_kwargs_from_checkpoint(ck):
               action_obs=int(env_io.get("action_obs") or 0) or None,
               goals=None if goals is None else np.asarray(goals["q"], dtype=np.float32),      # the stored rows; the recipe is not needed
               push=None if push is None else {"prob": push["prob"], "sigma": push["sigma"]})  # (the threshold follows from prob)
+    if (start := ck.get("env_start_poses")) is not None:      # (absent when off)
+        kw["start_poses"], kw["start_prob"] = np.asarray(start["q"], dtype=np.float32), float(start["prob"])
     # not replayed, each on purpose - critic_obs: only the actor is played back, and no critic row is needed
     # goal_curriculum: playback draws from the whole pool, the top level's draw
     # goal_row_stats: counts of the training run, nothing a step reads

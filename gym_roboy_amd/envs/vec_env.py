@@ -27,7 +27,7 @@ from . import goals as envgoals
 from . import reward as rw
 from .options import (SENSOR_NOISE_KEYS, TENDON_OBS_CHANNELS, _TENDON_OBS_BOUNDS, action_delay_range, action_obs_bounds,  # noqa: F401
                       action_obs_rows, critic_obs_spec, episode_log_capacity, episode_log_figures, parse_push, parse_reward_shaping, push_spec, reward_shaping_weights,
-                      sensor_noise_sigmas, tendon_obs_mask, tendon_obs_scales)
+                      sensor_noise_sigmas, start_pose_spec, tendon_obs_mask, tendon_obs_scales)
 from .robots import RoboyRobot
 from .simulations.hip_simulation_client import HipBatchSimulation
 
@@ -43,7 +43,8 @@ class RoboyVecEnv:
                  device: int = 0, env_id_offset: int = 0, max_episode_length: int = 400,
                  randomization=None, tendon_obs=None, tendon_obs_scale=None, sensor_noise=None, action_delay=None,
                  report_truncation: bool = False, action_obs=None, critic_obs=None, goals=None, goal_curriculum=None,
-                 goal_row_stats: bool = False, reward_shaping=None, push=None, episode_log=None):
+                 goal_row_stats: bool = False, reward_shaping=None, push=None, episode_log=None,
+                 start_poses=None, start_prob=1.0):
         """``randomization``: an ``envs.params.ParamRanges`` - every env gets its own physical parameters, drawn from these ranges by
         ``reset()`` and again whenever the env auto-resets (ball-joint robots).  None: every env is the robot itself.
         ``tendon_obs``: channel names out of ``("length", "rate", "activation", "force")`` - the observation row becomes
@@ -113,7 +114,16 @@ class RoboyVecEnv:
         short episodes as totals over whatever ended are.  ``reset()`` drops the episode under way without recording it.
         ``episode_log()`` reads the records, ``episode_log_summary(first_k)`` their sums and rates, ``episode_log_full()`` how many
         envs have all E, ``clear_episode_log()`` starts over; ``episode_log_capacity`` holds E (0 without the option).  None: the env
-        launches exactly what it launched before."""
+        launches exactly what it launched before.
+        ``start_poses``: an ``envs.goals.GoalPool`` (``reachable_goals(robot, m)``) or an array ``[m, n_q]`` inside the joint limits -
+        an episode, at ``reset()`` and at every auto-reset inside a step, begins at a row of this pool with zero velocity instead of
+        the zero pose: with probability ``round(start_prob * 2**24) / 2**24`` at row ``k(seed, global env id, start number)``,
+        otherwise at the zero pose as before (every robot, every kernel form, every option above but ``tendon_obs``).
+        The observation row returned for a started env reports the pose (under ``sensor_noise`` with the row's own noise), critic
+        rows the true pose; reward and done of the step that ended the previous episode are untouched.  ``start_pose_pool()``
+        returns the rows, ``set_start_poses(rows)`` replaces them in place by as many others, ``start_index()`` the row every env's
+        running episode began at (``_native.RB_START_INDEX_REST``: the zero pose); ``start_poses_size`` and ``start_prob`` hold the
+        pool's size (0 without the option) and the probability.  None: the env launches exactly what it launched before."""
         desc = robot.get_description()
         # 1. every ValueError of a bad option, before anything is allocated
         crit_names, crit_mask, crit_dim = critic_obs_spec(critic_obs, desc.n_q, desc.n_t, randomization is not None, action_delay, action_obs)
@@ -125,6 +135,10 @@ class RoboyVecEnv:
         shaping = reward_shaping_weights(reward_shaping)
         push_rec = push_spec(push, desc.n_q)
         log_capacity = episode_log_capacity(episode_log)
+        start = start_pose_spec(start_poses, start_prob, desc.n_q, desc.q_lo, desc.q_hi)      # (the joint limits, per joint: not the angle box)
+        if start is not None and obs_names:
+            raise ValueError("start_poses does not combine with tendon_obs: a started env's tendon columns would have to be evaluated at "
+                             "the new pose under the held command, and no readout does that yet")
         curriculum = envgoals.goal_curriculum_spec(goal_curriculum)
         if curriculum is not None:
             if goals is None:
@@ -159,8 +173,8 @@ class RoboyVecEnv:
         self.goal_recipe = dict(goals.recipe) if isinstance(goals, envgoals.GoalPool) else {}
         nat.check(self.sim._lib.rb_env_configure(self.sim.handle, ctypes.byref(cfg)))
         # 3. the options, in the one order they take (a call puts its kernels in the place of, in front of or behind those of the calls before
-        # it): pool, curriculum, row counts, tendon channels, action rows, buffers, randomization, io, truncation, critic rows, shaping, pushes,
-        # episode log
+        # it): pool, curriculum, row counts, tendon channels, action rows, buffers, randomization, io, start poses, truncation, critic rows, shaping,
+        # pushes, episode log
         self._configure_goal_pool(pool_rows)
         self._configure_goal_curriculum(curriculum)
         self._configure_goal_row_stats(goal_row_stats)
@@ -169,6 +183,7 @@ class RoboyVecEnv:
         self._allocate_buffers(seed)
         self._configure_randomization(randomization)
         self._configure_io(sensor_noise, action_delay, sig, *delay)
+        self._configure_start_poses(start)
         self._configure_truncation(report_truncation)
         self._configure_critic_obs(crit_names, crit_mask, crit_dim)
         self._configure_shaping(shaping)
@@ -256,6 +271,18 @@ class RoboyVecEnv:
                 io.sigma_tendon[c] = float(sig[2 + c])
             io.delay_lo, io.delay_hi, io.resample_on_reset = d_lo, d_hi, int(ranged)
             self._or_close(lambda: self.sim.configure_io(io))
+
+    def _configure_start_poses(self, start):
+        self.start_poses_size = 0             # the pool's number of rows m; 0: every episode begins at the zero pose
+        self.start_prob, self.start_recipe = (1.0, {}) if start is None else (start["prob"], dict(start["recipe"]))
+        if start is not None:
+            # behind the io configuration (the kernel restates the noise of the columns it replaces) and behind the tendon channels, which
+            # the library refuses beside it; before anything is captured into a graph: every reset kernel and every env-step launch is
+            # followed by the small kernel that puts the pool's rows in place of the zero pose
+            rows = start["q"]
+            self._or_close(lambda: nat.check(self.sim._lib.rb_env_start_poses_configure(self.sim.handle, nat.fptr(rows), rows.shape[0],
+                                                                                        float(start["prob"]))))
+            self.start_poses_size = int(rows.shape[0])
 
     def _configure_truncation(self, report_truncation):
         self.report_truncation = bool(report_truncation)
@@ -631,6 +658,48 @@ class RoboyVecEnv:
         out = ctypes.c_uint64()
         nat.check(self.sim._lib.rb_env_push_count(self.sim.handle, ctypes.byref(out), int(bool(reset))))
         return int(out.value)
+
+    # -- start poses (rb_env_start_poses_*) ------------------
+    def _start_planes(self):
+        self._need(self.start_poses_size, "this RoboyVecEnv starts every episode at the zero pose (start_poses=None)")
+        p = [ctypes.c_void_p() for _ in range(3)]
+        m = ctypes.c_int64()
+        nat.check(self.sim._lib.rb_env_start_poses_ptr(self.sim.handle, ctypes.byref(p[0]), ctypes.byref(m), ctypes.byref(p[1]), ctypes.byref(p[2])))
+        assert m.value == self.start_poses_size
+        return [x.value for x in p]            # pool, count, index
+
+    def start_pose_pool(self) -> np.ndarray:
+        """The pool's rows ``[m, n_q]`` as the device holds them; needs ``start_poses``."""
+        d_pool = self._start_planes()[0]
+        self.sim.synchronize()
+        return self.sim.download(d_pool, (self.start_poses_size, self.n_q))
+
+    def set_start_poses(self, rows):
+        """Replace the pool's rows in place by as many others (a ``GoalPool`` or an array ``[m, n_q]``), between steps: episodes that
+        start from now on - also in a captured graph's next replay, the device rows do not move - start at rows of the new pool; poses
+        already started from stay.  Needs ``start_poses``; ``ValueError`` for another size or a row outside the joint limits."""
+        self._start_planes()
+        desc = self.robot.get_description()
+        start = start_pose_spec(rows, self.start_prob, self.n_q, desc.q_lo, desc.q_hi, m=self.start_poses_size)
+        nat.check(self.sim._lib.rb_env_start_poses_set(self.sim.handle, nat.fptr(start["q"]), start["q"].shape[0]))
+        self.start_recipe = dict(start["recipe"])
+
+    def start_index(self):
+        """``[N]``: the pool row every env's running episode began at, ``_native.RB_START_INDEX_REST`` for the zero pose.  numpy
+        (uint32) after a numpy step, read after a synchronisation; after a torch step a CUDA int32 tensor VIEW of the handle's plane
+        (the rest pose reads -1) that the next step overwrites - clone it to keep it.  Needs ``start_poses``."""
+        d_index = self._start_planes()[2]
+        if _is_cuda_tensor(self._last_actions):
+            import torch
+            return _device_view_f32(d_index, self.num_envs, self._last_actions.device).view(torch.int32)
+        self.sim.synchronize()
+        return self.sim.download(d_index, (self.num_envs,), np.uint32)
+
+    def start_count(self) -> np.ndarray:
+        """``[N]`` uint32: the starts every env has made since the option was configured (numpy, read after a synchronisation)."""
+        d_count = self._start_planes()[1]
+        self.sim.synchronize()
+        return self.sim.download(d_count, (self.num_envs,), np.uint32)
 
     # -- episode log (rb_env_episode_log_*; DESIGN.md §29) ------------------
     def _episode_log_planes(self):

@@ -5,7 +5,7 @@ the checkpoint's deterministic policy (the action mean) runs on ``N`` envs until
 episodes (``ppo.evaluate_policy`` over the env's episode log), so short episodes are not over-represented as they are in
 totals over whatever ended.  The env is built under the conditions the checkpoint records (``envs.options.env_kwargs_from_checkpoint``);
 every env flag given on the command line (``envs.options.ENV_FLAGS``) REPLACES the checkpoint's condition: pushes, sensor noise, an
-action delay, the goal pool may change - that is what "evaluated under pushes it was not trained with" takes - while the row's
+action delay, the goal pool, the start poses may change - that is what "evaluated under pushes it was not trained with" takes - while the row's
 layout (``--tendon-obs``, ``--action-obs``) may not: the policy reads the columns it was trained on.  One line with the summary is printed;
 ``--json`` also writes it, with the conditions used, to a file.  Where ``visualize_agent`` plays one env at 30 ms per step, this plays
 thousands at a few microseconds per step."""
@@ -19,7 +19,8 @@ FLAG_KEYS = {"--tendon-obs": ("tendon_obs",), "--tendon-obs-scale": ("tendon_obs
              "--action-delay": ("action_delay",), "--action-obs": ("action_obs",), "--critic-obs": ("critic_obs",), "--goals": ("goals",),
              "--goal-levels": ("goal_curriculum",), "--goal-up": ("goal_curriculum",), "--goal-down": ("goal_curriculum",),
              "--goal-order": ("goal_row_stats",), "--goal-reorder-every": ("goal_row_stats",), "--reward-shaping": ("reward_shaping",),
-             "--push": ("push",), "--episode-log": ()}
+             "--push": ("push",), "--episode-log": (), "--start-poses": ("start_poses", "start_prob"),
+             "--start-prob": ("start_poses", "start_prob")}
 LAYOUT_FLAGS = ("--tendon-obs", "--action-obs")      # they change the observation row's width
 
 
@@ -45,7 +46,8 @@ def given_flags(argv):
 
 def env_conditions(ck, args, argv):
     """``(kwargs, given)``: RoboyVecEnv's keyword arguments for the evaluation - the checkpoint's conditions, each replaced where its
-    flag stands on the command line (``goals``: True where ``--goals`` asks for a pool that still has to be made; the episode log is
+    flag stands on the command line (``goals``: True where ``--goals`` asks for a pool that still has to be made, ``start_poses``: the
+    request ``{"m", "prob"}`` where ``--start-poses`` does; the episode log is
     the evaluation's own: ``--episodes``) - and the env flags that were given."""
     args.bootstrap_timeouts = False              # (the trainer's flag: evaluation needs no truncation codes)
     given = given_flags(argv)
@@ -90,6 +92,10 @@ def main(argv=None):
         kw["goals"] = reachable_goals(MsjRobot(), parse_goals(args.goals), seed=args.seed, integrator=kw["integrator"], device=args.device)
         if kw.get("goal_curriculum") is not None:
             kw["goals"] = kw["goals"].ordered()
+    if isinstance(kw.get("start_poses"), dict):      # --start-poses reachable[:M]: a pool made for this evaluation (the seed + 1: not the goal pool)
+        from .envs.options import start_pose_pool
+        pool, kw["start_prob"] = start_pose_pool(MsjRobot(), kw["start_poses"], args.seed, device=args.device)
+        kw["start_poses"] = pool.q
     torch.cuda.set_device(args.device)
     env = RoboyVecEnv(MsjRobot(), args.envs, device=args.device, **kw)
     try:

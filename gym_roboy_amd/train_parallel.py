@@ -130,6 +130,11 @@ def main(argv=None):
             goals = goals.ordered()
         if rank == 0:
             print("goal pool:", goals.recipe)
+    if "start_poses" in env_kw:                 # the request becomes the pool: the run's seed + 1, so it is not the goal pool
+        from .envs.options import start_pose_pool
+        env_kw["start_poses"], env_kw["start_prob"] = start_pose_pool(MsjRobot(), env_kw["start_poses"], args.seed, device=local_rank)
+        if rank == 0:
+            print("start poses:", env_kw["start_poses"].recipe, "start_prob", env_kw["start_prob"])
     env = RoboyVecEnv(MsjRobot(), args.num_envs, goals=goals, device=local_rank, env_id_offset=rank * args.num_envs, **env_kw)
     more_exploration = 0.1                      # train_parallel.py:30
     agent = PPO(env, n_steps=args.n_steps, ent_coef=more_exploration, device="cuda", dist=dist, seed=args.seed,
@@ -168,6 +173,10 @@ def main(argv=None):
         if env.reward_shaping is not None:      # the round's sum of step costs and its steps
             cost = env.shaping_stats(reset=True)
             segments.append(("shaping", [cost["sum_step_cost"], cost["n_steps"]]))
+        if env.start_poses_size:                # the envs whose running episode began at a pool row, and the envs
+            index = env.start_index()           # (a CUDA view reads the rest pose as -1, numpy as 0xFFFFFFFF)
+            index = (index.cpu().numpy() if torch.is_tensor(index) else index).astype(np.uint32)
+            segments.append(("start_poses", [float(np.count_nonzero(index != 0xFFFFFFFF)), float(env.num_envs)]))
         if eval_env is not None and (round_no + 1) % args.eval_every == 0:      # the evaluation's eight sums (every rank evaluates its shard)
             from .envs.options import EPISODE_LOG_SUMS
             figures = agent.evaluate(eval_env, episodes_per_env=args.eval_episodes)
@@ -191,6 +200,8 @@ def main(argv=None):
             for name, key in (("pushes", "pushes_per_step"), ("shaping", "shaping_cost_per_step")):
                 if name in total:                # (a sum of the round over its env steps)
                     summary[key] = float("%.4g" % (float(total[name][0]) / max(float(total[name][1]), 1.0)))
+            if "start_poses" in total:           # (a share of the envs as they stand at the round's end)
+                summary["start_pool_share"] = float("%.4g" % (float(total["start_poses"][0]) / max(float(total["start_poses"][1]), 1.0)))
             if "eval" in total:                  # (exactly --eval-episodes episodes of every evaluation env of every rank)
                 from .envs.options import episode_log_figures
                 figures = episode_log_figures([float(x) for x in total["eval"]], args.eval_envs * world)

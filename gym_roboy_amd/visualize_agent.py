@@ -54,6 +54,7 @@ def main(argv=None):
             return o[0], float(r[0]), False
         n_obs, n_act = vec.observation_space.shape[0], vec.action_space.shape[0]
     else:
+        # (start poses: the single RoboyEnv plays from the rest pose; only the one-env RoboyVecEnv above replays env_kw["start_poses"])
         env = RoboyEnv(simulation_client=HipSimulationClient(robot=MsjRobot(), goals=env_kw["goals"]))
         reset = env.reset
 

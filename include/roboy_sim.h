@@ -761,6 +761,41 @@ int rb_env_episode_log_clear(rb_sim *sim);
 int rb_env_episode_log_summary(rb_sim *sim, int32_t first_k, double out8[8]);
 int rb_env_episode_log_summary_dev(rb_sim *sim, int32_t first_k, double *d_out8);
 
+/* ---- start poses: episodes begin at a row of a pool instead of the zero pose ----
+ * Every robot, every kernel form, every env-step entry, every option above but tendon channels: no env-step kernel changes; ONE
+ * kernel is launched behind every reset kernel (in front of everything else rb_env_reset_dev enqueues: row kernels, sensor noise and
+ * critic rows work from what it left) and, on a handle configured with auto_reset, behind every env-step launch over envs
+ * [i0, i0 + cnt), on its stream, over the same envs - directly behind the goal kernel, in front of the critic rows, the episode log
+ * and the episode-end codes (the done words are read as flags, != 0).  Nothing of the option is enqueued in front of a step.
+ * A handle with the option holds the pool (float [m][n_q]) and two planes: count and index (uint32 [n]).  For env i of the handle,
+ * global id g = env_id_offset + i, at a reset or where done[i] != 0 behind a step (an env whose done word is 0 is not touched):
+ *   1. d = count[i]; count[i] = d + 1.  The counter wraps as a uint32, does not depend on the goal counter, and nothing but
+ *      rb_env_start_poses_configure resets it (neither a reset, an episode end nor rb_env_stats does).
+ *   2. w = philox_draw(seed, g, d, STREAM_START = 7, block 0) (csrc/philox.hpp).  The env starts FROM THE POOL iff
+ *      (w.v[1] >> 8) < threshold, threshold = round-half-even(prob 2^24): integer arithmetic only, 2^24 always, 0 never.
+ *   3. from the pool: k = (uint64(w.v[0]) m) >> 32; q = pool[k] bit for bit, qd = 0, feas = 1, index[i] = k, and columns [0, 2 n_q)
+ *      of the env's observation row become [pool[k], 0].  Behind a step of a handle with sensor noise on q / qd those columns get the
+ *      noise of the row the step has just written (row number rows[i] - 1, the sensor noise's own blocks and expression): the row is
+ *      what the step would have written had it reset to the pose.
+ *   4. otherwise the env stays at the zero pose the kernel in front wrote: index[i] = RB_START_INDEX_REST, nothing else is touched.
+ * The start pose does not change the reward or the done word of the step that ended the previous episode.  A pose that coincides
+ * with the env's goal ends the new episode at its first step as reached; nothing keeps poses and goals apart.
+ *   configure: needs rb_env_configure.  m == 0 (rows may be NULL): off, pool and planes are freed, the handle launches exactly what
+ *        it launched before.  RB_EINVAL for m < 0, prob outside [0, 1] (or NaN), a row that is not finite or outside the robot's joint
+ *        limits; RB_EUNSUPPORTED while tendon channels are in the observation (rb_env_obs_configure; that call refuses likewise while
+ *        start poses are configured); RB_ENOMEM when pool or planes cannot be allocated.  A refusal leaves the handle as it was.  A
+ *        successful call zeroes count and sets every index to RB_START_INDEX_REST; the envs keep the state they have until they
+ *        start again.  Drains the handle's streams and drops its graphs; call it before a caller captures env steps.
+ *        rb_rollout_fused_dev is RB_EUNSUPPORTED while the option is on.
+ *   set: replaces the rows in place by as many others (RB_EINVAL for another m, a bad row, or without the option).  Neither the
+ *        pointer nor m moves, so a captured graph reads the new rows at its next replay; poses already started from stay.
+ *   ptr: pool, m and the two device planes (any argument may be NULL); RB_EINVAL without the option.
+ * RB_ABI_VERSION is still 6 (nothing that existed changed): look rb_env_start_poses_configure up before relying on it. */
+#define RB_START_INDEX_REST 0xFFFFFFFFu
+int rb_env_start_poses_configure(rb_sim *sim, const float *rows /* [m][n_q] */, int64_t m, double prob);
+int rb_env_start_poses_set(rb_sim *sim, const float *rows /* [m][n_q] */, int64_t m);
+int rb_env_start_poses_ptr(rb_sim *sim, float **d_pool, int64_t *m, uint32_t **d_count, uint32_t **d_index);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
