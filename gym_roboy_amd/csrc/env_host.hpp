@@ -478,7 +478,8 @@ int episode_counters(rb_sim *s, CounterSite site) {
 //               q / qd columns (with the noise the step put on them), IN FRONT of the critic rows, which report the true start pose.
 //               Nothing of the option runs in front of the step: a refused step (step_form_check, dispatch) has enqueued nothing of it
 //           2. critic rows - from the planes as 1. left them
-//           3. episode log - the reward as 0. left it (what the caller receives), the done words still flags
+//           3. episode log - the reward as 0. left it (what the caller receives); in front of 4. by convention only: log and codes
+//              both test the done word against 0 and keep a `seen` plane of their own, so either order records the same
 //           4. episode-end codes - last: it turns the range's done words, which 0., 1. and 3. read as flags, into codes
 //   reset:  the reset kernel
 //           0. start poses - every env's zero pose becomes a pool row or stays, IN FRONT of everything below: the row kernels, the

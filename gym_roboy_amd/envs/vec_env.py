@@ -819,7 +819,8 @@ class RoboyVecEnv:
     def stats(self, reset: bool = False) -> dict:
         """The task's statistics.  With ``reward_shaping`` they are untouched: returns and ``sum_reward`` are those of the step's own
         reward, without the shaping cost, so the weights change them only through the policy and runs with different weights stay
-        comparable (the costs: ``shaping_stats()``)."""
+        comparable (the costs: ``shaping_stats()``).  ``sum_reward`` is the finished episodes' returns plus the running ones: the
+        rewards of an episode that ``reset()`` abandoned in mid-episode are in neither."""
         out = (ctypes.c_double * 8)()
         nat.check(self.sim._lib.rb_env_stats(self.sim.handle, out, int(reset)))
         keys = ("sum_return", "sum_return_sq", "n_episodes", "sum_length", "n_goal_reached",

@@ -286,7 +286,9 @@ int rb_env_step_range_dev(rb_sim *sim, int64_t first_env, int64_t n_envs, void *
 /* episode statistics summed over this handle's envs since the last reset of
  * the accumulators: [sum episode return, sum return^2, n_episodes, sum episode
  * length, n_goal_reached, n_infeasible_env_steps, n_env_steps, sum reward]
- * (fp64).  Without rb_env_configure only [5] (envs flagged infeasible at the
+ * (fp64).  [7] is the finished episodes' returns plus the running ones: what an episode that rb_env_reset_dev abandoned in
+ * mid-episode had collected is in neither, so [7] is the sum of every reward handed out only while no reset falls inside an
+ * episode.  Without rb_env_configure only [5] (envs flagged infeasible at the
  * time of the call) and [6] are non-zero.  The _dev form copies them into caller-owned device memory (e.g. a
  * torch tensor that is then all-reduced over RCCL); the host form synchronises. */
 int rb_env_stats(rb_sim *sim, double *stats8, int reset);

@@ -1,5 +1,6 @@
 """TEST HELPER for the per-env physical parameters (include/roboy_sim.h: rb_params_*): the descriptions the oracle steps an env
-with, random parameter sets, and the numpy restatement of the on-device draw."""
+with, random parameter sets, the numpy restatement of the on-device draw, and a stepper over the oracle with each env on its own
+description (importable without a GPU: tests/test_env_params_gpu.py and the composed model of tests/env_layer_model.py share it)."""
 import numpy as np
 
 from oracle import philox_np as ph
@@ -46,3 +47,55 @@ def draw(seed, env_ids, d, lo, hi):
         u = ph.u01(words)
         out[sel] = (hi - lo) * u + lo          # fp32: product rounded, then sum rounded (numpy does not contract)
     return out
+
+
+class PerEnvOracle:
+    """the fp64 oracle with each env on its own description (its parameters par [n, P]); states kept in float32.  The base of the
+    two steppers below and of tests/env_layer_model.py's, which is handed its parameters instead of drawing them."""
+
+    def __init__(self, robot, n, par0, integrator="euler"):
+        from oracle.c_oracle import COracle
+        self.COracle = COracle
+        self.desc = robot.get_description()
+        self.n, self.integ = n, 0 if integrator == "euler" else 1
+        self.par = par0.astype(np.float32).copy()
+        self.q = np.zeros((n, 3), np.float32)
+        self.qd = np.zeros((n, 3), np.float32)
+        self.f = np.ones(n, bool)
+        self.orc = [COracle(perturbed(self.desc, self.par[i].astype(np.float64)), "f64") for i in range(n)]
+
+    def step(self, sp):
+        nt = self.desc.n_t
+        for i in range(self.n):
+            qo, qdo, fo = self.orc[i].step(self.q[i:i + 1].astype(np.float64), self.qd[i:i + 1].astype(np.float64),
+                                           sp[i:i + 1].astype(np.float64) + self.par[i, nt:2 * nt].astype(np.float64), integrator=self.integ)
+            self.q[i], self.qd[i], self.f[i] = qo[0], qdo[0], fo[0]
+        return self.q.copy(), self.qd.copy(), self.f.copy()
+
+    def zero(self, mask):
+        self.q[mask] = 0.0
+        self.qd[mask] = 0.0
+        self.f[mask] = True
+
+    def set_params(self, mask, par):
+        for i in np.nonzero(mask)[0]:
+            self.par[i] = par[i]
+            self.orc[i] = self.COracle(perturbed(self.desc, self.par[i].astype(np.float64)), "f64")
+
+
+class ParamOracleStepper(PerEnvOracle):
+    """host_env_model's stepper interface over the fp64 oracle, each env on its own description; on reset(mask) the masked
+    envs' parameters become the next draw of the restatement (what the kernel draws where it redraws the goal)"""
+
+    def __init__(self, robot, n, seed, lo, hi, par0, draws0):
+        PerEnvOracle.__init__(self, robot, n, par0)
+        self.seed, self.lo, self.hi = seed, lo, hi
+        self.draws = draws0.astype(np.uint32).copy()
+
+    def reset(self, mask):
+        idx = np.nonzero(mask)[0]
+        self.zero(idx)
+        new = self.par.copy()
+        new[idx] = draw(self.seed, idx.astype(np.uint64), self.draws[idx], self.lo, self.hi)
+        self.draws[idx] += 1
+        self.set_params(np.asarray(mask, bool), new)

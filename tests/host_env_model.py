@@ -9,6 +9,8 @@ import numpy as np
 from gym_roboy_amd.envs import reward as rw
 from oracle import philox_np as ph
 
+REWARD_RTOL, REWARD_ATOL = 3e-5, 3e-4      # the device's fp32 reward against this model's float64 reward (the replay tests' bound)
+
 
 class HipStepper:
     def __init__(self, robot, n, seed, env_id_offset=0, integrator="euler", kernel=1):
@@ -92,6 +94,7 @@ class HostEnvModel:
         dist_v = rw.l2_distance(qd64, zero)
         reached = (dist_a < self.max_da / 200) & (dist_v < self.max_dv / 5)
         done = reached | (self.step_num > self.max_len)
+        self.last_reached = reached            # (tests/env_layer_model.py: the outcome every option behind the step keys on)
         margin = np.minimum(np.abs(dist_a - self.max_da / 200), np.abs(dist_v - self.max_dv / 5))
         self.ep_ret += reward
         s = self.stats

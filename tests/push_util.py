@@ -5,6 +5,7 @@ import ctypes
 
 import numpy as np
 
+from env_io_util import NOISE_TOL      # the project's bound on this fp32 Box-Muller expression, here relative to sigma
 from oracle import philox_np
 
 STREAM_PUSH = 6

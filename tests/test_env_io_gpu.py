@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 import pytest
 
-from env_io_util import DelayBook, column_sigmas, delay_draw, sensor_noise64
+from env_io_util import NOISE_TOL, DelayBook, column_sigmas, delay_draw, sensor_noise64
 from env_obs_util import channels_of, column_tolerances, env_rescale64, expected_columns
 from gym_roboy_amd import _native as nat
 from test_env_obs_gpu import RANGES, ROBOTS, _actions, _state, _vec
@@ -19,7 +19,6 @@ from test_env_params_gpu import _ball12, _msj
 pytestmark = pytest.mark.gpu
 
 N, N_RANGE, STEPS, MAX_LEN = 321, 577, 12, 5
-NOISE_TOL = 2e-3          # tests/test_policy_scale_gpu.py's bound on this Box-Muller expression in fp32 (observed there: 1.6e-6)
 SIGMA = {"q": 0.01, "qd": 0.05, "length": 5e-4, "rate": 1e-3, "activation": 0.02, "force": 2.0}
 
 

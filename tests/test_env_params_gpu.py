@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from gym_roboy_amd import _native as nat
-from env_params_util import draw, perturbed, random_params
+from env_params_util import ParamOracleStepper, draw, perturbed, random_params
 
 pytestmark = pytest.mark.gpu
 
@@ -184,39 +184,6 @@ def test_set_ranges_validation():
 
 
 # ---- 4. fused env step: redraw on auto-reset, obs / reward against a host replay over the oracle ----
-class ParamOracleStepper:
-    """host_env_model's stepper interface over the fp64 oracle, each env on its own description; on reset(mask) the masked
-    envs' parameters become the next draw of the restatement (what the kernel draws where it redraws the goal)"""
-
-    def __init__(self, robot, n, seed, lo, hi, par0, draws0):
-        from oracle.c_oracle import COracle
-        self.COracle = COracle
-        self.desc = robot.get_description()
-        self.n, self.seed, self.lo, self.hi = n, seed, lo, hi
-        self.par, self.draws = par0.astype(np.float32).copy(), draws0.astype(np.uint32).copy()
-        self.q = np.zeros((n, 3), np.float32)
-        self.qd = np.zeros((n, 3), np.float32)
-        self.orc = [COracle(perturbed(self.desc, self.par[i].astype(np.float64)), "f64") for i in range(n)]
-
-    def step(self, sp):
-        nt = self.desc.n_t
-        feas = np.zeros(self.n, bool)
-        for i in range(self.n):
-            qo, qdo, fo = self.orc[i].step(self.q[i:i + 1].astype(np.float64), self.qd[i:i + 1].astype(np.float64),
-                                           sp[i:i + 1].astype(np.float64) + self.par[i, nt:2 * nt].astype(np.float64))
-            self.q[i], self.qd[i], feas[i] = qo[0], qdo[0], fo[0]
-        return self.q.copy(), self.qd.copy(), feas
-
-    def reset(self, mask):
-        idx = np.nonzero(mask)[0]
-        self.q[idx] = 0.0
-        self.qd[idx] = 0.0
-        self.par[idx] = draw(self.seed, idx.astype(np.uint64), self.draws[idx], self.lo, self.hi)
-        self.draws[idx] += 1
-        for i in idx:
-            self.orc[i] = self.COracle(perturbed(self.desc, self.par[i].astype(np.float64)), "f64")
-
-
 def test_env_step_redraws_exactly_the_done_envs_and_matches_a_host_replay():
     from host_env_model import HostEnvModel
     from gym_roboy_amd.envs.params import ParamRanges

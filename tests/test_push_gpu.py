@@ -13,11 +13,10 @@ import pytest
 
 import push_util as pu
 from gym_roboy_amd import _native as nat
-from push_util import MAX_LEN, N, PROB, SEED, STEPS
+from push_util import MAX_LEN, N, NOISE_TOL, PROB, SEED, STEPS
 
 pytestmark = pytest.mark.gpu
 
-NOISE_TOL = 2e-3          # the project's bound on this fp32 Box-Muller expression (tests/test_env_io_gpu.py; observed there: 1.6e-6)
 LANE, OCTET, WAVE, SPLIT, PAIR, SPLIT2 = 1, 2, 3, 4, 5, 6
 
 

@@ -362,7 +362,7 @@ def test_fused_env_layer_on_random_robots_matches_host_replay(seed):
     """RoboyVecEnv over the joint-tree kernel on random robots: the replay check of tests/test_tree_robot_gpu.py
     (states and goals bit for bit against the plain kernel + numpy Philox, reward / done against reward.py in float64,
     episode statistics), with auto-reset and a 9-step episode horizon so that every bookkeeping path runs."""
-    from host_env_model import HipStepper, HostEnvModel
+    from host_env_model import REWARD_ATOL, REWARD_RTOL, HipStepper, HostEnvModel
     from gym_roboy_amd.envs.vec_env import RoboyVecEnv
     if isinstance(seed, str):
         robot, desc = random_tree_robot(100 + sorted(EXTREMES).index(seed), **EXTREMES[seed])
@@ -384,7 +384,7 @@ def test_fused_env_layer_on_random_robots_matches_host_replay(seed):
         assert np.array_equal(done, h_done) or (margin[done != h_done] < 1e-5).all()
         assert (done == h_done).all()
         assert np.array_equal(obs, h_obs.astype(np.float32))
-        np.testing.assert_allclose(rew, h_rew, rtol=3e-5, atol=3e-4)
+        np.testing.assert_allclose(rew, h_rew, rtol=REWARD_RTOL, atol=REWARD_ATOL)
         n_done += int(done.sum())
     assert n_done >= 2 * n
     st = vec.stats()
@@ -402,7 +402,7 @@ def test_fused_env_layer_of_the_hiprtc_built_lane_and_split_kernels_matches_host
     separate compilations of the same generated text; the text writes its fused multiply-adds out (rbl_fma), so the two agree bit
     for bit - while a*b + c*d was left to the compiler's contraction the one-wave form of this robot differed by 6e-7 after two
     steps."""
-    from host_env_model import HipStepper, HostEnvModel
+    from host_env_model import REWARD_ATOL, REWARD_RTOL, HipStepper, HostEnvModel
     from gym_roboy_amd.envs.vec_env import RoboyVecEnv
     robot, desc = random_tree_robot(4)
     n, env_seed, max_len = 130, 5, 7
@@ -423,7 +423,7 @@ def test_fused_env_layer_of_the_hiprtc_built_lane_and_split_kernels_matches_host
         h_obs, h_rew, h_done, margin = host.step(a)
         assert (done == h_done).all() or (margin[done != h_done] < 1e-5).all()
         assert np.array_equal(obs, h_obs.astype(np.float32))
-        np.testing.assert_allclose(rew, h_rew, rtol=3e-5, atol=3e-4)
+        np.testing.assert_allclose(rew, h_rew, rtol=REWARD_RTOL, atol=REWARD_ATOL)
         n_done += int(done.sum())
     assert n_done >= 2 * n
     assert vec.sim.info()["kernel"] == kernel
