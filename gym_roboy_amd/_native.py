@@ -108,6 +108,20 @@ class EnvPushConfig(ctypes.Structure):
     _fields_ = [("threshold", ctypes.c_uint32), ("_pad", ctypes.c_uint32), ("sigma", ctypes.c_float * 32)]
 
 
+class StateSegment(ctypes.Structure):
+    """rb_state_segment: one plane of the handle's state as it lies in the blob (rb_env_state_*)"""
+    _fields_ = [("name", ctypes.c_char * 48), ("dtype", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("offset", ctypes.c_int64)]
+
+
+class StateHost(ctypes.Structure):
+    """rb_state_host: the host members of the handle that move after configuration"""
+    _fields_ = [("env_steps", ctypes.c_double), ("reserved", ctypes.c_double * 7)]
+
+
+RB_STATE_F32, RB_STATE_U32, RB_STATE_F64, RB_STATE_U64 = range(4)
+STATE_DTYPES = {RB_STATE_F32: "float32", RB_STATE_U32: "uint32", RB_STATE_F64: "float64", RB_STATE_U64: "uint64"}      # rb_state_dtype -> numpy
+
 REWARD_SHAPING_TERMS = ("action_rate", "tension", "activation")      # RoboyVecEnv(reward_shaping=...): the keys, in the record's order
 
 _vp = ctypes.c_void_p
@@ -209,6 +223,10 @@ SIGNATURES = {
     "rb_env_start_poses_configure": (ctypes.c_int, [_sim, _fp, ctypes.c_int64, ctypes.c_double]),
     "rb_env_start_poses_set": (ctypes.c_int, [_sim, _fp, ctypes.c_int64]),
     "rb_env_start_poses_ptr": (ctypes.c_int, [_sim, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
+    "rb_env_state_segments": (ctypes.c_int, [_sim, ctypes.POINTER(StateSegment), ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    "rb_env_state_bytes": (ctypes.c_int, [_sim, ctypes.POINTER(ctypes.c_int64)]),
+    "rb_env_state_save_dev": (ctypes.c_int, [_sim, _vp, ctypes.c_int64, ctypes.POINTER(StateHost)]),
+    "rb_env_state_load_dev": (ctypes.c_int, [_sim, _vp, ctypes.c_int64, ctypes.POINTER(StateHost)]),
     "rb_dispatch_rows": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(DispatchRow))]),
     "rb_auto_rules": (ctypes.c_int, [ctypes.POINTER(ctypes.POINTER(AutoRule))]),
     "rb_get_launch_thresholds": (ctypes.c_int, [ctypes.POINTER(LaunchThresholds)]),

@@ -1399,4 +1399,65 @@ int rb_params_sample_dev(rb_sim *s, const uint8_t *d_mask) {
     return RB_OK;
 }
 
+// ---- the handle's state as one blob (state_segments(), roboy_sim.hip) ----
+int rb_env_state_segments(rb_sim *s, rb_state_segment *out, int32_t capacity, int32_t *count) {
+    if (check(s) || !count || capacity < 0 || (capacity > 0 && !out)) return fail(RB_EINVAL, "null argument");
+    const std::vector<StateSeg> segs = state_segments(s);
+    std::vector<int64_t> offsets;
+    state_layout(segs, &offsets);
+    *count = int32_t(segs.size());
+    for (size_t k = 0; k < segs.size() && k < size_t(capacity); ++k) {
+        rb_state_segment &o = out[k];
+        std::memset(&o, 0, sizeof(o));
+        std::strncpy(o.name, segs[k].name, sizeof(o.name) - 1);
+        o.dtype = segs[k].dtype; o.rows = segs[k].rows; o.cols = segs[k].cols; o.offset = offsets[k];
+    }
+    return RB_OK;
+}
+int rb_env_state_bytes(rb_sim *s, int64_t *bytes) {
+    if (check(s) || !bytes) return fail(RB_EINVAL, "null argument");
+    *bytes = state_layout(state_segments(s), nullptr);
+    return RB_OK;
+}
+namespace {
+int state_blob_check(const std::vector<StateSeg> &segs, const void *d_blob, int64_t bytes) {
+    if (!d_blob) return fail(RB_EINVAL, "null argument");
+    if (reinterpret_cast<uintptr_t>(d_blob) % 16) return fail(RB_EINVAL, "env state: the blob must be 16-byte aligned");
+    const int64_t want = state_layout(segs, nullptr);
+    if (bytes != want)
+        return fail(RB_EINVAL, "env state: the handle's state has " + std::to_string(want) + " bytes (rb_env_state_bytes), got " + std::to_string(bytes));
+    return RB_OK;
+}
+}  // namespace
+int rb_env_state_save_dev(rb_sim *s, void *d_blob, int64_t bytes, rb_state_host *host) {
+    if (check(s)) return RB_EINVAL;
+    const std::vector<StateSeg> segs = state_segments(s);
+    RB_RC(state_blob_check(segs, d_blob, bytes));
+    RB_HIP(hipSetDevice(s->device));
+    // (no drain, no graph dropped: copies on the handle's stream, behind whatever was enqueued or replayed there)
+    std::vector<int64_t> offsets;
+    state_layout(segs, &offsets);
+    for (size_t k = 0; k < segs.size(); ++k)
+        RB_HIP(hipMemcpyAsync(static_cast<char *>(d_blob) + offsets[k], segs[k].ptr, state_seg_bytes(segs[k]), hipMemcpyDeviceToDevice, s->stream));
+    if (host) { std::memset(host, 0, sizeof(*host)); host->env_steps = s->env_steps; }
+    return RB_OK;
+}
+int rb_env_state_load_dev(rb_sim *s, const void *d_blob, int64_t bytes, const rb_state_host *host) {
+    std::vector<StateSeg> segs;
+    // nothing in flight may still read or write a plane.  The graphs stay: every plane is written IN PLACE - no pointer moves - so a
+    // captured graph's next replay continues from the restored state
+    RB_RC(reconfigure(s, KEEP_GRAPHS, [&]() -> int {
+        segs = state_segments(s);
+        if (host && !(host->env_steps >= 0.0)) return fail(RB_EINVAL, "env state: env_steps must be >= 0");
+        return state_blob_check(segs, d_blob, bytes);
+    }));
+    std::vector<int64_t> offsets;
+    state_layout(segs, &offsets);
+    for (size_t k = 0; k < segs.size(); ++k)
+        RB_HIP(hipMemcpyAsync(segs[k].ptr, static_cast<const char *>(d_blob) + offsets[k], state_seg_bytes(segs[k]), hipMemcpyDeviceToDevice, s->stream));
+    RB_HIP(hipStreamSynchronize(s->stream));      // (the blob is the caller's: it may free it when the call returns)
+    if (host) s->env_steps = host->env_steps;
+    return RB_OK;
+}
+
 }  // extern "C"

@@ -680,6 +680,101 @@ struct rb_sim {
 
 namespace {
 
+// ---- the handle's state (rb_env_state_*, env_host.hpp) ----
+// The ONE list of "what is state": everything a later step, reset, statistic or accessor reads that an earlier one wrote, as the handle
+// is configured now, in blob order.  rb_env_state_segments / _bytes / _save_dev / _load_dev walk it and nothing else does.  Every
+// device-pointer member of rb_sim and of the Opt* records above is EITHER named here OR on the list below (tests/test_env_state_cpu.py
+// reads this text and fails for a member in neither or in both): a new option adds its planes here.
+// not state - staging and scratch, written in full before they are read:
+//   rb_sim.d_rows, rb_sim.d_state_rows, rb_sim.d_u8, rb_sim.d_stats, rb_sim.d_ts_out, OptGoals.d_hist, OptShaping.d_red,
+//   OptEpisodeLog.d_red, OptPush.d_total
+// not state - constants of the robot or the configuration:
+//   rb_sim.d_ten, rb_sim.d_tree_words, rb_sim.d_ts_lconst, OptParams.d_ranges
+struct StateSeg { const char *name; uint32_t dtype; int64_t rows, cols; void *ptr; };
+inline size_t state_elem_bytes(uint32_t dtype) { return dtype == RB_STATE_F32 || dtype == RB_STATE_U32 ? 4 : 8; }
+inline size_t state_seg_bytes(const StateSeg &g) { return state_elem_bytes(g.dtype) * size_t(g.rows) * size_t(g.cols); }
+std::vector<StateSeg> state_segments(rb_sim *s) {
+    std::vector<StateSeg> v;
+    const int64_t n = s->n, nq = s->n_q, nt = s->n_t;
+    auto seg = [&](const char *name, uint32_t dtype, int64_t rows, int64_t cols, void *p) {      // (an option that is off holds null planes)
+        if (p && rows > 0 && cols > 0) v.push_back(StateSeg{name, dtype, rows, cols, p});
+    };
+    // joint planes: [n_q][n] for the ball-joint classes, [n][n_q] for joint trees
+    const int64_t jr = s->tree ? n : nq, jc = s->tree ? nq : n;
+    seg("core.q", RB_STATE_F32, jr, jc, s->d_q);
+    seg("core.qd", RB_STATE_F32, jr, jc, s->d_qd);
+    seg("core.feas", RB_STATE_U32, 1, n, s->d_feas);
+    seg("core.goal_count", RB_STATE_U32, 1, n, s->d_goal_count);
+    if (s->env_ready) {
+        seg("env.goal", RB_STATE_F32, jr, jc, s->d_goal);
+        seg("env.ep_ret", RB_STATE_F32, 1, n, s->d_ep_ret);
+        seg("env.step_num", RB_STATE_U32, 1, n, s->d_step_num);
+        seg("env.ep_sum", RB_STATE_F64, 2, n, s->d_ep_sum);
+        seg("env.ep_cnt", RB_STATE_U32, 3, n, s->d_ep_cnt);
+        seg("env.infeas_n", RB_STATE_U32, 1, n, s->d_infeas_n);      // (only env steps count into it)
+    }
+    if (s->par.on) {
+        seg("par.planes", RB_STATE_F32, s->par.n, n, s->par.d_planes);
+        seg("par.draws", RB_STATE_U32, 1, n, s->par.d_draws);
+    }
+    if (s->io.on) {
+        seg("io.delay", RB_STATE_U32, 1, n, s->io.d_delay);
+        seg("io.draws", RB_STATE_U32, 1, n, s->io.d_draws);
+        seg("io.rows", RB_STATE_U32, 1, n, s->io.d_rows);
+    }
+    seg("io.ring", RB_STATE_F32, s->io.slots, n * nt, s->io.d_ring);      // (action rows keep a ring without an io configuration)
+    if (s->done.on) {
+        seg("done.seen", RB_STATE_U32, 1, n, s->done.d_seen);
+        seg("done.kind", RB_STATE_U32, 1, n, s->done.d_kind);
+    }
+    seg("critic.rows", RB_STATE_F32, n, s->critic.dim, s->critic.d_rows);
+    seg("goals.pool", RB_STATE_F32, s->goals.m, nq, s->goals.d_pool);
+    if (s->goals.L) {
+        seg("goals.level", RB_STATE_U32, 1, n, s->goals.d_level);
+        seg("goals.index", RB_STATE_U32, 1, n, s->goals.d_index);
+        seg("goals.seen", RB_STATE_U32, 1, n, s->goals.d_seen);
+    }
+    seg("goals.row_stats", RB_STATE_U64, 2, s->goals.m, s->goals.d_row_stats);
+    if (s->shaping.on) {
+        seg("shaping.prev", RB_STATE_F32, n, nt, s->shaping.d_prev);
+        seg("shaping.cost", RB_STATE_F32, 1, n, s->shaping.d_cost);
+        seg("shaping.run", RB_STATE_F64, 1, n, s->shaping.d_run);
+        seg("shaping.sums", RB_STATE_F64, 2, n, s->shaping.d_sums);
+        seg("shaping.cnt", RB_STATE_U32, 2, n, s->shaping.d_cnt);
+    }
+    if (s->push.on) {
+        seg("push.count", RB_STATE_U32, 1, n, s->push.d_count);
+        seg("push.last", RB_STATE_U32, 1, n, s->push.d_last);
+        seg("push.n", RB_STATE_U32, 1, n, s->push.d_n);
+        seg("push.impulse", RB_STATE_F32, n, nq, s->push.d_impulse);
+    }
+    if (s->elog.E) {
+        seg("elog.acc", RB_STATE_F32, 1, n, s->elog.d_acc);
+        seg("elog.ret", RB_STATE_F32, s->elog.E, n, s->elog.d_ret);
+        seg("elog.age", RB_STATE_U32, 1, n, s->elog.d_age);
+        seg("elog.seen", RB_STATE_U32, 1, n, s->elog.d_seen);
+        seg("elog.count", RB_STATE_U32, 1, n, s->elog.d_count);
+        seg("elog.len", RB_STATE_U32, s->elog.E, n, s->elog.d_len);
+        seg("elog.kind", RB_STATE_U32, s->elog.E, n, s->elog.d_kind);
+        seg("elog.full", RB_STATE_U32, 1, 1, s->elog.d_full);
+    }
+    if (s->start.m) {
+        seg("start.pool", RB_STATE_F32, s->start.m, nq, s->start.d_pool);
+        seg("start.count", RB_STATE_U32, 1, n, s->start.d_count);
+        seg("start.index", RB_STATE_U32, 1, n, s->start.d_index);
+    }
+    return v;
+}
+// the segments' byte offsets in the blob (each 16-byte aligned) and the blob's size
+inline int64_t state_layout(const std::vector<StateSeg> &segs, std::vector<int64_t> *offsets) {
+    int64_t at = 0;
+    for (const StateSeg &g : segs) {
+        if (offsets) offsets->push_back(at);
+        at += int64_t((state_seg_bytes(g) + 15) & ~size_t(15));
+    }
+    return at;
+}
+
 // Build the run-time specialised kernels of this robot once, outside any stream capture (hipModuleLoadData
 // is not capturable): called by the entry points before they launch or capture.
 // A stream that is being captured must not see the build: the attempt is left for a later call (the state stays

@@ -449,6 +449,82 @@ def check_env_checkpoint(env, ck, critic_dim=None) -> dict:
     return kept
 
 
+# ---- the env's state (RoboyVecEnv.state_dict / load_state_dict) ----
+ENV_STATE_VERSION = 1
+ENV_STATE_IDENTITY = ("n_envs", "n_q", "n_t", "seed", "env_id_offset", "integrator", "n_substeps", "step_size")
+ENV_STATE_KEYS = ("version", "identity", "segments", "blob", "host", "env", "slabs", "markers")
+ENV_STATE_SLABS = ("act", "obs", "rew", "done")
+_STATE_ITEM_BYTES = {"float32": 4, "uint32": 4, "float64": 8, "uint64": 8}
+
+
+def check_env_state_dict(sd) -> None:
+    """``ValueError`` where ``sd`` is no ``RoboyVecEnv.state_dict()``: not a dict, a key missing, another version, a segment table
+    that is no list of ``(name, dtype, rows, cols, offset)``, or a blob that is no ``uint8`` array as long as the table says.  Looks
+    at ``sd`` alone: no env, no library."""
+    if not isinstance(sd, dict):
+        raise ValueError("load_state_dict: a dict from RoboyVecEnv.state_dict(), got %s" % type(sd).__name__)
+    for key in ENV_STATE_KEYS:
+        if key not in sd:
+            raise ValueError("load_state_dict: the dict has no %r (not a RoboyVecEnv.state_dict())" % key)
+    if sd["version"] != ENV_STATE_VERSION:
+        raise ValueError("load_state_dict: state version %r, this package reads version %d" % (sd["version"], ENV_STATE_VERSION))
+    end = 0
+    for seg in sd["segments"]:
+        if not (isinstance(seg, (tuple, list)) and len(seg) == 5 and isinstance(seg[0], str) and seg[1] in _STATE_ITEM_BYTES
+                and all(isinstance(v, (int, np.integer)) and v >= 0 for v in seg[2:])):
+            raise ValueError("load_state_dict: %r is no segment (name, dtype, rows, cols, offset)" % (seg,))
+        if seg[4] % 16 or seg[4] < end:
+            raise ValueError("load_state_dict: segment %r lies at offset %d, behind a table that ends at %d" % (seg[0], seg[4], end))
+        end = seg[4] + _STATE_ITEM_BYTES[seg[1]] * seg[2] * seg[3]
+    blob = sd["blob"]
+    if not isinstance(blob, np.ndarray) or blob.dtype != np.uint8 or blob.ndim != 1:
+        raise ValueError("load_state_dict: the blob must be a one-dimensional uint8 numpy array")
+    if blob.nbytes != (end + 15) // 16 * 16:
+        raise ValueError("load_state_dict: the blob has %d bytes, its segment table describes %d" % (blob.nbytes, (end + 15) // 16 * 16))
+    for name in ENV_STATE_SLABS:
+        if not isinstance(sd["slabs"].get(name), np.ndarray):
+            raise ValueError("load_state_dict: the dict has no %r slab" % name)
+    if "env_steps" not in sd["host"]:
+        raise ValueError("load_state_dict: the host record has no env_steps")
+
+
+def compare_env_state(identity, segments, sd) -> None:
+    """Is ``sd`` (a ``state_dict()``) the state of an env like this one - ``identity`` (``{field: value}`` over ``ENV_STATE_IDENTITY``)
+    and ``segments`` (``HipBatchSimulation.state_segments()``)?  ``ValueError`` naming the FIRST identity field, then the first segment
+    that differs: one this env has and the dict lacks (or the other way round), another dtype, another shape, another place in the
+    blob.  A pure function of its arguments: nothing is copied before it has passed."""
+    theirs = sd["identity"]
+    for field in ENV_STATE_IDENTITY:
+        if field not in theirs:
+            raise ValueError("load_state_dict: the state's identity has no %r" % field)
+        if theirs[field] != identity[field]:
+            raise ValueError("load_state_dict: the state was taken from an env with %s = %r, this env has %s = %r"
+                             % (field, theirs[field], field, identity[field]))
+    own, other = [tuple(s) for s in segments], [tuple(s) for s in sd["segments"]]
+    own_names, other_names = [s[0] for s in own], [s[0] for s in other]
+    for k in range(max(len(own), len(other))):
+        a, b = own[k] if k < len(own) else None, other[k] if k < len(other) else None
+        if a == b:
+            continue
+        if a is None or (b is not None and a[0] != b[0] and b[0] not in own_names):
+            raise ValueError("load_state_dict: the state has the segment %r, this env has none (an option it does not run)" % b[0])
+        if b is None or a[0] != b[0]:
+            if a[0] not in other_names:
+                raise ValueError("load_state_dict: this env has the segment %r, the state has none (an option the saved env did not run)" % a[0])
+            raise ValueError("load_state_dict: segment %r stands at another place in the state's table (%r there)" % (a[0], b[0]))
+        if a[1] != b[1]:
+            raise ValueError("load_state_dict: segment %r is %s in the state, %s in this env" % (a[0], b[1], a[1]))
+        if a[2:4] != b[2:4]:
+            raise ValueError("load_state_dict: segment %r has shape [%d][%d] in the state, [%d][%d] in this env" % (a[0], b[2], b[3], a[2], a[3]))
+        raise ValueError("load_state_dict: segment %r lies at offset %d in the state, %d in this env" % (a[0], b[4], a[4]))
+
+
+def env_state_views(segments, blob) -> dict:
+    """``{name: array [rows, cols]}``: every segment as a numpy VIEW of the blob (no copy)"""
+    return {name: blob[offset:offset + _STATE_ITEM_BYTES[dtype] * rows * cols].view(dtype).reshape(rows, cols)
+            for name, dtype, rows, cols, offset in segments}
+
+
 def env_kwargs_from_checkpoint(ck):
     """A checkpoint -> ``(kwargs, needs_vec_env)``: the arguments of a one-env ``RoboyVecEnv`` that gives the policy's row under the conditions it
     was trained under, and whether playback needs one - ``RoboyEnv`` takes ``kwargs["goals"]`` and has no channels, noise, delay, action rows, pushes."""

@@ -45,6 +45,7 @@ class HipBatchSimulation:
         self.n_params = 0              # P while per-env parameters are enabled
         self._d_param_mask = None      # sample_params(mask): device copy of the mask (first use)
         self._goal_pool_m = 0          # rows of the goal pool set through set_goal_pool (0: none)
+        self._d_state = None           # save_state / load_state: (device buffer, bytes) of the blob (first use)
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
@@ -307,6 +308,54 @@ class HipBatchSimulation:
         nat.check(self._lib.rb_memcpy_d2h(self._h, out.ctypes.data_as(ctypes.c_void_p),
                                           ctypes.c_void_p(d_ptr), out.nbytes))
         return out
+
+    # -- the handle's state as one blob (rb_env_state_*) -----
+    def state_segments(self) -> list:
+        """The handle's state planes as configured now, in blob order: tuples ``(name, dtype, rows, cols, offset)`` - ``dtype`` a
+        numpy type name, ``offset`` the segment's byte offset in the blob."""
+        count = ctypes.c_int32()
+        nat.check(self._lib.rb_env_state_segments(self._h, None, 0, ctypes.byref(count)))
+        segs = (nat.StateSegment * max(count.value, 1))()
+        nat.check(self._lib.rb_env_state_segments(self._h, segs, count.value, ctypes.byref(count)))
+        return [(s.name.decode("ascii"), nat.STATE_DTYPES[s.dtype], int(s.rows), int(s.cols), int(s.offset)) for s in segs[:count.value]]
+
+    def state_bytes(self) -> int:
+        nbytes = ctypes.c_int64()
+        nat.check(self._lib.rb_env_state_bytes(self._h, ctypes.byref(nbytes)))
+        return int(nbytes.value)
+
+    def _state_blob(self, nbytes: int) -> int:
+        """the device buffer a snapshot passes through (kept: a trainer takes one per backup)"""
+        if self._d_state is None or self._d_state[1] < nbytes:
+            self._d_state = (self.malloc(max(nbytes, 16)), nbytes)
+        return self._d_state[0]
+
+    def save_state(self):
+        """``(blob, host)``: every state plane of the handle, copied out on its stream behind whatever is in flight there, as one
+        ``uint8`` numpy array laid out as ``state_segments()`` says, and the host members ``{"env_steps": float}``."""
+        nbytes, host = self.state_bytes(), nat.StateHost()
+        d_blob = self._state_blob(nbytes)
+        nat.check(self._lib.rb_env_state_save_dev(self._h, ctypes.c_void_p(d_blob), nbytes, ctypes.byref(host)))
+        blob, end = self.download(d_blob, (nbytes,), np.uint8), 0
+        for _, dtype, rows, cols, offset in self.state_segments() + [("", "uint8", 0, 0, nbytes)]:
+            blob[end:offset] = 0           # the padding between segments: the same state gives the same bytes
+            end = offset + np.dtype(dtype).itemsize * rows * cols
+        return blob, {"env_steps": float(host.env_steps)}
+
+    def load_state(self, blob, host=None):
+        """Write every state plane back in place from ``blob`` (``save_state``'s, of a handle configured like this one: the library
+        checks the byte count alone, ``ValueError``) and set the host members.  No pointer moves and no graph is dropped."""
+        blob = np.ascontiguousarray(blob, dtype=np.uint8).reshape(-1)
+        if blob.nbytes != self.state_bytes():
+            raise ValueError("env state: the handle's state has %d bytes, the blob has %d" % (self.state_bytes(), blob.nbytes))
+        d_blob = self._state_blob(blob.nbytes)
+        if blob.nbytes:
+            self.upload(d_blob, blob)
+        h = None
+        if host is not None:
+            h = nat.StateHost()
+            h.env_steps = float(host["env_steps"])
+        nat.check(self._lib.rb_env_state_load_dev(self._h, ctypes.c_void_p(d_blob), blob.nbytes, None if h is None else ctypes.byref(h)))
 
     def step_dev(self, d_act: int, act_scale: float = 1.0):
         nat.check(self._lib.rb_step_dev(self._h, ctypes.c_void_p(d_act), float(act_scale)))

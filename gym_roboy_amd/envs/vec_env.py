@@ -246,6 +246,7 @@ class RoboyVecEnv:
         n = self.num_envs                  # (behind the options that set obs_dim)
         self._d_act, self._d_obs = self.sim.malloc(4 * n * self.n_t), self.sim.malloc(4 * n * self.obs_dim)
         self._d_rew, self._d_done = self.sim.malloc(4 * n), self.sim.malloc(4 * n)
+        self._slabs_live = 0           # state_dict(): 0 = nothing of this env has written its slabs, 1 = a reset (obs), 2 = a numpy step (all)
         self._pending_actions = None
         self._last_actions = None      # tendon_state(): the last step's actions - _IN_SLAB (numpy: in _d_act) or the torch tensor
         self._d_ts = None              # tendon_state(): device outputs of the numpy path (4 x [N, n_t], first use)
@@ -485,6 +486,7 @@ class RoboyVecEnv:
             self.sim.sample_params()
         nat.check(self.sim._lib.rb_env_reset_dev(self.sim.handle, ctypes.c_void_p(self._d_obs)))
         self._last_cobs = None
+        self._slabs_live = max(self._slabs_live, 1)
         self.sim.synchronize()
         return self.sim.download(self._d_obs, (self.num_envs, self.obs_dim))
 
@@ -510,6 +512,7 @@ class RoboyVecEnv:
         self._last_actions = _IN_SLAB
         self._last_done_codes = None
         self._last_cobs = None
+        self._slabs_live = 2
         self.sim.synchronize()
         n = self.num_envs
         return (self.sim.download(self._d_obs, (n, self.obs_dim)),
@@ -859,6 +862,82 @@ class RoboyVecEnv:
         """Every env's physical parameters (``HipBatchSimulation.get_params``); needs ``randomization``."""
         self._need(self.randomization is not None, "this RoboyVecEnv has no per-env parameters (randomization=None)")
         return self.sim.get_params()
+
+    # -- snapshot and restore (rb_env_state_*; DESIGN.md §31) ---------------
+    def _state_identity(self) -> dict:
+        info = self.sim.info()
+        return {"n_envs": int(info["n_envs"]), "n_q": int(info["n_q"]), "n_t": int(info["n_t"]), "seed": self._seed,
+                "env_id_offset": int(info["env_id_offset"]), "integrator": int(info["integrator"]), "n_substeps": int(info["n_substeps"]),
+                "step_size": float(info["step_size"])}
+
+    def state_dict(self, dict_view: bool = False) -> dict:
+        """Everything a later ``step``, ``reset``, statistic or accessor of this env reads that an earlier one wrote, as a plain dict
+        ``torch.save`` takes: ``load_state_dict`` of it into an env constructed with the same arguments continues this env bit for bit
+        (every random draw is keyed by seed, global env id and a counter that is part of the state).  Keys: ``"identity"`` (batch
+        size, robot sizes, seed, env id offset, integrator, substeps, step size), ``"segments"`` (the library's table of state planes:
+        tuples ``(name, dtype, rows, cols, offset)``), ``"blob"`` (those planes, one ``uint8`` numpy array), ``"host"`` (the env-step
+        count kept on the host: the library's and the steps replayed from captured graphs as ONE number, as ``stats()`` reports them -
+        ``stats_dev`` of the restored env counts the replayed ones too), ``"env"`` (``options.env_checkpoint_record`` - the options in readable form), ``"slabs"`` (the env's
+        own action / observation / reward / done buffers) and ``"markers"``.  Taken on the env's stream behind whatever is in flight
+        there; work a caller put on another stream (a captured graph on a side stream) must have finished.
+        The markers say where the last step's actions, done codes and critic rows are.  A marker that named a CALLER's tensor - after
+        a torch step - comes back as None, so in the restored env, until its next step, ``tendon_state()`` without arguments reads
+        all set-points 0 and ``critic_obs()`` reads the handle's own plane (the rows of the last reset or numpy step), and the
+        accessors answer in numpy.  ``truncated()`` reads the handle's code plane, which is part of the state.
+        ``dict_view=True`` adds ``"views"``: every segment as a named numpy view ``[rows, cols]`` of the blob (tests, debugging)."""
+        if not isinstance(dict_view, (bool, np.bool_)):
+            raise ValueError("state_dict: dict_view must be a bool, got %r" % (dict_view,))
+        if getattr(self, "_pending_actions", None) is not None:
+            raise RuntimeError("state_dict() between step_async() and step_wait(): the pending actions are no part of a state")
+        from .options import ENV_STATE_VERSION, env_checkpoint_record, env_state_views
+        record = env_checkpoint_record(self)           # (reads through the accessors: before the snapshot, it changes no plane)
+        segments = self.sim.state_segments()
+        blob, host = self.sim.save_state()
+        host["env_steps"] += float(self._replayed_env_steps)      # one count: stats() adds the two, a captured rollout moves between them
+        n = self.num_envs
+        # (a slab nothing of this env has written yet holds whatever the allocation held: zeros stand for it, so that the same run gives
+        # the same bytes - torch steps and captured rollouts never touch them)
+        live = self._slabs_live
+        slabs = {"act": self.sim.download(self._d_act, (n, self.n_t)) if live > 1 else np.zeros((n, self.n_t), np.float32),
+                 "obs": self.sim.download(self._d_obs, (n, self.obs_dim)) if live > 0 else np.zeros((n, self.obs_dim), np.float32),
+                 "rew": self.sim.download(self._d_rew, (n,)) if live > 1 else np.zeros((n,), np.float32),
+                 "done": self.sim.download(self._d_done, (n,), np.uint32) if live > 1 else np.zeros((n,), np.uint32)}
+        sd = {"version": ENV_STATE_VERSION, "identity": self._state_identity(), "segments": segments, "blob": blob, "host": host,
+              "env": record, "slabs": slabs,
+              "markers": {"last_actions": "slab" if self._last_actions is _IN_SLAB else None, "last_done_codes": None, "last_cobs": None}}
+        if dict_view:
+            sd["views"] = env_state_views(segments, blob)
+        return sd
+
+    def load_state_dict(self, sd):
+        """Continue from ``sd`` (``state_dict()`` of an env constructed with the same arguments).  Identity and segment table are
+        compared first: ``ValueError`` naming the first field or segment that differs - another batch size or seed, an option this
+        env does not run or the saved one did not, another ring size or log capacity - and nothing has been copied then.  Every plane
+        is written in place, so a captured graph of this env's steps continues from the restored state at its next replay.  The pools'
+        recipes (``goal_recipe``, ``start_recipe``) come back with their rows; an action handed to ``step_async`` and not yet waited
+        for is dropped (``state_dict()`` refuses to be taken in that place)."""
+        from .options import ENV_STATE_SLABS, check_env_state_dict, compare_env_state
+        check_env_state_dict(sd)                       # (the dict alone: before any library call)
+        compare_env_state(self._state_identity(), self.sim.state_segments(), sd)
+        n = self.num_envs
+        shapes = {"act": (n, self.n_t), "obs": (n, self.obs_dim), "rew": (n,), "done": (n,)}
+        for name in ENV_STATE_SLABS:
+            if sd["slabs"][name].shape != shapes[name]:
+                raise ValueError("load_state_dict: the %s slab has shape %s, this env's has %s" % (name, sd["slabs"][name].shape, shapes[name]))
+        self.sim.load_state(sd["blob"], {"env_steps": sd["host"]["env_steps"]})
+        for name, d_ptr, dtype in (("act", self._d_act, np.float32), ("obs", self._d_obs, np.float32), ("rew", self._d_rew, np.float32),
+                                   ("done", self._d_done, np.uint32)):
+            self.sim.upload(d_ptr, np.ascontiguousarray(sd["slabs"][name], dtype=dtype))
+        self._slabs_live = 2
+        self._replayed_env_steps = 0.0                 # (the state's count holds the replayed steps: the library's counter has them now)
+        self._last_actions = _IN_SLAB if sd["markers"].get("last_actions") == "slab" else None
+        self._last_done_codes = self._last_cobs = None
+        self._pending_actions = None
+        # what set_goal_pool / set_start_poses / permute_goal_pool move beside the rows: the recipes a later checkpoint records
+        if self.goal_pool_size and "goals" in sd["env"]:
+            self.goal_recipe = dict(sd["env"]["goals"].get("recipe") or {})
+        if self.start_poses_size and "env_start_poses" in sd["env"]:
+            self.start_recipe = dict(sd["env"]["env_start_poses"].get("recipe") or {})
 
     def close(self):
         self.sim.close()

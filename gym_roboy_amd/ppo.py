@@ -962,6 +962,40 @@ def evaluate_policy(policy, env, episodes_per_env=1, poll_every=32, fused=None, 
     return summary
 
 
+def pack_arrays(x):
+    """a nest of dicts, lists and tuples with its numpy arrays as ``{"__ndarray__": bytes as a uint8 tensor, "dtype", "shape"}``: what
+    ``torch.load`` takes under ``weights_only=True``, whatever the arrays' types (a resume record holds the env's state blob)"""
+    if isinstance(x, dict):
+        return {k: pack_arrays(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(pack_arrays(v) for v in x)
+    if isinstance(x, np.ndarray):
+        flat = np.ascontiguousarray(x).reshape(-1).view(np.uint8)
+        return {"__ndarray__": torch.from_numpy(flat.copy()), "dtype": str(x.dtype), "shape": [int(d) for d in x.shape]}
+    if isinstance(x, np.generic):
+        return x.item()
+    return x
+
+
+def _tensors_to(x, device):
+    """a checkpoint's nest with its tensors on ``device`` (what ``torch.load(map_location=device)`` gives)"""
+    if isinstance(x, dict):
+        return type(x)((k, _tensors_to(v, device)) for k, v in x.items())
+    if isinstance(x, (list, tuple)):
+        return type(x)(_tensors_to(v, device) for v in x)
+    return x.to(device) if torch.is_tensor(x) else x
+
+
+def unpack_arrays(x):
+    if isinstance(x, dict):
+        if "__ndarray__" in x:
+            return x["__ndarray__"].cpu().numpy().view(np.dtype(x["dtype"])).reshape(x["shape"]).copy()
+        return {k: unpack_arrays(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(unpack_arrays(v) for v in x)
+    return x
+
+
 class PPO:
     def __init__(self, env, policy=None, n_steps=128, nminibatches=4, noptepochs=4, gamma=0.99, lam=0.95,
                  learning_rate=2.5e-4, cliprange=0.2, ent_coef=0.01, vf_coef=0.5, max_grad_norm=0.5,
@@ -1301,11 +1335,11 @@ class PPO:
         asym = self.asymmetric_critic
         if asym:
             b["cobs"], b["ccarry"] = z(T + 1, N, self.cobs_dim), z(N, self.cobs_dim)
-        if self._obs is None and self.reward_norm is not None:
+        fresh = self._obs is None             # (not fresh: load() restored a run - its observation and running returns go on)
+        if fresh and self.reward_norm is not None:
             self.reward_norm.reset_returns(N)
-        if self._boot_tail is not None:
+        if self._boot_tail is not None and (fresh or self._boot_tail.n_envs != N):
             self._boot_tail.reset_returns(N)
-        fresh = self._obs is None
         b["carry"].copy_(self._to_tensor(env.reset()) if fresh else self._obs)
         if asym:
             b["ccarry"].copy_(self._critic_rows() if fresh else self._cobs)
@@ -1699,7 +1733,69 @@ class PPO:
                 log(stats)
         return self
 
-    def save(self, path):
+    def resume_record(self):
+        """What ``collect()`` and ``update()`` carry from one call to the next beyond the checkpoint's own keys, and the env's state
+        (``save(path, resume=True)``'s ``"resume"`` key; a multi-rank trainer writes one per rank): with it a loaded agent continues the
+        run - on the fused paths bit for bit.  Only tensors, numbers and strings: ``torch.load`` takes it as it is."""
+        cpu = lambda t: None if t is None else t.detach().to("cpu", copy=True)
+        norm = lambda n: None if n is None else {"state": cpu(n.state), "norm": cpu(n.norm)}
+        rec = {"env": pack_arrays(self.env.state_dict()), "obs": cpu(self._obs), "cobs": cpu(self._cobs), "epoch": self._epoch,
+               "step_base": int(self._step_base.item()) if self._fused is not None else None,
+               "obs_norm_prime": self._obs_norm_prime, "reward_norm_prime": self._reward_norm_prime,
+               "obs_norm": norm(self.obs_norm), "critic_obs_norm": norm(self.cobs_norm), "reward_norm": norm(self.reward_norm),
+               "ret_carry": cpu(self.reward_norm.ret_carry) if self.reward_norm is not None else None,
+               "boot_ret_carry": cpu(self._boot_tail.ret_carry) if self._boot_tail is not None else None}
+        if self._fused is None or self._fgrad is None:       # the torch paths draw from torch's generators (no bit-for-bit claim)
+            rec["torch_rng"] = torch.get_rng_state()
+            rec["torch_cuda_rng"] = torch.cuda.get_rng_state(self.device) if self.device.type == "cuda" else None
+        return rec
+
+    def load_resume_record(self, rec):
+        """Continue from ``resume_record()``'s dict, behind a ``load()`` of the checkpoint written with it: the env's state first
+        (``ValueError`` for a record of another env, and nothing has changed then), then the agent's carries."""
+        self._load_resume_env(rec)
+        self._load_resume_agent(rec)
+
+    def _load_resume_env(self, rec):
+        if not callable(getattr(self.env, "load_state_dict", None)):
+            raise ValueError("a resume record needs an env with state_dict() / load_state_dict() (RoboyVecEnv)")
+        self.env.load_state_dict(unpack_arrays(rec["env"]))      # (compares identity and segment table first)
+
+    def _load_resume_agent(self, rec):
+        """the agent's side of a resume record (the env's has been loaded): tensors that a captured rollout reads by address are
+        written in place where they exist"""
+        def put(name, value):
+            cur = getattr(self, name)
+            if value is None:
+                setattr(self, name, None)
+            elif torch.is_tensor(cur) and tuple(cur.shape) == tuple(value.shape):
+                cur.copy_(value)                             # (graph mode: _obs IS the rollout's carry buffer)
+            else:
+                setattr(self, name, value.to(self.device))
+        put("_obs", rec["obs"]); put("_cobs", rec["cobs"])
+        self._epoch = int(rec["epoch"])
+        if self._fused is not None and rec["step_base"] is not None:
+            self._step_base.fill_(int(rec["step_base"]))     # the exact value: a priming rollout counts, num_timesteps does not know it
+        self._obs_norm_prime, self._reward_norm_prime = bool(rec["obs_norm_prime"]), bool(rec["reward_norm_prime"])
+        for n, saved in ((self.obs_norm, rec["obs_norm"]), (self.cobs_norm, rec["critic_obs_norm"]), (self.reward_norm, rec["reward_norm"])):
+            if n is not None and saved is not None:          # the float64 state and the float32 form as the device's merge left them
+                n.state.copy_(saved["state"]); n.norm.copy_(saved["norm"])
+        for rn, carry in ((self.reward_norm, rec["ret_carry"]), (self._boot_tail, rec["boot_ret_carry"])):
+            if rn is not None and carry is not None:
+                if rn.n_envs != int(carry.numel()):
+                    rn.reset_returns(int(carry.numel()))
+                rn.ret_carry.copy_(carry)
+        if rec.get("torch_rng") is not None and (self._fused is None or self._fgrad is None):
+            torch.set_rng_state(rec["torch_rng"].cpu())
+            if rec.get("torch_cuda_rng") is not None and self.device.type == "cuda":
+                torch.cuda.set_rng_state(rec["torch_cuda_rng"].cpu(), self.device)
+
+    def save(self, path, resume=False):
+        """``resume=True`` adds ONE key, ``"resume"``: the env's state (``RoboyVecEnv.state_dict``), the carried observation and
+        critic rows, the exact noise step base, the epoch count, the priming flags, the statistics as the device holds them and the
+        running returns - ``load`` then continues the run where it stopped instead of restarting the envs (on the fused paths the
+        continued run is the uninterrupted one bit for bit; the torch paths also restore torch's generators and claim nothing).
+        Without it the checkpoint is the one it always was."""
         opt = self._fadam.state_dict() if self._fgrad is not None else self.opt.state_dict()
         ck = {"policy": self.policy.state_dict(), "optimizer": opt, "num_timesteps": self.num_timesteps,
               "epoch": self._epoch, **env_checkpoint_record(self.env, critic=self.asymmetric_critic),
@@ -1716,16 +1812,46 @@ class PPO:
         if self.lr_schedule is not None:             # (an agent without a schedule writes the checkpoint it always wrote)
             ck["lr_schedule"] = {"kind": self.lr_schedule, "desired_kl": self.desired_kl, "lr_factor": self.lr_factor,
                                  "lr_min": self.lr_min, "lr_max": self.lr_max, "lr": self.learning_rate}
+        if resume:
+            if not callable(getattr(self.env, "state_dict", None)):
+                raise ValueError("save(resume=True) needs an env with state_dict() / load_state_dict() (RoboyVecEnv)")
+            ck["resume"] = self.resume_record()
         torch.save(ck, path)
 
-    def load(self, path):
-        ck = torch.load(path, map_location=self.device)
+    def _check_layout_options(self, ck):
         if ("critic_obs" in ck) != self.asymmetric_critic:
             raise ValueError("the checkpoint was trained %s an asymmetric critic, this agent runs %s one (PPO's asymmetric_critic)"
                              % (("with", "without") if not self.asymmetric_critic else ("without", "with")))
         if ck.get("symmetry") != self.symmetry:
             raise ValueError("the checkpoint was trained with symmetry=%r, this agent runs symmetry=%r (PPO's symmetry)"
                              % (ck.get("symmetry"), self.symmetry))
+
+    def _check_norm_options(self, ck):
+        if (ck.get("obs_norm") is not None) != (self.obs_norm is not None):      # (a checkpoint without the key: written without it)
+            raise ValueError("the checkpoint was trained %s observation normalisation, this agent runs %s it (PPO's normalize_obs)"
+                             % (("with", "without") if self.obs_norm is None else ("without", "with")))
+        if (ck.get("reward_norm") is not None) != (self.reward_norm is not None):
+            raise ValueError("the checkpoint was trained %s reward normalisation, this agent runs %s it (PPO's normalize_reward)"
+                             % (("with", "without") if self.reward_norm is None else ("without", "with")))
+
+    def load(self, path, resume=None):
+        """``resume``: None - continue from the checkpoint's ``"resume"`` record where it has one (``save(path, resume=True)``);
+        False - ignore the record: the envs start over as they always did; True - insist (``ValueError`` without a record).  A
+        record whose env is not this agent's env - another batch size, seed or option - raises ``RoboyVecEnv.load_state_dict``'s
+        ``ValueError`` before anything of the agent or the env has changed, and so do the agent options ``load`` has always refused
+        (asymmetric critic, symmetry, the normalisations): with a record they are looked at before the env is written."""
+        ck = torch.load(path, map_location="cpu")            # (the record's env blob stays on the host: the env takes numpy)
+        record = ck.pop("resume", None)
+        ck = _tensors_to(ck, self.device)                   # ... everything else where it always was
+        if not (resume is None or resume):
+            record = None
+        if resume and record is None:
+            raise ValueError("load(resume=True): the checkpoint has no resume record (save(path, resume=True))")
+        if record is not None:
+            self._check_layout_options(ck)
+            self._check_norm_options(ck)
+            self._load_resume_env(record)
+        self._check_layout_options(ck)
         if self.symmetry == "loss" and float(ck.get("symmetry_coef", self.symmetry_coef)) != self.symmetry_coef:
             # the coefficient is a weight, not a layout: the constructor's holds (a run may be resumed under another one), and says so
             import warnings
@@ -1734,12 +1860,7 @@ class PPO:
         # the env's side; what the env does not take over is kept as checkpoint_goals, _goal_row_stats, _goal_curriculum and _env_push
         for key, value in check_env_checkpoint(self.env, ck, self.cobs_dim).items():
             setattr(self, "checkpoint_" + key, value)
-        if (ck.get("obs_norm") is not None) != (self.obs_norm is not None):      # (a checkpoint without the key: written without it)
-            raise ValueError("the checkpoint was trained %s observation normalisation, this agent runs %s it (PPO's normalize_obs)"
-                             % (("with", "without") if self.obs_norm is None else ("without", "with")))
-        if (ck.get("reward_norm") is not None) != (self.reward_norm is not None):
-            raise ValueError("the checkpoint was trained %s reward normalisation, this agent runs %s it (PPO's normalize_reward)"
-                             % (("with", "without") if self.reward_norm is None else ("without", "with")))
+        self._check_norm_options(ck)
         if self.obs_norm is not None:
             self.obs_norm.load_state_dict(ck["obs_norm"])
             self._obs_norm_prime = self._obs_norm_prime and float(ck["obs_norm"]["count"]) == 0.0
@@ -1786,4 +1907,6 @@ class PPO:
             # resumed run does not replay the noise of its first rollouts
             n_envs = getattr(self.env, "num_envs", 1)
             self._step_base.fill_(int(self.num_timesteps // max(n_envs, 1)) & 0x7FFFFFFF)
+        if record is not None:
+            self._load_resume_agent(record)
         return self

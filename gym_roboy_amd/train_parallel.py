@@ -92,6 +92,12 @@ def main(argv=None):
                          "statistics then show eval_success_rate, eval_mean_return and eval_mean_length; 0 (default): no second env")
     ap.add_argument("--eval-envs", type=int, default=4096, metavar="N", help="evaluation envs per rank (default 4096)")
     ap.add_argument("--eval-episodes", type=int, default=1, metavar="E", help="episodes per evaluation env, at most 64 (default 1)")
+    ap.add_argument("--exact-resume", action="store_true",
+                    help="every backup also carries what continues the run: each rank writes resume.rank<R>.pt beside model.pkl - its env "
+                         "shard's state, its agent's carries and its evaluation env's state - and a start that finds model.pkl and these files "
+                         "continues where the backup was taken instead of restarting the envs (the same ranks and batch sizes); the count of "
+                         "completed rounds travels too, so --eval-every and --goal-reorder-every keep their cadence; files are written under a "
+                         "temporary name and renamed, so a stop in the middle of a backup leaves the previous one")
     args = ap.parse_args(argv)
     env_kw = env_kwargs_from_args(args)         # (bad values: before torch is imported or a GPU is touched)
     if args.eval_every < 0 or (args.eval_every and (args.eval_envs < 1 or not 1 <= args.eval_episodes <= 64)):
@@ -150,11 +156,30 @@ def main(argv=None):
         # ids, and a log of exactly the episodes asked for (the training env's own --episode-log, if any, stays the training env's)
         eval_env = RoboyVecEnv(MsjRobot(), args.eval_envs, goals=goals, device=local_rank, env_id_offset=rank * args.eval_envs,
                                **dict(env_kw, seed=args.seed + EVAL_SEED_OFFSET, episode_log=args.eval_episodes, goal_row_stats=False))
-    if os.path.exists(model_file):
-        agent.load(model_file)                  # resume from the last backup
-    last_stats = {}
+    resume_file = os.path.join(results, "resume.rank%d.pt" % rank)
     push_steps_seen = 0.0                       # (--push: the env steps counted up to the last round's end)
-    for round_no in range(args.rounds):
+    rounds_done = 0                             # (--exact-resume: the rounds completed before this start - what the cadences count from)
+    if os.path.exists(model_file):
+        agent.load(model_file, resume=False)    # resume from the last backup
+        if args.exact_resume and os.path.exists(resume_file):
+            # ... exactly: this rank's envs, carries and evaluation env as the backup left them (PPO.resume_record)
+            own = torch.load(resume_file, map_location="cpu")
+            if int(own["num_timesteps"]) != int(agent.num_timesteps) and os.path.exists(resume_file + ".prev"):
+                # the run was stopped between this file and model.pkl: the backup before it is whole
+                own = torch.load(resume_file + ".prev", map_location="cpu")
+            if (int(own["num_timesteps"]), int(own["world"])) != (int(agent.num_timesteps), world):
+                raise SystemExit("%s was written at %d timesteps by %d ranks, model.pkl holds %d and this run has %d: not one backup"
+                                 % (resume_file, own["num_timesteps"], own["world"], agent.num_timesteps, world))
+            agent.load_resume_record(own["resume"])
+            if eval_env is not None and own["eval_env"] is not None:
+                from .ppo import unpack_arrays
+                eval_env.load_state_dict(unpack_arrays(own["eval_env"]))
+            push_steps_seen = float(env.stats()["n_env_steps"])
+            rounds_done = int(own["rounds_done"])
+        elif args.exact_resume:
+            print("rank %d: %s is missing beside model.pkl - the policy is loaded, the envs start over" % (rank, resume_file))
+    last_stats = {}
+    for round_no in range(rounds_done, rounds_done + args.rounds):
         agent.learn(total_timesteps=args.steps_per_round,
                     log=(lambda s: (last_stats.update(s), print(log_line(s)))) if rank == 0 else None)
         # episode statistics of ALL ranks' envs, summed (RCCL; gloo: through the host): the env's 8 doubles, then a named segment per option
@@ -186,8 +211,23 @@ def main(argv=None):
         row_counts = total["row_counts"].numpy().astype(np.uint64).reshape(2, goals_m) if by_reach_rate else None
         if by_reach_rate and (round_no + 1) % args.goal_reorder_every == 0:      # every rank orders by the same sums: all ranks keep the same pool
             env.reorder_goals_by_reach_rate(attempts=row_counts[0], reached=row_counts[1])
-        if rank == 0:
+        if args.exact_resume:                    # every rank: its own shard (before model.pkl, which names the backup they belong to)
+            from .ppo import pack_arrays
+            os.makedirs(results, exist_ok=True)
+            torch.save({"resume": agent.resume_record(), "eval_env": None if eval_env is None else pack_arrays(eval_env.state_dict()),
+                        "num_timesteps": int(agent.num_timesteps), "world": world, "rank": rank, "rounds_done": round_no + 1},
+                       resume_file + ".tmp")
+            if os.path.exists(resume_file):                    # (kept until the next backup: model.pkl is replaced last, and a stop
+                os.replace(resume_file, resume_file + ".prev")  # between the two leaves model.pkl with the file it belongs to)
+            os.replace(resume_file + ".tmp", resume_file)
+            if world > 1:
+                dist.barrier()
+        if rank == 0 and args.exact_resume:
+            agent.save(model_file + ".tmp")
+            os.replace(model_file + ".tmp", model_file)
+        elif rank == 0:
             agent.save(model_file)
+        if rank == 0:
             summary = summarize(total["statistics"])
             if goal_curriculum is not None:
                 summary.update(level_summary(total["levels"]))

@@ -798,6 +798,47 @@ int rb_env_start_poses_configure(rb_sim *sim, const float *rows /* [m][n_q] */, 
 int rb_env_start_poses_set(rb_sim *sim, const float *rows /* [m][n_q] */, int64_t m);
 int rb_env_start_poses_ptr(rb_sim *sim, float **d_pool, int64_t *m, uint32_t **d_count, uint32_t **d_index);
 
+/* ---- the handle's state as one blob: snapshot and restore ----
+ * State is everything a later step, reset, statistic or accessor reads that an earlier one wrote: the core planes (q, qd, the
+ * feasibility words, the goal draw counters), the env layer's planes and counters, and every plane of every option that is configured
+ * - draw counters, delays, the action ring, the goal and start pools as they stand (they are permuted and rewritten while live),
+ * levels, indices, row counts, shaping sums, push planes, the episode log.  Staging buffers, reduction scratch and the constants of
+ * the robot or the configuration are not state.  ONE function of the library lists the segments of the handle as it is configured
+ * now; the four calls below walk that list.
+ *   segments: the table, in blob order.  `name` is a stable string ("core.q", "io.ring", "goals.row_stats", ...), `dtype` the element
+ *        type, rows x cols the plane as it lies in memory (row-major [rows][cols]), `offset` the segment's byte offset in the blob,
+ *        16-byte aligned.  *count receives the number of segments (also where capacity is smaller, or `out` NULL with capacity 0:
+ *        the first min(capacity, *count) entries are written).
+ *   bytes: the blob's size (the last segment's end, rounded up to 16).
+ *   save_dev: enqueues one device-to-device copy per segment on the handle's stream, behind whatever is in flight there, into d_blob
+ *        (device memory, 16-byte aligned), and fills *host (may be NULL).  It synchronises nothing: the blob is complete when the
+ *        stream has reached the copies (rb_synchronize, or work enqueued behind them on the same stream).
+ *   load_dev: waits until nothing of the handle is in flight, then copies every segment back IN PLACE and sets the host members from
+ *        *host (NULL leaves them).  No pointer moves and no graph is dropped, so a captured graph's next replay continues from the
+ *        restored state.  The blob must come from a handle of the same configuration (batch size, robot, options and their sizes):
+ *        the table is the caller's means to check that - the library checks the byte count alone.
+ *   Both return RB_EINVAL for a null blob or a byte count other than rb_env_state_bytes', and a refused call leaves the handle as it
+ *   was.  Both work on a handle without rb_env_configure: its segments are the four core planes.
+ * Configuration is not state: seed, env id offset, the option records' settings, parameter ranges.  A caller restores into a handle
+ * it has configured the same way (RoboyVecEnv.load_state_dict compares identity and table first).
+ * RB_ABI_VERSION is still 6 (nothing that existed changed): look rb_env_state_segments up before relying on these four. */
+enum rb_state_dtype { RB_STATE_F32 = 0, RB_STATE_U32 = 1, RB_STATE_F64 = 2, RB_STATE_U64 = 3 };
+typedef struct rb_state_segment {
+    char name[48];
+    uint32_t dtype;        /* rb_state_dtype                                            */
+    uint32_t reserved;
+    int64_t rows, cols;    /* as it lies in memory: [rows][cols]                        */
+    int64_t offset;        /* byte offset in the blob, 16-byte aligned                  */
+} rb_state_segment;
+typedef struct rb_state_host {
+    double env_steps;      /* env steps issued since the statistics were reset - the one host member that moves after configuration */
+    double reserved[7];
+} rb_state_host;
+int rb_env_state_segments(rb_sim *sim, rb_state_segment *out, int32_t capacity, int32_t *count);
+int rb_env_state_bytes(rb_sim *sim, int64_t *bytes);
+int rb_env_state_save_dev(rb_sim *sim, void *d_blob, int64_t bytes, rb_state_host *host);
+int rb_env_state_load_dev(rb_sim *sim, const void *d_blob, int64_t bytes, const rb_state_host *host);
+
 /* ---- which kernel instance a call launches: the library's dispatch table, readable (ABI 5) ----
  * Every launch of the three entry kinds goes through ONE table of kernel instances keyed by (robot class, entry kind, kernel form,
  * integrator, workgroup size, constants source, variant); RB_KERNEL_AUTO's thresholds are a list of rules (first match wins).  Both
