@@ -6,8 +6,9 @@ import math
 import numpy as np
 
 
-def random_tree_spec(seed, n_q=None, n_t=None, shape=None, p_massless=0.25):
-    """shape: None (random mix), "chain" (one serial chain), "star" (every joint a child of joint 0)."""
+def random_tree_spec(seed, n_q=None, n_t=None, shape=None, p_massless=0.25, inertia_scale=1.0):
+    """shape: None (random mix), "chain" (one serial chain), "star" (every joint a child of joint 0).  inertia_scale multiplies the
+    drawn inertia tensors behind every random draw: the generator's stream, and with it every other number, is that of the seed."""
     from gym_roboy_amd.envs.robots.description import FORMAT_TAG
     rng = np.random.default_rng(1000 + seed)
     n_q = int(rng.integers(1, 25)) if n_q is None else n_q
@@ -54,6 +55,8 @@ def random_tree_spec(seed, n_q=None, n_t=None, shape=None, p_massless=0.25):
             pts.append(rng.uniform(-0.06, 0.06, 3) + (0.0 if link >= 0 else rng.uniform(-0.1, 0.1, 3)))
         tendons.append({"name": "t%d" % k, "f_max": float(rng.uniform(4.0, 25.0)),
                         "via_points": [{"link": l, "pos": [float(x) for x in p]} for l, p in zip(links, pts)]})
+    for j in joints:
+        j["inertia"] = [float(x * inertia_scale) for x in j["inertia"]]
     return {"format": FORMAT_TAG, "name": "random%d" % seed, "gravity": [0.0, 0.0, -9.81], "joints": joints,
             "tendons": tendons,
             "muscle": {"kp": 10.0, "setpoint_scale": 0.02, "v_max": 8.0, "fl_width": 0.45, "kpe": 4.0, "e0": 0.6,
